@@ -2,6 +2,7 @@
 """bench.py — object-crops/sec through the refinement heads on MI355X (BASELINE.json's metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C4|C5] [--precision fp32|bf16|fp16|f16x3]
+                  [--full] [--dump-outputs DIR]
 
 Workload (`config.workload`): BASELINE.json configs[1] — StaticModelOneBoxEst, 4096 crops x 1024 points, fp32, per GPU;
 synthetic crops and random-init weights (3dal_pytorch_amd/synth.py; no dataset or checkpoint is reachable). One step =
@@ -13,12 +14,19 @@ and no launcher in the environment, the process starts the ranks itself as child
 relays rank 0's line; under `python -m torch.distributed.run` it is a rank.
 
 stdout carries ONE JSON line of at most LINE_CAP bytes (tests/test_launch_cpu.py holds it to that): the contract's
-fields, `roofline` (the step's dominant kernel, timed live with HIP events on the launch stream: algorithmic FLOP per
-launch / average duration vs the MFMA peak of the arithmetic type), `cpu_baseline` (the oracle on this box's host
-cores, a bounded sample of the same workload) and, for N > 1, `rccl`. The same record with the whole per-kernel table
-goes to gpurun_out/bench_full.json. Everything else this repo measures (16-bit and f16x3 runs of the workload, the
-max-pool's HBM roofline, the other configurations, the rows either side of the path) is tools/bench_extras.py's, which
-writes a file and prints nothing here (`--extras` runs it after the line is out).
+fields and, for N > 1, `rccl`. A plain run does only what that headline needs: set-up, W warm-up steps, K timed steps,
+the line; `roofline` and `cpu_baseline` are null. `--full` adds the side measurements and checks: `roofline` (the
+step's dominant kernel, timed live with HIP events on the launch stream: algorithmic FLOP per launch / average duration
+vs the MFMA peak of the arithmetic type), `cpu_baseline` (the oracle on the host cores, a bounded sample of the same
+workload), for N > 1 the all-gather latency, the gather self-check and the `strong` record, and the same record with
+the whole per-kernel table written to bench_full.json in the output folder (write_full). Everything else this repo
+measures (16-bit and f16x3 runs of the workload, the max-pool's HBM roofline, the other configurations, the rows either
+side of the path) is tools/bench_extras.py's, which writes a file and prints nothing here (`--extras` runs it after the
+line is out).
+
+`--dump-outputs DIR` writes what the timed path returned in its last timed step — the (n_total, 7) float32 boxes of
+every head, rank 0's gathered copy for N > 1 — as DIR/<head>_boxes.npy (dump_outputs). The inputs and weights are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -379,6 +387,23 @@ def write_full(rec):
         sys.stderr.write(f"bench.py: bench_full.json not written: {e}\n")
 
 
+DUMP_CAP = 64 << 20        # bytes of --dump-outputs in all
+
+
+def dump_outputs(out_dir, wl):
+    """--dump-outputs: each head's boxes of the last timed step as <head>_boxes.npy (float32). Past DUMP_CAP bytes in
+    all, a fixed seeded sample of rows per head is written instead, with its row indices as <head>_rows.npy (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    cap_rows = DUMP_CAP // (len(wl.parts) * (7 * 4 + 8))   # a sampled row costs its 7 floats and its float64 index
+    for part, boxes in zip(wl.parts, wl.last_boxes):
+        a = boxes.detach().float().cpu().numpy()
+        if a.shape[0] > cap_rows:
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], cap_rows, replace=False))
+            np.save(os.path.join(out_dir, f"{part.name}_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(out_dir, f"{part.name}_boxes.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -394,7 +419,11 @@ def main():
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16", "fp16", "f16x3"])
     ap.add_argument("--two-stage", action="store_true", help="static head: StaticModelTwoBoxEst instead of OneBoxEst")
     ap.add_argument("--serial-gather", action="store_true", help="wait for each step's all-gather inside the step")
-    ap.add_argument("--no-extras", action="store_true", help="timed steps only: no roofline / cpu_baseline legs (profiling runs)")
+    ap.add_argument("--full", action="store_true", help="also the side measurements and checks: roofline, cpu_baseline, "
+                    "bench_full.json and, for N > 1, the all-gather latency, the gather self-check and the strong record")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's boxes as DIR/<head>_boxes.npy (float32)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no roofline / cpu_baseline legs (profiling runs)")
     ap.add_argument("--extras", action="store_true", help="after the line: run tools/bench_extras.py (writes gpurun_out/bench_extras.json)")
     ap.add_argument("--plumbing-only", action="store_true", help="launcher + process group + gather only, no GPU work (CPU tests)")
     ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of host time the cpu_baseline leg may take")
@@ -460,20 +489,24 @@ def main():
                                       + (", collected one step later" if not args.serial_gather else ", serial"))
                       if use_dist else "single GPU", "algorithmic_gflop_per_item": round(wl.flop_item / 1e9, 4)},
            "roofline": None, "cpu_baseline": None}
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, wl)
     full = {}
     if use_dist:
         census = dal3_dist.world_census(dev)
         rec["ms_per_step_per_rank"] = [round(t / args.steps * 1e3, 3) for t in wl.rank_seconds]   # each rank's own clock
-        check = gather_self_check(wl, dev, rank, world)
-        rec["gather_equals_single_rank"] = check["equal"] if check and rank == 0 else None
-        rec["gather_self_check"] = check
-        rec["rccl"] = dict(census, allgather_us=gather_latency(wl, dev), ranks_share_gpus=share_gpu,
+        rec["rccl"] = dict(census, ranks_share_gpus=share_gpu,
                            message_bytes_per_rank=[((n_total + world - 1) // world) * 28 for _, _, n_total in wl.parts],
                            rccl_version=".".join(str(v) for v in torch.cuda.nccl.version()),
                            transport=transport_report(dev, backend, debug_dir))
+    if use_dist and args.full:
+        check = gather_self_check(wl, dev, rank, world)
+        rec["gather_equals_single_rank"] = check["equal"] if check and rank == 0 else None
+        rec["gather_self_check"] = check
+        rec["rccl"]["allgather_us"] = gather_latency(wl, dev)
         # ONE batch of the N = 1 size split over the ranks (C4 is that already)
         rec["strong"] = None if mixed else strong_leg(args, dev, rank, world, use_dist)
-    if rank == 0 and not args.no_extras and not mixed:
+    if rank == 0 and args.full and not args.no_extras and not mixed:
         # the dominant kernel, live: every kernel of the step through its own entry, HIP events on the launch stream
         kr, mean_count = kernel_table(wl.model, wl.inputs, wl.static, wl.B, wl.N, iters=max(3, min(args.steps, 10)))
         rec["roofline"] = roofline_of(kr, MFMA_PEAK_TFLOPS[args.precision], args.precision, wl.B, wl.N)
@@ -490,7 +523,8 @@ def main():
         rec["rccl"]["transport"] = transport_from_logs(rec["rccl"]["transport"])
     if rank == 0:
         os.write(real_stdout, (compact_line(rec) + "\n").encode())
-        write_full(dict(rec, **full))
+        if args.full:
+            write_full(dict(rec, **full))
     os.close(real_stdout)
     if rank == 0 and args.extras and world == 1:               # a child process, after the line is out; prints nothing here
         del wl

@@ -47,7 +47,7 @@ def _rehearsal(extra_args, timeout=900):
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(DAL3_BENCH_SHARE_GPU="1", DAL3_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"] + extra_args, capture_output=True,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full"] + extra_args, capture_output=True,
                          text=True, env=env, timeout=timeout)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -88,7 +88,7 @@ def test_one_rank_rccl_bench_line_carries_the_transport_report():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR")}
     env.update(DAL3_FORCE_DIST="1", MASTER_PORT="29547", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                          "--batch", "256", "--no-extras"], capture_output=True, text=True, env=env, timeout=900)
+                          "--batch", "256", "--no-extras", "--full"], capture_output=True, text=True, env=env, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1 and len(lines[0].encode()) <= 4096

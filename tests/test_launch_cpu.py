@@ -7,6 +7,7 @@ import json
 import os
 import subprocess
 import sys
+import types
 
 from _common import ROOT
 
@@ -191,3 +192,30 @@ def test_launcher_timeout_ends_the_whole_process_group():
     time.sleep(1.0)
     left = subprocess.run(["pgrep", "-f", "bench.py --gpus 2 --plumbing-only"], capture_output=True, text=True).stdout.split()
     assert left == [], f"ranks left behind: {left}"
+
+
+def test_dump_outputs_writes_every_head_and_samples_past_the_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float32 <head>_boxes.npy per head; past DUMP_CAP bytes a fixed seeded sample of rows,
+    with the sampled row indices beside it, and the same sample every time"""
+    import numpy as np
+    import torch
+    bench = importlib.import_module("bench")
+
+    class WL:
+        parts = [types.SimpleNamespace(name="static"), types.SimpleNamespace(name="dynamic")]
+        last_boxes = [torch.arange(37 * 7, dtype=torch.float32).view(37, 7), torch.ones((5, 7), dtype=torch.float32)]
+    bench.dump_outputs(str(tmp_path / "all"), WL)
+    assert sorted(os.listdir(tmp_path / "all")) == ["dynamic_boxes.npy", "static_boxes.npy"]
+    s = np.load(tmp_path / "all" / "static_boxes.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, WL.last_boxes[0].numpy())
+    monkeypatch.setattr(bench, "DUMP_CAP", 2 * 10 * (7 * 4 + 8))              # 10 rows per head
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), WL)
+    rows = np.load(tmp_path / "s1" / "static_rows.npy")
+    assert rows.dtype == np.float64 and len(rows) == 10 and np.all(np.diff(rows) > 0)
+    got = np.load(tmp_path / "s1" / "static_boxes.npy")
+    assert np.array_equal(got, WL.last_boxes[0].numpy()[rows.astype(np.int64)])
+    assert np.array_equal(got, np.load(tmp_path / "s2" / "static_boxes.npy"))
+    assert not os.path.exists(tmp_path / "s1" / "dynamic_rows.npy")         # 5 rows: under the cap, written whole
+    total = sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1"))
+    assert total <= bench.DUMP_CAP + 4 * 128                                # (+ the .npy headers)

@@ -15,7 +15,7 @@ cd /tmp; export TMPDIR=/tmp
 B="python3 $R/bench.py"
 X="python3 $R/tools/bench_extras.py"
 # ---- the driver's command, as the driver runs it; then everything that is NOT on the line
-$B --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; cp $O/bench_full.json $O/bench_full_headline.json
+$B --gpus 1 --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err; cp $O/bench_full.json $O/bench_full_headline.json
 $X --out $O/bench_extras.json > $O/bench_extras.log 2>&1
 # ---- kernel traces (rocprofv3 --kernel-trace --stats) of the timed steps alone
 trace_pass $O/prof_kt -- $B --no-extras --steps 10 --warmup 2;                          cp $O/prof_kt.out $O/bench_under_rocprof.json
@@ -85,8 +85,8 @@ python3 $R/tools/bench_latency.py > $O/bench_latency.json 2>/dev/null
 python3 $R/tools/bench_shares.py --out $O/share_efficiency.json 2> $O/share_efficiency.log
 [ -f $R/variants/decnoxcd.so ] && { bash $R/tools/pmc_decode_traffic.sh gpurun_out/pmc_dec 3dal_pytorch_amd/lib3dal_hip.so variants/decnoxcd.so > /dev/null 2>&1 || PROF_RC=1; }
 # ---- the N > 1 path rehearsed on this box's one GPU (two ranks on device 0, boxes gathered over gloo)
-DAL3_BENCH_SHARE_GPU=1 DAL3_BENCH_BACKEND=gloo $B --gpus 2 --steps 10 --warmup 3 > $O/bench_rehearsal_2ranks.json 2>/dev/null
-DAL3_BENCH_SHARE_GPU=1 DAL3_BENCH_BACKEND=gloo $B --gpus 2 --config C4 --steps 2 --warmup 1 --no-extras > $O/bench_rehearsal_2ranks_c4.json 2>/dev/null
+DAL3_BENCH_SHARE_GPU=1 DAL3_BENCH_BACKEND=gloo $B --gpus 2 --steps 10 --warmup 3 --full > $O/bench_rehearsal_2ranks.json 2>/dev/null
+DAL3_BENCH_SHARE_GPU=1 DAL3_BENCH_BACKEND=gloo $B --gpus 2 --config C4 --steps 2 --warmup 1 --full --no-extras > $O/bench_rehearsal_2ranks_c4.json 2>/dev/null
 $B --cpu-sweep 8 16 32 64 128 > $O/cpu_threads.json 2>/dev/null
 python3 $R/tools/prof_summary.py $TAG $O > $O/prof_summary.log 2>&1
 cp -n $R/profiles/${TAG}_* $R/profiles/traffic.json $O/ 2>/dev/null   # (-n: never over what this run wrote into $O itself)
