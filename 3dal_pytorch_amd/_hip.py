@@ -97,6 +97,8 @@ SIGNATURES = {
     "dal3_static_crop_labels": (_i, [vp, vp, vp, vp, _i, _i, _u64, _i64, vp, vp, vp]),
     "dal3_dynamic_item_labels": (_i, [vp, vp, vp, vp, vp, vp, vp, _i, _i, _i, _u64, _i64, vp, vp, vp, vp, vp]),
     "dal3_points_in_boxes": (_i, [vp, _i, _i64, _i64, vp, _i, _i, vp, vp]),
+    "dal3_box_iou_pairwise": (_i, [vp, _i64, vp, _i64, _i, vp, vp, vp]),
+    "dal3_box_iou_paired": (_i, [vp, vp, _i64, _i, vp, vp, vp]),
     "dal3_crop_workspace_bytes": (_sz, [_i64, _i64]),
     "dal3_crop_count": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, _sz, vp]),
     "dal3_crop_fill": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, vp, vp, vp, _i64, vp, _sz, vp]),

@@ -882,6 +882,35 @@ extern "C" int dal3_points_in_boxes(const void* points, int points_f64, int64_t 
     return 0;
 }
 
+static int box_iou_args_ok(const char* what, const void* a, int64_t n, const void* b, int64_t m, int boxes_f64,
+                           const float* iou_bev, const float* iou_3d, int64_t blocks) {
+    if (n < 0 || m < 0 || (boxes_f64 != 0 && boxes_f64 != 1))
+        return fail(DAL3_EINVAL, "%s: bad argument (n, m >= 0, boxes_f64 0 or 1)", what);
+    if (n > DAL3_MAX_ITEMS || m > DAL3_MAX_ITEMS)
+        return fail(DAL3_EINVAL, "%s: more than DAL3_MAX_ITEMS boxes on one side; split the call", what);
+    if (blocks > DAL3_MAX_TILES) return fail(DAL3_EINVAL, "%s: launch grid beyond DAL3_MAX_TILES; split the call", what);
+    if (!iou_bev && !iou_3d) return fail(DAL3_EINVAL, "%s: no output (iou_bev and iou_3d both NULL)", what);
+    if (n > 0 && m > 0 && (!a || !b)) return fail(DAL3_EINVAL, "%s: null boxes", what);
+    return 0;
+}
+
+extern "C" int dal3_box_iou_pairwise(const void* a, int64_t n, const void* b, int64_t m, int boxes_f64, float* iou_bev,
+                                     float* iou_3d, dal3_stream stream) {
+    // the block count is formed only once n, m are known to be <= 2^24 each: n * m / 1024 < 2^38, no overflow
+    const int64_t blocks = (n >= 0 && m >= 0 && n <= DAL3_MAX_ITEMS && m <= DAL3_MAX_ITEMS) ? box_iou_pairwise_blocks(n, m) : 0;
+    TRY(box_iou_args_ok("box_iou_pairwise", a, n, b, m, boxes_f64, iou_bev, iou_3d, blocks));
+    HIP_TRY(launch_box_iou_pairwise(a, n, b, m, boxes_f64, iou_bev, iou_3d, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+extern "C" int dal3_box_iou_paired(const void* a, const void* b, int64_t n, int boxes_f64, float* iou_bev, float* iou_3d,
+                                   dal3_stream stream) {
+    const int64_t blocks = (n >= 0 && n <= DAL3_MAX_ITEMS) ? box_iou_paired_blocks(n) : 0;
+    TRY(box_iou_args_ok("box_iou_paired", a, n, b, n, boxes_f64, iou_bev, iou_3d, blocks));
+    HIP_TRY(launch_box_iou_paired(a, b, n, boxes_f64, iou_bev, iou_3d, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 extern "C" size_t dal3_crop_workspace_bytes(int64_t K_total, int64_t max_points_per_frame) {
     if (K_total <= 0 || max_points_per_frame < 0) return 0;
     return crop_workspace_bytes(K_total, max_points_per_frame);

@@ -232,6 +232,13 @@ hipError_t launch_crop_fill(const float* points, const int64_t* point_offsets, c
                             int64_t out_capacity, hipStream_t s);
 hipError_t launch_crop_starts(const int64_t* counts, const int64_t* order, int64_t K, int64_t* box_start, int64_t* out_offsets,
                               int64_t out_capacity, hipStream_t s);
+// rotated-box IoU (dal3_iou.hip): boxes (n,7) / (m,7) [x,y,z,l,w,h,yaw] float32 or float64 (boxes_f64); outputs may be NULL
+int64_t box_iou_pairwise_blocks(int64_t n, int64_t m);
+int64_t box_iou_paired_blocks(int64_t n);
+hipError_t launch_box_iou_pairwise(const void* a, int64_t n, const void* b, int64_t m, int boxes_f64, float* iou_bev,
+                                   float* iou_3d, hipStream_t s);
+hipError_t launch_box_iou_paired(const void* a, const void* b, int64_t n, int boxes_f64, float* iou_bev, float* iou_3d,
+                                 hipStream_t s);
 hipError_t launch_points_in_boxes(const void* points, int points_f64, int64_t P, int64_t stride, const double* planes,
                                   int K, int f32_math, uint8_t* inside, hipStream_t s);
 hipError_t launch_writeback(const double* final_boxes, const int32_t* final_idx, const double* pose_best,

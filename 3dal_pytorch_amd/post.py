@@ -2,7 +2,8 @@
 reference's `postprocessing` (tools/static_eval.py:62-167, tools/dynamic_eval.py:43-141) on the device through
 dal3_writeback_boxes. The host side flattens (track, frame) pairs and the frames' detection arrays — once per segment
 (WritebackPlan) —; the box transforms, the 0.1 m centre match and the overwrite run on the GPU in float64. The IoU metrics that
-function also logs depend on an un-vendored module and are out of scope.
+function also logs are eval.box_metrics (the reference's samples and recipe, the rotated-box IoU of iou.py in place of the
+un-vendored fpointnet geometry).
 """
 import numpy as np
 import torch

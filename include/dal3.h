@@ -25,7 +25,7 @@ extern "C" {
 
 typedef void* dal3_stream;               /* hipStream_t */
 
-#define DAL3_VERSION 150                 /* 0.1.5: dal3_crop_starts_capped; upper bounds on B, N (DAL3_MAX_*); DAL3_BCN_NO_LDS_SAMPLER; 0.1.4: dal3_crop_starts, dal3_crop_fill takes out_capacity; 0.1.3: dal3_bcn.flags (DAL3_BCN_*); dal3_tr_linear_bn_stats / dal3_tr_linear_bnbwd_sums; .1: dal3_tr_fc_*, dal3_tr_wgrad_final_many, dal3_parse_box_pred* */
+#define DAL3_VERSION 160                 /* 0.1.6: dal3_box_iou_pairwise / dal3_box_iou_paired; 0.1.5: dal3_crop_starts_capped; upper bounds on B, N (DAL3_MAX_*); DAL3_BCN_NO_LDS_SAMPLER; 0.1.4: dal3_crop_starts, dal3_crop_fill takes out_capacity; 0.1.3: dal3_bcn.flags (DAL3_BCN_*); dal3_tr_linear_bn_stats / dal3_tr_linear_bnbwd_sums; .1: dal3_tr_fc_*, dal3_tr_wgrad_final_many, dal3_parse_box_pred* */
 
 enum {
     DAL3_OK = 0,
@@ -303,6 +303,21 @@ int dal3_dynamic_item_labels(const double* points, const int64_t* frame_offsets,
  * float32 boxes, the reference's sweep case), in float64 otherwise. NaN coordinates count as inside (as there). */
 int dal3_points_in_boxes(const void* points, int points_f64, int64_t P, int64_t stride, const double* planes, int K,
                          int f32_math, uint8_t* inside, dal3_stream stream);
+
+/* ---- rotated-box IoU: the quantity of det3d/ops/iou3d_nms/iou3d_nms_utils.py boxes_iou_bev / boxes_iou3d_gpu.
+ * Boxes (.,7) row-major [x, y, z, l, w, h, yaw] (z the centre, yaw about +z, l along the heading: the det3d convention
+ * boxes_iou3d_gpu takes before its to_pcdet mirror, and the one the heads emit), float32 (boxes_f64 = 0) or float64
+ * (boxes_f64 = 1). Outputs are float32; iou_bev and iou_3d may each be NULL (that output is skipped), not both.
+ *   iou_bev = area(A n B) / area(A u B) of the bird's-eye-view rectangles;
+ *   iou_3d  = area(A n B) * z_overlap / (l_a w_a h_a + l_b w_b h_b - area(A n B) * z_overlap)   (iou3d_nms_utils.py:52-72).
+ * A union <= 0 gives 0, a non-finite input NaN for its pairs, a negative size counts as 0. The centre and yaw
+ * differences of a pair are taken in the input precision, the rest in float32: the result does not depend on where
+ * the pair sits in the world. dal3_box_iou_pairwise(a[i], b[j]) and dal3_box_iou_paired on that pair are the same bits.
+ * Bounds: n, m <= DAL3_MAX_ITEMS and the launch grid (ceil(n/16) * ceil(m/64), resp. ceil(n/256)) <= DAL3_MAX_TILES. */
+int dal3_box_iou_pairwise(const void* a, int64_t n, const void* b, int64_t m, int boxes_f64, float* iou_bev,
+                          float* iou_3d, dal3_stream stream);   /* (n, m) row-major */
+int dal3_box_iou_paired(const void* a, const void* b, int64_t n, int boxes_f64, float* iou_bev, float* iou_3d,
+                        dal3_stream stream);                    /* (n): a[k] vs b[k] */
 
 /* ---- crop extraction from full sweeps: the per-detection loop of _create_pd_detection
  * (det3d/datasets/waymo/waymo_common.py:166-171, 193) for F frames at once. points (P_total,3) f32 vehicle-frame
