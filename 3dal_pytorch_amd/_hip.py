@@ -68,6 +68,27 @@ class DynamicArgs(C.Structure):
                 ("workspace", vp), ("workspace_bytes", C.c_size_t)]
 
 
+class BoxMetricAcc(C.Structure):
+    """dal3_box_metric_acc (48 bytes)"""
+    _fields_ = [("sum_iou_bev", C.c_double), ("sum_iou_3d", C.c_double), ("sum_loss", C.c_double),
+                ("n_iou_3d_pass", C.c_uint64), ("n_seg_correct", C.c_uint64), ("n_items", C.c_uint64)]
+
+
+class BoxMetricArgs(C.Structure):
+    """dal3_box_metric_args"""
+    _fields_ = [("B", C.c_int64), ("N", C.c_int64)] + [
+        f for name in ("center", "heading_scores", "heading_residuals", "size_scores", "size_residuals", "center_label",
+                       "heading_class_label", "heading_residual_label", "size_class_label", "size_residual_label")
+        for f in ((name, vp), ("ld_" + name, C.c_int64))] + [
+        ("f64_fields", C.c_int32), ("i32_fields", C.c_int32),
+        ("logits", vp), ("logits_stride_b", C.c_int64), ("logits_stride_n", C.c_int64), ("logits_stride_c", C.c_int64),
+        ("mask_label", vp), ("mask_stride_b", C.c_int64), ("mask_stride_n", C.c_int64), ("mask_dtype", C.c_int32),
+        ("thr", C.c_float), ("loss", vp), ("iou_bev", vp), ("iou_3d", vp), ("acc", vp)]
+
+
+MASK_U8, MASK_F32 = 0, 1
+
+
 # every symbol include/dal3.h declares: (restype, argtypes)
 _i, _i64, _u64, _sz = C.c_int, C.c_int64, C.c_uint64, C.c_size_t
 SIGNATURES = {
@@ -99,6 +120,7 @@ SIGNATURES = {
     "dal3_points_in_boxes": (_i, [vp, _i, _i64, _i64, vp, _i, _i, vp, vp]),
     "dal3_box_iou_pairwise": (_i, [vp, _i64, vp, _i64, _i, vp, vp, vp]),
     "dal3_box_iou_paired": (_i, [vp, vp, _i64, _i, vp, vp, vp]),
+    "dal3_box_estimation_metrics": (_i, [C.POINTER(BoxMetricArgs), vp]),
     "dal3_crop_workspace_bytes": (_sz, [_i64, _i64]),
     "dal3_crop_count": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, _sz, vp]),
     "dal3_crop_fill": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, vp, vp, vp, _i64, vp, _sz, vp]),

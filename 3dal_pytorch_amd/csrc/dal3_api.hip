@@ -911,6 +911,41 @@ extern "C" int dal3_box_iou_paired(const void* a, const void* b, int64_t n, int 
     return 0;
 }
 
+extern "C" int dal3_box_estimation_metrics(const dal3_box_metric_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "box_estimation_metrics: null args");
+    const dal3_box_metric_args& a = *args;
+    if (a.B < 0 || a.N < 0 || a.B > DAL3_MAX_ITEMS || a.N > DAL3_MAX_POINTS_PER_ITEM)
+        return fail(DAL3_EINVAL, "box_estimation_metrics: bad B / N (0 <= B <= DAL3_MAX_ITEMS, 0 <= N <= DAL3_MAX_POINTS_PER_ITEM)");
+    if (!a.acc && !a.iou_bev && !a.iou_3d) return fail(DAL3_EINVAL, "box_estimation_metrics: no accumulator and no output");
+    if ((a.f64_fields & ~255) || (a.i32_fields & ~3))
+        return fail(DAL3_EINVAL, "box_estimation_metrics: unknown bits in f64_fields / i32_fields");
+    if (a.B > 0) {
+        const void* need[10] = {a.center, a.heading_scores, a.heading_residuals, a.size_scores, a.size_residuals,
+                                a.center_label, a.heading_class_label, a.heading_residual_label, a.size_class_label,
+                                a.size_residual_label};
+        const int64_t ld[10] = {a.ld_center, a.ld_heading_scores, a.ld_heading_residuals, a.ld_size_scores,
+                                a.ld_size_residuals, a.ld_center_label, a.ld_heading_class_label,
+                                a.ld_heading_residual_label, a.ld_size_class_label, a.ld_size_residual_label};
+        for (int k = 0; k < 10; ++k) {
+            if (!need[k]) return fail(DAL3_EINVAL, "box_estimation_metrics: null field %d", k);
+            if (ld[k] < 0) return fail(DAL3_EINVAL, "box_estimation_metrics: negative row stride of field %d", k);
+        }
+    }
+    if (a.logits) {
+        if (!a.acc) return fail(DAL3_EINVAL, "box_estimation_metrics: the segmentation term needs the accumulator");
+        if (a.B > 0 && a.N > 0 && !a.mask_label) return fail(DAL3_EINVAL, "box_estimation_metrics: null mask_label");
+        if (a.mask_dtype != DAL3_MASK_U8 && a.mask_dtype != DAL3_MASK_F32)
+            return fail(DAL3_EINVAL, "box_estimation_metrics: mask_dtype must be DAL3_MASK_U8 or DAL3_MASK_F32");
+        if (a.logits_stride_b < 0 || a.logits_stride_n < 0 || a.logits_stride_c < 0 || a.mask_stride_b < 0 ||
+            a.mask_stride_n < 0)
+            return fail(DAL3_EINVAL, "box_estimation_metrics: negative stride");
+        if (1 + a.B * box_estimation_metrics_chunks(a.N) > DAL3_MAX_TILES)
+            return fail(DAL3_EINVAL, "box_estimation_metrics: launch grid beyond DAL3_MAX_TILES; split the call");
+    }
+    HIP_TRY(launch_box_estimation_metrics(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 extern "C" size_t dal3_crop_workspace_bytes(int64_t K_total, int64_t max_points_per_frame) {
     if (K_total <= 0 || max_points_per_frame < 0) return 0;
     return crop_workspace_bytes(K_total, max_points_per_frame);

@@ -239,6 +239,9 @@ hipError_t launch_box_iou_pairwise(const void* a, int64_t n, const void* b, int6
                                    float* iou_3d, hipStream_t s);
 hipError_t launch_box_iou_paired(const void* a, const void* b, int64_t n, int boxes_f64, float* iou_bev, float* iou_3d,
                                  hipStream_t s);
+// box-estimation training metrics (dal3_metrics.hip): one launch of 1 + B * chunks(N) blocks (chunks only with logits)
+int64_t box_estimation_metrics_chunks(int64_t N);
+hipError_t launch_box_estimation_metrics(const dal3_box_metric_args* a, hipStream_t s);
 hipError_t launch_points_in_boxes(const void* points, int points_f64, int64_t P, int64_t stride, const double* planes,
                                   int K, int f32_math, uint8_t* inside, hipStream_t s);
 hipError_t launch_writeback(const double* final_boxes, const int32_t* final_idx, const double* pose_best,

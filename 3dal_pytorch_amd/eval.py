@@ -169,6 +169,42 @@ def _dynamic_items(track, annos):
     return items
 
 
+def numpy_stream_parts(batch, items, tracks, r, n_per_frame, prepare):
+    """The dynamic Dataset's substitution on the global NumPy stream, for one batch of dataset indices: an item whose
+    own frame lacks the matched annotation makes its window draws, then `np.random.randint(len(items))` picks the
+    item that takes its place (dynamic_model.py:487-489), recursively. prepare(list of indices) runs on every run of
+    items that can be prepared, in stream order; returns the list of its results."""
+    n = len(items)
+    parts, seg = [], []
+    for k in batch:
+        k = int(k)
+        while not items[k][2]:                              # replaced item: its draws, then the pick of its substitute
+            if seg:
+                parts.append(prepare(seg))
+                seg = []
+            t, it, _ = items[k]
+            for i in range(it - r, it + r + 1):
+                if 0 <= i < len(tracks[t]["point"]) and len(tracks[t]["point"][i]) > 0:
+                    np.random.choice(len(tracks[t]["point"][i]), n_per_frame, replace=True)
+            k = int(np.random.randint(n))
+        seg.append(k)
+    parts.append(prepare(seg))
+    return parts
+
+
+def join_dynamic_parts(parts):
+    """prepare_dynamic_batch results of consecutive runs -> one batch; pts and box joined in the point-major storage
+    their views come from, a label dict (4th value, if any) joined per key"""
+    if len(parts) == 1:
+        return parts[0]
+    out = [torch.cat([p[0].transpose(2, 1) for p in parts], 0).transpose(2, 1),
+           torch.cat([p[1].transpose(2, 1) for p in parts], 0).transpose(2, 1),
+           torch.cat([p[2] for p in parts], 0)]
+    if len(parts[0]) > 3:
+        out.append({key: torch.cat([p[3][key] for p in parts], 0) for key in parts[0][3]})
+    return tuple(out)
+
+
 def refine_dynamic_tracks(model, track, annos, batch_size=64, n_per_frame=1024, sampler="numpy", seed=SEED, group=None):
     """`test_one_epoch` of dynamic_eval.py:213-245 over DYNAMICTRACK(track): (sum of track lengths, 7) float64,
     one refined box per track-frame in that frame's vehicle frame (see the module docstring for the rows of
@@ -193,33 +229,13 @@ def refine_dynamic_tracks(model, track, annos, batch_size=64, n_per_frame=1024, 
                                           n_per_frame=n_per_frame, r=model.r, s=model.s, sampler=sampler, seed=seed,
                                           item_offset=first, device=dev)
 
-    def burn(k):
-        t, it, _ = items[k]
-        for i in range(it - model.r, it + model.r + 1):
-            if 0 <= i < len(tracks[t]["point"]) and len(tracks[t]["point"][i]) > 0:
-                np.random.choice(len(tracks[t]["point"][i]), n_per_frame, replace=True)
-
     for a in range(lo, hi, batch_size):
         b = min(a + batch_size, hi)
         if sampler == "device":
             pts, box, init = prepare(list(range(a, b)), a)
         else:
-            parts, seg = [], []
-            for k in range(a, b):
-                while not items[k][2]:                      # replaced item: its draws, then the pick of its substitute
-                    if seg:
-                        parts.append(prepare(seg, 0))
-                        seg = []
-                    burn(k)
-                    k = int(np.random.randint(n))
-                seg.append(k)
-            parts.append(prepare(seg, 0))
-            if len(parts) == 1:
-                pts, box, init = parts[0]
-            else:                                           # joined in the point-major storage the views come from
-                pts = torch.cat([p[0].transpose(2, 1) for p in parts], 0).transpose(2, 1)
-                box = torch.cat([p[1].transpose(2, 1) for p in parts], 0).transpose(2, 1)
-                init = torch.cat([p[2] for p in parts], 0)
+            parts = numpy_stream_parts(range(a, b), items, tracks, model.r, n_per_frame, lambda seg: prepare(seg, 0))
+            pts, box, init = join_dynamic_parts(parts)[:3]
         model.item_offset = a
         local[a - lo:b - lo] = model.refine(pts, box, init)
     model.item_offset = 0

@@ -25,7 +25,7 @@ extern "C" {
 
 typedef void* dal3_stream;               /* hipStream_t */
 
-#define DAL3_VERSION 160                 /* 0.1.6: dal3_box_iou_pairwise / dal3_box_iou_paired; 0.1.5: dal3_crop_starts_capped; upper bounds on B, N (DAL3_MAX_*); DAL3_BCN_NO_LDS_SAMPLER; 0.1.4: dal3_crop_starts, dal3_crop_fill takes out_capacity; 0.1.3: dal3_bcn.flags (DAL3_BCN_*); dal3_tr_linear_bn_stats / dal3_tr_linear_bnbwd_sums; .1: dal3_tr_fc_*, dal3_tr_wgrad_final_many, dal3_parse_box_pred* */
+#define DAL3_VERSION 170                 /* 0.1.7: dal3_box_estimation_metrics (dal3_box_metric_args / dal3_box_metric_acc); 0.1.6: dal3_box_iou_pairwise / dal3_box_iou_paired; 0.1.5: dal3_crop_starts_capped; upper bounds on B, N (DAL3_MAX_*); DAL3_BCN_NO_LDS_SAMPLER; 0.1.4: dal3_crop_starts, dal3_crop_fill takes out_capacity; 0.1.3: dal3_bcn.flags (DAL3_BCN_*); dal3_tr_linear_bn_stats / dal3_tr_linear_bnbwd_sums; .1: dal3_tr_fc_*, dal3_tr_wgrad_final_many, dal3_parse_box_pred* */
 
 enum {
     DAL3_OK = 0,
@@ -318,6 +318,69 @@ int dal3_box_iou_pairwise(const void* a, int64_t n, const void* b, int64_t m, in
                           float* iou_3d, dal3_stream stream);   /* (n, m) row-major */
 int dal3_box_iou_paired(const void* a, const void* b, int64_t n, int boxes_f64, float* iou_bev, float* iou_3d,
                         dal3_stream stream);                    /* (n): a[k] vs b[k] */
+
+/* ---- box-estimation training metrics: compute_box3d_iou (tools/utils.py:81-103) plus the per-epoch accumulation of
+ * static_train.py:96-129 / static_eval.py:204-250 for one batch of B items, in ONE launch, with no host sync.
+ * Per item, on both sides (prediction / label), in float64:
+ *   heading = hc (2 pi / 12) + residual[hc], minus 2 pi when > pi          (class2angle(..., to_label_format=True))
+ *   size    = MEAN_SIZE[sc] + size_residual[sc]                            (class2size)
+ * with hc = argmax(heading_scores[0:12]), sc = argmax(size_scores[0:3]) on the prediction side (first index on ties,
+ * a NaN is the maximum: np.argmax / torch.argmax) and the class labels on the label side; then the BEV and 3D IoU of
+ * the pair [center, size, heading] through the function of dal3_box_iou_paired with float64 boxes: iou_bev[k] and
+ * iou_3d[k] are the bits of dal3_box_iou_paired(pred_k, label_k, boxes_f64 = 1). A class label outside its range gives
+ * NaN for that item (nothing is read out of the row). Segmentation: correct = argmax(logits[b, n, 0:2]) ==
+ * (int64)mask_label[b, n], torch.argmax's rule; a non-finite float mask label never matches.
+ *
+ * Every per-item field is read through its row stride (in elements); the elements of a row are contiguous (a (B,3,3)
+ * size_residuals row is its 9 values). Float fields are float32 unless their DAL3_BM_* bit is set in f64_fields;
+ * class labels are int64 unless their bit is set in i32_fields.
+ *
+ * Accumulation (acc, may be NULL when an output is given and logits is NULL): stream-ordered read-modify-write, so a
+ * run of calls on one stream sums batch after batch. The float sums of a batch are formed by one workgroup in a
+ * fixed order and the counts are integers: the accumulator is bitwise reproducible run to run. No workspace. */
+enum { DAL3_BM_CENTER = 1, DAL3_BM_HEADING_SCORES = 2, DAL3_BM_HEADING_RESIDUALS = 4, DAL3_BM_SIZE_SCORES = 8,
+       DAL3_BM_SIZE_RESIDUALS = 16, DAL3_BM_CENTER_LABEL = 32, DAL3_BM_HEADING_RESIDUAL_LABEL = 64,
+       DAL3_BM_SIZE_RESIDUAL_LABEL = 128 };                            /* f64_fields */
+enum { DAL3_BM_HEADING_CLASS_LABEL = 1, DAL3_BM_SIZE_CLASS_LABEL = 2 };  /* i32_fields */
+enum { DAL3_MASK_U8 = 0, DAL3_MASK_F32 = 1 };                           /* mask_dtype: uint8 / bool, float32 */
+
+typedef struct dal3_box_metric_acc {     /* 48 bytes; zero it to start an epoch */
+    double sum_iou_bev;                  /* sum of iou_bev over the items */
+    double sum_iou_3d;                   /* sum of iou_3d */
+    double sum_loss;                     /* sum of *loss over the calls that gave one */
+    uint64_t n_iou_3d_pass;              /* items with iou_3d >= thr (float32 compare; NaN does not pass) */
+    uint64_t n_seg_correct;              /* points whose argmax matches the mask label */
+    uint64_t n_items;                    /* items (B per call) */
+} dal3_box_metric_acc;
+
+typedef struct dal3_box_metric_args {
+    int64_t B, N;                        /* items; points per item (segmentation term) */
+    const void* center;                  int64_t ld_center;                  /* (B,3) */
+    const void* heading_scores;          int64_t ld_heading_scores;          /* (B,12) */
+    const void* heading_residuals;       int64_t ld_heading_residuals;       /* (B,12) */
+    const void* size_scores;             int64_t ld_size_scores;             /* (B,3) */
+    const void* size_residuals;          int64_t ld_size_residuals;          /* (B,3,3) */
+    const void* center_label;            int64_t ld_center_label;            /* (B,3) */
+    const void* heading_class_label;     int64_t ld_heading_class_label;     /* (B) */
+    const void* heading_residual_label;  int64_t ld_heading_residual_label;  /* (B) */
+    const void* size_class_label;        int64_t ld_size_class_label;        /* (B) */
+    const void* size_residual_label;     int64_t ld_size_residual_label;     /* (B,3) */
+    int32_t f64_fields;                  /* DAL3_BM_* bits */
+    int32_t i32_fields;                  /* DAL3_BM_*_CLASS_LABEL bits */
+    const float* logits;                 /* (B,N,2) float32 at the strides below; NULL: no segmentation term */
+    int64_t logits_stride_b, logits_stride_n, logits_stride_c;
+    const void* mask_label;              /* (B,N) at the strides below, mask_dtype */
+    int64_t mask_stride_b, mask_stride_n;
+    int32_t mask_dtype;
+    float thr;                           /* the box estimation accuracy threshold on iou_3d */
+    const float* loss;                   /* optional: one float32 value added to acc->sum_loss (in float64) */
+    float* iou_bev;                      /* optional (B) float32 */
+    float* iou_3d;                       /* optional (B) float32 */
+    dal3_box_metric_acc* acc;            /* optional, see above */
+} dal3_box_metric_args;
+
+/* Bounds: B <= DAL3_MAX_ITEMS, N <= DAL3_MAX_POINTS_PER_ITEM, 1 + B ceil(N / 1024) <= DAL3_MAX_TILES. */
+int dal3_box_estimation_metrics(const dal3_box_metric_args* args, dal3_stream stream);
 
 /* ---- crop extraction from full sweeps: the per-detection loop of _create_pd_detection
  * (det3d/datasets/waymo/waymo_common.py:166-171, 193) for F frames at once. points (P_total,3) f32 vehicle-frame
