@@ -89,6 +89,28 @@ class BoxMetricArgs(C.Structure):
 MASK_U8, MASK_F32 = 0, 1
 
 
+class TrackArgs(C.Structure):
+    """dal3_track_args"""
+    _fields_ = [("S", C.c_int64), ("F", C.c_int64), ("K", C.c_int64), ("seq_offsets", vp), ("frame_offsets", vp),
+                ("ct", vp), ("tracking", vp), ("label", vp), ("score", vp), ("max_dist", C.c_float * 3),
+                ("max_age", C.c_int32), ("score_thresh", C.c_double), ("capacity", C.c_int64),
+                ("max_workgroups", C.c_int32), ("reserved", C.c_int32), ("id_base", vp), ("box_ids", vp),
+                ("tracking_ids", vp), ("out_count", vp), ("id_total", vp), ("status", vp), ("workspace", vp),
+                ("workspace_bytes", C.c_size_t)]
+
+
+class TrackMatchArgs(C.Structure):
+    """dal3_track_match_args"""
+    _fields_ = [("F", C.c_int64), ("K", C.c_int64), ("frame_offsets", vp), ("out_count", vp), ("box_ids", vp),
+                ("tracking_ids", vp), ("id_base", vp), ("boxes", vp), ("gt_offsets", vp), ("gt_boxes", vp),
+                ("thr", C.c_float), ("reserved", C.c_int32), ("match_frame", vp), ("match_obj", vp), ("status", vp),
+                ("workspace", vp), ("workspace_bytes", C.c_size_t)]
+
+
+TRACK_MAX_CAPACITY = 65536
+TRACK_OVERFLOW, TRACK_BAD_LABEL, TRACK_BAD_ID = 1, 2, 4
+
+
 # every symbol include/dal3.h declares: (restype, argtypes)
 _i, _i64, _u64, _sz = C.c_int, C.c_int64, C.c_uint64, C.c_size_t
 SIGNATURES = {
@@ -121,6 +143,10 @@ SIGNATURES = {
     "dal3_box_iou_pairwise": (_i, [vp, _i64, vp, _i64, _i, vp, vp, vp]),
     "dal3_box_iou_paired": (_i, [vp, vp, _i64, _i, vp, vp, vp]),
     "dal3_box_estimation_metrics": (_i, [C.POINTER(BoxMetricArgs), vp]),
+    "dal3_track_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "dal3_track": (_i, [C.POINTER(TrackArgs), vp]),
+    "dal3_track_match_workspace_bytes": (_sz, [_i64]),
+    "dal3_track_match": (_i, [C.POINTER(TrackMatchArgs), vp]),
     "dal3_crop_workspace_bytes": (_sz, [_i64, _i64]),
     "dal3_crop_count": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, _sz, vp]),
     "dal3_crop_fill": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, vp, vp, vp, _i64, vp, _sz, vp]),

@@ -6,7 +6,8 @@ launches (count, scan, fill) instead of one Python iteration per detection.
 In: per frame, the sweep `points_xyz` (P,3) float32 (lidar pickle), the detector's boxes
 `box3d_lidar` (K,7|9) float32 and the frame's flat-16 `veh_to_global`. Out: the `trackData` fields the downstream
 tracker files hold: 'bbox' (7,) global frame, 'point' (k,3) float64 global frame, plus `boxes_lidar` (the det_annos
-rows). Proto serialisation, uuid assignment and the IoU match against ground truth stay with the reference.
+rows). Proto serialisation stays with the reference; the tracking ids and the IoU match against ground truth
+are track.py's (dal3_track / dal3_track_match).
 """
 import numpy as np
 import torch

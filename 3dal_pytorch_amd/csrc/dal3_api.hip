@@ -946,6 +946,49 @@ extern "C" int dal3_box_estimation_metrics(const dal3_box_metric_args* args, dal
     return 0;
 }
 
+extern "C" size_t dal3_track_workspace_bytes(int64_t S, int64_t K, int64_t capacity) {
+    if (S < 0 || K < 0 || capacity < 1 || capacity > DAL3_TRACK_MAX_CAPACITY) return 0;
+    return track_workspace_bytes(S, K, capacity);
+}
+
+extern "C" int dal3_track(const dal3_track_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "track: null args");
+    const dal3_track_args& a = *args;
+    if (a.S < 0 || a.F < 0 || a.K < 0 || a.K > DAL3_MAX_ITEMS || a.F > DAL3_MAX_ITEMS)
+        return fail(DAL3_EINVAL, "track: bad S / F / K (0 <= F, K <= DAL3_MAX_ITEMS)");
+    if (a.capacity < 1 || a.capacity > DAL3_TRACK_MAX_CAPACITY)
+        return fail(DAL3_EINVAL, "track: capacity must be in [1, DAL3_TRACK_MAX_CAPACITY]");
+    if (a.max_workgroups < 0) return fail(DAL3_EINVAL, "track: negative max_workgroups");
+    if (!a.seq_offsets || !a.frame_offsets || !a.status || !a.workspace)
+        return fail(DAL3_EINVAL, "track: null offsets / status / workspace");
+    if (a.F > 0 && !a.out_count) return fail(DAL3_EINVAL, "track: null out_count");
+    if (a.K > 0 && (!a.ct || !a.tracking || !a.label || !a.score || !a.box_ids || !a.tracking_ids))
+        return fail(DAL3_EINVAL, "track: null detection input / output");
+    if (a.workspace_bytes < track_workspace_bytes(a.S, a.K, a.capacity))
+        return fail(DAL3_EWORKSPACE, "track: workspace too small (dal3_track_workspace_bytes)");
+    HIP_TRY(launch_track(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+extern "C" size_t dal3_track_match_workspace_bytes(int64_t K) {
+    if (K < 0) return 0;
+    return track_match_workspace_bytes(K);
+}
+
+extern "C" int dal3_track_match(const dal3_track_match_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "track_match: null args");
+    const dal3_track_match_args& a = *args;
+    if (a.F < 0 || a.K < 0 || a.K > DAL3_MAX_ITEMS || a.F > DAL3_MAX_ITEMS)
+        return fail(DAL3_EINVAL, "track_match: bad F / K (0 <= F, K <= DAL3_MAX_ITEMS)");
+    if (a.K > 0 && a.F > 0 && (!a.frame_offsets || !a.out_count || !a.box_ids || !a.tracking_ids || !a.boxes ||
+                               !a.gt_offsets || !a.match_frame || !a.match_obj || !a.status || !a.workspace))
+        return fail(DAL3_EINVAL, "track_match: null argument");
+    if (a.workspace_bytes < track_match_workspace_bytes(a.K))
+        return fail(DAL3_EWORKSPACE, "track_match: workspace too small (dal3_track_match_workspace_bytes)");
+    HIP_TRY(launch_track_match(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 extern "C" size_t dal3_crop_workspace_bytes(int64_t K_total, int64_t max_points_per_frame) {
     if (K_total <= 0 || max_points_per_frame < 0) return 0;
     return crop_workspace_bytes(K_total, max_points_per_frame);

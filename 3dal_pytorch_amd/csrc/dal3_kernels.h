@@ -242,6 +242,11 @@ hipError_t launch_box_iou_paired(const void* a, const void* b, int64_t n, int bo
 // box-estimation training metrics (dal3_metrics.hip): one launch of 1 + B * chunks(N) blocks (chunks only with logits)
 int64_t box_estimation_metrics_chunks(int64_t N);
 hipError_t launch_box_estimation_metrics(const dal3_box_metric_args* a, hipStream_t s);
+// tracking run (dal3_track.hip)
+size_t track_workspace_bytes(int64_t S, int64_t K, int64_t capacity);
+size_t track_match_workspace_bytes(int64_t K);
+hipError_t launch_track(const dal3_track_args* a, hipStream_t s);
+hipError_t launch_track_match(const dal3_track_match_args* a, hipStream_t s);
 hipError_t launch_points_in_boxes(const void* points, int points_f64, int64_t P, int64_t stride, const double* planes,
                                   int K, int f32_math, uint8_t* inside, hipStream_t s);
 hipError_t launch_writeback(const double* final_boxes, const int32_t* final_idx, const double* pose_best,

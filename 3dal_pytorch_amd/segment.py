@@ -11,7 +11,7 @@
                                       dynamic_eval.py:43-141)
 
 What is host work is what does not depend on a point: the tracker's association (which detection of which frame
-belongs to which track — the reference's tracker, out of scope, hands it over as lists), the detections' face equations,
+belongs to which track — track.py's tracker on the device, or the reference's, hands it over as lists: track.segment_tracks), the detections' face equations,
 the poses' inverses, each track's best-score frame and its box, the (track, frame) pairs of the write-back. All of it is
 done ONCE per segment in `SegmentPlan.__init__` (before the sweeps are touched: off the critical path) and uploaded;
 `run()` only enqueues kernels and returns device tensors. The one size that depends on the points — the number of rows

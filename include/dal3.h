@@ -25,7 +25,7 @@ extern "C" {
 
 typedef void* dal3_stream;               /* hipStream_t */
 
-#define DAL3_VERSION 170                 /* 0.1.7: dal3_box_estimation_metrics (dal3_box_metric_args / dal3_box_metric_acc); 0.1.6: dal3_box_iou_pairwise / dal3_box_iou_paired; 0.1.5: dal3_crop_starts_capped; upper bounds on B, N (DAL3_MAX_*); DAL3_BCN_NO_LDS_SAMPLER; 0.1.4: dal3_crop_starts, dal3_crop_fill takes out_capacity; 0.1.3: dal3_bcn.flags (DAL3_BCN_*); dal3_tr_linear_bn_stats / dal3_tr_linear_bnbwd_sums; .1: dal3_tr_fc_*, dal3_tr_wgrad_final_many, dal3_parse_box_pred* */
+#define DAL3_VERSION 170                 /* 0.1.7 (+ dal3_track / dal3_track_match, dal3_track_args / dal3_track_match_args, DAL3_TRACK_*: additions only, the number is pinned by the existing tests): dal3_box_estimation_metrics (dal3_box_metric_args / dal3_box_metric_acc); 0.1.6: dal3_box_iou_pairwise / dal3_box_iou_paired; 0.1.5: dal3_crop_starts_capped; upper bounds on B, N (DAL3_MAX_*); DAL3_BCN_NO_LDS_SAMPLER; 0.1.4: dal3_crop_starts, dal3_crop_fill takes out_capacity; 0.1.3: dal3_bcn.flags (DAL3_BCN_*); dal3_tr_linear_bn_stats / dal3_tr_linear_bnbwd_sums; .1: dal3_tr_fc_*, dal3_tr_wgrad_final_many, dal3_parse_box_pred* */
 
 enum {
     DAL3_OK = 0,
@@ -381,6 +381,86 @@ typedef struct dal3_box_metric_args {
 
 /* Bounds: B <= DAL3_MAX_ITEMS, N <= DAL3_MAX_POINTS_PER_ITEM, 1 + B ceil(N / 1024) <= DAL3_MAX_TILES. */
 int dal3_box_estimation_metrics(const dal3_box_metric_args* args, dal3_stream stream);
+
+/* ---- tracking run: CenterPoint's greedy tracker (tools/waymo_tracking/tracker.py, PubTracker.step_centertrack, driven
+ * by test.py:84-134) over every frame of S sequences in ONE call, and the ground-truth match of
+ * _create_pd_detection(tracking=True) (det3d/datasets/waymo/waymo_common.py:173-189).
+ *
+ * dal3_track: frames are flat, sequence after sequence, in the order test.py's sort_detections gives them
+ * (seq_id * 1000 + frame_id); sequence s = frames [seq_offsets[s], seq_offsets[s+1]), its first frame the
+ * `frame_id == 0` frame that resets the tracks (the id counter runs on); frame f = detections
+ * [frame_offsets[f], frame_offsets[f+1]), numbered within the frame as box ids. Per detection: ct (K,2) float64 global
+ * x, y; tracking (K,2) float64 = velocity * -1 * time_lag; label 0..2; score float32. The detection side of the
+ * distance is float32(ct + float32(tracking)), the track side float32(ct); every tracker.py rule is kept bit for bit
+ * (dal3_track.hip restates each with its line). Output: frame f's active entries (tracker.py `active != 0`: matched,
+ * then new) at [frame_offsets[f], frame_offsets[f] + out_count[f]): box_ids (the detection's index in its frame) and
+ * tracking_ids (int64, counted from *id_base + 1 — id_base optional, NULL = 0 — across the sequences in order, as the
+ * reference's one tracker counts them). id_total (optional) = *id_base + the ids handed out: pass it as the next
+ * call's id_base to continue the count on the device.
+ * capacity: live tracks per sequence, <= DAL3_TRACK_MAX_CAPACITY. With max_age A, a frame never holds more than the
+ * detections of its last A frames (a track of age a came from a detection a - 1 frames back), so that sum's maximum
+ * over the sequence is always enough. A sequence that needs more sets DAL3_TRACK_OVERFLOW in *status (ids then
+ * undefined); a label outside 0..2 sets DAL3_TRACK_BAD_LABEL (that detection matches nothing). status is OR-ed
+ * into, zero it first. max_workgroups (0: one per sequence) caps the grid; the result does not depend on it.
+ * workspace: dal3_track_workspace_bytes(S, K, capacity). */
+#define DAL3_TRACK_MAX_CAPACITY 65536
+enum { DAL3_TRACK_OVERFLOW = 1, DAL3_TRACK_BAD_LABEL = 2, DAL3_TRACK_BAD_ID = 4 };   /* status bits */
+
+typedef struct dal3_track_args {
+    int64_t S, F, K;                     /* sequences, frames, detections */
+    const int64_t* seq_offsets;          /* (S+1) into the frames */
+    const int64_t* frame_offsets;        /* (F+1) into the detections */
+    const double* ct;                    /* (K,2) */
+    const double* tracking;              /* (K,2) */
+    const int32_t* label;                /* (K) */
+    const float* score;                  /* (K) */
+    float max_dist[3];                   /* max_diff per class: VEHICLE, PEDESTRIAN, CYCLIST (float32 compare) */
+    int32_t max_age;
+    double score_thresh;                 /* a new id needs score > score_thresh (float64 compare) */
+    int64_t capacity;
+    int32_t max_workgroups;
+    int32_t reserved;
+    const int64_t* id_base;              /* optional (1) */
+    int32_t* box_ids;                    /* (K) */
+    int64_t* tracking_ids;               /* (K) */
+    int32_t* out_count;                  /* (F) */
+    int64_t* id_total;                   /* optional (1) */
+    int32_t* status;                     /* (1) */
+    void* workspace;
+    size_t workspace_bytes;
+} dal3_track_args;
+
+/* dal3_track_match: for every output entry of dal3_track (frame order, then output order) the 3D IoU of its box
+ * against its frame's annotation boxes (dal3_box_iou_* geometry, float32 boxes, the detection as `a`): boxes (K,7)
+ * Waymo convention [x,y,z,l,w,h,heading] by detection (row frame_offsets[f] + box id); gt_boxes (G,7) =
+ * obj['box'][[0,1,2,3,4,5,-1]], frame f's at [gt_offsets[f], gt_offsets[f+1]). The first maximum counts; a NaN in the
+ * row or a maximum not above thr gives none. A tracking id's match is its first candidate in that order, kept for every
+ * later entry of the id (`matching`); entries before it have none. Out: match_frame / match_obj (K) by output position,
+ * -1 for None. Ids must lie in (*id_base, *id_base + K] (else DAL3_TRACK_BAD_ID). workspace:
+ * dal3_track_match_workspace_bytes(K). */
+typedef struct dal3_track_match_args {
+    int64_t F, K;
+    const int64_t* frame_offsets;        /* (F+1) as for dal3_track */
+    const int32_t* out_count;            /* (F) */
+    const int32_t* box_ids;              /* (K) */
+    const int64_t* tracking_ids;         /* (K) */
+    const int64_t* id_base;              /* optional (1), as given to dal3_track */
+    const float* boxes;                  /* (K,7) */
+    const int64_t* gt_offsets;           /* (F+1) */
+    const float* gt_boxes;               /* (G,7) */
+    float thr;                           /* 0.75 */
+    int32_t reserved;
+    int32_t* match_frame;                /* (K) */
+    int32_t* match_obj;                  /* (K) */
+    int32_t* status;                     /* (1) */
+    void* workspace;
+    size_t workspace_bytes;
+} dal3_track_match_args;
+
+size_t dal3_track_workspace_bytes(int64_t S, int64_t K, int64_t capacity);
+int dal3_track(const dal3_track_args* args, dal3_stream stream);
+size_t dal3_track_match_workspace_bytes(int64_t K);
+int dal3_track_match(const dal3_track_match_args* args, dal3_stream stream);
 
 /* ---- crop extraction from full sweeps: the per-detection loop of _create_pd_detection
  * (det3d/datasets/waymo/waymo_common.py:166-171, 193) for F frames at once. points (P_total,3) f32 vehicle-frame
