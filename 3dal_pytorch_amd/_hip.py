@@ -111,6 +111,37 @@ TRACK_MAX_CAPACITY = 65536
 TRACK_OVERFLOW, TRACK_BAD_LABEL, TRACK_BAD_ID = 1, 2, 4
 
 
+class GroupArgs(C.Structure):
+    """dal3_group_args"""
+    _fields_ = [("E", C.c_int64), ("T", C.c_int64), ("F", C.c_int64), ("keys", vp), ("key_base", vp), ("key_bias", C.c_int64),
+                ("frame_offsets", vp), ("out_count", vp), ("group_start", vp), ("entry", vp), ("n_groups", vp), ("status", vp),
+                ("max_workgroups", C.c_int64), ("workspace", vp), ("workspace_bytes", C.c_size_t)]
+
+
+class TrackFeatureArgs(C.Structure):
+    """dal3_track_feature_args"""
+    _fields_ = [("T", C.c_int64), ("E", C.c_int64), ("group_start", vp), ("entry", vp), ("n_groups", vp), ("center", vp), ("type", vp),
+                ("score", vp), ("n_points", vp), ("match", vp), ("n", vp), ("type0", vp), ("match_last", vp),
+                ("points_sum", vp), ("best", vp), ("keep", vp), ("feature", vp), ("max_workgroups", C.c_int64)]
+
+
+class GtTableArgs(C.Structure):
+    """dal3_gt_table_args"""
+    _fields_ = [("T", C.c_int64), ("E", C.c_int64), ("F", C.c_int64), ("group_start", vp), ("entry", vp), ("box", vp),
+                ("frame", vp), ("pose", vp), ("box_global", vp), ("vel", vp), ("n", vp), ("dist", vp), ("max_vel", vp),
+                ("is_static", vp), ("status", vp), ("max_workgroups", C.c_int64)]
+
+
+class MotionClassifyArgs(C.Structure):
+    """dal3_motion_classify_args"""
+    _fields_ = [("T", C.c_int64), ("feature", vp), ("keep", vp), ("w", C.c_double * 2), ("b", C.c_double), ("decision", vp),
+                ("is_static", vp), ("static_ids", vp), ("dynamic_ids", vp), ("counts", vp), ("max_workgroups", C.c_int64),
+                ("workspace", vp), ("workspace_bytes", C.c_size_t)]
+
+
+MOTION_BAD_KEY = 8
+
+
 # every symbol include/dal3.h declares: (restype, argtypes)
 _i, _i64, _u64, _sz = C.c_int, C.c_int64, C.c_uint64, C.c_size_t
 SIGNATURES = {
@@ -147,6 +178,12 @@ SIGNATURES = {
     "dal3_track": (_i, [C.POINTER(TrackArgs), vp]),
     "dal3_track_match_workspace_bytes": (_sz, [_i64]),
     "dal3_track_match": (_i, [C.POINTER(TrackMatchArgs), vp]),
+    "dal3_group_workspace_bytes": (_sz, [_i64, _i64]),
+    "dal3_group_by_key": (_i, [C.POINTER(GroupArgs), vp]),
+    "dal3_track_features": (_i, [C.POINTER(TrackFeatureArgs), vp]),
+    "dal3_gt_table": (_i, [C.POINTER(GtTableArgs), vp]),
+    "dal3_motion_classify_workspace_bytes": (_sz, [_i64]),
+    "dal3_motion_classify": (_i, [C.POINTER(MotionClassifyArgs), vp]),
     "dal3_crop_workspace_bytes": (_sz, [_i64, _i64]),
     "dal3_crop_count": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, _sz, vp]),
     "dal3_crop_fill": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, vp, vp, vp, _i64, vp, _sz, vp]),

@@ -989,6 +989,73 @@ extern "C" int dal3_track_match(const dal3_track_match_args* args, dal3_stream s
     return 0;
 }
 
+extern "C" size_t dal3_group_workspace_bytes(int64_t E, int64_t T) {
+    if (E < 0 || T < 0 || E > DAL3_MAX_ITEMS || T > DAL3_MAX_ITEMS) return 0;
+    return group_workspace_bytes(E, T);
+}
+
+extern "C" int dal3_group_by_key(const dal3_group_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "group_by_key: null args");
+    const dal3_group_args& a = *args;
+    if (a.E < 0 || a.T < 0 || a.F < 0 || a.E > DAL3_MAX_ITEMS || a.T > DAL3_MAX_ITEMS || a.F > DAL3_MAX_ITEMS)
+        return fail(DAL3_EINVAL, "group_by_key: bad E / T / F (0 <= E, T, F <= DAL3_MAX_ITEMS)");
+    if (a.max_workgroups < 0) return fail(DAL3_EINVAL, "group_by_key: negative max_workgroups");
+    if (!a.group_start || !a.status) return fail(DAL3_EINVAL, "group_by_key: null group_start / status");
+    if (a.E > 0 && (!a.keys || !a.entry || !a.workspace)) return fail(DAL3_EINVAL, "group_by_key: null keys / entry / workspace");
+    if ((a.frame_offsets == nullptr) != (a.out_count == nullptr))
+        return fail(DAL3_EINVAL, "group_by_key: frame_offsets and out_count go together");
+    if (!a.frame_offsets && a.F != 0) return fail(DAL3_EINVAL, "group_by_key: F without frame_offsets");
+    if (a.workspace_bytes < group_workspace_bytes(a.E, a.T))
+        return fail(DAL3_EWORKSPACE, "group_by_key: workspace too small (dal3_group_workspace_bytes)");
+    HIP_TRY(launch_group_by_key(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+extern "C" int dal3_track_features(const dal3_track_feature_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "track_features: null args");
+    const dal3_track_feature_args& a = *args;
+    if (a.T < 0 || a.E < 0 || a.E > DAL3_MAX_ITEMS || a.T > DAL3_MAX_ITEMS || a.max_workgroups < 0)
+        return fail(DAL3_EINVAL, "track_features: bad T / E / max_workgroups");
+    if (a.T > 0 && (!a.group_start || !a.n || !a.type0 || !a.match_last || !a.points_sum || !a.best || !a.keep || !a.feature))
+        return fail(DAL3_EINVAL, "track_features: null group_start / output");
+    if (a.T > 0 && a.E > 0 && (!a.entry || !a.center || !a.type || !a.score || !a.n_points || !a.match))
+        return fail(DAL3_EINVAL, "track_features: null per-entry input");
+    HIP_TRY(launch_track_features(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+extern "C" int dal3_gt_table(const dal3_gt_table_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "gt_table: null args");
+    const dal3_gt_table_args& a = *args;
+    if (a.T < 0 || a.E < 0 || a.F < 0 || a.E > DAL3_MAX_ITEMS || a.T > DAL3_MAX_ITEMS || a.max_workgroups < 0)
+        return fail(DAL3_EINVAL, "gt_table: bad T / E / F / max_workgroups");
+    if (!a.status) return fail(DAL3_EINVAL, "gt_table: null status");
+    if (a.T > 0 && (!a.group_start || !a.n || !a.dist || !a.max_vel || !a.is_static))
+        return fail(DAL3_EINVAL, "gt_table: null group_start / output");
+    if (a.E > 0 && (!a.entry || !a.box || !a.frame || !a.box_global || !a.vel || (a.F > 0 && !a.pose)))
+        return fail(DAL3_EINVAL, "gt_table: null per-entry argument");
+    HIP_TRY(launch_gt_table(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+extern "C" size_t dal3_motion_classify_workspace_bytes(int64_t T) {
+    if (T < 0 || T > DAL3_MAX_ITEMS) return 0;
+    return motion_classify_workspace_bytes(T);
+}
+
+extern "C" int dal3_motion_classify(const dal3_motion_classify_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "motion_classify: null args");
+    const dal3_motion_classify_args& a = *args;
+    if (a.T < 0 || a.T > DAL3_MAX_ITEMS || a.max_workgroups < 0) return fail(DAL3_EINVAL, "motion_classify: bad T / max_workgroups");
+    if (!a.counts || !a.workspace) return fail(DAL3_EINVAL, "motion_classify: null counts / workspace");
+    if (a.T > 0 && (!a.feature || !a.keep || !a.decision || !a.is_static || !a.static_ids || !a.dynamic_ids))
+        return fail(DAL3_EINVAL, "motion_classify: null argument");
+    if (a.workspace_bytes < motion_classify_workspace_bytes(a.T))
+        return fail(DAL3_EWORKSPACE, "motion_classify: workspace too small (dal3_motion_classify_workspace_bytes)");
+    HIP_TRY(launch_motion_classify(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 extern "C" size_t dal3_crop_workspace_bytes(int64_t K_total, int64_t max_points_per_frame) {
     if (K_total <= 0 || max_points_per_frame < 0) return 0;
     return crop_workspace_bytes(K_total, max_points_per_frame);

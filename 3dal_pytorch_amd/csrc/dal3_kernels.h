@@ -247,6 +247,13 @@ size_t track_workspace_bytes(int64_t S, int64_t K, int64_t capacity);
 size_t track_match_workspace_bytes(int64_t K);
 hipError_t launch_track(const dal3_track_args* a, hipStream_t s);
 hipError_t launch_track_match(const dal3_track_match_args* a, hipStream_t s);
+// motion-state run (dal3_motion.hip)
+size_t group_workspace_bytes(int64_t E, int64_t T);
+size_t motion_classify_workspace_bytes(int64_t T);
+hipError_t launch_group_by_key(const dal3_group_args* a, hipStream_t s);
+hipError_t launch_track_features(const dal3_track_feature_args* a, hipStream_t s);
+hipError_t launch_gt_table(const dal3_gt_table_args* a, hipStream_t s);
+hipError_t launch_motion_classify(const dal3_motion_classify_args* a, hipStream_t s);
 hipError_t launch_points_in_boxes(const void* points, int points_f64, int64_t P, int64_t stride, const double* planes,
                                   int K, int f32_math, uint8_t* inside, hipStream_t s);
 hipError_t launch_writeback(const double* final_boxes, const int32_t* final_idx, const double* pose_best,

@@ -25,7 +25,7 @@ extern "C" {
 
 typedef void* dal3_stream;               /* hipStream_t */
 
-#define DAL3_VERSION 170                 /* 0.1.7 (+ dal3_track / dal3_track_match, dal3_track_args / dal3_track_match_args, DAL3_TRACK_*: additions only, the number is pinned by the existing tests): dal3_box_estimation_metrics (dal3_box_metric_args / dal3_box_metric_acc); 0.1.6: dal3_box_iou_pairwise / dal3_box_iou_paired; 0.1.5: dal3_crop_starts_capped; upper bounds on B, N (DAL3_MAX_*); DAL3_BCN_NO_LDS_SAMPLER; 0.1.4: dal3_crop_starts, dal3_crop_fill takes out_capacity; 0.1.3: dal3_bcn.flags (DAL3_BCN_*); dal3_tr_linear_bn_stats / dal3_tr_linear_bnbwd_sums; .1: dal3_tr_fc_*, dal3_tr_wgrad_final_many, dal3_parse_box_pred* */
+#define DAL3_VERSION 170                 /* 0.1.7 (+ dal3_group_by_key / dal3_track_features / dal3_gt_table / dal3_motion_classify and their argument structs, DAL3_MOTION_BAD_KEY: additions only, as dal3_track was; + dal3_track / dal3_track_match, dal3_track_args / dal3_track_match_args, DAL3_TRACK_*: additions only, the number is pinned by the existing tests): dal3_box_estimation_metrics (dal3_box_metric_args / dal3_box_metric_acc); 0.1.6: dal3_box_iou_pairwise / dal3_box_iou_paired; 0.1.5: dal3_crop_starts_capped; upper bounds on B, N (DAL3_MAX_*); DAL3_BCN_NO_LDS_SAMPLER; 0.1.4: dal3_crop_starts, dal3_crop_fill takes out_capacity; 0.1.3: dal3_bcn.flags (DAL3_BCN_*); dal3_tr_linear_bn_stats / dal3_tr_linear_bnbwd_sums; .1: dal3_tr_fc_*, dal3_tr_wgrad_final_many, dal3_parse_box_pred* */
 
 enum {
     DAL3_OK = 0,
@@ -461,6 +461,109 @@ size_t dal3_track_workspace_bytes(int64_t S, int64_t K, int64_t capacity);
 int dal3_track(const dal3_track_args* args, dal3_stream stream);
 size_t dal3_track_match_workspace_bytes(int64_t K);
 int dal3_track_match(const dal3_track_match_args* args, dal3_stream stream);
+
+/* ---- motion-state run: the regrouping of tools/trackData.py as a stable sort on the device, trackFeature of
+ * tools/motionState.py:30-67, the GT table of tools/trackGT.py:43-66 and the decision of SVC(kernel='linear').
+ * Every entry below is enqueued on `stream` and reads nothing back; problems are OR-ed into a device status word
+ * (DAL3_MOTION_BAD_KEY shares the word and the numbering of the DAL3_TRACK_* bits).
+ *
+ * dal3_group_by_key: a stable counting sort of E entries by key = keys[i] - (*key_base, optional) - key_bias into
+ * T groups: group g's entries are entry[group_start[g] : group_start[g + 1]], input positions in ascending order
+ * (= frame order, the order trackData.py appends in). With frame_offsets / out_count (both or neither; as dal3_track
+ * holds them) only slots frame_offsets[f] + [0, out_count[f]) are entries. group_start[T] = the number of entries
+ * grouped; n_groups (optional) = the largest key + 1. T is the caller's capacity (E always suffices for ids counted
+ * from 1). A key outside [0, T) sets DAL3_MOTION_BAD_KEY and the entry is left out. The result is a function of the
+ * input alone: the same bits for every max_workgroups (0 = no cap) and every run.
+ * E, T <= DAL3_MAX_ITEMS. workspace: dal3_group_workspace_bytes(E, T). */
+enum { DAL3_MOTION_BAD_KEY = 8 };                /* status bit, beside DAL3_TRACK_* */
+
+typedef struct dal3_group_args {
+    int64_t E, T, F;                     /* entries (slots), group capacity, frames (0 without frame_offsets) */
+    const int64_t* keys;                 /* (E) */
+    const int64_t* key_base;             /* optional (1), subtracted on the device (dal3_track's id_base) */
+    int64_t key_bias;                    /* subtracted too: 1 for tracking ids, which are counted from id_base + 1 */
+    const int64_t* frame_offsets;        /* optional (F+1) */
+    const int32_t* out_count;            /* optional (F) */
+    int64_t* group_start;                /* (T+1) */
+    int32_t* entry;                      /* (E) */
+    int64_t* n_groups;                   /* optional (1) */
+    int32_t* status;                     /* (1) OR-ed */
+    int64_t max_workgroups;              /* 0: no cap */
+    void* workspace;
+    size_t workspace_bytes;
+} dal3_group_args;
+
+/* dal3_track_features: per group of a dal3_group_by_key result, over per-entry arrays indexed by input position:
+ * n, type[first], match[last], sum(n_points), best = position inside the group of the first maximum of score
+ * (np.argmax), keep = !(match[last] < 0 || n < 7 || type[first] == 2 || sum(n_points) == 0), and
+ * feature = [ ||c[first] - c[last]||, ||var(c, axis=0)|| ] in float64: the mean is the sequential sum in entry order
+ * / n, the variance the sequential sum of squared deviations / n (NumPy's two passes; an empty group gives zeros). */
+typedef struct dal3_track_feature_args {
+    int64_t T, E;
+    const int64_t* group_start;          /* (T+1) */
+    const int32_t* entry;                /* (E) */
+    const int64_t* n_groups;             /* optional (1): dal3_group_by_key's; groups from there on are empty */
+    const double* center;                /* (E,3) global frame */
+    const int32_t* type;                 /* (E) */
+    const float* score;                  /* (E) */
+    const int32_t* n_points;             /* (E) */
+    const int32_t* match;                /* (E) GT object index or -1 */
+    int32_t* n;                          /* (T) */
+    int32_t* type0;                      /* (T) */
+    int32_t* match_last;                 /* (T) */
+    int64_t* points_sum;                 /* (T) */
+    int32_t* best;                       /* (T) */
+    uint8_t* keep;                       /* (T) */
+    double* feature;                     /* (T,2) */
+    int64_t max_workgroups;
+} dal3_track_feature_args;
+
+/* dal3_gt_table: entries are annotation rows: box (E,9) float64 = obj['box'] in its frame's vehicle frame, frame (E)
+ * the row's frame, pose (F,16) that frame's veh_to_global. Per entry box_global (E,7) = transform_box of
+ * box[[0,1,2,3,4,5,8]] and vel = ||box[6:8]||; per group (GT object) n, dist = ||c[first] - c[last]||, max_vel and
+ * is_static = dist < 1 && max_vel < 1. A frame index outside [0, F) sets DAL3_MOTION_BAD_KEY (that row becomes NaN). */
+typedef struct dal3_gt_table_args {
+    int64_t T, E, F;
+    const int64_t* group_start;          /* (T+1) */
+    const int32_t* entry;                /* (E) */
+    const double* box;                   /* (E,9) */
+    const int32_t* frame;                /* (E) */
+    const double* pose;                  /* (F,16) */
+    double* box_global;                  /* (E,7) */
+    double* vel;                         /* (E) */
+    int32_t* n;                          /* (T) */
+    double* dist;                        /* (T) */
+    double* max_vel;                     /* (T) */
+    uint8_t* is_static;                  /* (T) */
+    int32_t* status;                     /* (1) OR-ed */
+    int64_t max_workgroups;
+} dal3_gt_table_args;
+
+/* dal3_motion_classify: decision = feature[0] * w[0] + feature[1] * w[1] + b (float64, in that order), is_static =
+ * decision > 0 for every group; the kept groups are compacted in ascending group order into static_ids and
+ * dynamic_ids, counts = {statics, dynamics}. workspace: dal3_motion_classify_workspace_bytes(T). */
+typedef struct dal3_motion_classify_args {
+    int64_t T;
+    const double* feature;               /* (T,2) */
+    const uint8_t* keep;                 /* (T) */
+    double w[2];
+    double b;
+    double* decision;                    /* (T) */
+    uint8_t* is_static;                  /* (T) */
+    int32_t* static_ids;                 /* (T) */
+    int32_t* dynamic_ids;                /* (T) */
+    int64_t* counts;                     /* (2) */
+    int64_t max_workgroups;
+    void* workspace;
+    size_t workspace_bytes;
+} dal3_motion_classify_args;
+
+size_t dal3_group_workspace_bytes(int64_t E, int64_t T);
+int dal3_group_by_key(const dal3_group_args* args, dal3_stream stream);
+int dal3_track_features(const dal3_track_feature_args* args, dal3_stream stream);
+int dal3_gt_table(const dal3_gt_table_args* args, dal3_stream stream);
+size_t dal3_motion_classify_workspace_bytes(int64_t T);
+int dal3_motion_classify(const dal3_motion_classify_args* args, dal3_stream stream);
 
 /* ---- crop extraction from full sweeps: the per-detection loop of _create_pd_detection
  * (det3d/datasets/waymo/waymo_common.py:166-171, 193) for F frames at once. points (P_total,3) f32 vehicle-frame
