@@ -61,6 +61,10 @@ static InsSegW ins_seg_walk(Cursor& c) {
     w.enc_stream = c.take4((size_t)ENC_FRAGS * 256);
     w.dec_stream = c.take4((size_t)DEC_FRAGS * 256);
     w.lat_stream = c.take4((size_t)LAT_FRAGS * 256);
+    w.w5row = c.take((size_t)1024 * 128);
+    w.w5h = c.take4((size_t)32 * 4 * 2 * 256);
+    w.scr_pq = c.take(2 * 1024);
+    w.scr_flag = reinterpret_cast<const int32_t*>(c.take(64));
     return w;
 }
 
@@ -416,6 +420,10 @@ extern "C" int dal3_pack_weights(int head_kind, const dal3_layer* L, int n_layer
         TRY(pack_frag(L[6], PACK_FRAG_MT_MAJOR, 0, 512, w.lat_stream, LAT_W2, nullptr, s));
         HIP_TRY(launch_pack_weight(L[9], PACK_ROWMAJOR, 0, 128, 0, 0, mut(w.dw5), s));
         HIP_TRY(launch_pack_bias(L[9], mut(w.db5), s));
+        // the screened encoder's copies of conv5: fp32 rows, fp16 fragments, per-channel error-bound coefficients
+        HIP_TRY(launch_pack_weight(L[4], PACK_ROWMAJOR, 0, 128, 0, 0, mut(w.w5row), s));
+        HIP_TRY(launch_pack_weight_lp(L[4], DAL3_F16, 0, 0, 128, 32, 4, reinterpret_cast<uint16_t*>(mut(w.w5h)), s));
+        HIP_TRY(launch_pack_enc_screen(L[4], mut(w.scr_pq), reinterpret_cast<int32_t*>(mut(w.scr_flag)), s));
         return 0;
     }
     if (head_kind == DAL3_HEAD_DYNAMIC_BOX_EST) {

@@ -1,0 +1,320 @@
+// dal3_enc_screen.hip — the fp32 throughput encoder with conv5 SCREENED (DESIGN.md "Screened conv5").
+//
+// conv5 (128 -> 1024) is 89 % of the encoder's multiply-adds and the network keeps only the channel maxima of its
+// output. Two launches replace ins_seg_encode_kernel<T> for large jobs; both run conv1..conv4 in fp32 exactly as the
+// dense kernel does and then evaluate conv5 on the fp16 MFMA (16 x the fp32 rate) with a PROVED error bound
+//   |s16(c,p) - chain32(c,p)| <= E_c = X * P_c + Q_c        (X >= ||x_p||_2 for every point of the wave),
+// chain32 being the dense kernel's value (a k-ordered fmaf chain from a zero accumulator):
+//   pass A  g[c] <- max(g[c], relu(fl(max_p s16 - E_c + b_c)))        a LOWER bound of the final value, in g itself
+//   pass B  (c,p) is a candidate iff s16(c,p) > g[c] - b_c - E_c (rounded down); every candidate is recomputed with
+//           the exact fp32 chain on the VALU (same operands, same order, same roundings as the f32 MFMA) and
+//           relu(fl(chain + b_c)) goes to g with the same integer atomicMax as the dense kernel's.
+// A pair that is not a candidate has fl(chain + b_c) <= g[c] already, so it cannot change g: the result has the dense
+// kernel's bits. Whatever does not fit the proof or the lists takes the dense conv_max_layer, per wave: activations
+// beyond fp16's range, conv5 weights beyond it (blob flag), more than SCR_CAP candidates in a 32-point tile.
+#include "dal3_device.h"
+#include "dal3_kernels.h"
+#include "dal3_lp.h"
+
+#ifndef SCR_CAP
+#define SCR_CAP 1024                    // candidate entries per wave and 32-point tile (bench input: 83 on average, 321 at most in the CPU model)
+#endif
+#define SCR_XLD 132                     // floats per point row of the LDS copy of x4: 128 + 4, rows start 4 banks apart
+#define SCR_XMAX_BITS 0x476A6000        // 60000.0f: activations up to here round to a FINITE fp16
+
+// Diagnostic build only (-DDAL3_SCREEN_COUNT): [0] waves, [1] waves dense for range, [2] waves dense for list overflow,
+// [3] candidates, [4] recompute rounds. No counter executes in the shipped library.
+#ifdef DAL3_SCREEN_COUNT
+__device__ unsigned long long g_scr_count[8];
+extern "C" int dal3_debug_screen_counts(unsigned long long* out, int reset) {
+    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_scr_count), sizeof(g_scr_count));
+    if (e == hipSuccess && reset) {
+        unsigned long long z[8] = {};
+        e = hipMemcpyToSymbol(HIP_SYMBOL(g_scr_count), z, sizeof(z));
+    }
+    return (int)e;
+}
+#define SCR_COUNT(k, v)                                           \
+    do {                                                          \
+        if (lane == 0) atomicAdd(&g_scr_count[k], (unsigned long long)(v)); \
+    } while (0)
+#else
+#define SCR_COUNT(k, v)
+#endif
+
+template <int PASS, int T>
+__global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_encode_screen_kernel(InsSegW w, BCN pts, int c_in, int n_pts,
+                                                                                  int tiles_per_item, float* __restrict__ g) {
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int h = lane >> 5;
+    const int64_t b = blockIdx.x / tiles_per_item;
+    const int n0 = ((blockIdx.x % tiles_per_item) * DAL3_WG_WAVES + wave) * (32 * T);
+    __shared__ float s_b5[1024];                       // conv5's folded bias
+    __shared__ int s_max[1024];                        // the workgroup's maxima (bit patterns >= 0), as in the dense kernel
+    __shared__ f32x2 s_pq[1024];                       // (P_c, Q_c)
+    __shared__ float s_g[PASS == 1 ? 1024 : 1];        // pass B: the crop's row of g = the thresholds
+    __shared__ __attribute__((aligned(16))) float s_x[PASS == 1 ? DAL3_WG_WAVES * 32 * SCR_XLD : 4];
+    __shared__ uint32_t s_list[PASS == 1 ? DAL3_WG_WAVES * T * SCR_CAP : 1];
+    int* gi = reinterpret_cast<int*>(g + b * 1024);
+    // static LDS: the four tables, the waves' x4 copies and candidate lists. One workgroup per CU by LDS alone (the
+    // kernel holds one wave per SIMD by registers anyway). Too large: lower SCR_CAP, DAL3_WG_WAVES or DAL3_ENC_T.
+    static_assert(20 * 1024 + DAL3_WG_WAVES * (32 * SCR_XLD * 4 + T * SCR_CAP * 4) <= 160 * 1024,
+                  "pass B's LDS exceeds a CU's 160 KiB: lower SCR_CAP, DAL3_WG_WAVES or DAL3_ENC_T");
+    // conv5 not finite in fp16 (the blob's flag): pass A was the dense encoder, nothing is left to do. (Uniform: one word.)
+    if (PASS == 1 && *w.scr_flag != 0) return;
+    // No early exit for a crop flagged by nonfinite_rows_kernel: its quiet-NaN pattern lies above every value either pass
+    // sends to atomicMax, exactly as for the dense kernel. A non-finite threshold (that pattern, or +Inf / NaN written by
+    // a dense wave of a crop whose activations overflow fp32) is final for its channel: pass B takes no candidate there.
+    for (int i = threadIdx.x; i < 1024; i += 64 * DAL3_WG_WAVES) {
+        s_b5[i] = w.b5[i];
+        s_max[i] = 0;
+        s_pq[i] = reinterpret_cast<const f32x2*>(w.scr_pq)[i];
+        // (other workgroups of the crop may be raising g already: any value read here is <= the final one, which is all
+        // the threshold needs)
+        if (PASS == 1) s_g[i] = __int_as_float(__hip_atomic_load(gi + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    }
+    __syncthreads();
+    if (n0 < n_pts) {                                  // (no early return: every wave meets the barrier below)
+        WRing<DAL3_PF> ring;
+        ring.init(w.enc_stream, lane);                 // conv2 | conv3 | conv4 | conv5
+        f32x16 bias = tile_from_channels(w.b2, h);
+        float in[T][2];
+        load_points<2, T>(pts, b, n0, n_pts, c_in, in, lane);
+        f32x16 x1[T][2], x2[T][2], x3[T][2], x4[T][4];
+        first_layer<2, 2, T>(w.w1, w.b1, in, x1, lane);
+        mlp_layer_ring<2, 2, T>(ring, w.b2, w.b3, bias, x1, x2, lane);
+        mlp_layer_ring<2, 2, T>(ring, w.b3, w.b4, bias, x2, x3, lane);
+        mlp_layer_ring<2, 4, T>(ring, w.b4, w.b4, bias, x3, x4, lane);
+        SCR_COUNT(0, 1);
+
+        // fp16 holds every activation of the wave? (x4 >= +0 after the ReLU: the integer order of the bit patterns is
+        // the order of the values, and a NaN / Inf pattern lies above the limit.) The decision depends on the wave's
+        // own points only, so both passes take it alike.
+        int xm = 0;
+#pragma unroll
+        for (int j = 0; j < T; ++j) {
+#pragma unroll
+            for (int kt = 0; kt < 4; ++kt) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int v = __float_as_int(x4[j][kt][r]);
+                    xm = v > xm ? v : xm;
+                }
+            }
+        }
+        const bool dense = *w.scr_flag != 0 || __builtin_amdgcn_ballot_w64(xm > SCR_XMAX_BITS) != 0;
+        if (dense) {
+            // pass A writes the exact values (also valid lower bounds); pass B has nothing to add for this wave
+            SCR_COUNT(1, 1);
+            if (PASS == 0) conv_max_layer<4, T>(ring, s_b5, x4, reinterpret_cast<float*>(s_max), 32, lane);
+        } else {
+            // X >= ||x_p||_2 for every point of the wave (lane half h holds 64 of a point's 128 channels)
+            float x2max = 0.0f;
+#pragma unroll
+            for (int j = 0; j < T; ++j) {
+                float ss = 0.0f;
+#pragma unroll
+                for (int kt = 0; kt < 4; ++kt) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) ss = fmaf(x4[j][kt][r], x4[j][kt][r], ss);
+                }
+                ss += __shfl_xor(ss, 32);
+                x2max = __builtin_fmaxf(x2max, ss);
+            }
+#pragma unroll
+            for (int d = 16; d >= 1; d >>= 1) x2max = __builtin_fmaxf(x2max, __shfl_xor(x2max, d));
+            const float X = sqrtf(x2max) * (1.0f + 0x1p-16f);      // (margin: 128 roundings of the sum, the root, the products below)
+
+            ActTile<FP16> xh[T][4];
+#pragma unroll
+            for (int j = 0; j < T; ++j) {
+#pragma unroll
+                for (int kt = 0; kt < 4; ++kt) xh[j][kt] = pack_relu<FP16>(x4[j][kt]);
+            }
+
+            uint32_t* const list = s_list + (PASS == 1 ? wave * T * SCR_CAP : 0);
+            uint32_t cnt[T];
+#pragma unroll
+            for (int j = 0; j < T; ++j) cnt[j] = 0;
+
+            // Per 32-channel block the wave holds ONE constant per lane (= channel): pass A the error bound E_c, pass B the
+            // threshold on the fp16 score. chain32 <= s16 + E; s16 <= thr <= G - b - E  ==>  chain32 + b <= G  ==>
+            // fl(chain32 + b) <= G: such a pair cannot raise g. (E, thr: every rounding is covered by the 2^-20 / 2^-22 terms.)
+            auto block_const = [&](int mt) -> float {
+                const int c = 32 * mt + (lane & 31);
+                const f32x2 pq = s_pq[c];
+                float E = fmaf(X, pq[0], pq[1]);
+                E = fmaf(E, 0x1p-20f, E);
+                if (PASS == 0) return E;
+                const float G = s_g[c], bb = s_b5[c];
+                if (bits_nonfinite(G)) return 3.0e38f;     // above every finite score: no candidate (decided on the bit pattern)
+                return (G - bb) - fmaf(__builtin_fabsf(G) + __builtin_fabsf(bb), 0x1p-22f, E);
+            };
+            // The epilogue of a block is cut into 8 slices (registers 2i, 2i+1 of every tile) that ride behind the MFMAs
+            // of the NEXT block's fragment i, like MaxEpilogueT's steps: pass A a running max, pass B one bit per
+            // (tile, register) whose score is above the threshold. No branch, no ballot inside the MFMA stream.
+            static_assert(16 * T <= 32, "one hit bit per (tile, register) in a 32-bit word");
+            float m = 0.0f;
+            uint32_t hb = 0;
+            auto ep_slice = [&](const f32x16 (&acc)[T], int i, float k) {
+#pragma unroll
+                for (int rr = 0; rr < 2; ++rr) {
+#pragma unroll
+                    for (int j = 0; j < T; ++j) {
+                        const int r = 2 * i + rr;
+                        if (PASS == 0)
+                            m = (r == 0 && j == 0) ? acc[0][0] : __builtin_fmaxf(m, acc[j][r]);
+                        else
+                            hb |= acc[j][r] > k ? (1u << (16 * j + r)) : 0u;
+                    }
+                }
+            };
+            auto ep_finish = [&](int mt, float k) {
+                const int c = 32 * mt + (lane & 31);
+                if (PASS == 0) {
+                    m = __builtin_fmaxf(m, __shfl_xor(m, 32));
+                    // y <= max_p chain32 (the subtraction's own rounding is inside the 2^-22 term); x -> fl(x + b) is monotone
+                    const float y = m - fmaf(__builtin_fabsf(m), 0x1p-22f, k);
+                    int bits = __float_as_int(y + s_b5[c]);
+                    bits = bits > 0 ? bits : 0;
+                    if (lane < 32 && bits > 0) atomicMax(&s_max[c], bits);
+                } else {
+                    uint32_t bits = hb;                // the block's hits of this lane: one (channel, point) pair per bit
+                    hb = 0;
+                    while (__builtin_amdgcn_ballot_w64(bits != 0)) {
+                        const bool act = bits != 0;
+                        const int idx = act ? __builtin_ctz(bits) : 0;
+                        const int r = idx & 15;
+                        const uint32_t e = ((uint32_t)c << 8) | (uint32_t)((r & 3) + 8 * (r >> 2) + 4 * h);   // tile_chan(r, h)
+#pragma unroll
+                        for (int j = 0; j < T; ++j) {
+                            const bool mine = act && (idx >> 4) == j;
+                            const unsigned long long mask = __builtin_amdgcn_ballot_w64(mine);
+                            if (mask) {
+                                const uint32_t pos = cnt[j] + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+                                if (mine && pos < SCR_CAP) list[j * SCR_CAP + pos] = e;
+                                cnt[j] += (uint32_t)__builtin_popcountll(mask);
+                            }
+                        }
+                        bits &= bits - 1;
+                    }
+                }
+            };
+
+            WRing<8> r16;
+            r16.init(w.w5h, lane);                     // [out-tile][kt][s] fragments of 1 KiB; a block's 8 are fetched a block ahead
+            // transposed tile, as conv_max_layer: points on the registers, channels on the lanes
+            auto mm = [&](f32x16 (&acc)[T], auto side) {
+#pragma unroll
+                for (int j = 0; j < T; ++j) acc[j] = f32x16{};
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const f16x8_t a = __builtin_bit_cast(f16x8_t, r16.slot[i]);
+                    r16.slot[i] = r16.fetch();
+#pragma unroll
+                    for (int j = 0; j < T; ++j) acc[j] = FP16::mfma(xh[j][i >> 1].k[i & 1], a, acc[j]);
+                    DAL3_SCHED_FENCE();
+                    side(i);
+                    DAL3_SCHED_FENCE();
+                }
+            };
+            f32x16 accA[T], accB[T];
+            float kA = block_const(0), kB;
+            mm(accA, NoSide());                                                    // block 0
+            int mt = 1;
+            for (; mt + 1 < 32; mt += 2) {             // (two whole blocks per trip and nothing else: see conv_max_layer)
+                kB = block_const(mt);
+                mm(accB, [&](int i) { ep_slice(accA, i, kA); });
+                ep_finish(mt - 1, kA);
+                kA = block_const(mt + 1);
+                mm(accA, [&](int i) { ep_slice(accB, i, kB); });
+                ep_finish(mt, kB);
+            }
+            kB = block_const(mt);                                                  // mt == 31
+            mm(accB, [&](int i) { ep_slice(accA, i, kA); });
+            ep_finish(mt - 1, kA);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) ep_slice(accB, i, kB);                     // last block: nothing left to hide under
+            ep_finish(mt, kB);
+
+            if (PASS == 1) {
+                bool overflow = false;
+#pragma unroll
+                for (int j = 0; j < T; ++j) {
+                    overflow |= cnt[j] > SCR_CAP;
+                    SCR_COUNT(3, cnt[j]);
+                }
+                if (overflow) {                        // the lists do not hold the tile's candidates: the dense layer, exact
+                    SCR_COUNT(2, 1);
+                    WRing<DAL3_PF> r32;
+                    r32.init(w.enc_stream + ENC_W5 * 64, lane);
+                    conv_max_layer<4, T>(r32, s_b5, x4, reinterpret_cast<float*>(s_max), 32, lane);
+                } else {
+                    float* const xw = s_x + wave * 32 * SCR_XLD;
+#pragma unroll
+                    for (int j = 0; j < T; ++j) {
+                        // this tile's x4 in fp32, point-major, channels in natural order: registers 4q..4q+3 of k-tile
+                        // kt are channels 32kt + 8q + 4h .. +3 of point lane&31
+                        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                        for (int kt = 0; kt < 4; ++kt) {
+#pragma unroll
+                            for (int q = 0; q < 4; ++q) {
+                                f32x4 v;
+                                v[0] = x4[j][kt][4 * q + 0];
+                                v[1] = x4[j][kt][4 * q + 1];
+                                v[2] = x4[j][kt][4 * q + 2];
+                                v[3] = x4[j][kt][4 * q + 3];
+                                *reinterpret_cast<f32x4*>(xw + (lane & 31) * SCR_XLD + 32 * kt + 8 * q + 4 * h) = v;
+                            }
+                        }
+                        __builtin_amdgcn_wave_barrier();
+                        // one candidate per lane: the dense kernel's chain. v_mfma_f32_32x32x2_f32 from a zero
+                        // accumulator is, per output, fma(a1, b1, fma(a0, b0, acc)) over its k-steps in issue order,
+                        // k = 0 from lane half 0: channels 8i, 8i+4, 8i+1, 8i+5, ... for i = 4 kt + q.
+                        for (uint32_t base = 0; base < cnt[j]; base += 64) {
+                            SCR_COUNT(4, 1);
+                            const uint32_t idx = base + lane;
+                            const bool live = idx < cnt[j];
+                            const uint32_t e = list[j * SCR_CAP + (live ? idx : 0u)];
+                            const int c = (int)(e >> 8), p = (int)(e & 31u);
+                            const f32x4* wr = reinterpret_cast<const f32x4*>(w.w5row + c * 128);
+                            const f32x4* xr = reinterpret_cast<const f32x4*>(xw + p * SCR_XLD);
+                            float a = 0.0f;
+#pragma unroll
+                            for (int i = 0; i < 16; ++i) {
+                                const f32x4 w0 = wr[2 * i], w1 = wr[2 * i + 1];
+                                const f32x4 x0 = xr[2 * i], x1 = xr[2 * i + 1];
+#pragma unroll
+                                for (int q = 0; q < 4; ++q) {
+                                    a = fmaf(x0[q], w0[q], a);
+                                    a = fmaf(x1[q], w1[q], a);
+                                }
+                            }
+                            int bits = __float_as_int(a + s_b5[c]);
+                            bits = bits > 0 ? bits : 0;
+                            if (live && bits > 0) atomicMax(&s_max[c], bits);
+                        }
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < 1024; c += 64 * DAL3_WG_WAVES) {
+        const int v = s_max[c];
+        if (v > 0) atomicMax(gi + c, v);
+    }
+}
+
+hipError_t launch_ins_seg_encode_screen(const InsSegW& w, BCN pts, int c_in, int B, int N, float* g, hipStream_t s) {
+    constexpr int T = DAL3_ENC_T;
+    const int tpi = (N + 32 * DAL3_WG_WAVES * T - 1) / (32 * DAL3_WG_WAVES * T);
+    const dim3 grid((unsigned)((int64_t)B * tpi)), block(64 * DAL3_WG_WAVES);
+    hipLaunchKernelGGL((ins_seg_encode_screen_kernel<0, T>), grid, block, 0, s, w, pts, c_in, N, tpi, g);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((ins_seg_encode_screen_kernel<1, T>), grid, block, 0, s, w, pts, c_in, N, tpi, g);
+    return hipGetLastError();
+}

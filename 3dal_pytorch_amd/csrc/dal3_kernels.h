@@ -18,6 +18,12 @@
 #define DAL3_HEAD_T 1
 #endif
 
+// the fp32 throughput encoder screens conv5 on the fp16 MFMA and recomputes the candidates exactly (dal3_enc_screen.hip);
+// 0: the dense kernel for every job (A/B builds: make OUT=... EXTRA=-DDAL3_ENC_SCREEN=0)
+#ifndef DAL3_ENC_SCREEN
+#define DAL3_ENC_SCREEN 1
+#endif
+
 // waves per workgroup of the shared-MLP kernels (waves never cooperate, so this only sets the
 // granularity at which the dispatcher refills a CU)
 #ifndef DAL3_WG_WAVES
@@ -58,7 +64,13 @@ struct InsSegW {
     const f32x4* enc_stream;
     const f32x4* dec_stream;
     const f32x4* lat_stream;  // dconv1a (16 out-tiles x 2 k-tiles) | dconv2 (8 x 16), OUT-TILE major: the latency kernels
-};                            // (dal3_latency.hip) give each wave whole output tiles; dec_stream interleaves them K-major
+                              // (dal3_latency.hip) give each wave whole output tiles; dec_stream interleaves them K-major
+    // the screened encoder (dal3_enc_screen.hip, DESIGN.md "Screened conv5"): conv5 three more times
+    const float* w5row;       // row-major (1024,128) fp32, folded: one candidate's weights in natural channel order
+    const f32x4* w5h;         // fp16 MFMA fragments [32 out-tiles][4 kt][2 s] of 1 KiB, the 16-bit family's layout
+    const float* scr_pq;      // (1024,2): eps(c) = X * P_c + Q_c bounds |fp16 score - fp32 chain| for ||x||_2 <= X
+    const int32_t* scr_flag;  // nonzero: a folded conv5 weight is not finite in fp16 -> the dense kernel runs
+};
 enum {                        // stream geometry in fragments of 256 floats
     ENC_W2 = 0, ENC_W3 = 16, ENC_W4 = 32, ENC_W5 = 64, ENC_FRAGS = 64 + 512,
     DEC_W2 = 0, DEC_MIX = 16, DEC_MIX_FRAGS = 8 + 16 * 40, DEC_W3 = 16 + 648, DEC_W4 = 16 + 648 + 128,
@@ -180,6 +192,8 @@ void point_head_dims(int head_kind, int* c_in, int* ks, int c[4], int* n_fc, int
 
 // ---- launchers (all asynchronous on s)
 hipError_t launch_ins_seg_encode(const InsSegW& w, BCN pts, int c_in, int B, int N, float* g, hipStream_t s);
+hipError_t launch_ins_seg_encode_screen(const InsSegW& w, BCN pts, int c_in, int B, int N, float* g, hipStream_t s);
+hipError_t launch_pack_enc_screen(const dal3_layer& L, float* pq, int32_t* flag, hipStream_t s);
 hipError_t launch_ins_seg_decode(const InsSegW& w, BCN pts, int c_in, int B, int N, const float* gbias,
                                  float* logits, uint8_t* mask, hipStream_t s);
 // distinct (B) i32 or NULL: only the first distinct[b] points of item b are distinct (the rest duplicate them)

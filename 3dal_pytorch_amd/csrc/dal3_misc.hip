@@ -137,6 +137,31 @@ hipError_t launch_pack_weight(const dal3_layer& L, int mode, int col_off, int n_
     return hipGetLastError();
 }
 
+// Error-bound coefficients of the screened encoder (DESIGN.md "Screened conv5"): for a point with ||x||_2 <= X,
+//   |fp16-MFMA score(c) - fp32 chain(c)| <= X * P_c + Q_c,
+//   P_c = kappa ||w_c||_2 + 2^-24 sqrt(128),  Q_c = 2^-24 ||w_c||_1 + 2^-40,  kappa = 1.02 * 2^-10 + 128 * 2^-23,
+// evaluated in double and rounded to fp32 with a relative margin of 1e-6 (>> 2^-24). flag: a weight that fp16 cannot hold.
+__global__ void pack_enc_screen_kernel(dal3_layer L, float* __restrict__ pq, int32_t* __restrict__ flag) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= 1024) return;
+    double s2 = 0.0, s1 = 0.0;
+    bool bad = false;
+    for (int k = 0; k < 128; ++k) {
+        const float v = folded_w(L, c, k, 0, 128);
+        bad |= !(fabsf(v) < 65504.0f);
+        s2 += (double)v * (double)v;
+        s1 += fabs((double)v);
+    }
+    const double kappa = 1.02 * 0x1p-10 + 128.0 * 0x1p-23;
+    pq[2 * c] = (float)((kappa * sqrt(s2) + 0x1p-24 * 11.3137085) * (1.0 + 1e-6));
+    pq[2 * c + 1] = (float)((0x1p-24 * s1 + 0x1p-40) * (1.0 + 1e-6));
+    if (bad) atomicOr(flag, 1);
+}
+hipError_t launch_pack_enc_screen(const dal3_layer& L, float* pq, int32_t* flag, hipStream_t s) {
+    hipLaunchKernelGGL(pack_enc_screen_kernel, dim3(4), dim3(256), 0, s, L, pq, flag);
+    return hipGetLastError();
+}
+
 hipError_t launch_pack_bias(const dal3_layer& L, float* out, hipStream_t s) {
     const int padded = (L.c_out + 31) / 32 * 32;
     hipLaunchKernelGGL(pack_bias_kernel, dim3((padded + 255) / 256), dim3(256), 0, s, L, out, padded);

@@ -480,6 +480,8 @@ hipError_t launch_ins_seg_encode(const InsSegW& w, BCN pts, int c_in, int B, int
         hipLaunchKernelGGL(ins_seg_encode_kernel<1>, dim3((unsigned)((int64_t)B * tpi1)), dim3(64 * DAL3_WG_WAVES), 0, s, w, pts, c_in, N, tpi1, g);
         return hipGetLastError();
     }
+    // large jobs: conv5 screened in fp16, candidates recomputed exactly (dal3_enc_screen.hip); the same bits
+    if (DAL3_ENC_SCREEN) return launch_ins_seg_encode_screen(w, pts, c_in, B, N, g, s);
     const int tpi = tiles_per_item(N, T);
     hipLaunchKernelGGL(ins_seg_encode_kernel<T>, dim3((unsigned)((int64_t)B * tpi)), dim3(64 * DAL3_WG_WAVES), 0, s, w, pts, c_in, N, tpi, g);
     return hipGetLastError();

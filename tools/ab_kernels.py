@@ -69,7 +69,10 @@ for name, lib in libs:
     ws = torch.empty(lib.dal3_point_head_workspace_bytes(B), dtype=torch.uint8, device=dev)
     bp = torch.empty((B, 39), device=dev)
     d = dict(w_seg=w_seg, w_box=w_box, g=g, gb=gb, logits=logits, mask=mask, ws=ws, bp=bp)
-    d["enc"] = lambda lib=lib, d=d: lib.dal3_ins_seg_encode(hip.ptr(d["w_seg"]), DT, 3, x, B, N, hip.ptr(d["g"]), st)
+    # g is zeroed before EVERY encode, as a step does (nonfinite_rows_kernel): the screened fp32 encoder's second launch
+    # reads its thresholds from g, and on a g that already holds the final maxima it would find fewer candidates than it
+    # ever does in a step. (The fill is a 16.8-MB memset, ~5 us, the same for every build.)
+    d["enc"] = lambda lib=lib, d=d: (d["g"].zero_(), lib.dal3_ins_seg_encode(hip.ptr(d["w_seg"]), DT, 3, x, B, N, hip.ptr(d["g"]), st))[1]
     d["dec"] = lambda lib=lib, d=d: lib.dal3_ins_seg_decode(hip.ptr(d["w_seg"]), DT, 3, x, B, N, hip.ptr(d["gb"]),
                                                             hip.ptr(d["logits"]), hip.ptr(d["mask"]), st)
     d["head"] = lambda lib=lib, d=d: lib.dal3_point_head_forward(hip.HEAD_STATIC_BOX_EST, hip.ptr(d["w_box"]), DT, xo, B, 512,
