@@ -142,6 +142,28 @@ class MotionClassifyArgs(C.Structure):
 MOTION_BAD_KEY = 8
 
 
+class ScoreAcc(C.Structure):
+    """dal3_score_acc (72 bytes)"""
+    _fields_ = [("sum_iou_bev", C.c_double), ("sum_iou_3d", C.c_double), ("n_iou_3d_pass", C.c_uint64),
+                ("n_type", C.c_uint64 * 4), ("n_scored", C.c_uint64), ("n_samples", C.c_uint64)]
+
+
+class ScoreArgs(C.Structure):
+    """dal3_score_args"""
+    _fields_ = [("S", C.c_int64), ("R", C.c_int64), ("F", C.c_int64), ("boxes", vp), ("box_row", vp), ("frame", vp),
+                ("pose_inv", vp), ("gt", vp), ("has_gt", vp), ("type", vp), ("gt_f64", C.c_int32),
+                ("max_workgroups", C.c_int32), ("thr", C.c_float * 3), ("thr_other", C.c_float), ("iou_bev", vp),
+                ("iou_3d", vp), ("pred_box", vp), ("label_box", vp), ("acc", vp), ("workspace", vp),
+                ("workspace_bytes", C.c_size_t)]
+
+
+class BestGtArgs(C.Structure):
+    """dal3_best_gt_args"""
+    _fields_ = [("Q", C.c_int64), ("F", C.c_int64), ("G", C.c_int64), ("queries", vp), ("query_frame", vp),
+                ("gt_offsets", vp), ("gt_boxes", vp), ("boxes_f64", C.c_int32), ("max_workgroups", C.c_int32),
+                ("best_iou_3d", vp), ("best_iou_bev", vp), ("best_index", vp)]
+
+
 # every symbol include/dal3.h declares: (restype, argtypes)
 _i, _i64, _u64, _sz = C.c_int, C.c_int64, C.c_uint64, C.c_size_t
 SIGNATURES = {
@@ -184,6 +206,9 @@ SIGNATURES = {
     "dal3_gt_table": (_i, [C.POINTER(GtTableArgs), vp]),
     "dal3_motion_classify_workspace_bytes": (_sz, [_i64]),
     "dal3_motion_classify": (_i, [C.POINTER(MotionClassifyArgs), vp]),
+    "dal3_score_workspace_bytes": (_sz, [_i64]),
+    "dal3_score_tracks": (_i, [C.POINTER(ScoreArgs), vp]),
+    "dal3_best_gt_iou": (_i, [C.POINTER(BestGtArgs), vp]),
     "dal3_crop_workspace_bytes": (_sz, [_i64, _i64]),
     "dal3_crop_count": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, _sz, vp]),
     "dal3_crop_fill": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, vp, vp, vp, _i64, vp, _sz, vp]),

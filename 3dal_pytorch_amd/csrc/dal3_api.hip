@@ -1064,6 +1064,48 @@ extern "C" int dal3_motion_classify(const dal3_motion_classify_args* args, dal3_
     return 0;
 }
 
+extern "C" size_t dal3_score_workspace_bytes(int64_t S) {
+    if (S < 0 || S > DAL3_MAX_ITEMS) return 0;
+    return score_workspace_bytes(S);
+}
+
+extern "C" int dal3_score_tracks(const dal3_score_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "score_tracks: null args");
+    const dal3_score_args& a = *args;
+    if (a.S < 0 || a.R < 0 || a.F < 0 || a.S > DAL3_MAX_ITEMS || a.R > DAL3_MAX_ITEMS || a.F > DAL3_MAX_ITEMS)
+        return fail(DAL3_EINVAL, "score_tracks: bad S / R / F (0 <= S, R, F <= DAL3_MAX_ITEMS)");
+    if ((a.gt_f64 != 0 && a.gt_f64 != 1) || a.max_workgroups < 0)
+        return fail(DAL3_EINVAL, "score_tracks: bad argument (gt_f64 0 or 1, max_workgroups >= 0)");
+    if (!a.acc && !a.iou_bev && !a.iou_3d && !a.pred_box && !a.label_box)
+        return fail(DAL3_EINVAL, "score_tracks: no accumulator and no output");
+    if (a.S == 0) return 0;                                 // nothing to score: acc stays as it is
+    if (!a.box_row || !a.frame || !a.has_gt || !a.type) return fail(DAL3_EINVAL, "score_tracks: null per-sample table");
+    if ((a.R > 0 && !a.boxes) || (a.F > 0 && !a.pose_inv) || !a.gt) return fail(DAL3_EINVAL, "score_tracks: null boxes / pose_inv / gt");
+    if (a.acc) {
+        if (!a.workspace) return fail(DAL3_EINVAL, "score_tracks: the accumulator needs a workspace");
+        if (a.workspace_bytes < score_workspace_bytes(a.S))
+            return fail(DAL3_EWORKSPACE, "score_tracks: workspace too small (dal3_score_workspace_bytes)");
+        if (reinterpret_cast<uintptr_t>(a.workspace) & 7) return fail(DAL3_EINVAL, "score_tracks: workspace must be 8-byte aligned");
+    }
+    HIP_TRY(launch_score_tracks(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+extern "C" int dal3_best_gt_iou(const dal3_best_gt_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "best_gt_iou: null args");
+    const dal3_best_gt_args& a = *args;
+    if (a.Q < 0 || a.F < 0 || a.G < 0 || a.Q > DAL3_MAX_ITEMS || a.F > DAL3_MAX_ITEMS)
+        return fail(DAL3_EINVAL, "best_gt_iou: bad Q / F / G (0 <= Q, F <= DAL3_MAX_ITEMS, G >= 0)");
+    if ((a.boxes_f64 != 0 && a.boxes_f64 != 1) || a.max_workgroups < 0)
+        return fail(DAL3_EINVAL, "best_gt_iou: bad argument (boxes_f64 0 or 1, max_workgroups >= 0)");
+    if (a.Q == 0) return 0;
+    if (!a.best_iou_3d) return fail(DAL3_EINVAL, "best_gt_iou: no output (best_iou_3d is NULL)");
+    if (!a.queries || !a.query_frame || (a.F > 0 && !a.gt_offsets) || (a.G > 0 && !a.gt_boxes))
+        return fail(DAL3_EINVAL, "best_gt_iou: null queries / query_frame / gt_offsets / gt_boxes");
+    HIP_TRY(launch_best_gt_iou(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 extern "C" size_t dal3_crop_workspace_bytes(int64_t K_total, int64_t max_points_per_frame) {
     if (K_total <= 0 || max_points_per_frame < 0) return 0;
     return crop_workspace_bytes(K_total, max_points_per_frame);

@@ -268,6 +268,10 @@ hipError_t launch_group_by_key(const dal3_group_args* a, hipStream_t s);
 hipError_t launch_track_features(const dal3_track_feature_args* a, hipStream_t s);
 hipError_t launch_gt_table(const dal3_gt_table_args* a, hipStream_t s);
 hipError_t launch_motion_classify(const dal3_motion_classify_args* a, hipStream_t s);
+// baseline runs (dal3_score.hip): one slab entry per 256-sample chunk; the second stage is a launch of its own
+size_t score_workspace_bytes(int64_t S);
+hipError_t launch_score_tracks(const dal3_score_args* a, hipStream_t s);
+hipError_t launch_best_gt_iou(const dal3_best_gt_args* a, hipStream_t s);
 hipError_t launch_points_in_boxes(const void* points, int points_f64, int64_t P, int64_t stride, const double* planes,
                                   int K, int f32_math, uint8_t* inside, hipStream_t s);
 hipError_t launch_writeback(const double* final_boxes, const int32_t* final_idx, const double* pose_best,

@@ -22,10 +22,19 @@ class WritebackPlan:
         plan = WritebackPlan(tracks, veh_to_global, has_gt, dets, static=True)
         new_dets, match = plan.apply(final_bboxes)       # any number of times
 
-    The detection array on the device is restored from a pristine copy before every apply (the kernel overwrites it)."""
+    The detection array on the device is restored from a pristine copy before every apply (the kernel overwrites it).
 
-    def __init__(self, tracks, veh_to_global, has_gt, dets, static, device="cuda"):
+    pose_best (static only; default None = the best-score frame's veh_to_global, as postprocessing has it): an
+    (n_tracks, 16) array of the flat matrix that carries track i's final box to the global frame. baseline.run_static
+    passes identity rows with final boxes that already are global (tools/static_init.py:220-228). track_of_pair (P)
+    names each pair's track, for callers that read `owner`."""
+
+    def __init__(self, tracks, veh_to_global, has_gt, dets, static, device="cuda", pose_best=None):
         self.static = bool(static)
+        if pose_best is not None:
+            if not static:
+                raise ValueError("pose_best belongs to the static write-back")
+            pose_best = np.asarray(pose_best, np.float64).reshape(len(tracks), 16)
         self.tokens = list(dets.keys())
         self.start, off = {}, 0
         for t in self.tokens:
@@ -34,13 +43,14 @@ class WritebackPlan:
         self.lens = {t: len(dets[t]) for t in self.tokens}
         det_all = np.concatenate([np.asarray(dets[t], np.float32).reshape(-1, 7) for t in self.tokens], 0)
         inv = {t: np.linalg.inv(np.reshape(veh_to_global[t], [4, 4])).reshape(16) for t in self.tokens}
-        f_idx, p_best, p_inv, tbox, d_start, d_cnt, act = [], [], [], [], [], [], []
+        f_idx, p_best, p_inv, tbox, d_start, d_cnt, act, owner_track = [], [], [], [], [], [], [], []
         index = 0
         for i, tr in enumerate(tracks):
             best = tr["token"][int(np.argmax(np.stack(tr["score"])))]
             for j, t in enumerate(tr["token"]):
                 f_idx.append(i if static else index + j)
-                p_best.append(np.asarray(veh_to_global[best], np.float64).reshape(16))
+                p_best.append(np.asarray(veh_to_global[best], np.float64).reshape(16) if pose_best is None else pose_best[i])
+                owner_track.append(i)
                 p_inv.append(inv[t])
                 tbox.append(np.asarray(tr["bbox"][j], np.float64).reshape(7))
                 d_start.append(self.start[t])
@@ -50,6 +60,7 @@ class WritebackPlan:
         self.P = len(f_idx)
         self.n_final = len(tracks) if static else index
         self.act = np.asarray(act, np.uint8)
+        self.track_of_pair = np.asarray(owner_track, np.int64)
         self.dev = dev = torch.device(device)
 
         def up(a, dt):

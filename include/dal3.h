@@ -565,6 +565,91 @@ int dal3_gt_table(const dal3_gt_table_args* args, dal3_stream stream);
 size_t dal3_motion_classify_workspace_bytes(int64_t T);
 int dal3_motion_classify(const dal3_motion_classify_args* args, dal3_stream stream);
 
+/* ---- baseline runs: the tracker's own boxes scored against ground truth — the per-(track, frame) loop of
+ * tools/static_init.py:58-141 (calculate_init_iou), :143-241 (calculate_static_iou) and tools/dynamic_init.py:37-123,
+ * and the "best IoU over the frame's GT boxes" of tools/eval.py:72-87. (Additions only; DAL3_VERSION is pinned by the
+ * existing tests, as for dal3_track.)
+ *
+ * dal3_score_tracks: S samples = (track, frame) pairs from flat tables. Per sample s, in float64:
+ *   init   = transform_box(boxes[box_row[s]], pose_inv[frame[s]]): centre = (R c summed in einsum's order) + t,
+ *            yaw + atan2(R10, R00)                                                  (static_init.py:42-56)
+ *   pred   = [init centre, class2size(size2class(init size)), 0.0]   (class2angle(angle2class(0)) is exactly 0.0)
+ *   label  = [gt centre (NOT rotated into init's frame: the reference's quirk, kept), class2size(size2class(gt size)),
+ *             class2angle(angle2class(gt yaw - init yaw))]                          (tools/utils.py:53-79)
+ * and the pair goes through the function of dal3_box_iou_paired with float64 boxes: iou_bev[s] / iou_3d[s] are the bits
+ * of dal3_box_iou_paired(pred_s, label_s, boxes_f64 = 1). "Own box" is box_row[s] = the sample's own row, "best box"
+ * box_row[s] = the row of its track's best-score frame: one kernel. pose_inv is inv(veh_to_global) formed by the caller
+ * (np.linalg.inv on the host). gt (S,7) = obj['box'][[0,1,2,3,4,5,-1]] of the matched object, float32 (gt_f64 = 0, the
+ * annotations' dtype) or float64, read only where has_gt[s] != 0. A sample without ground truth — or whose box_row /
+ * frame lies outside [0, R) / [0, F), which is the caller's contract — is NOT scored: NaN in every per-sample output,
+ * nothing added to the sums, but counted in n_samples (static_init.py:71,157: the means divide by all samples).
+ * Accuracy: iou_3d >= thr[0] / thr[1] / thr[2] for type 1 / 2 / 4, thr_other for any other type (float32 compare; NaN
+ * does not pass); the static / dynamic scripts differ only in these numbers and in how they read n_type.
+ *
+ * Accumulation (acc optional when an output is given): the sums ADD into *acc, stream-ordered, so the calls of a
+ * split's track files accumulate without a host read. Reproducible: sample s belongs to chunk s / 256 whatever the
+ * grid; a chunk is reduced in a fixed tree and written to the workspace with ordinary stores, and a second
+ * one-workgroup launch adds the chunks in a fixed order. The accumulator's bytes are a function of the inputs and the
+ * order of the calls alone (not of max_workgroups, not of the scheduling); no floating-point atomics. The float64 sums
+ * are of the float32 per-sample values (NumPy of the reference's time; today's accumulates them in float32).
+ * workspace: dal3_score_workspace_bytes(S), needed only with acc; contents undefined afterwards.
+ * Bounds: S, R, F <= DAL3_MAX_ITEMS. S == 0 succeeds and launches nothing (acc is left as it is). */
+typedef struct dal3_score_acc {          /* 72 bytes; zero it to start a run */
+    double sum_iou_bev;                  /* sum of iou_bev over the scored samples */
+    double sum_iou_3d;                   /* sum of iou_3d */
+    uint64_t n_iou_3d_pass;              /* scored samples at or above their type's threshold */
+    uint64_t n_type[4];                  /* scored samples of type 1, 2, 4, any other */
+    uint64_t n_scored;                   /* samples with ground truth */
+    uint64_t n_samples;                  /* all samples (S per call): the means' denominator */
+} dal3_score_acc;
+
+typedef struct dal3_score_args {
+    int64_t S, R, F;                     /* samples, box rows, frames */
+    const double* boxes;                 /* (R,7) global-frame track boxes [x,y,z,l,w,h,yaw] */
+    const int32_t* box_row;              /* (S) row of `boxes` the sample is scored with */
+    const int32_t* frame;                /* (S) row of pose_inv */
+    const double* pose_inv;              /* (F,16) row-major inv(veh_to_global) */
+    const void* gt;                      /* (S,7) float32, or float64 when gt_f64 != 0 */
+    const uint8_t* has_gt;               /* (S) */
+    const int32_t* type;                 /* (S) Waymo type of the track-frame */
+    int32_t gt_f64;                      /* 0 or 1 */
+    int32_t max_workgroups;              /* 0: 8 per CU of the current device; the result does not depend on it */
+    float thr[3];                        /* iou_3d threshold of type 1, 2, 4 */
+    float thr_other;                     /* ... of any other type */
+    float* iou_bev;                      /* optional (S) */
+    float* iou_3d;                       /* optional (S) */
+    double* pred_box;                    /* optional (S,7): the decoded prediction; NULL = not written */
+    double* label_box;                   /* optional (S,7): the decoded label */
+    dal3_score_acc* acc;                 /* optional, see above */
+    void* workspace;
+    size_t workspace_bytes;
+} dal3_score_args;
+
+size_t dal3_score_workspace_bytes(int64_t S);
+int dal3_score_tracks(const dal3_score_args* args, dal3_stream stream);
+
+/* dal3_best_gt_iou: Q query boxes, query q against the GT boxes [gt_offsets[f], gt_offsets[f+1]) of its own frame
+ * f = query_frame[q] (tools/eval.py:72-87: boxes_iou3d_gpu of a (1,7) box against the frame's (G,7), np.max /
+ * np.argmax). Boxes float32 (boxes_f64 = 0, what eval.py casts to) or float64, both sides alike. best_iou_3d[q] = the
+ * maximum of dal3_box_iou_pairwise(query, gt)'s 3D IoU over the range (the same bits), best_iou_bev[q] the BEV IoU of
+ * that pair, best_index[q] the FIRST arg-max within the range (a NaN counts as the maximum, as np.argmax has it). An
+ * empty range, or a frame outside [0, F), gives NaN and -1. Ranges are clipped to [0, G]. Q, F <= DAL3_MAX_ITEMS.
+ * Q == 0 succeeds and launches nothing. No workspace. */
+typedef struct dal3_best_gt_args {
+    int64_t Q, F, G;                     /* queries, frames, GT boxes */
+    const void* queries;                 /* (Q,7) */
+    const int32_t* query_frame;          /* (Q) */
+    const int64_t* gt_offsets;           /* (F+1) into gt_boxes */
+    const void* gt_boxes;                /* (G,7) */
+    int32_t boxes_f64;                   /* 0 or 1 */
+    int32_t max_workgroups;              /* 0: 8 per CU of the current device */
+    float* best_iou_3d;                  /* (Q) */
+    float* best_iou_bev;                 /* optional (Q) */
+    int32_t* best_index;                 /* optional (Q) */
+} dal3_best_gt_args;
+
+int dal3_best_gt_iou(const dal3_best_gt_args* args, dal3_stream stream);
+
 /* ---- crop extraction from full sweeps: the per-detection loop of _create_pd_detection
  * (det3d/datasets/waymo/waymo_common.py:166-171, 193) for F frames at once. points (P_total,3) f32 vehicle-frame
  * sweeps concatenated, point_offsets (F+1); planes (K_total,6,4) f64 face equations of every frame's detections
