@@ -70,6 +70,10 @@ struct InsSegW {
     const f32x4* w5h;         // fp16 MFMA fragments [32 out-tiles][4 kt][2 s] of 1 KiB, the 16-bit family's layout
     const float* scr_pq;      // (1024,2): eps(c) = X * P_c + Q_c bounds |fp16 score - fp32 chain| for ||x||_2 <= X
     const int32_t* scr_flag;  // nonzero: a folded conv5 weight is not finite in fp16 -> the dense kernel runs
+    // the compacted dconv2 of the throughput decoder (dal3_pointmlp.hip, DESIGN.md "Compacted dconv2")
+    const float* dw2c;        // dconv2 folded, [k 0..511][row 0..31][out-tile 0..7]: W'[32 mt + row][32 c + tile_chan(r, h)] at
+                              // chain index k = 32 c + 2 r + h (chunk, accumulator register, lane half: the dense k order)
+    const int32_t* dec_flag;  // nonzero: a folded dconv2 weight is not finite or a folded dconv2 bias is -0 -> dense path only
 };
 enum {                        // stream geometry in fragments of 256 floats
     ENC_W2 = 0, ENC_W3 = 16, ENC_W4 = 32, ENC_W5 = 64, ENC_FRAGS = 64 + 512,
@@ -194,6 +198,8 @@ void point_head_dims(int head_kind, int* c_in, int* ks, int c[4], int* n_fc, int
 hipError_t launch_ins_seg_encode(const InsSegW& w, BCN pts, int c_in, int B, int N, float* g, hipStream_t s);
 hipError_t launch_ins_seg_encode_screen(const InsSegW& w, BCN pts, int c_in, int B, int N, float* g, hipStream_t s);
 hipError_t launch_pack_enc_screen(const dal3_layer& L, float* pq, int32_t* flag, hipStream_t s);
+// db2: the layer's packed bias (written earlier on s)
+hipError_t launch_pack_dec_sparse(const dal3_layer& L, const float* db2, float* dw2c, int32_t* flag, hipStream_t s);
 hipError_t launch_ins_seg_decode(const InsSegW& w, BCN pts, int c_in, int B, int N, const float* gbias,
                                  float* logits, uint8_t* mask, hipStream_t s);
 // distinct (B) i32 or NULL: only the first distinct[b] points of item b are distinct (the rest duplicate them)

@@ -162,6 +162,25 @@ hipError_t launch_pack_enc_screen(const dal3_layer& L, float* pq, int32_t* flag,
     return hipGetLastError();
 }
 
+// The compacted dconv2's weight copy (dal3_kernels.h::InsSegW::dw2c) and its guard: skipping a dead channel's term is
+// exact only while 0 * w is a zero (w finite) and no accumulator chain starts from -0 (DESIGN.md "Compacted dconv2").
+__global__ void pack_dec_sparse_kernel(dal3_layer L, const float* __restrict__ db2, float* __restrict__ out,
+                                       int32_t* __restrict__ flag) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 512 * 256) return;
+    const int mt = i & 7, row = (i >> 3) & 31, k = i >> 8;
+    const int c = k >> 5, r = (k & 31) >> 1, h = k & 1;
+    const float v = folded_w(L, 32 * mt + row, 32 * c + tile_chan(r, h), 0, 512);
+    out[i] = v;
+    bool bad = (__float_as_uint(v) & 0x7F800000u) == 0x7F800000u;
+    if (i < 256) bad |= __float_as_uint(db2[i]) == 0x80000000u;
+    if (bad) atomicOr(flag, 1);
+}
+hipError_t launch_pack_dec_sparse(const dal3_layer& L, const float* db2, float* dw2c, int32_t* flag, hipStream_t s) {
+    hipLaunchKernelGGL(pack_dec_sparse_kernel, dim3(512), dim3(256), 0, s, L, db2, dw2c, flag);
+    return hipGetLastError();
+}
+
 hipError_t launch_pack_bias(const dal3_layer& L, float* out, hipStream_t s) {
     const int padded = (L.c_out + 31) / 32 * 32;
     hipLaunchKernelGGL(pack_bias_kernel, dim3((padded + 255) / 256), dim3(256), 0, s, L, out, padded);

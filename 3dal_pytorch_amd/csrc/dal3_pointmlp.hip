@@ -86,40 +86,69 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_encode_kernel(InsS
 }
 
 // ------------------------------------------------------------------------------------------------
-template <int T>
-__global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_decode_kernel(InsSegW w, BCN pts, int c_in, int n_pts,
-                                                             int tiles_per_item, const float* __restrict__ gbias,
-                                                             float* __restrict__ logits, uint8_t* __restrict__ mask) {
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int h = lane >> 5;
-    // Which (crop, tile) this workgroup takes. The hardware deals consecutive workgroup ids round-robin over the 8 XCDs,
-    // each with an L2 of its own; with id -> (id / tiles_per_item, id % tiles_per_item) the 8 workgroups of a 1024-point
-    // crop land on 8 different XCDs and each XCD's L2 fetches the crop's 2-KiB dconv1 term `gbias` from memory for itself:
-    // 8 x 8.4 MB of the 130.7 MB this kernel read per 4096 x 1024 launch against 58.7 MB of points + terms (VERDICT r5 #6;
-    // profiles/r06_pmc_decode_traffic.txt). Round 6: XCD x (ids = x mod 8) takes a CONTIGUOUS range of logical blocks, so a
-    // crop's tiles share one L2. Pure index arithmetic; per-tile work is independent: bit-identical results.
-#ifndef DAL3_DEC_XCD
-#define DAL3_DEC_XCD 1
+// Compacted dconv2 (DESIGN.md "Compacted dconv2"). dconv2's input is relu(dconv1), and on real crops almost half of a
+// 32-channel chunk is +0 in all 32 points of a wave's tile (the per-crop term gb drives whole channels negative). A term
+// fmaf(w, +0, acc) with finite w leaves acc as it is (up to the sign of a zero accumulator, which the ReLU after dconv2
+// removes), so the dead channels are dropped from the k loop and every output keeps its chain of the live terms in the
+// dense order — the same bits. Per chunk: 16 wave ballots give the live mask in chain order (bit 2r + h = accumulator
+// register r, lane half h); a chunk with all 32 channels live and nothing pending takes the dense register path on the
+// fragment stream; any other chunk puts its activations through the wave's LDS slab (row 2r + h, 32 points) and runs
+// popcount / 2 compact k-steps: half-wave h reads the slab row of live channel L[2s + h] as the B operand and 32 bytes
+// per lane of the chain-ordered weight copy dw2c[k][row][out-tile] as the A operands of the step's eight MFMAs. An odd
+// live channel waits in slab row 32 for the next chunk's first live one; the very last one is paired with row 33 (zeros).
+// The weight ring has by then fetched the first DAL3_PF dense fragments of the chunk: they are dropped, the stream
+// offset jumps over the chunk's other fragments and the ring is refilled while the compact steps run.
+#ifndef DAL3_DEC_SPARSE
+#define DAL3_DEC_SPARSE 1               // 0: every chunk on the dense path (A/B builds)
 #endif
-    unsigned blk = blockIdx.x;
-    if (DAL3_DEC_XCD) {
-        const unsigned per = gridDim.x >> 3, rem = gridDim.x & 7u, x = blockIdx.x & 7u;
-        blk = x * per + (x < rem ? x : rem) + (blockIdx.x >> 3);
+#ifndef DAL3_DEC_NB
+#define DAL3_DEC_NB 3                   // compact k-steps whose operands are in flight (2 KiB of weights + one LDS row each)
+#endif
+#define DEC_SLAB_FLOATS (34 * 32)       // rows 0..31: the chunk in chain order | 32: the pending channel | 33: zeros
+// Diagnostic build only (-DDAL3_DEC_COUNT): [0] tiles, [1] dense chunks, [2] compacted chunks, [3] compact k-steps (the
+// final zero-padded one included), [4] live channels, [5] tiles in the compacted body. No counter executes in the shipped library.
+#ifdef DAL3_DEC_COUNT
+__device__ unsigned long long g_dec_count[8];
+extern "C" int dal3_debug_dec_counts(unsigned long long* out, int reset) {
+    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_dec_count), sizeof(g_dec_count));
+    if (e == hipSuccess && reset) {
+        unsigned long long z[8] = {};
+        e = hipMemcpyToSymbol(HIP_SYMBOL(g_dec_count), z, sizeof(z));
     }
-    const int64_t b = blk / tiles_per_item;
-    const int n0 = ((blk % tiles_per_item) * DAL3_WG_WAVES + wave) * (32 * T);
-    if (n0 >= n_pts) return;
+    return (int)e;
+}
+#endif
+struct DecStep {                        // operands of one compact k-step: weights of the 8 out-tiles, one activation
+    f32x4 a0, a1;
+    float b;
+};
 
+// One wave's tile(s): SP = with the compacted dconv2 (slab: the wave's DEC_SLAB_FLOATS of LDS)
+template <int T, bool SP>
+__device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN& pts, int c_in, int n_pts, int64_t b, int n0,
+                                                    const float* __restrict__ gb, float* __restrict__ logits,
+                                                    uint8_t* __restrict__ mask, float* __restrict__ slab, int lane, int wave) {
+    const int h = lane >> 5;
     STAMP(0);
     // stream: conv2 | dconv1a(0) | { dconv1a(c+1), dconv2(c) } c = 0..15 | dconv3 | dconv4
     WRing<DAL3_PF> ring;
     ring.init(w.dec_stream, lane);
     f32x16 bias = tile_from_channels(w.b2, h);
-    const float* gb = gbias + b * 512;                 // W1g . g + b1' of this crop
-    // a crop with a non-finite coordinate: its pooled feature, hence this term, is NaN (dal3_device.h); as in the
-    // reference every logit of the crop is then NaN and its mask empty (static_model.py:284-289, :59)
+    // gb = W1g . g + b1' of this crop. A crop with a non-finite coordinate: its pooled feature, hence this term, is NaN
+    // (dal3_device.h); as in the reference every logit of the crop is then NaN and its mask empty
+    // (static_model.py:284-289, :59)
     const bool crop_bad = bits_nonfinite(gb[0]);
+
+    const int pt = lane & 31;
+    __amdgpu_buffer_rsrc_t wc = ring.rsrc;
+    uint32_t live = 0, pend = 0, pend_k = 0;           // this chunk's live mask; a channel waiting for a partner, its k
+    if constexpr (SP) {
+        wc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(w.dw2c), 0, 512 * 1024, 0x00020000);
+        slab[33 * 32 + pt] = 0.0f;
+    }
+#ifdef DAL3_DEC_COUNT
+    uint32_t n_dense = 0, n_comp = 0, n_steps = 0, n_live = 0;
+#endif
 
     f32x16 x2[T][2];
     {
@@ -159,6 +188,103 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_decode_kernel(InsS
             DAL3_SCHED_FENCE();
         }
     };
+    // post-ReLU bits: negatives and -0 are +0 already, NaN / Inf are live. Two scalar bits per accumulator register.
+    auto note_live = [&](float v, int r) {
+        const uint64_t bal = __builtin_amdgcn_ballot_w64(__float_as_uint(v) != 0u);
+        // "word != 0" as s_min_u32 word, 1 on the scalar unit: written as a compare, hipcc turns the boolean into a lane
+        // mask and a v_cndmask, and the mask and everything computed from it moves to the vector ALU
+        uint32_t lo, hi;
+        asm("s_min_u32 %0, %2, 1\n\ts_min_u32 %1, %3, 1" : "=&s"(lo), "=s"(hi) : "s"((uint32_t)bal), "s"((uint32_t)(bal >> 32)) : "scc");
+        live |= (lo | (hi << 1)) << (2 * r);
+    };
+    auto compact_mma = [&](const DecStep& S) {
+#pragma unroll
+        for (int mt = 0; mt < 8; ++mt) a2[0][mt] = mfma32(mt < 4 ? S.a0[mt & 3] : S.a1[mt & 3], S.b, a2[0][mt]);
+    };
+    // half-wave h: weights of chain index k_h (32 bytes per lane), activation row r_h of the slab
+    auto compact_load = [&](DecStep& S, uint32_t k0, uint32_t r0, uint32_t k1, uint32_t r1) {
+        const uint32_t k = h ? k1 : k0, r = h ? r1 : r0;
+        const uint32_t voff = k * 1024u + (uint32_t)pt * 32u;
+        S.b = slab[r * 32u + (uint32_t)pt];
+        S.a0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wc, voff, 0, 0));
+        S.a1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wc, voff + 16u, 0, 0));
+    };
+    auto dconv2_compact = [&](const f32x16 (&t)[T], int c) {
+        // the stream: drop the DAL3_PF dense fragments of this chunk the ring holds, skip the others, refill
+        ring.soff += (32 - DAL3_PF) * 1024;
+#pragma unroll
+        for (int i = 0; i < DAL3_PF; ++i) ring.slot[i] = ring.fetch();
+        // (LDS operations of a wave execute in order: the next chunk's rows never overtake this chunk's reads, one slab is enough)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+#pragma unroll
+        for (int r = 0; r < 16; ++r) slab[r * 64 + lane] = t[0][r];       // row 2r + h
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const uint32_t n = __builtin_popcount(live), total = n + pend, steps = total >> 1;
+        // (scalar bit arithmetic only: a select or a borrow on these wave-uniform words sends them to the vector ALU)
+        uint32_t mm = live;
+        auto pop = [&](uint32_t keep) {                // next live channel in chain order (31 once the mask is empty);
+            const uint32_t p = (uint32_t)__builtin_ctz(mm | 0x80000000u);   // keep = ~0: look, do not take
+            mm &= (mm - 1u) | keep;
+            return p;
+        };
+        auto next = [&](DecStep& S, uint32_t wait) {   // operands of the next step in order (harmless past the last);
+            const uint32_t p0 = pop(wait);             // wait = ~0: the waiting channel is this step's low half
+            const uint32_t k0 = (pend_k & wait) | ((32u * c + p0) & ~wait), r0 = (32u & wait) | (p0 & ~wait);
+            const uint32_t r1 = pop(0u);
+            compact_load(S, k0, r0, 32u * c + r1, r1);
+        };
+        DecStep S[DAL3_DEC_NB];                        // operands in flight, rotating by name
+#pragma unroll
+        for (int u = 0; u < DAL3_DEC_NB; ++u) next(S[u], u == 0 ? 0u - pend : 0u);
+        uint32_t s = 0;
+        for (; s + DAL3_DEC_NB <= steps; s += DAL3_DEC_NB) {
+#pragma unroll
+            for (int u = 0; u < DAL3_DEC_NB; ++u) {
+                compact_mma(S[u]);
+                next(S[u], 0u);
+                DAL3_SCHED_FENCE();
+            }
+        }
+#pragma unroll
+        for (int u = 0; u + 1 < DAL3_DEC_NB; ++u) {
+            if (s + u < steps) compact_mma(S[u]);
+        }
+        if ((total & 1u) && n) {                       // the last live channel waits (an older one still waiting stays)
+            const uint32_t hi = 31u - (uint32_t)__builtin_clz(live);
+            const float v = slab[hi * 32u + (uint32_t)pt];
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            slab[32 * 32 + pt] = v;
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            pend_k = 32u * c + hi;
+        }
+        pend = total & 1u;
+#ifdef DAL3_DEC_COUNT
+        ++n_comp, n_steps += steps, n_live += n;
+#endif
+    };
+    auto dconv2_chunk = [&](const f32x16 (&t)[T], int c) {
+        if constexpr (SP) {
+            if (!(live == 0xffffffffu && pend == 0u)) {
+                dconv2_compact(t, c);
+                return;
+            }
+        }
+#ifdef DAL3_DEC_COUNT
+        ++n_dense, n_live += 32;
+#endif
+        dconv2_part(t);
+    };
+    auto relu_note = [&](f32x16& t, int i) {           // ReLU and liveness of two registers per fragment group
+        t[2 * i] = relu1(t[2 * i]);
+        t[2 * i + 1] = relu1(t[2 * i + 1]);
+        if constexpr (SP) {
+            if (i == 0) live = 0;
+            note_live(t[2 * i], 2 * i);
+            note_live(t[2 * i + 1], 2 * i + 1);
+        }
+    };
 #pragma unroll
     for (int j = 0; j < T; ++j) tA[j] = bias;
     mma_block_ring<2, T>(ring, x2, tA, [&](int i) {
@@ -170,12 +296,9 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_decode_kernel(InsS
         mma_block_ring<2, T>(ring, x2, tB, [&](int i) {                // chunk c+1; ReLU(chunk c) in its shadow
             if (i == 0) bias = tile_from_channels(gb + 32 * ((c + 2) & 15), h);
 #pragma unroll
-            for (int j = 0; j < T; ++j) {              // two registers per fragment group
-                tA[j][2 * i] = relu1(tA[j][2 * i]);
-                tA[j][2 * i + 1] = relu1(tA[j][2 * i + 1]);
-            }
+            for (int j = 0; j < T; ++j) relu_note(tA[j], i);
         });
-        dconv2_part(tA);
+        dconv2_chunk(tA, c);
 #pragma unroll
         for (int j = 0; j < T; ++j) tA[j] = bias;
         // chunk c+2 (on the last round its 8 fragments are the stream's zero filler; the result is unused)
@@ -183,13 +306,30 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_decode_kernel(InsS
             if (i == 0)
                 bias = c + 2 < 16 ? tile_from_channels(gb + 32 * ((c + 3) & 15), h) : tile_from_channels(w.db3, h);
 #pragma unroll
-            for (int j = 0; j < T; ++j) {
-                tB[j][2 * i] = relu1(tB[j][2 * i]);
-                tB[j][2 * i + 1] = relu1(tB[j][2 * i + 1]);
-            }
+            for (int j = 0; j < T; ++j) relu_note(tB[j], i);
         });
-        dconv2_part(tB);
+        dconv2_chunk(tB, c + 1);
     }
+    if constexpr (SP) {
+        if (pend) {                                    // the very last live channel: its partner is the row of zeros
+            DecStep S;
+            compact_load(S, pend_k, 32, pend_k, 33);
+            compact_mma(S);
+#ifdef DAL3_DEC_COUNT
+            ++n_steps;
+#endif
+        }
+    }
+#ifdef DAL3_DEC_COUNT
+    if (lane == 0) {
+        atomicAdd(&g_dec_count[0], 1ull);
+        atomicAdd(&g_dec_count[5], SP ? 1ull : 0ull);
+        atomicAdd(&g_dec_count[1], (unsigned long long)n_dense);
+        atomicAdd(&g_dec_count[2], (unsigned long long)n_comp);
+        atomicAdd(&g_dec_count[3], (unsigned long long)n_steps);
+        atomicAdd(&g_dec_count[4], (unsigned long long)n_live);
+    }
+#endif
     STAMP(2);
 #pragma unroll
     for (int j = 0; j < T; ++j) {
@@ -238,6 +378,59 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_decode_kernel(InsS
         }
     }
     STAMP(4);
+}
+
+// The compacted body is taken by the tiles of a crop whose term gb is negative in at least DAL3_DEC_MIN_DEAD of the 512
+// dconv1 channels — the channels that are dead for (nearly) every point of the crop — and never when the blob's guard
+// flag is set. Every other tile runs the dense body, which is the kernel as it was: no ballot, no branch in its chunk
+// loop. (The choice is about speed only: both bodies give the same bits. Inside the compacted body a fully live chunk
+// still takes the register path, but the branch around it costs that body's chunk loop ~100 accumulator register copies
+// per chunk, profiles/LEDGER_r08.md; a crop with few dead channels would lose more there than compaction returns.)
+// 192 = 0.375 of the channels is the smallest dead share with a measured gain: with exactly that share dead in every
+// tile (the other channels live) the compacted body runs the 4096 x 1024 launch in 13.75 / 13.29 / 12.75 / 12.27 ms at
+// 0.25 / 0.3125 / 0.375 / 0.4375 against 12.97 ms dense — break-even near 0.35 (LEDGER_r08.md, section 3).
+#ifndef DAL3_DEC_MIN_DEAD
+#define DAL3_DEC_MIN_DEAD 192
+#endif
+template <int T>
+__global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_decode_kernel(InsSegW w, BCN pts, int c_in, int n_pts,
+                                                             int tiles_per_item, const float* __restrict__ gbias,
+                                                             float* __restrict__ logits, uint8_t* __restrict__ mask) {
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    // Which (crop, tile) this workgroup takes. The hardware deals consecutive workgroup ids round-robin over the 8 XCDs,
+    // each with an L2 of its own; with id -> (id / tiles_per_item, id % tiles_per_item) the 8 workgroups of a 1024-point
+    // crop land on 8 different XCDs and each XCD's L2 fetches the crop's 2-KiB dconv1 term `gbias` from memory for itself:
+    // 8 x 8.4 MB of the 130.7 MB this kernel read per 4096 x 1024 launch against 58.7 MB of points + terms (VERDICT r5 #6;
+    // profiles/r06_pmc_decode_traffic.txt). Round 6: XCD x (ids = x mod 8) takes a CONTIGUOUS range of logical blocks, so a
+    // crop's tiles share one L2. Pure index arithmetic; per-tile work is independent: bit-identical results.
+#ifndef DAL3_DEC_XCD
+#define DAL3_DEC_XCD 1
+#endif
+    unsigned blk = blockIdx.x;
+    if (DAL3_DEC_XCD) {
+        const unsigned per = gridDim.x >> 3, rem = gridDim.x & 7u, x = blockIdx.x & 7u;
+        blk = x * per + (x < rem ? x : rem) + (blockIdx.x >> 3);
+    }
+    const int64_t b = blk / tiles_per_item;
+    const int n0 = ((blk % tiles_per_item) * DAL3_WG_WAVES + wave) * (32 * T);
+    if (n0 >= n_pts) return;
+    const float* gb = gbias + b * 512;                 // W1g . g + b1' of this crop
+    constexpr bool SP = DAL3_DEC_SPARSE != 0 && T == 1;    // one tile per wave only: the live mask is the tile's
+    __shared__ float s_slab[SP ? DAL3_WG_WAVES * DEC_SLAB_FLOATS : 1];
+    if constexpr (SP) {
+        const f32x4 g0 = reinterpret_cast<const f32x4*>(gb)[2 * lane], g1 = reinterpret_cast<const f32x4*>(gb)[2 * lane + 1];
+        uint32_t neg = 0;                              // sign bits among the crop's 512 entries (a NaN term counts or not: dense either way is right)
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            neg += __builtin_popcountll(__builtin_amdgcn_ballot_w64(__float_as_int(g0[e]) < 0)) +
+                   __builtin_popcountll(__builtin_amdgcn_ballot_w64(__float_as_int(g1[e]) < 0));
+        if (neg >= DAL3_DEC_MIN_DEAD && *w.dec_flag == 0) {
+            ins_seg_decode_tile<T, true>(w, pts, c_in, n_pts, b, n0, gb, logits, mask, s_slab + wave * DEC_SLAB_FLOATS, lane, wave);
+            return;
+        }
+    }
+    ins_seg_decode_tile<T, false>(w, pts, c_in, n_pts, b, n0, gb, logits, mask, s_slab, lane, wave);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -106,7 +106,12 @@ const float* dal3_mean_size(void);
  * kernels consume. Call with packed_dev == NULL to query *bytes_inout. Layers come in forward
  * order (ins_seg: conv1..5, dconv1..5; *_BOX_EST / *_EMB: conv1..4 then fc1..).
  * Replaces: nothing in the reference (it keeps nn.Conv1d/nn.BatchNorm1d modules,
- * static_model.py:249-269); this is the derived cache of SURVEY.md 8(b). */
+ * static_model.py:249-269); this is the derived cache of SURVEY.md 8(b).
+ * The image is opaque and its size may change between builds of the library: always take it from the query. The
+ * DAL3_F32 image of DAL3_HEAD_INS_SEG ends (in front of its tail padding) with the compacted dconv2's region: the
+ * folded dconv2 weights once more, [k 0..511 in the kernel's accumulation order][row 0..31][out-tile 0..7] fp32
+ * (512 KiB), and a 256-byte section whose first int32 is nonzero when a folded dconv2 weight is not finite or a folded
+ * dconv2 bias is -0: the decode kernel then never skips a dead channel (DESIGN.md "Compacted dconv2"). */
 int dal3_pack_weights(int head_kind, const dal3_layer* layers, int n_layers, int dtype,
                       void* packed_dev, size_t* bytes_inout, dal3_stream stream);
 

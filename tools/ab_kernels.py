@@ -11,6 +11,7 @@ import os
 import statistics
 import sys
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -24,6 +25,11 @@ ap.add_argument("--B", type=int, default=4096)
 ap.add_argument("--N", type=int, default=1024)
 ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--dtype", type=int, default=0, help="0 fp32, 1 bf16, 2 fp16")
+ap.add_argument("--dbn1-shift", type=float, default=0.0,
+                help="added to dconv1's folded bias: +1e6 = no dead channel in dconv2's input, -1e6 = every channel dead")
+ap.add_argument("--dead-frac", type=float, default=None,
+                help="dconv1's folded bias -1e6 on this fraction of the 512 channels (scattered), +1e6 on the others: exactly "
+                     "that share of dconv2's input is dead in every tile")
 args = ap.parse_args()
 B, N = args.B, args.N
 DT = args.dtype
@@ -41,7 +47,14 @@ def load(path):
 
 
 model = sm.StaticModelOneBoxEst()
-model.load_state_dict({k: torch.as_tensor(v) for k, v in synth.state_dict("static_one").items()})
+sd = dict(synth.state_dict("static_one"))
+if args.dead_frac is not None:
+    shift = np.full(512, 1e6, np.float32)
+    shift[np.random.default_rng(0).permutation(512)[:int(round(args.dead_frac * 512))]] = -1e6
+    sd["ins_seg.dbn1.bias"] = sd["ins_seg.dbn1.bias"] + shift
+if args.dbn1_shift:
+    sd["ins_seg.dbn1.bias"] = sd["ins_seg.dbn1.bias"] + np.float32(args.dbn1_shift)
+model.load_state_dict({k: torch.as_tensor(v) for k, v in sd.items()})
 model = model.to(dev).eval()
 pts_np, init_np, _ = synth.static_crops(min(B, 512), N)
 reps = (B + pts_np.shape[0] - 1) // pts_np.shape[0]
@@ -79,7 +92,16 @@ for name, lib in libs:
                                                                  hip.ptr(d["bp"]), 39, hip.ptr(d["ws"]), d["ws"].numel(), st)
     assert d["enc"]() == 0, lib.dal3_last_error()
     assert lib.dal3_ins_seg_global_bias(hip.ptr(w_seg), DT, hip.ptr(g), B, hip.ptr(gb), st) == 0
+    if hasattr(lib, "dal3_debug_dec_counts"):         # a -DDAL3_DEC_COUNT build: what the compacted dconv2 saw in ONE launch
+        cnt = (C.c_ulonglong * 8)()
+        lib.dal3_debug_dec_counts(cnt, 1)
     assert d["dec"]() == 0 and d["head"]() == 0, lib.dal3_last_error()
+    if hasattr(lib, "dal3_debug_dec_counts"):
+        torch.cuda.synchronize()
+        lib.dal3_debug_dec_counts(cnt, 1)
+        tiles, dense, comp, steps, live, sp_tiles = (int(v) for v in cnt[:6])
+        print(f"{name}: decode tiles {tiles} ({sp_tiles} in the compacted body), dense chunks {dense}, compacted chunks {comp}, compact k-steps {steps} "
+              f"({(steps + 16 * dense) / (256.0 * tiles):.4f} of the dense k-steps), live channels {live / (512.0 * tiles):.4f}")
     state.append(d)
 torch.cuda.synchronize()
 ref = state[0]
