@@ -5,22 +5,35 @@
 // dense kernel does and then evaluate conv5 on the fp16 MFMA (16 x the fp32 rate) with a PROVED error bound
 //   |s16(c,p) - chain32(c,p)| <= E_c = X * P_c + Q_c        (X >= ||x_p||_2 for every point of the wave),
 // chain32 being the dense kernel's value (a k-ordered fmaf chain from a zero accumulator):
-//   pass A  g[c] <- max(g[c], relu(fl(max_p s16 - E_c + b_c)))        a LOWER bound of the final value, in g itself
+//   pass A  g[c] <- max(g[c], relu(fl(max_p s16 - E_c + b_c)))        a LOWER bound of the final value, in g itself;
+//           the maximum over ANY subset of the crop's points is one, and pass A takes every DAL3_SCR_A_STRIDE-th
+//           wave-slot of 64 points only (slot 0 always): a weaker threshold, more candidates, a fraction of the sweep
 //   pass B  (c,p) is a candidate iff s16(c,p) > g[c] - b_c - E_c (rounded down); every candidate is recomputed with
 //           the exact fp32 chain on the VALU (same operands, same order, same roundings as the f32 MFMA) and
 //           relu(fl(chain + b_c)) goes to g with the same integer atomicMax as the dense kernel's.
 // A pair that is not a candidate has fl(chain + b_c) <= g[c] already, so it cannot change g: the result has the dense
 // kernel's bits. Whatever does not fit the proof or the lists takes the dense conv_max_layer, per wave: activations
 // beyond fp16's range, conv5 weights beyond it (blob flag), more than SCR_CAP candidates in a 32-point tile.
+// PASS B OWNS EVERY EXACT VALUE: it sweeps every point, and a wave that leaves the screen is computed densely there and
+// nowhere else. Pass A only ever writes lower bounds from screened waves: a visited wave that leaves the screen
+// contributes nothing, and with the blob's flag set pass A returns at once.
 #include "dal3_device.h"
 #include "dal3_kernels.h"
 #include "dal3_lp.h"
 
 #ifndef SCR_CAP
-#define SCR_CAP 1024                    // candidate entries per wave and 32-point tile (bench input: 83 on average, 321 at most in the CPU model)
+#define SCR_CAP 1024                    // candidate entries per wave and 32-point tile (bench input: 130 on average, 426 at most in the CPU model)
 #endif
 #define SCR_XLD 132                     // floats per point row of the LDS copy of x4: 128 + 4, rows start 4 banks apart
 #define SCR_XMAX_BITS 0x476A6000        // 60000.0f: activations up to here round to a FINITE fp16
+// Pass A visits the wave-slots (32 * DAL3_ENC_T consecutive points) of a crop whose index is a multiple of this stride.
+// 1: every slot, the launches of the unstrided kernel (A/B builds). Measured (profiles/LEDGER_r09.md): the encoder at
+// 4096 x 1024 takes 5.97 / 5.37 / 5.67 / 7.02 ms at 1 / 2 / 4 / 8 — beyond 2 pass B's extra candidates (100 / 150 / 281
+// per 32-point tile against 82) cost more than pass A still saves — and at 1024 x 5120 6.70 / 5.71 / 5.36 / 5.55 ms.
+#ifndef DAL3_SCR_A_STRIDE
+#define DAL3_SCR_A_STRIDE 2
+#endif
+static_assert(DAL3_SCR_A_STRIDE >= 1, "pass A's stride over the wave-slots");
 
 // Diagnostic build only (-DDAL3_SCREEN_COUNT): [0] waves, [1] waves dense for range, [2] waves dense for list overflow,
 // [3] candidates, [4] recompute rounds. No counter executes in the shipped library.
@@ -49,7 +62,8 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_encode_screen_kern
     const int wave = threadIdx.x >> 6;
     const int h = lane >> 5;
     const int64_t b = blockIdx.x / tiles_per_item;
-    const int n0 = ((blockIdx.x % tiles_per_item) * DAL3_WG_WAVES + wave) * (32 * T);
+    // pass A: the four waves of a workgroup take four consecutive VISITED slots of one crop; pass B: every slot
+    const int n0 = ((blockIdx.x % tiles_per_item) * DAL3_WG_WAVES + wave) * (PASS == 0 ? DAL3_SCR_A_STRIDE : 1) * (32 * T);
     __shared__ float s_b5[1024];                       // conv5's folded bias
     __shared__ int s_max[1024];                        // the workgroup's maxima (bit patterns >= 0), as in the dense kernel
     __shared__ f32x2 s_pq[1024];                       // (P_c, Q_c)
@@ -61,8 +75,9 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_encode_screen_kern
     // kernel holds one wave per SIMD by registers anyway). Too large: lower SCR_CAP, DAL3_WG_WAVES or DAL3_ENC_T.
     static_assert(20 * 1024 + DAL3_WG_WAVES * (32 * SCR_XLD * 4 + T * SCR_CAP * 4) <= 160 * 1024,
                   "pass B's LDS exceeds a CU's 160 KiB: lower SCR_CAP, DAL3_WG_WAVES or DAL3_ENC_T");
-    // conv5 not finite in fp16 (the blob's flag): pass A was the dense encoder, nothing is left to do. (Uniform: one word.)
-    if (PASS == 1 && *w.scr_flag != 0) return;
+    // conv5 not finite in fp16 (the blob's flag): no wave can be screened, pass A has no bound to give and pass B is the
+    // dense encoder. (Uniform: one word.)
+    if (PASS == 0 && *w.scr_flag != 0) return;
     // No early exit for a crop flagged by nonfinite_rows_kernel: its quiet-NaN pattern lies above every value either pass
     // sends to atomicMax, exactly as for the dense kernel. A non-finite threshold (that pattern, or +Inf / NaN written by
     // a dense wave of a crop whose activations overflow fp32) is final for its channel: pass B takes no candidate there.
@@ -90,7 +105,7 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_encode_screen_kern
 
         // fp16 holds every activation of the wave? (x4 >= +0 after the ReLU: the integer order of the bit patterns is
         // the order of the values, and a NaN / Inf pattern lies above the limit.) The decision depends on the wave's
-        // own points only, so both passes take it alike.
+        // own points and the blob only; it matters in pass B alone, which sees every wave.
         int xm = 0;
 #pragma unroll
         for (int j = 0; j < T; ++j) {
@@ -105,9 +120,9 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_encode_screen_kern
         }
         const bool dense = *w.scr_flag != 0 || __builtin_amdgcn_ballot_w64(xm > SCR_XMAX_BITS) != 0;
         if (dense) {
-            // pass A writes the exact values (also valid lower bounds); pass B has nothing to add for this wave
+            // pass A has no bound for this wave; pass B computes its exact values
             SCR_COUNT(1, 1);
-            if (PASS == 0) conv_max_layer<4, T>(ring, s_b5, x4, reinterpret_cast<float*>(s_max), 32, lane);
+            if (PASS == 1) conv_max_layer<4, T>(ring, s_b5, x4, reinterpret_cast<float*>(s_max), 32, lane);
         } else {
             // X >= ||x_p||_2 for every point of the wave (lane half h holds 64 of a point's 128 channels)
             float x2max = 0.0f;
@@ -311,8 +326,11 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_encode_screen_kern
 hipError_t launch_ins_seg_encode_screen(const InsSegW& w, BCN pts, int c_in, int B, int N, float* g, hipStream_t s) {
     constexpr int T = DAL3_ENC_T;
     const int tpi = (N + 32 * DAL3_WG_WAVES * T - 1) / (32 * DAL3_WG_WAVES * T);
-    const dim3 grid((unsigned)((int64_t)B * tpi)), block(64 * DAL3_WG_WAVES);
-    hipLaunchKernelGGL((ins_seg_encode_screen_kernel<0, T>), grid, block, 0, s, w, pts, c_in, N, tpi, g);
+    // pass A: ceil(slots / stride) visited wave-slots per crop, DAL3_WG_WAVES of them per workgroup
+    const int slots = (N + 32 * T - 1) / (32 * T);
+    const int tpi_a = ((slots + DAL3_SCR_A_STRIDE - 1) / DAL3_SCR_A_STRIDE + DAL3_WG_WAVES - 1) / DAL3_WG_WAVES;
+    const dim3 grid_a((unsigned)((int64_t)B * tpi_a)), grid((unsigned)((int64_t)B * tpi)), block(64 * DAL3_WG_WAVES);
+    hipLaunchKernelGGL((ins_seg_encode_screen_kernel<0, T>), grid_a, block, 0, s, w, pts, c_in, N, tpi_a, g);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((ins_seg_encode_screen_kernel<1, T>), grid, block, 0, s, w, pts, c_in, N, tpi, g);

@@ -91,9 +91,9 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_encode_kernel(InsS
 // fmaf(w, +0, acc) with finite w leaves acc as it is (up to the sign of a zero accumulator, which the ReLU after dconv2
 // removes), so the dead channels are dropped from the k loop and every output keeps its chain of the live terms in the
 // dense order — the same bits. Per chunk: 16 wave ballots give the live mask in chain order (bit 2r + h = accumulator
-// register r, lane half h); a chunk with all 32 channels live and nothing pending takes the dense register path on the
-// fragment stream; any other chunk puts its activations through the wave's LDS slab (row 2r + h, 32 points) and runs
-// popcount / 2 compact k-steps: half-wave h reads the slab row of live channel L[2s + h] as the B operand and 32 bytes
+// register r, lane half h); every chunk of the compacted body, a fully live one included (16 k-steps in the dense order),
+// puts its activations through the wave's LDS slab (row 2r + h, 32 points) and runs popcount / 2 compact k-steps:
+// half-wave h reads the slab row of live channel L[2s + h] as the B operand and 32 bytes
 // per lane of the chain-ordered weight copy dw2c[k][row][out-tile] as the A operands of the step's eight MFMAs. An odd
 // live channel waits in slab row 32 for the next chunk's first live one; the very last one is paired with row 33 (zeros).
 // The weight ring has by then fetched the first DAL3_PF dense fragments of the chunk: they are dropped, the stream
@@ -264,17 +264,18 @@ __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN&
         ++n_comp, n_steps += steps, n_live += n;
 #endif
     };
+    // ONE route per body: the compacted body sends every chunk through the slab (a fully live chunk is 16 k-steps in the
+    // dense order), the dense body every chunk through the registers. A second route inside the compacted body made the
+    // compiler move the dconv2 accumulators between two register sets at every chunk (profiles/LEDGER_r09.md).
     auto dconv2_chunk = [&](const f32x16 (&t)[T], int c) {
         if constexpr (SP) {
-            if (!(live == 0xffffffffu && pend == 0u)) {
-                dconv2_compact(t, c);
-                return;
-            }
-        }
+            dconv2_compact(t, c);
+        } else {
 #ifdef DAL3_DEC_COUNT
-        ++n_dense, n_live += 32;
+            ++n_dense, n_live += 32;
 #endif
-        dconv2_part(t);
+            dconv2_part(t);
+        }
     };
     auto relu_note = [&](f32x16& t, int i) {           // ReLU and liveness of two registers per fragment group
         t[2 * i] = relu1(t[2 * i]);
@@ -383,14 +384,14 @@ __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN&
 // The compacted body is taken by the tiles of a crop whose term gb is negative in at least DAL3_DEC_MIN_DEAD of the 512
 // dconv1 channels — the channels that are dead for (nearly) every point of the crop — and never when the blob's guard
 // flag is set. Every other tile runs the dense body, which is the kernel as it was: no ballot, no branch in its chunk
-// loop. (The choice is about speed only: both bodies give the same bits. Inside the compacted body a fully live chunk
-// still takes the register path, but the branch around it costs that body's chunk loop ~100 accumulator register copies
-// per chunk, profiles/LEDGER_r08.md; a crop with few dead channels would lose more there than compaction returns.)
-// 192 = 0.375 of the channels is the smallest dead share with a measured gain: with exactly that share dead in every
-// tile (the other channels live) the compacted body runs the 4096 x 1024 launch in 13.75 / 13.29 / 12.75 / 12.27 ms at
-// 0.25 / 0.3125 / 0.375 / 0.4375 against 12.97 ms dense — break-even near 0.35 (LEDGER_r08.md, section 3).
+// loop. (The choice is about speed only: both bodies give the same bits. The compacted body sends every chunk, a fully
+// live one included, through the slab: a crop with few dead channels would lose more to the ballots, the slab and the
+// mask walk than compaction returns.)
+// 160 = 0.3125 of the channels is the smallest dead share with a measured gain: with exactly that share dead in every
+// tile (the other channels live) the compacted body runs the 4096 x 1024 launch in 14.32 / 13.28 / 12.75 / 12.16 / 11.66 ms
+// at 0.125 / 0.25 / 0.3125 / 0.375 / 0.4375 against 12.98 - 13.06 ms dense — break-even near 0.28 (LEDGER_r09.md, section 3).
 #ifndef DAL3_DEC_MIN_DEAD
-#define DAL3_DEC_MIN_DEAD 192
+#define DAL3_DEC_MIN_DEAD 160
 #endif
 template <int T>
 __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_decode_kernel(InsSegW w, BCN pts, int c_in, int n_pts,
