@@ -164,6 +164,37 @@ class BestGtArgs(C.Structure):
                 ("best_iou_3d", vp), ("best_iou_bev", vp), ("best_index", vp)]
 
 
+NMS_MAX_PRE = 65536
+NMS_ROTATE, NMS_CIRCLE = 0, 1
+NMS_TOO_MANY, NMS_BAD_SEGMENT, DECODE_OVERFLOW = 16, 32, 64
+
+
+class NmsArgs(C.Structure):
+    """dal3_nms_args"""
+    _fields_ = [("F", C.c_int64), ("K", C.c_int64), ("seg_offsets", vp), ("seg_offsets_host", vp), ("seg_count", vp),
+                ("boxes", vp), ("scores", vp), ("box_stride", C.c_int64), ("yaw_col", C.c_int32), ("boxes_f64", C.c_int32),
+                ("mode", C.c_int32), ("thresh", C.c_float), ("pre_max", C.c_int64), ("post_max", C.c_int64),
+                ("stride", C.c_int64), ("max_workgroups", C.c_int32), ("mirror", C.c_int32), ("keep", vp),
+                ("keep_count", vp), ("order", vp), ("status", vp), ("workspace", vp), ("workspace_bytes", C.c_size_t)]
+
+
+class Map(C.Structure):
+    """dal3_map: a float32 (B, H, W, C) view by element strides"""
+    _fields_ = [("data", vp), ("stride_b", C.c_int64), ("stride_h", C.c_int64), ("stride_w", C.c_int64),
+                ("stride_c", C.c_int64)]
+
+
+class CenterDecodeArgs(C.Structure):
+    """dal3_center_decode_args"""
+    _fields_ = [("B", C.c_int64), ("H", C.c_int64), ("W", C.c_int64), ("C", C.c_int32), ("has_range", C.c_int32),
+                ("hm", Map), ("reg", Map), ("height", Map), ("dim", Map), ("rot", Map), ("vel", Map),
+                ("out_size_factor", C.c_float), ("voxel_size", C.c_float * 2), ("pc_range", C.c_float * 2),
+                ("score_threshold", C.c_float), ("range", C.c_float * 6), ("F", C.c_int64), ("K", C.c_int64),
+                ("seg_first", C.c_int64), ("seg_step", C.c_int64), ("seg_offsets", vp), ("boxes", vp), ("scores", vp),
+                ("labels", vp), ("cell", vp), ("seg_count", vp), ("status", vp), ("max_workgroups", C.c_int64),
+                ("workspace", vp), ("workspace_bytes", C.c_size_t)]
+
+
 # every symbol include/dal3.h declares: (restype, argtypes)
 _i, _i64, _u64, _sz = C.c_int, C.c_int64, C.c_uint64, C.c_size_t
 SIGNATURES = {
@@ -209,6 +240,10 @@ SIGNATURES = {
     "dal3_score_workspace_bytes": (_sz, [_i64]),
     "dal3_score_tracks": (_i, [C.POINTER(ScoreArgs), vp]),
     "dal3_best_gt_iou": (_i, [C.POINTER(BestGtArgs), vp]),
+    "dal3_nms_workspace_bytes": (_sz, [_i64, _i]),
+    "dal3_nms": (_i, [C.POINTER(NmsArgs), vp]),
+    "dal3_center_decode_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "dal3_center_decode": (_i, [C.POINTER(CenterDecodeArgs), vp]),
     "dal3_crop_workspace_bytes": (_sz, [_i64, _i64]),
     "dal3_crop_count": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, _sz, vp]),
     "dal3_crop_fill": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, vp, vp, vp, _i64, vp, _sz, vp]),

@@ -1110,6 +1110,78 @@ extern "C" int dal3_best_gt_iou(const dal3_best_gt_args* args, dal3_stream strea
     return 0;
 }
 
+extern "C" size_t dal3_nms_workspace_bytes(int64_t K, int boxes_f64) {
+    if (K < 0 || K > DAL3_MAX_ITEMS || (boxes_f64 != 0 && boxes_f64 != 1)) return 0;
+    return nms_workspace_bytes(K, boxes_f64);
+}
+
+extern "C" int dal3_nms(const dal3_nms_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "nms: null args");
+    const dal3_nms_args& a = *args;
+    if (a.F < 0 || a.K < 0 || a.F > DAL3_MAX_ITEMS || a.K > DAL3_MAX_ITEMS)
+        return fail(DAL3_EINVAL, "nms: bad F / K (0 <= F, K <= DAL3_MAX_ITEMS)");
+    if (a.mode != DAL3_NMS_ROTATE && a.mode != DAL3_NMS_CIRCLE) return fail(DAL3_EINVAL, "nms: unknown mode %d", (int)a.mode);
+    if ((a.boxes_f64 != 0 && a.boxes_f64 != 1) || (a.mirror != 0 && a.mirror != 1) || a.max_workgroups < 0)
+        return fail(DAL3_EINVAL, "nms: bad argument (boxes_f64 0 or 1, mirror 0 or 1, max_workgroups >= 0)");
+    if (a.box_stride < 7 || a.yaw_col < 6 || a.yaw_col >= a.box_stride)
+        return fail(DAL3_EINVAL, "nms: bad box layout (box_stride >= 7, 6 <= yaw_col < box_stride)");
+    if (a.pre_max < 0 || a.post_max < 0 || a.stride < 0) return fail(DAL3_EINVAL, "nms: negative pre_max / post_max / stride");
+    if (a.pre_max > DAL3_NMS_MAX_PRE) return fail(DAL3_EINVAL, "nms: pre_max above DAL3_NMS_MAX_PRE (%d)", DAL3_NMS_MAX_PRE);
+    if (a.thresh != a.thresh) return fail(DAL3_EINVAL, "nms: thresh is NaN");
+    if (a.F == 0) return 0;
+    if (!a.keep_count || !a.status || !a.seg_offsets || !a.seg_offsets_host)
+        return fail(DAL3_EINVAL, "nms: null keep_count / status / seg_offsets / seg_offsets_host");
+    int64_t max_n = 0;
+    for (int64_t f = 0; f < a.F; ++f) {
+        const int64_t d0 = a.seg_offsets_host[f], d1 = a.seg_offsets_host[f + 1];
+        if (d0 < 0 || d1 < d0 || d1 > a.K)
+            return fail(DAL3_EINVAL, "nms: seg_offsets must be non-decreasing within [0, K] (segment %lld: %lld .. %lld)",
+                        (long long)f, (long long)d0, (long long)d1);
+        if (d1 - d0 > max_n) max_n = d1 - d0;
+    }
+    const int64_t need = a.post_max > 0 && a.post_max < max_n ? a.post_max : max_n;
+    if (a.stride < need)
+        return fail(DAL3_EINVAL, "nms: stride %lld too small (min(post_max or N, N) = %lld)", (long long)a.stride, (long long)need);
+    if (a.stride > 0 && !a.keep) return fail(DAL3_EINVAL, "nms: null keep");
+    if (a.K > 0 && (!a.boxes || !a.scores || !a.workspace)) return fail(DAL3_EINVAL, "nms: null boxes / scores / workspace");
+    if (a.workspace_bytes < nms_workspace_bytes(a.K, a.boxes_f64))
+        return fail(DAL3_EWORKSPACE, "nms: workspace too small (dal3_nms_workspace_bytes)");
+    if (reinterpret_cast<uintptr_t>(a.workspace) & 7) return fail(DAL3_EINVAL, "nms: workspace must be 8-byte aligned");
+    HIP_TRY(launch_nms(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+extern "C" size_t dal3_center_decode_workspace_bytes(int64_t B, int64_t H, int64_t W) {
+    if (B < 0 || H < 0 || W < 0 || B > DAL3_MAX_ITEMS || H > DAL3_MAX_ITEMS || W > DAL3_MAX_ITEMS || H * W > DAL3_MAX_ITEMS)
+        return 0;
+    return center_decode_workspace_bytes(B, H, W);
+}
+
+extern "C" int dal3_center_decode(const dal3_center_decode_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "center_decode: null args");
+    const dal3_center_decode_args& a = *args;
+    if (a.B < 0 || a.H <= 0 || a.W <= 0 || a.B > DAL3_MAX_ITEMS || a.H > DAL3_MAX_ITEMS || a.W > DAL3_MAX_ITEMS ||
+        a.H * a.W > DAL3_MAX_ITEMS)
+        return fail(DAL3_EINVAL, "center_decode: bad B / H / W (H, W >= 1, B, H W <= DAL3_MAX_ITEMS)");
+    if (a.C < 1 || a.C > 64) return fail(DAL3_EINVAL, "center_decode: bad C (1 <= C <= 64)");
+    if (a.F < 0 || a.K < 0 || a.F > DAL3_MAX_ITEMS || a.K > DAL3_MAX_ITEMS || a.max_workgroups < 0)
+        return fail(DAL3_EINVAL, "center_decode: bad F / K / max_workgroups");
+    if (a.B == 0) return 0;
+    const int64_t last = a.seg_first + (a.B - 1) * a.seg_step;
+    if (a.seg_first < 0 || a.seg_first >= a.F || last < 0 || last >= a.F || (a.B > 1 && a.seg_step == 0))
+        return fail(DAL3_EINVAL, "center_decode: segments seg_first + b * seg_step must be distinct and lie in [0, F)");
+    if (!a.hm.data || !a.reg.data || !a.height.data || !a.dim.data || !a.rot.data)
+        return fail(DAL3_EINVAL, "center_decode: null hm / reg / height / dim / rot");
+    if (!a.seg_offsets || !a.seg_count || !a.status || !a.workspace)
+        return fail(DAL3_EINVAL, "center_decode: null seg_offsets / seg_count / status / workspace");
+    if (a.K > 0 && (!a.boxes || !a.scores || !a.labels || !a.cell))
+        return fail(DAL3_EINVAL, "center_decode: null boxes / scores / labels / cell");
+    if (a.workspace_bytes < center_decode_workspace_bytes(a.B, a.H, a.W))
+        return fail(DAL3_EWORKSPACE, "center_decode: workspace too small (dal3_center_decode_workspace_bytes)");
+    HIP_TRY(launch_center_decode(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 extern "C" size_t dal3_crop_workspace_bytes(int64_t K_total, int64_t max_points_per_frame) {
     if (K_total <= 0 || max_points_per_frame < 0) return 0;
     return crop_workspace_bytes(K_total, max_points_per_frame);

@@ -278,6 +278,11 @@ hipError_t launch_motion_classify(const dal3_motion_classify_args* a, hipStream_
 size_t score_workspace_bytes(int64_t S);
 hipError_t launch_score_tracks(const dal3_score_args* a, hipStream_t s);
 hipError_t launch_best_gt_iou(const dal3_best_gt_args* a, hipStream_t s);
+// detector post-processing (dal3_nms.hip): sort + suppress, one workgroup per segment; count / scan / fill of the decode
+size_t nms_workspace_bytes(int64_t K, int boxes_f64);
+hipError_t launch_nms(const dal3_nms_args* a, hipStream_t s);
+size_t center_decode_workspace_bytes(int64_t B, int64_t H, int64_t W);
+hipError_t launch_center_decode(const dal3_center_decode_args* a, hipStream_t s);
 hipError_t launch_points_in_boxes(const void* points, int points_f64, int64_t P, int64_t stride, const double* planes,
                                   int K, int f32_math, uint8_t* inside, hipStream_t s);
 hipError_t launch_writeback(const double* final_boxes, const int32_t* final_idx, const double* pose_best,

@@ -655,6 +655,119 @@ typedef struct dal3_best_gt_args {
 
 int dal3_best_gt_iou(const dal3_best_gt_args* args, dal3_stream stream);
 
+/* ---- detector post-processing: the non-maximum suppression of det3d/core/bbox/box_torch_ops.py:248-277
+ * (rotate_nms_pcdet -> iou3d_nms_cuda.nms_gpu, det3d/ops/iou3d_nms/iou3d_nms_utils.py:75-92) and of
+ * det3d/core/utils/circle_nms_jit.py (center_head.py:498-506), for F segments in one enqueue with no host round trip,
+ * and the head decode of det3d/models/bbox_heads/center_head.py:342-419, 459-471.
+ *
+ * dal3_nms. A segment is one (frame, task) pair: rows [seg_offsets[f], seg_offsets[f+1]) of boxes (K, box_stride) and
+ * scores (K) float32, of which the first n = seg_count[f] are used (seg_count optional: NULL = all of them). Boxes are
+ * [x, y, z, l, w, h, ...] in the det3d convention with the yaw in column yaw_col (6 for plain (K,7) boxes; 8 with
+ * box_stride 9 reads center_head.py:471's boxes_for_nms out of the 9-column boxes without a copy), float32 or float64.
+ * The boxes are taken as dal3_box_iou_pairwise takes them (column 3 the extent along the yaw): what nms_gpu is handed.
+ * rotate_nms_pcdet first converts ITS boxes to that convention (box_torch_ops.py:255-257: columns 3 and 4 swapped,
+ * yaw -> -yaw - pi/2). The centres stay while the rectangles turn from yaw to -yaw, so this is not an isometry of the
+ * pair and it does change the IoUs; mirror = 1 applies it as each box is loaded, in the input precision (float32:
+ * -yaw - float32(pi/2), as torch forms it), and every statement below then holds for the converted boxes.
+ * Per segment the result is defined exactly:
+ *   order       the rows by score descending, NaN scores first (torch.sort(descending=True), argsort()[::-1]), equal
+ *               scores (-0 == +0) by ascending row. The reference's sorts are not stable; this order is the definition here.
+ *   candidates  the first m = min(n, pre_max) of that order (pre_max 0: no cut), m <= DAL3_NMS_MAX_PRE.
+ *   scan        in that order a candidate is kept when no earlier KEPT candidate suppresses it. DAL3_NMS_ROTATE: i
+ *               suppresses j when iou_bev(i, j) > thresh, iou_bev the bits of dal3_box_iou_pairwise(box_i, box_j); a NaN
+ *               IoU suppresses nothing (a non-finite box is kept and suppresses nobody). DAL3_NMS_CIRCLE: i suppresses j
+ *               when dx*dx + dy*dy <= thresh, dx and dy the centre differences (taken in the input precision, rounded
+ *               to float32), the two products and the sum each rounded in float32; the SQUARED distance is compared
+ *               with thresh as given, as circle_nms does.
+ *   output      the kept candidates' rows relative to the segment, in scan order, the first post_max of them
+ *               (post_max 0: no cut): keep[f * stride + [0, keep_count[f])). The scan stops at post_max keeps.
+ * stride >= min(post_max or N, N), N the largest segment (by seg_offsets). seg_offsets is given twice: on the device for
+ * the kernels and on the HOST (seg_offsets_host, the same values, read only during the call) for the checks made before
+ * any launch: non-decreasing, within [0, K], stride. order (optional, (K)): the full sorted order of every segment at
+ * its rows. Nothing is read back: a segment whose candidates exceed DAL3_NMS_MAX_PRE (pre_max 0 and n larger) sets
+ * DAL3_NMS_TOO_MANY in *status and keeps nothing; device offsets that differ from a valid CSR set DAL3_NMS_BAD_SEGMENT
+ * likewise. status is OR-ed into (the bits are numbered beside DAL3_TRACK_* / DAL3_MOTION_*). The result is a function
+ * of the segment alone: the same for every max_workgroups (0: one workgroup per segment), every run, and however the
+ * segments are split over calls. Only the IoUs of KEPT candidates against later ones are ever evaluated and no n x n
+ * mask exists: workspace is dal3_nms_workspace_bytes(K, boxes_f64) = O(K). F, K <= DAL3_MAX_ITEMS. */
+#define DAL3_NMS_MAX_PRE 65536
+enum { DAL3_NMS_ROTATE = 0, DAL3_NMS_CIRCLE = 1 };
+enum { DAL3_NMS_TOO_MANY = 16, DAL3_NMS_BAD_SEGMENT = 32, DAL3_DECODE_OVERFLOW = 64 };   /* status bits */
+
+typedef struct dal3_nms_args {
+    int64_t F, K;                        /* segments, rows */
+    const int64_t* seg_offsets;          /* (F+1) device */
+    const int64_t* seg_offsets_host;     /* (F+1) HOST copy of the same values */
+    const int32_t* seg_count;            /* optional (F) device: rows in use per segment (dal3_center_decode's) */
+    const void* boxes;                   /* (K, box_stride) */
+    const float* scores;                 /* (K) */
+    int64_t box_stride;                  /* elements per box row, >= 7 */
+    int32_t yaw_col;                     /* 6 <= yaw_col < box_stride */
+    int32_t boxes_f64;                   /* 0 or 1 */
+    int32_t mode;                        /* DAL3_NMS_ROTATE / DAL3_NMS_CIRCLE */
+    float thresh;
+    int64_t pre_max, post_max;           /* 0: no cut */
+    int64_t stride;                      /* keep's row length */
+    int32_t max_workgroups;              /* 0: one per segment */
+    int32_t mirror;                      /* 0 or 1: convert each box as rotate_nms_pcdet does (see above) */
+    int32_t* keep;                       /* (F, stride) */
+    int32_t* keep_count;                 /* (F) */
+    int32_t* order;                      /* optional (K) */
+    int32_t* status;                     /* (1) OR-ed */
+    void* workspace;
+    size_t workspace_bytes;
+} dal3_nms_args;
+
+size_t dal3_nms_workspace_bytes(int64_t K, int boxes_f64);
+int dal3_nms(const dal3_nms_args* args, dal3_stream stream);
+
+/* dal3_center_decode: CenterHead.predict's arithmetic for one task (center_head.py:342-419 without double_flip) and
+ * post_processing's masks (center_head.py:459-469), B samples in one enqueue. The maps are float32 views (B, H, W, C)
+ * with ELEMENT strides: NHWC as the reference's permute(0, 2, 3, 1).contiguous() leaves them, or the network's NCHW as
+ * it is. Per cell (row, col), every operation a separately rounded float32, in this order:
+ *   score = max over classes of sigmoid(hm) = 1 / (1 + exp(-hm)), label = the FIRST maximum (torch.max);
+ *   x = ((col + reg[0]) * out_size_factor) * voxel_size[0] + pc_range[0], y likewise from row and reg[1]; z = height;
+ *   dim = exp(dim); rot = atan2(rot[0], rot[1]).
+ * A cell survives when score > score_threshold (a NaN fails) and, with has_range, x, y, z lie inside
+ * post_center_limit_range = range[0..2] .. range[3..5] inclusive. Sample b's survivors go, IN CELL ORDER (an ordered
+ * compaction by ballot scans: no atomic decides a position), to the rows of segment f = seg_first + b * seg_step:
+ * boxes (K, 9) [x, y, z, dim0, dim1, dim2, vel0, vel1, rot] with vel, else (K, 7); scores; labels (class within the
+ * task); cell = row * W + col; seg_count[f] = their number. A segment holds seg_offsets[f+1] - seg_offsets[f] rows:
+ * more survivors set DAL3_DECODE_OVERFLOW in *status and the first that fit are kept; nothing is written outside the
+ * segment's rows, nor outside [0, K) (DAL3_NMS_BAD_SEGMENT). H * W <= DAL3_MAX_ITEMS, B <= DAL3_MAX_ITEMS, C <= 64.
+ * workspace: dal3_center_decode_workspace_bytes(B, H, W). */
+typedef struct dal3_map {
+    const float* data;
+    int64_t stride_b, stride_h, stride_w, stride_c;   /* in elements */
+} dal3_map;
+
+typedef struct dal3_center_decode_args {
+    int64_t B, H, W;
+    int32_t C;                           /* classes of this task (hm's channels) */
+    int32_t has_range;                   /* 0: post_center_limit_range is empty */
+    dal3_map hm, reg, height, dim, rot, vel;   /* vel.data NULL: no velocity, 7-column boxes */
+    float out_size_factor;
+    float voxel_size[2];
+    float pc_range[2];
+    float score_threshold;
+    float range[6];
+    int64_t F, K;                        /* segments and rows of the outputs */
+    int64_t seg_first, seg_step;         /* sample b -> segment seg_first + b * seg_step */
+    const int64_t* seg_offsets;          /* (F+1) device */
+    float* boxes;                        /* (K, 9 or 7) */
+    float* scores;                       /* (K) */
+    int32_t* labels;                     /* (K) */
+    int32_t* cell;                       /* (K) */
+    int32_t* seg_count;                  /* (F): written for this call's segments only */
+    int32_t* status;                     /* (1) OR-ed */
+    int64_t max_workgroups;              /* 0: no cap */
+    void* workspace;
+    size_t workspace_bytes;
+} dal3_center_decode_args;
+
+size_t dal3_center_decode_workspace_bytes(int64_t B, int64_t H, int64_t W);
+int dal3_center_decode(const dal3_center_decode_args* args, dal3_stream stream);
+
 /* ---- crop extraction from full sweeps: the per-detection loop of _create_pd_detection
  * (det3d/datasets/waymo/waymo_common.py:166-171, 193) for F frames at once. points (P_total,3) f32 vehicle-frame
  * sweeps concatenated, point_offsets (F+1); planes (K_total,6,4) f64 face equations of every frame's detections
