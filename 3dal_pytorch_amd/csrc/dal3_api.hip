@@ -4,6 +4,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include "dal3_block.h"     // Carver: the workspace carving
 #include "dal3_kernels.h"
 #include "dal3_lp.h"
 
@@ -482,22 +483,6 @@ extern "C" int dal3_pack_weights(int head_kind, const dal3_layer* L, int n_layer
     TRY(pack_frag(L[3], PACK_FRAG_MT_MAJOR, 0, c[2], w.stream, f4, w.b4, s));
     return pack_fc(L + 4, w.fc, s);
 }
-
-// ---------------------------------------------------------------------------------- workspace carving
-struct Carver {
-    char* base;
-    size_t size, off;
-    bool ok;
-    Carver(void* p, size_t n) : base(static_cast<char*>(p)), size(n), off(0), ok(true) {}
-    template <typename T>
-    T* take(size_t count) {
-        const size_t bytes = (count * sizeof(T) + 255) & ~(size_t)255;
-        char* p = base ? base + off : nullptr;
-        off += bytes;
-        if (base && off > size) ok = false;
-        return reinterpret_cast<T*>(p);
-    }
-};
 
 static BCN to_bcn(const dal3_bcn& t) { return BCN{t.data, t.stride_b, t.stride_c, t.stride_n, t.dtype, t.flags}; }
 

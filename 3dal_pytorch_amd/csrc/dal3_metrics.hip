@@ -45,12 +45,6 @@ __device__ __forceinline__ int bm_argmax(const void* p, int64_t row, int f64) {
     return best;
 }
 
-__device__ __forceinline__ double bm_mean(int sc, int j) {     // MEAN_SIZE_ARR[sc][j], float64 as the reference's table
-    constexpr double m[9] = {DAL3_MEAN_SIZE_VALUES};
-    return sc == 0 ? (j == 0 ? m[0] : j == 1 ? m[1] : m[2])
-                   : sc == 1 ? (j == 0 ? m[3] : j == 1 ? m[4] : m[5]) : (j == 0 ? m[6] : j == 1 ? m[7] : m[8]);
-}
-
 // [cx, cy, cz, l, w, h, yaw] of class2angle / class2size; an out-of-range class gives NaN and reads nothing
 __device__ __forceinline__ void bm_box(const void* center, int64_t c_row, int c_f64, int64_t hc, const void* hres,
                                        int64_t h_at, int h_f64, int64_t sc, const void* sres, int64_t s_at, int s_f64,
@@ -67,7 +61,7 @@ __device__ __forceinline__ void bm_box(const void* center, int64_t c_row, int c_
         box[6] = nan;
     }
 #pragma unroll
-    for (int j = 0; j < 3; ++j) box[3 + j] = (sc >= 0 && sc < 3) ? bm_mean((int)sc, j) + bm_ld(sres, s_at + j, s_f64) : nan;
+    for (int j = 0; j < 3; ++j) box[3 + j] = (sc >= 0 && sc < 3) ? mean_size_f64((int)sc, j) + bm_ld(sres, s_at + j, s_f64) : nan;
 }
 
 __global__ __launch_bounds__(BM_BLOCK) void box_estimation_metrics_kernel(const dal3_box_metric_args a, int64_t chunks) {

@@ -446,6 +446,7 @@ __device__ __forceinline__ uint32_t hash_key(uint64_t seed, uint64_t item, uint3
 }
 
 // exclusive prefix of `flag` over the 256 threads of the block (thread order); *total = block sum
+// (not dal3_block.h's block_rank: the barrier sits BEFORE the LDS write, so back-to-back calls can reuse lds_wave)
 __device__ __forceinline__ int block_scan_flag(bool flag, int* total, int* lds_wave /*[8]*/) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const unsigned long long bal = __ballot(flag);

@@ -16,6 +16,7 @@
 //
 // Features are one wave per group: the float64 sums are the sequential sums NumPy forms along axis 0, taken in two
 // passes (mean, then squared deviations); the integer reductions run across the lanes.
+#include "dal3_block.h"
 #include "dal3_kernels.h"
 
 // no FMA contraction: the sums restate NumPy's float64 operations one by one
@@ -30,7 +31,6 @@ constexpr int64_t MO_CHUNK = (int64_t)MO_BLOCK * MO_TILES;       // 4096 entries
 constexpr int MO_SCAN_BLOCK = 1024;
 constexpr int64_t MO_FLAG_TILE = 1024;                           // groups per compaction tile (4 per thread)
 
-__host__ __device__ inline size_t mo_align(size_t b) { return (b + 255) & ~(size_t)255; }
 __host__ __device__ inline int64_t mo_chunks(int64_t E) { return (E + MO_CHUNK - 1) / MO_CHUNK; }
 
 struct GroupWs {
@@ -39,16 +39,25 @@ struct GroupWs {
     int32_t* hist;                              // (256, chunks)
 };
 
-__host__ __device__ inline GroupWs group_ws(void* base, int64_t E) {
-    char* p = static_cast<char*>(base);
+inline GroupWs carve_group(Carver& c, int64_t E) {
     GroupWs w;
-    w.key[0] = reinterpret_cast<int32_t*>(p);
-    p += mo_align((size_t)E * 4);
-    w.key[1] = reinterpret_cast<int32_t*>(p);
-    p += mo_align((size_t)E * 4);
-    w.pos = reinterpret_cast<int32_t*>(p);
-    p += mo_align((size_t)E * 4);
-    w.hist = reinterpret_cast<int32_t*>(p);
+    w.key[0] = c.take<int32_t>((size_t)E);
+    w.key[1] = c.take<int32_t>((size_t)E);
+    w.pos = c.take<int32_t>((size_t)E);
+    w.hist = c.take<int32_t>((size_t)256 * (size_t)mo_chunks(E));
+    return w;
+}
+
+struct ClassifyWs {
+    int32_t* stat;                              // (tiles) each: the tiles' kept static / dynamic groups
+    int32_t* dyn;
+};
+
+inline ClassifyWs carve_classify(Carver& c, int64_t T) {
+    const size_t tiles = (size_t)((T + MO_FLAG_TILE - 1) / MO_FLAG_TILE);
+    ClassifyWs w;
+    w.stat = c.take<int32_t>(tiles);
+    w.dyn = c.take<int32_t>(tiles);
     return w;
 }
 
@@ -102,29 +111,11 @@ __global__ __launch_bounds__(MO_BLOCK) void radix_hist_kernel(const int32_t* key
     }
 }
 
-// in-place exclusive scan of n int32 by ONE workgroup: thread t owns the contiguous span [t * per, (t + 1) * per)
+// in-place exclusive scan of n int32 by ONE workgroup
 __global__ __launch_bounds__(MO_SCAN_BLOCK) void scan_kernel(int32_t* data, int64_t n, int64_t* total) {
     __shared__ int64_t s_part[MO_SCAN_BLOCK];
-    const int t = threadIdx.x;
-    const int64_t per = (n + MO_SCAN_BLOCK - 1) / MO_SCAN_BLOCK;
-    const int64_t lo = t * per < n ? t * per : n, hi = lo + per < n ? lo + per : n;
-    int64_t sum = 0;
-    for (int64_t i = lo; i < hi; ++i) sum += data[i];
-    s_part[t] = sum;
-    __syncthreads();
-    for (int off = 1; off < MO_SCAN_BLOCK; off <<= 1) {         // inclusive scan of the spans' sums
-        const int64_t add = t >= off ? s_part[t - off] : 0;
-        __syncthreads();
-        s_part[t] += add;
-        __syncthreads();
-    }
-    int64_t run = s_part[t] - sum;
-    for (int64_t i = lo; i < hi; ++i) {
-        const int32_t v = data[i];
-        data[i] = (int32_t)run;
-        run += v;
-    }
-    if (total && t == MO_SCAN_BLOCK - 1) *total = s_part[t];
+    const int64_t sum = block_scan_spans<MO_SCAN_BLOCK>(data, n, s_part);
+    if (total && threadIdx.x == MO_SCAN_BLOCK - 1) *total = sum;
 }
 
 // pos_in == nullptr: the first pass, the position is the index itself
@@ -133,45 +124,20 @@ __global__ __launch_bounds__(MO_BLOCK) void radix_scatter_kernel(const int32_t* 
                                                                  int32_t* pos_out) {
     __shared__ int32_t s_base[256];             // where the chunk's next entry of each digit goes
     __shared__ int32_t s_wave[MO_WAVES][256];   // the tile's count of each digit, per wave
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     const int64_t chunks = mo_chunks(E);
     for (int64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
         s_base[t] = hist[(int64_t)t * chunks + c];
         const int64_t e0 = c * MO_CHUNK;
         for (int r = 0; r < MO_TILES; ++r) {
-#pragma unroll
-            for (int w = 0; w < MO_WAVES; ++w) s_wave[w][t] = 0;
-            __syncthreads();                    // s_base / the zeroes are in place
             const int64_t i = e0 + (int64_t)r * MO_BLOCK + t;
             const bool live = i < E;
             const int32_t k = live ? key_in[i] : 0;
-            const int d = (k >> shift) & 255;
-            // the lanes of this wave that hold the same digit
-            unsigned long long peers = __ballot(live);
-#pragma unroll
-            for (int b = 0; b < 8; ++b) {
-                const bool bit = (d >> b) & 1;
-                const unsigned long long m = __ballot(bit);
-                peers &= bit ? m : ~m;
+            const int64_t o = radix_tile_step<MO_WAVES>(live, (k >> shift) & 255, s_base, s_wave);
+            if (o >= 0 && o < E) {              // live; the bound always holds for a table hist/scan made from these keys
+                key_out[o] = k;
+                pos_out[o] = pos_in ? pos_in[i] : (int32_t)i;
             }
-            const int32_t before = __popcll(peers & ((1ull << lane) - 1ull));
-            if (live && before == 0) s_wave[wave][d] = __popcll(peers);
-            __syncthreads();
-            if (live) {
-                int32_t off = before;
-#pragma unroll
-                for (int w = 0; w < MO_WAVES; ++w) off += w < wave ? s_wave[w][d] : 0;
-                const int64_t o = (int64_t)s_base[d] + off;
-                if (o >= 0 && o < E) {          // always true for a table hist/scan made from these keys
-                    key_out[o] = k;
-                    pos_out[o] = pos_in ? pos_in[i] : (int32_t)i;
-                }
-            }
-            __syncthreads();                    // every read of s_base is done
-            int32_t add = 0;
-#pragma unroll
-            for (int w = 0; w < MO_WAVES; ++w) add += s_wave[w][t];
-            s_base[t] += add;
             __syncthreads();
         }
     }
@@ -419,7 +385,7 @@ __global__ __launch_bounds__(MO_BLOCK) void classify_count_kernel(const dal3_mot
 __global__ __launch_bounds__(MO_BLOCK) void classify_fill_kernel(const dal3_motion_classify_args a, const int32_t* stat_start,
                                                                  const int32_t* dyn_start) {
     __shared__ int32_t s_cnt[MO_WAVES];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     const int64_t tiles = (a.T + MO_FLAG_TILE - 1) / MO_FLAG_TILE;
     for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         int32_t base[2] = {stat_start[tile], dyn_start[tile]};
@@ -429,19 +395,10 @@ __global__ __launch_bounds__(MO_BLOCK) void classify_fill_kernel(const dal3_moti
             const bool st = kept && a.is_static[g];
             for (int which = 0; which < 2; ++which) {
                 const bool flag = which == 0 ? st : (kept && !st);
-                const unsigned long long b = __ballot(flag);
-                if (lane == 0) s_cnt[wave] = __popcll(b);
-                __syncthreads();
-                int32_t before = __popcll(b & ((1ull << lane) - 1ull)), total = 0;
-#pragma unroll
-                for (int w = 0; w < MO_WAVES; ++w) {
-                    before += w < wave ? s_cnt[w] : 0;
-                    total += s_cnt[w];
-                }
-                const int64_t o = (int64_t)base[which] + before;
+                int32_t total;
+                const int64_t o = (int64_t)base[which] + block_rank<MO_WAVES>(flag, s_cnt, total);
                 if (flag && o >= 0 && o < a.T) (which == 0 ? a.static_ids : a.dynamic_ids)[o] = (int32_t)g;
                 base[which] += total;
-                __syncthreads();
             }
         }
     }
@@ -464,16 +421,20 @@ inline int radix_passes(int64_t T) {            // keys lie in [0, T]
 
 size_t group_workspace_bytes(int64_t E, int64_t T) {
     (void)T;
-    return 3 * mo_align((size_t)E * 4) + mo_align((size_t)256 * (size_t)mo_chunks(E) * 4);
+    Carver c(nullptr, 0);
+    carve_group(c, E);
+    return c.off;
 }
 
 size_t motion_classify_workspace_bytes(int64_t T) {
-    const size_t tiles = (size_t)((T + MO_FLAG_TILE - 1) / MO_FLAG_TILE);
-    return 2 * mo_align(tiles * 4);
+    Carver c(nullptr, 0);
+    carve_classify(c, T);
+    return c.off;
 }
 
 hipError_t launch_group_by_key(const dal3_group_args* a, hipStream_t s) {
-    const GroupWs ws = group_ws(a->workspace, a->E);
+    Carver c(a->workspace, a->workspace_bytes);
+    const GroupWs ws = carve_group(c, a->E);
     const int64_t E = a->E, chunks = mo_chunks(E);
     const int passes = radix_passes(a->T);
     const int32_t* sorted = ws.key[0];
@@ -520,8 +481,9 @@ hipError_t launch_gt_table(const dal3_gt_table_args* a, hipStream_t s) {
 
 hipError_t launch_motion_classify(const dal3_motion_classify_args* a, hipStream_t s) {
     const int64_t tiles = (a->T + MO_FLAG_TILE - 1) / MO_FLAG_TILE;
-    int32_t* stat = static_cast<int32_t*>(a->workspace);
-    int32_t* dyn = reinterpret_cast<int32_t*>(static_cast<char*>(a->workspace) + mo_align((size_t)tiles * 4));
+    Carver c(a->workspace, a->workspace_bytes);
+    const ClassifyWs ws = carve_classify(c, a->T);
+    int32_t *stat = ws.stat, *dyn = ws.dyn;
     if (tiles > 0)
         hipLaunchKernelGGL(classify_count_kernel, dim3(mo_grid(tiles, a->max_workgroups)), dim3(MO_BLOCK), 0, s, *a, stat, dyn);
     // with T == 0 the scans only write the two zero totals

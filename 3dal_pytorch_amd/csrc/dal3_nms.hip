@@ -27,6 +27,7 @@
 // The decode is an ordered compaction in three launches: per chunk of DEC_CHUNK cells the number of survivors, one
 // exclusive scan per sample, then each chunk again with ballot ranks. A cell's mask and values come from one function
 // (cell_eval) in both passes.
+#include "dal3_block.h"
 #include "dal3_kernels.h"
 
 // no FMA contraction: the IoU must be the bits of dal3_iou.hip's kernels (dal3_iou_pair.h), and the decode restates
@@ -44,8 +45,6 @@ constexpr int64_t DEC_CHUNK = (int64_t)DEC_BLOCK * DEC_TILES;    // 1024 cells
 
 #include "dal3_iou_pair.h"
 
-__host__ __device__ inline size_t nms_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct NmsWs {
     uint32_t* key[2];                           // (K) each: the sort keys, ping-pong
     int32_t* idx[2];                            // (K) each: the rows (relative to the segment), ping-pong; [0] ends sorted
@@ -53,22 +52,13 @@ struct NmsWs {
     void* table;                                // (K) IouBox<T> in sorted order
 };
 
-__host__ __device__ inline size_t nms_box_bytes(int f64) { return f64 ? sizeof(IouBox<double>) : sizeof(IouBox<float>); }
-
-__host__ __device__ inline NmsWs nms_ws(void* base, int64_t K) {
-    char* p = static_cast<char*>(base);
+inline NmsWs carve_nms(Carver& c, int64_t K, int f64) {
     NmsWs w;
-    for (int i = 0; i < 2; ++i) {
-        w.key[i] = reinterpret_cast<uint32_t*>(p);
-        p += nms_align((size_t)K * 4);
-    }
-    for (int i = 0; i < 2; ++i) {
-        w.idx[i] = reinterpret_cast<int32_t*>(p);
-        p += nms_align((size_t)K * 4);
-    }
-    w.kept = reinterpret_cast<int32_t*>(p);
-    p += nms_align((size_t)K * 4);
-    w.table = p;
+    for (int i = 0; i < 2; ++i) w.key[i] = c.take<uint32_t>((size_t)K);
+    for (int i = 0; i < 2; ++i) w.idx[i] = c.take<int32_t>((size_t)K);
+    w.kept = c.take<int32_t>((size_t)K);
+    if (f64) w.table = c.take<IouBox<double>>((size_t)K);
+    else w.table = c.take<IouBox<float>>((size_t)K);
     return w;
 }
 
@@ -122,7 +112,7 @@ __global__ __launch_bounds__(NMS_BLOCK) void nms_sort_kernel(const dal3_nms_args
     __shared__ int32_t s_base[256];             // where the segment's next entry of each digit goes
     __shared__ int32_t s_scan[256];
     __shared__ int32_t s_wave[NMS_WAVES][256];  // the tile's count of each digit, per wave
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     for (int64_t f = blockIdx.x; f < a.F; f += gridDim.x) {
         int64_t d0, n, m;
         nms_segment(a, f, d0, n, m);
@@ -146,46 +136,17 @@ __global__ __launch_bounds__(NMS_BLOCK) void nms_sort_kernel(const dal3_nms_args
             const int32_t mine = s_base[t];
             s_scan[t] = mine;
             __syncthreads();
-            for (int off = 1; off < 256; off <<= 1) {
-                const int32_t add = t >= off ? s_scan[t - off] : 0;
-                __syncthreads();
-                s_scan[t] += add;
-                __syncthreads();
-            }
+            block_scan_inclusive<256>(s_scan);
             s_base[t] = s_scan[t] - mine;
             for (int64_t e0 = 0; e0 < n; e0 += NMS_BLOCK) {
-#pragma unroll
-                for (int w = 0; w < NMS_WAVES; ++w) s_wave[w][t] = 0;
-                __syncthreads();                // s_base / the zeroes are in place
                 const int64_t i = e0 + t;
                 const bool live = i < n;
                 const uint32_t k = live ? key_in[i] : 0u;
-                const int d = (k >> shift) & 255;
-                unsigned long long peers = __ballot(live);      // the lanes of this wave that hold the same digit
-#pragma unroll
-                for (int b = 0; b < 8; ++b) {
-                    const bool bit = (d >> b) & 1;
-                    const unsigned long long mk = __ballot(bit);
-                    peers &= bit ? mk : ~mk;
+                const int64_t o = radix_tile_step<NMS_WAVES>(live, (k >> shift) & 255, s_base, s_wave);
+                if (o >= 0 && o < n) {          // live; the bound always holds for counts made from these keys
+                    key_out[o] = k;
+                    idx_out[o] = idx_in[i];
                 }
-                const int32_t before = __popcll(peers & ((1ull << lane) - 1ull));
-                if (live && before == 0) s_wave[wave][d] = __popcll(peers);
-                __syncthreads();
-                if (live) {
-                    int32_t off = before;
-#pragma unroll
-                    for (int w = 0; w < NMS_WAVES; ++w) off += w < wave ? s_wave[w][d] : 0;
-                    const int64_t o = (int64_t)s_base[d] + off;
-                    if (o >= 0 && o < n) {      // always true for counts made from these keys
-                        key_out[o] = k;
-                        idx_out[o] = idx_in[i];
-                    }
-                }
-                __syncthreads();                // every read of s_base is done
-                int32_t add = 0;
-#pragma unroll
-                for (int w = 0; w < NMS_WAVES; ++w) add += s_wave[w][t];
-                s_base[t] += add;
             }
             __syncthreads();                    // the pass's stores are visible to the whole workgroup
         }
@@ -343,29 +304,9 @@ __global__ __launch_bounds__(DEC_BLOCK) void decode_count_kernel(const dal3_cent
 __global__ __launch_bounds__(DEC_BLOCK) void decode_scan_kernel(const dal3_center_decode_args a, int32_t* counts,
                                                                 int64_t chunks) {
     __shared__ int64_t s_part[DEC_BLOCK];
-    const int t = threadIdx.x;
     for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {
-        int32_t* data = counts + b * chunks;
-        const int64_t per = (chunks + DEC_BLOCK - 1) / DEC_BLOCK;
-        const int64_t lo = t * per < chunks ? t * per : chunks, hi = lo + per < chunks ? lo + per : chunks;
-        int64_t sum = 0;
-        for (int64_t i = lo; i < hi; ++i) sum += data[i];
-        s_part[t] = sum;
-        __syncthreads();
-        for (int off = 1; off < DEC_BLOCK; off <<= 1) {
-            const int64_t add = t >= off ? s_part[t - off] : 0;
-            __syncthreads();
-            s_part[t] += add;
-            __syncthreads();
-        }
-        int64_t run = s_part[t] - sum;
-        for (int64_t i = lo; i < hi; ++i) {
-            const int32_t v = data[i];
-            data[i] = (int32_t)run;
-            run += v;
-        }
-        if (t == DEC_BLOCK - 1) {
-            const int64_t total = s_part[t];
+        const int64_t total = block_scan_spans<DEC_BLOCK>(counts + b * chunks, chunks, s_part);
+        if (threadIdx.x == DEC_BLOCK - 1) {
             const int64_t f = a.seg_first + b * a.seg_step;
             const int64_t d0 = a.seg_offsets[f], d1 = a.seg_offsets[f + 1];
             int64_t cap = d1 - d0;
@@ -384,7 +325,7 @@ __global__ __launch_bounds__(DEC_BLOCK) void decode_scan_kernel(const dal3_cente
 __global__ __launch_bounds__(DEC_BLOCK) void decode_fill_kernel(const dal3_center_decode_args a, const int32_t* counts,
                                                                 int64_t chunks) {
     __shared__ int32_t s_wave[DEC_WAVES];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     const int64_t HW = a.H * a.W;
     const int cols = a.vel.data ? 9 : 7;
     for (int64_t job = blockIdx.x; job < a.B * chunks; job += gridDim.x) {
@@ -398,16 +339,8 @@ __global__ __launch_bounds__(DEC_BLOCK) void decode_fill_kernel(const dal3_cente
             const uint32_t row = (uint32_t)cell / (uint32_t)a.W, col = (uint32_t)cell - row * (uint32_t)a.W;
             Cell o;
             const bool ok = cell < HW && cell_eval(a, b, row, col, o);
-            const unsigned long long mk = __ballot(ok);
-            if (lane == 0) s_wave[wave] = __popcll(mk);
-            __syncthreads();
-            int64_t pos = base + __popcll(mk & ((1ull << lane) - 1ull));
-            int32_t tile = 0;
-#pragma unroll
-            for (int w = 0; w < DEC_WAVES; ++w) {
-                pos += w < wave ? s_wave[w] : 0;
-                tile += s_wave[w];
-            }
+            int32_t tile;
+            const int64_t pos = base + block_rank<DEC_WAVES>(ok, s_wave, tile);
             if (ok && pos >= 0 && pos < cap) {
                 const int64_t k = d0 + pos;
                 float* q = a.boxes + k * cols;
@@ -427,7 +360,6 @@ __global__ __launch_bounds__(DEC_BLOCK) void decode_fill_kernel(const dal3_cente
                 a.cell[k] = (int32_t)cell;
             }
             base += tile;
-            __syncthreads();                    // s_wave is free again
         }
     }
 }
@@ -435,7 +367,9 @@ __global__ __launch_bounds__(DEC_BLOCK) void decode_fill_kernel(const dal3_cente
 }  // namespace
 
 size_t nms_workspace_bytes(int64_t K, int boxes_f64) {
-    return 5 * nms_align((size_t)K * 4) + nms_align((size_t)K * nms_box_bytes(boxes_f64));
+    Carver c(nullptr, 0);
+    carve_nms(c, K, boxes_f64);
+    return c.off;
 }
 
 hipError_t launch_nms(const dal3_nms_args* args, hipStream_t s) {
@@ -443,7 +377,8 @@ hipError_t launch_nms(const dal3_nms_args* args, hipStream_t s) {
     if (a.F <= 0) return hipSuccess;
     int64_t grid = a.F;
     if (a.max_workgroups > 0 && grid > a.max_workgroups) grid = a.max_workgroups;
-    const NmsWs ws = nms_ws(a.workspace, a.K);
+    Carver c(a.workspace, a.workspace_bytes);
+    const NmsWs ws = carve_nms(c, a.K, a.boxes_f64);
     const dim3 g((unsigned)grid), blk(NMS_BLOCK);
     if (a.K > 0) {
         if (a.boxes_f64) hipLaunchKernelGGL(nms_sort_kernel<double>, g, blk, 0, s, a, ws);
@@ -461,15 +396,23 @@ hipError_t launch_nms(const dal3_nms_args* args, hipStream_t s) {
 
 static int64_t decode_chunks(int64_t H, int64_t W) { return (H * W + DEC_CHUNK - 1) / DEC_CHUNK; }
 
+// the one array: every (sample, chunk)'s survivors, then their exclusive scan per sample
+static int32_t* carve_decode(Carver& c, int64_t B, int64_t H, int64_t W) {
+    return c.take<int32_t>((size_t)(B * decode_chunks(H, W)));
+}
+
 size_t center_decode_workspace_bytes(int64_t B, int64_t H, int64_t W) {
-    return nms_align((size_t)(B * decode_chunks(H, W)) * 4);
+    Carver c(nullptr, 0);
+    carve_decode(c, B, H, W);
+    return c.off;
 }
 
 hipError_t launch_center_decode(const dal3_center_decode_args* args, hipStream_t s) {
     const dal3_center_decode_args& a = *args;
     if (a.B <= 0) return hipSuccess;
     const int64_t chunks = decode_chunks(a.H, a.W);
-    int32_t* counts = static_cast<int32_t*>(a.workspace);
+    Carver c(a.workspace, a.workspace_bytes);
+    int32_t* counts = carve_decode(c, a.B, a.H, a.W);
     int64_t jobs = a.B * chunks, samples = a.B;
     if (a.max_workgroups > 0 && jobs > a.max_workgroups) jobs = a.max_workgroups;
     if (a.max_workgroups > 0 && samples > a.max_workgroups) samples = a.max_workgroups;

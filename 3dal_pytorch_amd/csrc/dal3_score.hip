@@ -28,12 +28,6 @@ struct ScorePartial {                           // one chunk's sums (40 bytes)
     uint32_t n[SC_COUNTS];
 };
 
-__device__ __forceinline__ double sc_mean(int sc, int j) {     // MEAN_SIZE_ARR[sc][j], float64 as the reference's table
-    constexpr double m[9] = {DAL3_MEAN_SIZE_VALUES};
-    return sc == 0 ? (j == 0 ? m[0] : j == 1 ? m[1] : m[2])
-                   : sc == 1 ? (j == 0 ? m[3] : j == 1 ? m[4] : m[5]) : (j == 0 ? m[6] : j == 1 ? m[7] : m[8]);
-}
-
 // class2size(*size2class(lwh)) of tools/utils.py:62-67,77-79: the class is np.argmin of np.linalg.norm(lwh - MEAN,
 // axis=1) (the first minimum; a NaN is the minimum), the size MEAN[class] + (lwh - MEAN[class])
 __device__ __forceinline__ void sc_size_round_trip(const double (&lwh)[3], double (&out)[3]) {
@@ -41,7 +35,7 @@ __device__ __forceinline__ void sc_size_round_trip(const double (&lwh)[3], doubl
     double bv = 0.0;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        const double dx = lwh[0] - sc_mean(c, 0), dy = lwh[1] - sc_mean(c, 1), dz = lwh[2] - sc_mean(c, 2);
+        const double dx = lwh[0] - mean_size_f64(c, 0), dy = lwh[1] - mean_size_f64(c, 1), dz = lwh[2] - mean_size_f64(c, 2);
         const double d = sqrt(dx * dx + dy * dy + dz * dz);
         if (c == 0) {
             bv = d;
@@ -51,7 +45,7 @@ __device__ __forceinline__ void sc_size_round_trip(const double (&lwh)[3], doubl
         }
     }
 #pragma unroll
-    for (int j = 0; j < 3; ++j) out[j] = sc_mean(best, j) + (lwh[j] - sc_mean(best, j));
+    for (int j = 0; j < 3; ++j) out[j] = mean_size_f64(best, j) + (lwh[j] - mean_size_f64(best, j));
 }
 
 // a % b of NumPy / Python floats for b > 0 (npy_divmod): fmod, moved into [0, b) when negative

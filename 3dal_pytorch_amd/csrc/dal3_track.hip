@@ -11,6 +11,7 @@
 //      output (box id, tracking id) written.
 // Ids are counted per sequence from 1; dal3_track_finalize adds the exclusive scan of the per-sequence counts, so the
 // ids do not depend on which workgroup ran which sequence.
+#include "dal3_block.h"
 #include "dal3_kernels.h"
 
 // no FMA contraction: the distance is numpy's float32 dx*dx + dy*dy then sqrt, and the match scores pairs with the
@@ -40,21 +41,19 @@ struct TrackWs {
     int64_t* seq_ids;                           // (S) new ids of each sequence
 };
 
-__host__ __device__ inline size_t tk_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
-__host__ __device__ inline TrackWs track_ws(void* base, int64_t S, int64_t K, int64_t cap) {
-    char* p = static_cast<char*>(base);
+__host__ __device__ inline TrackWs carve_track(Carver& c, int64_t S, int64_t K, int64_t cap) {
     TrackWs w;
-    w.slots = reinterpret_cast<TrackSlot*>(p);
-    p += tk_align((size_t)S * 2 * (size_t)cap * sizeof(TrackSlot));
-    w.row_best = reinterpret_cast<int32_t*>(p);
-    p += tk_align((size_t)K * 4);
-    w.row_nan = reinterpret_cast<int32_t*>(p);
-    p += tk_align((size_t)K * 4);
-    w.row_col = reinterpret_cast<int32_t*>(p);
-    p += tk_align((size_t)K * 4);
-    w.seq_ids = reinterpret_cast<int64_t*>(p);
+    w.slots = c.take<TrackSlot>((size_t)S * 2 * (size_t)cap);
+    w.row_best = c.take<int32_t>((size_t)K);
+    w.row_nan = c.take<int32_t>((size_t)K);
+    w.row_col = c.take<int32_t>((size_t)K);
+    w.seq_ids = c.take<int64_t>((size_t)S);
     return w;
+}
+
+__device__ __forceinline__ TrackWs track_ws(const dal3_track_args& a) {
+    Carver c(a.workspace, a.workspace_bytes);
+    return carve_track(c, a.S, a.K, a.capacity);
 }
 
 // lexicographic (value, column) minimum across the wave; NaN never enters (it is tracked apart)
@@ -117,30 +116,12 @@ __device__ __forceinline__ void row_scan(const TrackSlot* old, int32_t M, float 
     best = (bj != TK_NONE && (double)bv < 1e16) ? bj : -1;
 }
 
-// exclusive rank of `flag` among the block's 256 threads, and the block's count; every thread must call it
-__device__ __forceinline__ int32_t block_rank(bool flag, int32_t* s_cnt, int32_t& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long b = __ballot(flag);
-    const int32_t in_wave = __popcll(b & ((1ull << lane) - 1ull));
-    if (lane == 0) s_cnt[wave] = __popcll(b);
-    __syncthreads();
-    int32_t before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < TK_WAVES; ++w) {
-        before += w < wave ? s_cnt[w] : 0;
-        total += s_cnt[w];
-    }
-    __syncthreads();
-    return before + in_wave;
-}
-
 __global__ __launch_bounds__(TK_BLOCK) void track_kernel(const dal3_track_args a) {
     __shared__ uint32_t s_taken[DAL3_TRACK_MAX_CAPACITY / 32];
     __shared__ int32_t s_cnt[TK_WAVES];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int64_t cap = a.capacity;
-    const TrackWs ws = track_ws(a.workspace, a.S, a.K, cap);
+    const TrackWs ws = track_ws(a);
     for (int64_t s = blockIdx.x; s < a.S; s += gridDim.x) {
         TrackSlot* buf[2] = {ws.slots + (2 * s) * cap, ws.slots + (2 * s + 1) * cap};
         int cur = 0;
@@ -211,7 +192,7 @@ __global__ __launch_bounds__(TK_BLOCK) void track_kernel(const dal3_track_args a
                 const int32_t i = i0 + t;
                 const int32_t col = (M > 0 && i < N) ? ws.row_col[d0 + i] : -1;
                 int32_t cm;
-                const int32_t rm = block_rank(col >= 0, s_cnt, cm);
+                const int32_t rm = block_rank<TK_WAVES>(col >= 0, s_cnt, cm);
                 if (col >= 0) {
                     a.box_ids[d0 + n_match + rm] = i;           // n_match + rm < N: inside the frame's rows
                     a.tracking_ids[d0 + n_match + rm] = old[col].id;
@@ -224,8 +205,8 @@ __global__ __launch_bounds__(TK_BLOCK) void track_kernel(const dal3_track_args a
                 const bool m = col >= 0;
                 const bool fresh = i < N && !m && (double)a.score[d0 + i] > a.score_thresh;
                 int32_t cm, cf;
-                const int32_t rm = block_rank(m, s_cnt, cm);
-                const int32_t rf = block_rank(fresh, s_cnt, cf);
+                const int32_t rm = block_rank<TK_WAVES>(m, s_cnt, cm);
+                const int32_t rf = block_rank<TK_WAVES>(fresh, s_cnt, cf);
                 TrackSlot e;
                 int64_t slot = -1;
                 if (m) {
@@ -254,7 +235,7 @@ __global__ __launch_bounds__(TK_BLOCK) void track_kernel(const dal3_track_args a
                 const int32_t j = j0 + t;
                 const bool keep = j < M && !tk_taken(s_taken, j) && old[j].age < a.max_age;
                 int32_t ck;
-                const int32_t rk = block_rank(keep, s_cnt, ck);
+                const int32_t rk = block_rank<TK_WAVES>(keep, s_cnt, ck);
                 const int64_t slot = (int64_t)n_match + n_fresh + n_keep + rk;
                 if (keep && slot < cap) {
                     TrackSlot e = old[j];
@@ -284,7 +265,7 @@ __global__ __launch_bounds__(TK_BLOCK) void track_kernel(const dal3_track_args a
 __global__ __launch_bounds__(TK_BLOCK) void track_finalize_kernel(const dal3_track_args a) {
     __shared__ int64_t s_sum[TK_BLOCK];
     const int t = threadIdx.x;
-    const TrackWs ws = track_ws(a.workspace, a.S, a.K, a.capacity);
+    const TrackWs ws = track_ws(a);
     const int64_t base = a.id_base ? *a.id_base : 0;
     for (int64_t s = blockIdx.x; s < a.S || (s == 0 && a.S == 0); s += gridDim.x) {
         int64_t part = 0;
@@ -314,19 +295,21 @@ struct MatchWs {
     int32_t* cand_obj;                          // (K) the frame's annotation index with IoU > thr, -1 none
 };
 
-__host__ __device__ inline MatchWs match_ws(void* base, int64_t K) {
-    char* p = static_cast<char*>(base);
+__host__ __device__ inline MatchWs carve_match(Carver& c, int64_t K) {
     MatchWs w;
-    w.first = reinterpret_cast<unsigned long long*>(p);
-    p += tk_align((size_t)K * 8);
-    w.cand_frame = reinterpret_cast<int32_t*>(p);
-    p += tk_align((size_t)K * 4);
-    w.cand_obj = reinterpret_cast<int32_t*>(p);
+    w.first = c.take<unsigned long long>((size_t)K);
+    w.cand_frame = c.take<int32_t>((size_t)K);
+    w.cand_obj = c.take<int32_t>((size_t)K);
     return w;
 }
 
+__device__ __forceinline__ MatchWs match_ws(const dal3_track_match_args& a) {
+    Carver c(a.workspace, a.workspace_bytes);
+    return carve_match(c, a.K);
+}
+
 __global__ __launch_bounds__(TK_BLOCK) void match_init_kernel(const dal3_track_match_args a) {
-    const MatchWs ws = match_ws(a.workspace, a.K);
+    const MatchWs ws = match_ws(a);
     for (int64_t k = (int64_t)blockIdx.x * TK_BLOCK + threadIdx.x; k < a.K; k += (int64_t)gridDim.x * TK_BLOCK)
         ws.first[k] = ~0ull;
 }
@@ -335,7 +318,7 @@ __global__ __launch_bounds__(TK_BLOCK) void match_init_kernel(const dal3_track_m
 // boxes_iou3d_gpu(det3d_t, bboxs_t); np.argmax's first maximum, a NaN anywhere in the row wins the argmax and fails
 // `> thr` (waymo_common.py:181-188)
 __global__ __launch_bounds__(TK_BLOCK) void match_candidates_kernel(const dal3_track_match_args a) {
-    const MatchWs ws = match_ws(a.workspace, a.K);
+    const MatchWs ws = match_ws(a);
     const int64_t base = a.id_base ? *a.id_base : 0;
     for (int64_t f = blockIdx.x; f < a.F; f += gridDim.x) {
         const int64_t d0 = a.frame_offsets[f], g0 = a.gt_offsets[f], G = a.gt_offsets[f + 1] - g0;
@@ -371,7 +354,7 @@ __global__ __launch_bounds__(TK_BLOCK) void match_candidates_kernel(const dal3_t
 
 // an id's match from its first candidate on (`matching[o.object.id]`, waymo_common.py:176-177); None before it
 __global__ __launch_bounds__(TK_BLOCK) void match_fill_kernel(const dal3_track_match_args a) {
-    const MatchWs ws = match_ws(a.workspace, a.K);
+    const MatchWs ws = match_ws(a);
     const int64_t base = a.id_base ? *a.id_base : 0;
     for (int64_t f = blockIdx.x; f < a.F; f += gridDim.x) {
         const int64_t d0 = a.frame_offsets[f];
@@ -389,11 +372,16 @@ __global__ __launch_bounds__(TK_BLOCK) void match_fill_kernel(const dal3_track_m
 }  // namespace
 
 size_t track_workspace_bytes(int64_t S, int64_t K, int64_t capacity) {
-    return tk_align((size_t)S * 2 * (size_t)capacity * sizeof(TrackSlot)) + 3 * tk_align((size_t)K * 4) +
-           tk_align((size_t)S * 8);
+    Carver c(nullptr, 0);
+    carve_track(c, S, K, capacity);
+    return c.off;
 }
 
-size_t track_match_workspace_bytes(int64_t K) { return tk_align((size_t)K * 8) + 2 * tk_align((size_t)K * 4); }
+size_t track_match_workspace_bytes(int64_t K) {
+    Carver c(nullptr, 0);
+    carve_match(c, K);
+    return c.off;
+}
 
 hipError_t launch_track(const dal3_track_args* a, hipStream_t s) {
     int64_t grid = a->S;

@@ -85,6 +85,47 @@ def test_candidates_and_values_against_the_reference(run):
             check_scores(r["scores"][rows].cpu().numpy(), g[key + "score"], key + "score")
 
 
+def _decode_entry(task, cfg, max_workgroups):
+    """dal3_center_decode on one task's NCHW maps, every cell a row of capacity -> (cell, labels, boxes, scores, counts)"""
+    maps = {k: detect._map(torch.from_numpy(v).to(DEV), "NCHW", None, k) for k, v in task.items()}
+    n, H, W, C = maps["hm"].shape
+    off = torch.arange(n + 1, dtype=torch.int64, device=DEV) * (H * W)
+    K = n * H * W
+    boxes, scores = torch.empty((K, 9), dtype=torch.float32, device=DEV), torch.empty(K, dtype=torch.float32, device=DEV)
+    labels, cell = torch.empty(K, dtype=torch.int32, device=DEV), torch.empty(K, dtype=torch.int32, device=DEV)
+    count, status = torch.zeros(n, dtype=torch.int32, device=DEV), torch.zeros(1, dtype=torch.int32, device=DEV)
+    lib = hip.lib()
+    ws = torch.empty(lib.dal3_center_decode_workspace_bytes(n, H, W), dtype=torch.uint8, device=DEV)
+    a = hip.CenterDecodeArgs(B=n, H=H, W=W, C=C, has_range=1, out_size_factor=float(cfg["out_size_factor"]),
+                             score_threshold=float(cfg["score_threshold"]), F=n, K=K, seg_first=0, seg_step=1,
+                             seg_offsets=hip.ptr(off), boxes=hip.ptr(boxes), scores=hip.ptr(scores), labels=hip.ptr(labels),
+                             cell=hip.ptr(cell), seg_count=hip.ptr(count), status=hip.ptr(status),
+                             max_workgroups=max_workgroups, workspace=hip.ptr(ws), workspace_bytes=ws.numel(),
+                             **{k: detect._map_struct(v) for k, v in maps.items()})
+    a.voxel_size[:], a.pc_range[:], a.range[:] = cfg["voxel_size"], cfg["pc_range"], cfg["post_center_limit_range"]
+    hip.check(lib.dal3_center_decode(a, hip.stream()))
+    assert int(status[0]) == 0
+    return cell.cpu().numpy(), labels.cpu().numpy(), boxes.cpu().numpy(), scores.cpu().numpy(), count.cpu().numpy()
+
+
+@pytest.mark.parametrize("H,W", [(31, 33), (32, 32), (25, 41)])
+def test_rows_and_order_at_the_decode_chunk_edge(H, W):
+    """1023, 1024 and 1025 cells: one short of a compaction chunk, the full chunk, one cell in a second chunk. Rows, their
+    order, the scores and `cell` against the NumPy restatement, whatever the grid."""
+    cfg = dict(nms_ref.CONFIGS["ref"], score_threshold=0.17)     # the better of two classes: a third of the cells above
+    (task,) = nms_ref.head_maps(1000 + W, True, B=2, H=H, W=W, num_classes=[2])
+    want = nms_ref.decode(task, cfg)
+    for wg in (0, 1):
+        cell, labels, boxes, scores, count = _decode_entry(task, cfg, wg)
+        for b, (w_cell, w_label, w_boxes, w_score) in enumerate(want):
+            assert 0.25 * H * W < w_cell.size < 0.42 * H * W        # about a third of the cells survive
+            rows = slice(b * H * W, b * H * W + int(count[b]))
+            assert count[b] == w_cell.size and np.array_equal(cell[rows], w_cell), (wg, b)
+            assert np.array_equal(labels[rows], w_label), (wg, b)
+            check_boxes(boxes[rows], w_boxes, True, f"{H}x{W} grid {wg} sample {b} boxes")
+            check_scores(scores[rows], w_score, f"{H}x{W} grid {wg} sample {b} score")
+
+
 def test_nhwc_views_give_the_same_bits():
     g = golden("nms")
     tasks = nms_ref.head_maps(int(g["head_seed"]), True)

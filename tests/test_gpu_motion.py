@@ -68,6 +68,40 @@ def test_group_by_key_large_any_grid_any_run():
     assert (n[empty] == 0).all() and n[single] == 1 and n[long] == 198
 
 
+@pytest.mark.parametrize("T", (1, 255, 256, 65536))
+@pytest.mark.parametrize("E", (1, 255, 256, 257, 4095, 4096, 4097, 8193))
+def test_group_by_key_at_the_tile_chunk_and_pass_edges(E, T):
+    """keys in [0, T] take 1 (T = 1, 255), 2 (256) and 3 (65536) radix passes; E crosses the 256-entry tile and the
+    4096-entry chunk, so the last tile is full, ragged or a single entry. At most five distinct keys: the order inside
+    a key is decided by position alone."""
+    rng = np.random.default_rng(E * 100_003 + T)
+    keys = rng.integers(0, T, 5)[rng.integers(0, 5, E)].astype(np.int64)
+    want = np.argsort(keys, kind="stable").astype(np.int32)
+    d = dev(keys)
+    for wg in (0, 1):
+        g = motion.group_by_key(d, T, max_workgroups=wg)
+        g.check()
+        assert np.array_equal(g.entry.cpu().numpy(), want), wg
+        assert np.array_equal(np.diff(g.group_start.cpu().numpy()), np.bincount(keys, minlength=T)), wg
+        assert int(g.n_groups.item()) == int(keys.max()) + 1
+
+
+@pytest.mark.parametrize("T", (1023, 1024, 1025, 2049))
+def test_classify_ids_at_the_compaction_tile_edges(T):
+    """a compaction tile is 1024 groups, ranked 256 at a time: one tile short of full, full, one group into the second,
+    one into the third; about half the groups kept"""
+    rng = np.random.default_rng(T)
+    feat, keep = rng.normal(0, 1, (T, 2)), (rng.uniform(0, 1, T) < 0.5).astype(np.uint8)
+    model = (np.array([0.7, -1.3]), 0.05)
+    d = feat[:, 0] * model[0][0] + feat[:, 1] * model[0][1] + model[1]
+    for wg in (0, 1):
+        c = motion.classify(dev(feat), dev(keep), model, max_workgroups=wg)
+        s, dyn = c.ids()
+        assert np.array_equal(s, np.flatnonzero((keep > 0) & (d > 0))), wg
+        assert np.array_equal(dyn, np.flatnonzero((keep > 0) & ~(d > 0))), wg
+        assert c.counts.cpu().tolist() == [len(s), len(dyn)]
+
+
 def test_group_by_key_bad_key_empty_input_and_no_groups():
     keys = np.array([3, 1, 99, 1, -5, 0, 3], np.int64)
     g = motion.group_by_key(dev(keys), 4)

@@ -70,12 +70,22 @@ def test_kept_rows_equal_the_references(case):
 
 # ---------------------------------------------------------------------------------- bit-exact self-consistency
 @pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
-@pytest.mark.parametrize("n", [0, 1, 2, 63, 64, 65, 128, 129, 300])
+@pytest.mark.parametrize("n", [0, 1, 2, 63, 64, 65, 128, 129, 300, 255, 256, 257, 513])
 def test_keep_is_the_greedy_scan_over_the_packages_own_iou(n, dtype):
     boxes, scores = scene(n, 100 + n, dtype)
     for thresh in (0.7, 0.2):
         assert np.array_equal(run_one(boxes, scores, "rotate", thresh), host_greedy(boxes, scores, thresh)), thresh
     assert np.array_equal(run_one(boxes, scores, "rotate", 0.5, mirror=True), host_greedy(boxes, scores, 0.5, mirror=True))
+
+
+def test_three_distinct_scores_over_three_sort_tiles_go_by_row():
+    """513 rows = two full 256-entry tiles of the one-workgroup sort and one entry: with three score values the order
+    inside a score is the rows', across the waves of a tile and across the tiles"""
+    boxes, _ = scene(513, 613)
+    scores = np.array([0.25, 0.5, 0.75], np.float32)[np.random.default_rng(613).integers(0, 3, 513)]
+    keep, count, order = nms.batched_nms(dev(boxes), dev(scores), [0, 513], "rotate", 0.7, return_order=True)
+    assert np.array_equal(order.cpu().numpy(), nms_ref.order(scores))
+    assert np.array_equal(keep[0, :int(count[0])].cpu().numpy(), host_greedy(boxes, scores, 0.7))
 
 
 def test_large_segment_with_both_cuts():
