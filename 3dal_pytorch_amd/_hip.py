@@ -195,6 +195,27 @@ class CenterDecodeArgs(C.Structure):
                 ("workspace", vp), ("workspace_bytes", C.c_size_t)]
 
 
+PILLAR_OVERFLOW = 128
+PILLAR_PACK_FLOATS = 5120
+
+
+class VoxelizeArgs(C.Structure):
+    """dal3_voxelize_args"""
+    _fields_ = [("B", C.c_int64), ("N", C.c_int64), ("points", vp), ("point_stride", C.c_int64), ("C", C.c_int32),
+                ("reverse_index", C.c_int32), ("point_offsets", vp), ("point_offsets_host", vp), ("voxel_size", C.c_float * 3),
+                ("pc_range", C.c_float * 6), ("grid", C.c_int32 * 3), ("max_points", C.c_int32), ("max_voxels", C.c_int64),
+                ("capacity", C.c_int64), ("voxels", vp), ("coordinates", vp), ("num_points", vp), ("voxel_offsets", vp),
+                ("status", vp), ("max_workgroups", C.c_int64), ("workspace", vp), ("workspace_bytes", C.c_size_t)]
+
+
+class PillarFeatureArgs(C.Structure):
+    """dal3_pillar_feature_args"""
+    _fields_ = [("P", C.c_int64), ("n_pillars", vp), ("voxels", vp), ("num_points", vp), ("coordinates", vp), ("C", C.c_int32),
+                ("max_points", C.c_int32), ("n_layers", C.c_int32), ("c_out", C.c_int32), ("vx", C.c_float), ("vy", C.c_float),
+                ("x_offset", C.c_float), ("y_offset", C.c_float), ("packed", vp), ("features", vp), ("canvas", vp),
+                ("canvas_B", C.c_int64), ("ny", C.c_int64), ("nx", C.c_int64), ("max_workgroups", C.c_int64)]
+
+
 # every symbol include/dal3.h declares: (restype, argtypes)
 _i, _i64, _u64, _sz = C.c_int, C.c_int64, C.c_uint64, C.c_size_t
 SIGNATURES = {
@@ -244,6 +265,12 @@ SIGNATURES = {
     "dal3_nms": (_i, [C.POINTER(NmsArgs), vp]),
     "dal3_center_decode_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "dal3_center_decode": (_i, [C.POINTER(CenterDecodeArgs), vp]),
+    "dal3_voxelize_workspace_bytes": (_sz, [_i64, _i64]),
+    "dal3_voxelize": (_i, [C.POINTER(VoxelizeArgs), vp]),
+    "dal3_pillar_pack": (_i, [C.POINTER(Layer), _i, _i, C.c_double, vp, vp]),
+    "dal3_pillar_features": (_i, [C.POINTER(PillarFeatureArgs), vp]),
+    "dal3_pillar_scatter": (_i, [vp, vp, _i64, vp, _i, vp, _i64, _i64, _i64, vp]),
+    "dal3_voxel_mean": (_i, [vp, vp, _i64, vp, _i, _i, vp, vp]),
     "dal3_crop_workspace_bytes": (_sz, [_i64, _i64]),
     "dal3_crop_count": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, _sz, vp]),
     "dal3_crop_fill": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, vp, vp, vp, _i64, vp, _sz, vp]),

@@ -1167,6 +1167,120 @@ extern "C" int dal3_center_decode(const dal3_center_decode_args* args, dal3_stre
     return 0;
 }
 
+// ---------------------------------------------------------------------------------- the PointPillars reader
+extern "C" size_t dal3_voxelize_workspace_bytes(int64_t B, int64_t N) {
+    if (B < 0 || N < 0 || B > DAL3_MAX_ITEMS || N > DAL3_MAX_ITEMS) return 0;
+    return voxelize_workspace_bytes(B, N);
+}
+
+extern "C" int dal3_voxelize(const dal3_voxelize_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "voxelize: null args");
+    const dal3_voxelize_args& a = *args;
+    if (a.B < 0 || a.N < 0 || a.B > DAL3_MAX_ITEMS || a.N > DAL3_MAX_ITEMS)
+        return fail(DAL3_EINVAL, "voxelize: bad B / N (0 <= B, N <= DAL3_MAX_ITEMS)");
+    if (a.C < 3 || a.C > 8 || a.point_stride < a.C) return fail(DAL3_EINVAL, "voxelize: bad point layout (3 <= C <= 8, point_stride >= C)");
+    if ((a.reverse_index != 0 && a.reverse_index != 1) || a.max_workgroups < 0)
+        return fail(DAL3_EINVAL, "voxelize: bad argument (reverse_index 0 or 1, max_workgroups >= 0)");
+    if (a.max_points < 1 || a.max_points > 65536 || a.max_voxels < 1 || a.capacity < 0)
+        return fail(DAL3_EINVAL, "voxelize: bad max_points (1 .. 65536) / max_voxels (>= 1) / capacity (>= 0)");
+    for (int j = 0; j < 3; ++j) {
+        if (a.grid[j] < 1) return fail(DAL3_EINVAL, "voxelize: grid[%d] = %d, every axis needs a cell", j, (int)a.grid[j]);
+        if (!(a.voxel_size[j] > 0.f) || !(a.pc_range[j] - a.pc_range[j] == 0.f) || !(a.voxel_size[j] - a.voxel_size[j] == 0.f))
+            return fail(DAL3_EINVAL, "voxelize: voxel_size must be positive and finite, pc_range finite");
+    }
+    const int64_t cells = (int64_t)a.grid[0] * a.grid[1] * a.grid[2];
+    if (a.grid[0] > 65536 || a.grid[1] > 65536 || a.grid[2] > 65536 || cells >= 2147483647 || (a.B > 0 && cells >= 2147483647 / a.B))
+        return fail(DAL3_EINVAL, "voxelize: the (sample, cell) key needs B * cells < 2^31 - 1 (split the batch)");
+    if (!a.voxel_offsets || !a.status) return fail(DAL3_EINVAL, "voxelize: null voxel_offsets / status");
+    if (a.B > 0 && (!a.point_offsets || !a.point_offsets_host))
+        return fail(DAL3_EINVAL, "voxelize: null point_offsets / point_offsets_host");
+    int64_t need = 0;
+    for (int64_t b = 0; b < a.B; ++b) {
+        const int64_t d0 = a.point_offsets_host[b], d1 = a.point_offsets_host[b + 1];
+        if (d0 < 0 || d1 < d0 || d1 > a.N)
+            return fail(DAL3_EINVAL, "voxelize: point_offsets must be non-decreasing within [0, N] (sample %lld: %lld .. %lld)",
+                        (long long)b, (long long)d0, (long long)d1);
+        int64_t n = d1 - d0;
+        if (n > a.max_voxels) n = a.max_voxels;
+        if (n > cells) n = cells;
+        need += n;
+    }
+    if (a.capacity < need)
+        return fail(DAL3_EINVAL, "voxelize: capacity %lld too small (the samples' min(points, max_voxels, cells) sum to %lld)",
+                    (long long)a.capacity, (long long)need);
+    if (a.capacity > DAL3_MAX_ITEMS) return fail(DAL3_EINVAL, "voxelize: capacity above DAL3_MAX_ITEMS");
+    if (a.capacity > 0 && (!a.voxels || !a.coordinates || !a.num_points))
+        return fail(DAL3_EINVAL, "voxelize: null voxels / coordinates / num_points");
+    if (a.N > 0 && a.B > 0) {
+        if (!a.points || !a.workspace) return fail(DAL3_EINVAL, "voxelize: null points / workspace");
+        if (a.workspace_bytes < voxelize_workspace_bytes(a.B, a.N))
+            return fail(DAL3_EWORKSPACE, "voxelize: workspace too small (dal3_voxelize_workspace_bytes)");
+        if (reinterpret_cast<uintptr_t>(a.workspace) & 7) return fail(DAL3_EINVAL, "voxelize: workspace must be 8-byte aligned");
+    }
+    HIP_TRY(launch_voxelize(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+extern "C" int dal3_pillar_pack(const dal3_layer* layers, int n_layers, int C, double eps, float* out, dal3_stream stream) {
+    if (!layers || !out) return fail(DAL3_EINVAL, "pillar_pack: null layers / out");
+    if (n_layers != 1 && n_layers != 2) return fail(DAL3_EINVAL, "pillar_pack: %d layers (1 or 2)", n_layers);
+    if (C < 3 || C > 8 || !(eps > 0.0)) return fail(DAL3_EINVAL, "pillar_pack: bad C (3 .. 8) / eps (> 0)");
+    const int want_in[2] = {C + 5, 64}, want_out[2] = {n_layers == 1 ? 64 : 32, 64};
+    for (int i = 0; i < n_layers; ++i) {
+        const dal3_layer& L = layers[i];
+        if (L.c_in != want_in[i] || L.c_out != want_out[i])
+            return fail(DAL3_EINVAL, "pillar_pack: layer %d is %d -> %d, the kernel serves %d -> %d", i, (int)L.c_in, (int)L.c_out,
+                        want_in[i], want_out[i]);
+        if (!L.weight || L.bias || !L.bn_weight || !L.bn_bias || !L.bn_mean || !L.bn_var)
+            return fail(DAL3_EINVAL, "pillar_pack: layer %d needs weight and BatchNorm pointers and no bias", i);
+    }
+    if (reinterpret_cast<uintptr_t>(out) & 15) return fail(DAL3_EINVAL, "pillar_pack: out must be 16-byte aligned");
+    HIP_TRY(launch_pillar_pack(layers, n_layers, eps, out, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+static int canvas_ok(const char* who, int c_out, const float* canvas, int64_t canvas_B, int64_t ny, int64_t nx) {
+    if (!canvas) return fail(DAL3_EINVAL, "%s: null canvas", who);
+    if (canvas_B < 1 || ny < 1 || nx < 1 || canvas_B > DAL3_MAX_ITEMS || ny > 65536 || nx > 65536 ||
+        canvas_B * c_out * ny * nx > ((int64_t)1 << 40))
+        return fail(DAL3_EINVAL, "%s: bad canvas shape (canvas_B, ny, nx >= 1)", who);
+    return 0;
+}
+
+extern "C" int dal3_pillar_features(const dal3_pillar_feature_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "pillar_features: null args");
+    const dal3_pillar_feature_args& a = *args;
+    if (a.P < 0 || a.P > DAL3_MAX_ITEMS || a.max_workgroups < 0) return fail(DAL3_EINVAL, "pillar_features: bad P / max_workgroups");
+    if (a.C < 3 || a.C > 8 || a.max_points < 1 || a.max_points > 64)
+        return fail(DAL3_EINVAL, "pillar_features: bad C (3 .. 8) / max_points (1 .. 64)");
+    if ((a.n_layers != 1 && a.n_layers != 2) || a.c_out != 64) return fail(DAL3_EINVAL, "pillar_features: n_layers 1 or 2, c_out 64");
+    if (!a.packed || (reinterpret_cast<uintptr_t>(a.packed) & 15)) return fail(DAL3_EINVAL, "pillar_features: packed is null or not 16-byte aligned");
+    if (a.canvas) TRY(canvas_ok("pillar_features", a.c_out, a.canvas, a.canvas_B, a.ny, a.nx));
+    else if (a.P > 0 && !a.features) return fail(DAL3_EINVAL, "pillar_features: no output (features and canvas are NULL)");
+    if (a.P > 0 && (!a.voxels || !a.num_points || !a.coordinates))
+        return fail(DAL3_EINVAL, "pillar_features: null voxels / num_points / coordinates");
+    HIP_TRY(launch_pillar_features(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+extern "C" int dal3_pillar_scatter(const float* features, const int32_t* coordinates, int64_t P, const int64_t* n_pillars, int c_out,
+                                   float* canvas, int64_t canvas_B, int64_t ny, int64_t nx, dal3_stream stream) {
+    if (P < 0 || P > DAL3_MAX_ITEMS || c_out < 1 || c_out > 4096) return fail(DAL3_EINVAL, "pillar_scatter: bad P / c_out");
+    TRY(canvas_ok("pillar_scatter", c_out, canvas, canvas_B, ny, nx));
+    if (P > 0 && (!features || !coordinates)) return fail(DAL3_EINVAL, "pillar_scatter: null features / coordinates");
+    HIP_TRY(launch_pillar_scatter(features, coordinates, P, n_pillars, c_out, canvas, canvas_B, ny, nx, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+extern "C" int dal3_voxel_mean(const float* voxels, const int32_t* num_points, int64_t P, const int64_t* n_pillars, int max_points,
+                               int C, float* out, dal3_stream stream) {
+    if (P < 0 || P > DAL3_MAX_ITEMS || max_points < 1 || max_points > 65536 || C < 1 || C > 64)
+        return fail(DAL3_EINVAL, "voxel_mean: bad P / max_points / C");
+    if (P > 0 && (!voxels || !num_points || !out)) return fail(DAL3_EINVAL, "voxel_mean: null voxels / num_points / out");
+    HIP_TRY(launch_voxel_mean(voxels, num_points, P, n_pillars, max_points, C, out, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 extern "C" size_t dal3_crop_workspace_bytes(int64_t K_total, int64_t max_points_per_frame) {
     if (K_total <= 0 || max_points_per_frame < 0) return 0;
     return crop_workspace_bytes(K_total, max_points_per_frame);

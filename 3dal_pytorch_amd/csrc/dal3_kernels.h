@@ -288,6 +288,15 @@ size_t nms_workspace_bytes(int64_t K, int boxes_f64);
 hipError_t launch_nms(const dal3_nms_args* a, hipStream_t s);
 size_t center_decode_workspace_bytes(int64_t B, int64_t H, int64_t W);
 hipError_t launch_center_decode(const dal3_center_decode_args* a, hipStream_t s);
+// the PointPillars reader (dal3_pillars.hip): voxelisation as a stable radix sort over chunks, the fused feature kernel
+size_t voxelize_workspace_bytes(int64_t B, int64_t N);
+hipError_t launch_voxelize(const dal3_voxelize_args* a, hipStream_t s);
+hipError_t launch_pillar_pack(const dal3_layer* layers, int n_layers, double eps, float* out, hipStream_t s);
+hipError_t launch_pillar_features(const dal3_pillar_feature_args* a, hipStream_t s);
+hipError_t launch_pillar_scatter(const float* features, const int32_t* coordinates, int64_t P, const int64_t* n_pillars, int c_out,
+                                 float* canvas, int64_t canvas_B, int64_t ny, int64_t nx, hipStream_t s);
+hipError_t launch_voxel_mean(const float* voxels, const int32_t* num_points, int64_t P, const int64_t* n_pillars, int max_points,
+                             int C, float* out, hipStream_t s);
 hipError_t launch_points_in_boxes(const void* points, int points_f64, int64_t P, int64_t stride, const double* planes,
                                   int K, int f32_math, uint8_t* inside, hipStream_t s);
 hipError_t launch_writeback(const double* final_boxes, const int32_t* final_idx, const double* pose_best,

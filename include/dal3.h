@@ -768,6 +768,108 @@ typedef struct dal3_center_decode_args {
 size_t dal3_center_decode_workspace_bytes(int64_t B, int64_t H, int64_t W);
 int dal3_center_decode(const dal3_center_decode_args* args, dal3_stream stream);
 
+/* ---- the PointPillars reader: points_to_voxel (det3d/ops/point_cloud/point_cloud_ops.py:7-184, through
+ * VoxelGenerator.generate and collate_kitti's batch column), PillarFeatureNet and PointPillarsScatter
+ * (det3d/models/readers/pillar_encoder.py:15-209) and VoxelFeatureExtractorV3 (voxel_encoder.py:9-24), for B samples in
+ * one enqueue with no host round trip.
+ *
+ * dal3_voxelize. points (N, point_stride) float32, the first C (3 <= C <= 8) columns of a row are the point; sample b is
+ * rows [point_offsets[b], point_offsets[b+1]) (given on the device and, the same values, on the HOST for the checks made
+ * before any launch). Defined exactly, per sample:
+ *   cell        c_j = floor((p_j - pc_range[j]) / voxel_size[j]), j = x, y, z: a float32 subtraction, a correctly rounded
+ *               float32 division, a floor. The point is dropped when c_j < 0 or c_j >= grid[j] for any j (a lower face
+ *               is in, an upper face is out; +-Inf fails the test as in the reference) or p_j is NaN (the reference casts
+ *               the NaN to an index, which is undefined). grid = round((hi - lo) / size) in float32 comes from the caller.
+ *   voxel       a cell's voxel index is its rank by first appearance among the sample's in-range points in input order;
+ *               cells of rank >= max_voxels are dropped with all their points, later points of an earlier cell are kept.
+ *   rows        the voxel's first max_points points in input order, all C columns, zeros after them;
+ *               num_points = min(count, max_points).
+ *   coordinates [b, z, y, x] with reverse_index (what VoxelGenerator asks for), else [b, x, y, z], int32.
+ * The samples' voxels are packed back to back: sample b's are rows [voxel_offsets[b], voxel_offsets[b+1]) of voxels
+ * (capacity, max_points, C), coordinates (capacity, 4) and num_points (capacity); voxel_offsets (B+1) is written on the
+ * device. capacity >= the sum over samples of min(points of the sample, max_voxels, cells of the grid), which the host
+ * knows; rows from voxel_offsets[B] on are zero. No atomic decides a position: a stable least-significant-digit radix
+ * sort of (sample, cell) keys over chunks of 4096 points (histogram, scan, scatter, as dal3_group_by_key) orders the
+ * points of a cell by their index, the head of each run is flagged at its original position, an exclusive scan of the
+ * flags in point order is the voxel index and a point's place in its run is its row. The result is a function of the
+ * input alone, the same for every max_workgroups and every run, and of a sample alone whatever else is in the batch.
+ * Device offsets that differ from the host's so that a row would fall outside the capacity set DAL3_PILLAR_OVERFLOW in
+ * *status (OR-ed) and the row is not written. B * cells < 2^31 - 1, N <= DAL3_MAX_ITEMS, max_points <= 64 * 1024.
+ * workspace: dal3_voxelize_workspace_bytes(B, N) = O(N). */
+enum { DAL3_PILLAR_OVERFLOW = 128 };     /* status bit, numbered beside DAL3_NMS_* */
+
+typedef struct dal3_voxelize_args {
+    int64_t B, N;                        /* samples, rows of points */
+    const float* points;                 /* (N, point_stride) */
+    int64_t point_stride;                /* elements per row, >= C */
+    int32_t C;                           /* 3 .. 8 */
+    int32_t reverse_index;               /* 0 or 1 */
+    const int64_t* point_offsets;        /* (B+1) device */
+    const int64_t* point_offsets_host;   /* (B+1) HOST copy of the same values */
+    float voxel_size[3];
+    float pc_range[6];
+    int32_t grid[3];                     /* cells along x, y, z */
+    int32_t max_points;
+    int64_t max_voxels;                  /* per sample */
+    int64_t capacity;                    /* rows of the outputs */
+    float* voxels;                       /* (capacity, max_points, C) */
+    int32_t* coordinates;                /* (capacity, 4) */
+    int32_t* num_points;                 /* (capacity) */
+    int64_t* voxel_offsets;              /* (B+1) */
+    int32_t* status;                     /* (1) OR-ed */
+    int64_t max_workgroups;              /* 0: no cap */
+    void* workspace;
+    size_t workspace_bytes;
+} dal3_voxelize_args;
+
+size_t dal3_voxelize_workspace_bytes(int64_t B, int64_t N);
+int dal3_voxelize(const dal3_voxelize_args* args, dal3_stream stream);
+
+/* dal3_pillar_pack: the eval-mode PFNLayers (Linear without bias, BatchNorm1d, ReLU) of a PillarFeatureNet folded, in
+ * float64 and rounded once, to W' = W * g / sqrt(var + eps), b' = beta - mean * g / sqrt(var + eps), and laid out as the
+ * MFMA fragments the feature kernel keeps in registers. layers: 1 (C + 5 -> 64) or 2 (C + 5 -> 32, 64 -> 64), every
+ * pointer of a layer but `bias` (which must be NULL) a device pointer. out: DAL3_PILLAR_PACK_FLOATS floats.
+ *
+ * dal3_pillar_features: (voxels, num_points, coordinates) -> features (P, c_out) in one kernel. Per pillar, in float32,
+ * each operation rounded by itself (no contraction where a product feeds a sum):
+ *   mean        the sum over all max_points rows (padding rows are zero) / num_points;
+ *   row         [p (C columns), p_xyz - mean, x - (coor_x * vx + x_offset), y - (coor_y * vy + y_offset)], times the
+ *               padding mask (row < num_points); coor_x = coordinates[3], coor_y = coordinates[2] (the reversed layout);
+ *   layer 1     relu(W1' row + b1') for EVERY one of the max_points rows (a padding row carries relu(b1')), the max over them;
+ *   layer 2     relu(W2a' x + (W2b' max1 + b2')) for every row, W2' = [W2a' | W2b'], the max over the rows.
+ * The products run on the fp32 MFMA with channels on its rows and the pillar's rows on its columns; columns beyond
+ * max_points repeat a real row and never take part as zeros. With `canvas` the result goes to canvas[b, :, y, x] of a
+ * (canvas_B, c_out, ny, nx) map that the call first fills with +0, and `features` may be NULL; without it the rows go to
+ * features. n_pillars (optional, device): only the first min(*n_pillars, P) pillars exist (voxel_offsets[B] of
+ * dal3_voxelize). A pillar whose coordinates fall outside the canvas is not written. 1 <= max_points <= 64.
+ *
+ * dal3_pillar_scatter: features (P, c_out) -> the same canvas, zero-filled first; cells are unique per sample, so no
+ * atomics. dal3_voxel_mean: VoxelFeatureExtractorV3, out (P, C) = the sum over the max_points rows / num_points. */
+#define DAL3_PILLAR_PACK_FLOATS 5120
+
+typedef struct dal3_pillar_feature_args {
+    int64_t P;                           /* rows of voxels / features */
+    const int64_t* n_pillars;            /* optional device (1): pillars in use */
+    const float* voxels;                 /* (P, max_points, C) */
+    const int32_t* num_points;           /* (P) */
+    const int32_t* coordinates;          /* (P, 4) [b, z, y, x] */
+    int32_t C, max_points;
+    int32_t n_layers, c_out;             /* 1 or 2; 64 */
+    float vx, vy, x_offset, y_offset;
+    const float* packed;                 /* dal3_pillar_pack's */
+    float* features;                     /* (P, c_out), or NULL with a canvas */
+    float* canvas;                       /* optional (canvas_B, c_out, ny, nx) */
+    int64_t canvas_B, ny, nx;
+    int64_t max_workgroups;              /* 0: no cap */
+} dal3_pillar_feature_args;
+
+int dal3_pillar_pack(const dal3_layer* layers, int n_layers, int C, double eps, float* out, dal3_stream stream);
+int dal3_pillar_features(const dal3_pillar_feature_args* args, dal3_stream stream);
+int dal3_pillar_scatter(const float* features, const int32_t* coordinates, int64_t P, const int64_t* n_pillars, int c_out,
+                        float* canvas, int64_t canvas_B, int64_t ny, int64_t nx, dal3_stream stream);
+int dal3_voxel_mean(const float* voxels, const int32_t* num_points, int64_t P, const int64_t* n_pillars, int max_points, int C,
+                    float* out, dal3_stream stream);
+
 /* ---- crop extraction from full sweeps: the per-detection loop of _create_pd_detection
  * (det3d/datasets/waymo/waymo_common.py:166-171, 193) for F frames at once. points (P_total,3) f32 vehicle-frame
  * sweeps concatenated, point_offsets (F+1); planes (K_total,6,4) f64 face equations of every frame's detections
