@@ -4,8 +4,10 @@ from the reference's own points_to_voxel, PillarFeatureNet, PointPillarsScatter 
 
 `voxelize` is the PARALLEL formulation the kernels use — a stable sort by cell, run heads, ranks of the heads in point order
 — not the reference's loop: that it equals the loop's recorded output bit for bit, cap included, is what
-tests/test_pillars_cpu.py pins. `reader_f64` is the float64 truth of the feature net, `judge` the measures the GPU test
-holds against the torch-CPU fp32 module's own error."""
+tests/test_pillars_cpu.py pins. `voxelize_loop` is that loop itself, written from the definition of include/dal3.h and
+pinned to the same recorded output: the oracle of the cases no fixture holds (the tables of tests/
+test_gpu_pillars_edges.py, kept here so that the CPU suite walks them too). `reader_f64` is the float64 truth of the
+feature net, `judge` the measures the GPU test holds against the torch-CPU fp32 module's own error."""
 import importlib
 import os
 import sys
@@ -141,6 +143,29 @@ def voxelize_index(points, voxel_size, pc_range, max_points, max_voxels):
     return index, cell, np.minimum(count, max_points)
 
 
+def voxelize_loop(points, voxel_size, pc_range, max_points, max_voxels):
+    """the definition of include/dal3.h as the sequential loop it is stated as: walk the points in order, a dict from
+    cell to voxel index assigned by first appearance, a new cell is dropped once max_voxels voxels exist, a point is
+    appended while its voxel has fewer than max_points rows. No dense grid. -> voxelize_index's triple"""
+    ok, c = cells(points, voxel_size, pc_range)
+    voxel_of, rows, cell = {}, [], []
+    for i in np.nonzero(ok)[0].tolist():
+        key = (int(c[i, 0]), int(c[i, 1]), int(c[i, 2]))
+        v = voxel_of.get(key)
+        if v is None:
+            if len(rows) >= max_voxels:
+                continue
+            v = voxel_of[key] = len(rows)
+            rows.append([])
+            cell.append(key)
+        if len(rows[v]) < max_points:
+            rows[v].append(i)
+    index = -np.ones((len(rows), max_points), np.int64)
+    for v, r in enumerate(rows):
+        index[v, :len(r)] = r
+    return index, np.asarray(cell, np.int64).reshape(-1, 3), np.asarray([len(r) for r in rows], np.int64)
+
+
 def gather(points, index):
     """the voxels of an index map: (M, max_points, C), zeros at -1"""
     out = points[np.maximum(index, 0)]
@@ -175,6 +200,128 @@ def batch_points():
     parts = [cloud(f"batch{b}", n, PILLAR, PILLAR["C"], with_nan=True, outside=(b == 2)) for b, n in enumerate(BATCH_COUNTS)]
     off = np.concatenate([[0], np.cumsum(BATCH_COUNTS)]).astype(np.int64)
     return np.concatenate(parts), off
+
+
+# ------------------------------------------------------------------- the cases of tests/test_gpu_pillars_edges.py
+# Every input is seeded from cloud / synth; tests/test_pillars_cpu.py walks the same tables and pins voxelize_index (what
+# the GPU is compared with) to voxelize_loop on each of them.
+#
+# The key-width table: name -> (voxel_size, pc_range, grid, B, B * cells, radix passes). `none` = B * cells sorts behind
+# every real key and sets the number of 8-bit passes: 1 (the result ends in the second ping-pong buffer), 2, 3 (the
+# production pillar grid) and 4, with `none` on and one short of a power of 256, and keys up to bit 30.
+KEY_N, KEY_B_N, KEY_C, KEY_MAX_POINTS, KEY_MAX_VOXELS = 9001, 3000, 5, 7, 3000
+KEY_WIDTHS = {
+    "one_pass": ((1.0, 1.0, 1.0), (0.0, 0.0, 0.0, 4.0, 4.0, 1.0), (4, 4, 1), 3, 48, 1),
+    "2^8-1": ((0.5, 0.25, 1.0), (-1.0, 0.0, -2.0, 1.5, 4.25, 1.0), (5, 17, 3), 1, 255, 1),
+    "2^8": ((0.5, 0.5, 4.0), (0.0, -4.0, -3.0, 8.0, 4.0, 1.0), (16, 16, 1), 1, 256, 2),
+    "2^16-1": ((0.25, 0.25, 4.0), (0.0, 0.0, -3.0, 63.75, 64.25, 1.0), (255, 257, 1), 1, 65535, 2),
+    "2^16": ((0.25, 0.25, 4.0), (-32.0, -32.0, -3.0, 32.0, 32.0, 1.0), (256, 256, 1), 1, 65536, 3),
+    "production": ((0.32, 0.32, 6.0), (-74.88, -74.88, -2.0, 74.88, 74.88, 4.0), (468, 468, 1), 4, 876096, 3),
+    "2^24": ((0.25,) * 3, (-32.0,) * 3 + (32.0,) * 3, (256, 256, 256), 1, 1 << 24, 4),
+    "top": ((0.125,) * 3, (-64.0, -64.0, -32.0, 64.0, 64.0, 32.0), (1024, 1024, 512), 3, 3 << 29, 4),
+}
+PRODUCTION = dict(voxel_size=(0.32, 0.32, 6.0), pc_range=(-74.88, -74.88, -2.0, 74.88, 74.88, 4.0), max_points=20, C=5)
+
+
+def sort_passes(B, grid):
+    """-> (none = B * cells, the 8-bit passes of the voxeliser's sort) as launch_voxelize forms them: as many bits as
+    `none` itself needs, since it has to sort behind every real key"""
+    none = int(B) * int(np.prod(np.asarray(grid, np.int64)))
+    bits = 0
+    while bits < 32 and (1 << bits) <= none:
+        bits += 1
+    return none, (bits + 7) // 8
+
+
+def key_width_case(name):
+    """-> (points, offsets (B + 1), cfg): one cloud of KEY_N points, or B clouds of KEY_B_N with different tags"""
+    vs, rng, _, B, _, _ = KEY_WIDTHS[name]
+    cfg = dict(voxel_size=vs, pc_range=rng, max_points=KEY_MAX_POINTS, C=KEY_C)
+    if B == 1:
+        return cloud("key/" + name, KEY_N, cfg, KEY_C), np.array([0, KEY_N], np.int64), cfg
+    parts = [cloud(f"key/{name}/{b}", KEY_B_N, cfg, KEY_C) for b in range(B)]
+    return np.concatenate(parts), np.arange(B + 1, dtype=np.int64) * KEY_B_N, cfg
+
+
+RUN_N, RUN_SMALL_AT = 9001, (0, 4096, 9000)
+RUN_BIG_CELL, RUN_SMALL_CELL = (5, 7), (20, 3)              # (x, y) on PILLAR's grid
+RUN_MAX_POINTS = (1, 64, 5000, 10000)
+
+
+def run_length_points():
+    """RUN_N points of PILLAR's grid, all in range: those at RUN_SMALL_AT sit mid-cell in one cell, every other one
+    mid-cell in another, whose run spans three sort chunks of 4096. Column 3 is the point's index. The small cell has
+    the smaller key, so its run starts at sorted entry 0 and the large one ends at entry N."""
+    lo, vs = np.asarray(PILLAR["pc_range"][:3], np.float64), np.asarray(PILLAR["voxel_size"], np.float64)
+    pts = np.zeros((RUN_N, 5), np.float32)
+    pts[:, :2] = lo[:2] + (np.asarray(RUN_BIG_CELL) + 0.5) * vs[:2]
+    pts[list(RUN_SMALL_AT), :2] = lo[:2] + (np.asarray(RUN_SMALL_CELL) + 0.5) * vs[:2]
+    pts[:, 2] = lo[2] + 0.5 * vs[2]
+    pts[:, 3] = np.arange(RUN_N)
+    pts[:, 4] = 0.5
+    return pts
+
+
+BIG_B, BIG_N, BIG_HEAD, BIG_TAIL, BIG_CAP = 300, 6000, 5, 11, 40
+BIG_SIZES = (0, 0, 1, 37, 0, 255, 256, 257, 3)
+BIG_ACTIVE = ((0, 45), (256, 300))      # the samples that take sizes from the cycle; those between are a run of empty ones
+
+
+def many_samples():
+    """-> (points (BIG_N, 5), offsets (BIG_B + 1)): sample sizes cycle through BIG_SIZES over the samples of BIG_ACTIVE
+    (so that samples behind the 256th, which the offsets kernel's second stride serves, hold points and hit the cap),
+    cut off where the points run out; BIG_HEAD points in front of offsets[0] and BIG_TAIL behind offsets[B] belong to no
+    sample and are in range, so that they show if they are not dropped."""
+    sizes = np.zeros(BIG_B, np.int64)
+    for a, b in BIG_ACTIVE:
+        sizes[a:b] = [BIG_SIZES[(i - a) % len(BIG_SIZES)] for i in range(a, b)]
+    room = BIG_N - BIG_HEAD - BIG_TAIL
+    ends = np.minimum(np.cumsum(sizes), room)
+    off = BIG_HEAD + np.concatenate([[0], ends]).astype(np.int64)
+    pts = cloud("many_samples", BIG_N, PILLAR, 5)
+    lo, vs = np.asarray(PILLAR["pc_range"][:3], np.float64), np.asarray(PILLAR["voxel_size"], np.float64)
+    stray = np.r_[0:BIG_HEAD, BIG_N - BIG_TAIL:BIG_N]
+    pts[stray, :3] = (lo + (np.stack([stray % 29, stray % 31, 0 * stray], 1) + 0.5) * vs).astype(np.float32)
+    return pts, off
+
+
+OVERFLOW_N, OVERFLOW_CAP = 6000, 50
+OVERFLOW_OFFSETS = ((0, 3000, 6000), (0, 4, 9))     # the device's offsets: more, and fewer, points than the host's (0, 10, 20)
+
+
+def in_range_points(tag, n):
+    """n seeded points of PILLAR's range, every one in it"""
+    lo, hi = np.asarray(PILLAR["pc_range"][:3]), np.asarray(PILLAR["pc_range"][3:])
+    u = synth.uniform(SEED, "pillars/" + tag, (n, 5), 0.0, 1.0)
+    u[:, :3] = lo + (0.001 + 0.998 * u[:, :3]) * (hi - lo)
+    return u.astype(np.float32)
+
+
+FAR_P, FAR_AT = 64, (0, 1, 233, 234, 466, 467)
+
+
+def far_pillars():
+    """-> (voxels (FAR_P, 20, 5), num_points, coordinates (P, 4) [b, z, y, x]) on PRODUCTION's 468 x 468 grid with x and y
+    indices from FAR_AT: a point's x and y are its pillar's centre +- up to half a cell, so that at index 467 the
+    decoration x - (coor * vx + x_offset) cancels 74 m against 74 m"""
+    cfg = PRODUCTION
+    T, C = cfg["max_points"], cfg["C"]
+    lo, hi = np.asarray(cfg["pc_range"][:3], np.float64), np.asarray(cfg["pc_range"][3:], np.float64)
+    vs = np.asarray(cfg["voxel_size"], np.float64)
+    pairs = [(y, x) for y in FAR_AT for x in FAR_AT]
+    p = np.arange(FAR_P)
+    yx = np.asarray([pairs[i % len(pairs)] for i in p], np.int64)
+    co = np.stack([p // len(pairs), np.zeros(FAR_P, np.int64), yx[:, 0], yx[:, 1]], 1).astype(np.int32)
+    u = synth.uniform(SEED, "far", (FAR_P, T, C), 0.0, 1.0)
+    vox = u.copy()
+    vox[:, :, 0] = lo[0] + (yx[:, 1:2] + 0.5 + (u[:, :, 0] - 0.5) * 0.998) * vs[0]
+    vox[:, :, 1] = lo[1] + (yx[:, 0:1] + 0.5 + (u[:, :, 1] - 0.5) * 0.998) * vs[1]
+    vox[:, :, 2] = lo[2] + u[:, :, 2] * (hi[2] - lo[2])
+    num = (1 + (p * 7) % T).astype(np.int32)
+    num[:3] = [1, T, T - 1]
+    vox = vox.astype(np.float32)
+    vox[np.arange(T)[None, :] >= num[:, None]] = 0
+    return vox, num, co
 
 
 # ------------------------------------------------------------------------------------- the reader
@@ -228,13 +375,16 @@ def reader_f64(sd, voxels, num_points, coords, voxel_size, pc_range, eps=EPS, fa
 
 # The GPU test's bars: multiples of the yardstick (the torch-CPU fp32 module's own error against the float64 truth on the
 # same rows). The rule: the worst ratio recorded in profiles/pillars_measured.json (DAL3_PILLARS_RECORD, tests/
-# test_gpu_pillars.py) x at most 2, rounded up to one significant digit, and under a tenth of the smallest planted-fault
-# ratio of tests/test_pillars_cpu.py (3.4e3). No MI355X run was to be had when they were first set, so they stand on
-# reasoning: kernel and yardstick are fp32 evaluations of the same chain of <= 64-term dot products; the kernel rounds
-# every folded weight once more (the rms error of a term grows by at most sqrt(2)) and sums in another order (the same
-# bound), and the per-channel measures are maxima over 64 channels of a few hundred rows, which move by about 2x between
-# two equally good evaluations: 4 = sqrt(2) x 2, rounded up to one significant digit.
-BARS = {"tensor": 4.0, "chan_rms": 4.0, "chan_max": 4.0}
+# test_gpu_pillars.py and tests/test_gpu_pillars_edges.py in one session) x at most 2, rounded up to one significant
+# digit, and under a tenth of the smallest planted-fault ratio of tests/test_pillars_cpu.py (3.4e3); a bar comes down
+# or stays, it does not go up. They were first set without an MI355X run, at 4 each, on reasoning: kernel and yardstick
+# are fp32 evaluations of the same chain of <= 64-term dot products; the kernel rounds every folded weight once more
+# (the rms error of a term grows by at most sqrt(2)) and sums in another order (the same bound), and the per-channel
+# measures are maxima over 64 channels of a few hundred rows, which move by about 2x between two equally good
+# evaluations: 4 = sqrt(2) x 2, rounded up. The first run on an MI355X (17 rows, the far corner of the production grid
+# among them) recorded at worst tensor 1.34 (reader1), chan_rms 2.17 (rows64/c6/l1) and chan_max 1.96 (rows1/c3/l2):
+# x 2 gives 2.7 -> 3, 4.3 (the bar stays at 4 = 1.8 x the worst) and 3.9 -> 4.
+BARS = {"tensor": 3.0, "chan_rms": 4.0, "chan_max": 4.0}
 FAULTS = ("padding_out_of_max", "eps_1e-5", "mean_by_max_points", "offsets_swapped")
 MEASURES = ("tensor", "chan_rms", "chan_max")
 

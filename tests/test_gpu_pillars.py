@@ -4,12 +4,10 @@
 Voxelisation is exact: voxel count, coordinates, num_points and every row equal the reference's bit for bit. The feature net
 is judged per element and per channel against the float64 truth by the rule of tests/test_gpu_f64_parity.py: each measure
 <= bar x the torch-CPU fp32 module's own figure on the same rows (pillars_ref.BARS; how they were set is written there).
-With DAL3_PILLARS_RECORD=<path> in the environment the run also writes every measure, yardstick and ratio to <path> (how
-profiles/pillars_measured.json was made)."""
+With DAL3_PILLARS_RECORD=<path> in the environment the run also writes every measure, yardstick and ratio to <path>
+(tests/pillars_gpu.py; how profiles/pillars_measured.json was made)."""
 import copy
 import importlib
-import json
-import os
 
 import numpy as np
 import pytest
@@ -17,47 +15,16 @@ import torch
 
 import pillars_ref as R
 from _common import golden
+from pillars_gpu import _dev, _hold, _module, _record_file, _run, _same       # _record_file: the autouse fixture
 
 hip = importlib.import_module("3dal_pytorch_amd._hip")
 pillars = importlib.import_module("3dal_pytorch_amd.pillars")
 pytestmark = pytest.mark.gpu
-_RECORD = {}
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _record_file():
-    yield
-    path = os.environ.get("DAL3_PILLARS_RECORD")
-    if path and _RECORD:
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "w") as f:
-            json.dump(_RECORD, f, indent=1, sort_keys=True)
 
 
 @pytest.fixture(scope="module")
 def g():
     return golden("pillars")
-
-
-def _dev(x):
-    return torch.as_tensor(np.ascontiguousarray(x)).cuda()
-
-
-def _run(points, off, cfg, max_voxels, reverse=True, **kw):
-    """-> the collated batch as host arrays, and the result object"""
-    r = pillars.voxelize(_dev(points), off, cfg["voxel_size"], cfg["pc_range"], cfg["max_points"], max_voxels, reverse, **kw)
-    voxels, coords, num, nv = r.finish()
-    assert int(r.status.item()) == 0
-    # everything behind the last voxel is zero
-    m = voxels.shape[0]
-    assert not r.voxels[m:].any() and not r.num_points[m:].any() and not r.coordinates[m:].any()
-    return (voxels.cpu().numpy(), coords.cpu().numpy(), num.cpu().numpy(), nv.cpu().numpy()), r
-
-
-def _same(got, want):
-    for a, b in zip(got, want):
-        assert a.shape == b.shape, (a.shape, b.shape)
-        assert np.array_equal(a.view(np.uint32) if a.dtype == np.float32 else a, b.view(np.uint32) if b.dtype == np.float32 else b)
 
 
 def _single(g, name):
@@ -116,27 +83,10 @@ def test_a_sample_is_independent_of_its_batch_and_of_the_run():
     _same([t.cpu().numpy() for t in r.finish()[:3]], alone[:3])
 
 
-def _module(n_layers, C=5):
-    net = pillars.PillarFeatureNet(num_input_features=C, num_filters=(64,) * n_layers, voxel_size=R.PILLAR["voxel_size"],
-                                   pc_range=R.PILLAR["pc_range"], norm_cfg=dict(type="BN1d", eps=R.EPS, momentum=0.01))
-    net.load_state_dict({k: torch.as_tensor(v) for k, v in R.reader_weights(n_layers, C).items()}, strict=True)
-    return net.cuda().eval()
-
-
 def _reader_inputs(g):
     pts, off = R.batch_points()
     rows = g["reader_rows"]
     return R.gather(pts, g["batch_index"])[rows], g["batch_num"][rows], g["batch_coords"][rows]
-
-
-def _hold(row, got, f32, truth):
-    ratio, m, y = R.ratios(got, f32, truth)
-    _RECORD[row] = {"measured": {k: m[k] for k in R.MEASURES}, "yardstick": {k: y[k] for k in R.MEASURES}, "ratio": ratio}
-    for k in R.MEASURES:
-        print(f"{row:28s} {k:9s} {m[k]:10.3e}  yardstick {y[k]:10.3e}  ratio {ratio[k]:7.2f}  bar {R.BARS[k]:g}")
-    assert m["dead_ok"]
-    bad = [(k, m[k], ratio[k]) for k in R.MEASURES if ratio[k] > R.BARS[k]]
-    assert not bad, (row, bad)
 
 
 @pytest.mark.parametrize("n_layers", [1, 2])

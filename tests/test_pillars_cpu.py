@@ -60,6 +60,99 @@ def test_sorted_restatement_equals_the_reference_on_the_ragged_batch():
     assert np.array_equal(coords, g["batch_coords"]) and np.array_equal(num, g["batch_num"])
 
 
+def _index_equals_loop(pts, cfg, max_points, cap):
+    """the sort-based restatement against the sequential loop on one sample -> the triple"""
+    a = R.voxelize_index(pts, cfg["voxel_size"], cfg["pc_range"], max_points, cap)
+    b = R.voxelize_loop(pts, cfg["voxel_size"], cfg["pc_range"], max_points, cap)
+    for x, y in zip(a, b):
+        assert x.shape == y.shape and np.array_equal(x, y)
+    return b
+
+
+@pytest.mark.parametrize("name", sorted(R.PILLAR_CAPS) + sorted(R.VOXELNET_CASES))
+def test_sequential_loop_equals_the_references_recorded_output(name):
+    """voxelize_loop is the definition of include/dal3.h written as the loop it is stated as: it reproduces what the
+    reference's points_to_voxel recorded, cap1 and the NaN points included, and so anchors the new cases"""
+    g = golden("pillars")
+    pts, cfg, cap, rev = _cloud(g, name)
+    index, cell, count = R.voxelize_loop(pts, cfg["voxel_size"], cfg["pc_range"], cfg["max_points"], cap)
+    assert np.array_equal(index, g[name + "_index"]) and np.array_equal(count, g[name + "_num"])
+    assert np.array_equal(cell[:, ::-1] if rev else cell, g[name + "_coords"])
+    _index_equals_loop(pts, cfg, cfg["max_points"], cap)
+
+
+def test_sequential_loop_equals_the_reference_on_the_ragged_batch():
+    g = golden("pillars")
+    pts, off = R.batch_points()
+    index, coords, num = [], [], []
+    for b in range(len(off) - 1):
+        i, c, n = R.voxelize_loop(pts[off[b]:off[b + 1]], R.PILLAR["voxel_size"], R.PILLAR["pc_range"], R.PILLAR["max_points"],
+                                  R.BATCH_CAP)
+        index.append(np.where(i >= 0, i + off[b], -1))
+        coords.append(np.concatenate([np.full((c.shape[0], 1), b, np.int64), c[:, ::-1]], 1))
+        num.append(n)
+    assert [n.size for n in num] == g["batch_num_voxels"].tolist()
+    # the fixture stores the rows as points, so compare the points the indices name
+    assert np.array_equal(R.gather(pts, np.concatenate(index)).view(np.uint32), R.gather(pts, g["batch_index"]).view(np.uint32))
+    assert np.array_equal(np.concatenate(coords), g["batch_coords"]) and np.array_equal(np.concatenate(num), g["batch_num"])
+
+
+@pytest.mark.parametrize("name", list(R.KEY_WIDTHS))
+def test_key_width_cases_are_what_the_table_says_and_equal_the_loop(name):
+    """grid, B * cells and the sort's passes of every row; every sample equals the sequential loop; keys reach the top of
+    the row's range (the last sample holds in-range points: for `top` that is bit 30 of the key)"""
+    vs, rng, grid, B, none, passes = R.KEY_WIDTHS[name]
+    pts, off, cfg = R.key_width_case(name)
+    assert R.grid_of(vs, rng).tolist() == list(grid) and off.size == B + 1
+    assert R.sort_passes(B, R.grid_of(vs, rng)) == (none, passes)
+    cells = int(np.prod(grid))
+    for b in range(B):
+        part = pts[off[b]:off[b + 1]]
+        index, cell, count = _index_equals_loop(part, cfg, R.KEY_MAX_POINTS, R.KEY_MAX_VOXELS)
+        assert 0 < count.size <= min(cells, R.KEY_MAX_VOXELS)
+        if cells <= 256:
+            assert count.size >= 0.95 * cells                       # the small grids fill (nearly) every cell
+        key = b * cells + (cell[:, 2] * grid[1] + cell[:, 1]) * grid[0] + cell[:, 0]
+        assert key.max() < none < 2 ** 31 - 1
+        if b == B - 1:
+            assert key.max() >= (B - 1) * cells and int(key.max()).bit_length() == (none - 1).bit_length()
+    if name == "top":
+        assert key.max() >> 30 == 1
+    if name == "2^8-1":                                             # every axis reaches its own, different, extent
+        assert cell.max(0).tolist() == [4, 16, 2]
+
+
+def test_run_length_and_many_sample_cases_equal_the_loop():
+    pts = R.run_length_points()
+    for max_points in R.RUN_MAX_POINTS:
+        index, cell, count = _index_equals_loop(pts, R.PILLAR, max_points, 2)
+        small, big = np.asarray(R.RUN_SMALL_AT), np.setdiff1d(np.arange(R.RUN_N), R.RUN_SMALL_AT)
+        assert count.tolist() == [min(3, max_points), min(big.size, max_points)]
+        assert index[0, :count[0]].tolist() == small[:max_points].tolist()
+        assert index[1, :count[1]].tolist() == big[:max_points].tolist() and (index[1, count[1]:] == -1).all()
+        assert cell.tolist() == [list(R.RUN_SMALL_CELL) + [0], list(R.RUN_BIG_CELL) + [0]]
+        index, cell, count = _index_equals_loop(pts, R.PILLAR, max_points, 1)       # the large cell is dropped whole
+        assert count.tolist() == [min(3, max_points)] and index[0, :count[0]].tolist() == small[:max_points].tolist()
+    pts, off = R.many_samples()
+    sizes = np.diff(off)
+    assert off.size == R.BIG_B + 1 and off[0] == R.BIG_HEAD and off[-1] == R.BIG_N - R.BIG_TAIL
+    assert sizes[:9].tolist() == list(R.BIG_SIZES) and not sizes[45:256].any() and sizes[256:].max() == 257
+    assert R.cells(pts[:off[0]], R.PILLAR["voxel_size"], R.PILLAR["pc_range"])[0].all()
+    assert R.cells(pts[off[-1]:], R.PILLAR["voxel_size"], R.PILLAR["pc_range"])[0].all()
+    capped = 0
+    for b in np.nonzero(sizes)[0]:
+        count = _index_equals_loop(pts[off[b]:off[b + 1]], R.PILLAR, R.PILLAR["max_points"], R.BIG_CAP)[2]
+        capped += count.size == R.BIG_CAP
+    assert capped >= 10                                             # the cap is met, behind the 256th sample too
+    assert _index_equals_loop(pts[off[262]:off[263]], R.PILLAR, R.PILLAR["max_points"], R.BIG_CAP)[2].size == R.BIG_CAP
+    # the overflow case: both sets of device offsets
+    pts = R.in_range_points("overflow", R.OVERFLOW_N)
+    assert R.cells(pts, R.PILLAR["voxel_size"], R.PILLAR["pc_range"])[0].all()
+    for off, sizes in zip(R.OVERFLOW_OFFSETS, ([R.OVERFLOW_CAP] * 2, [4, 5])):
+        got = [_index_equals_loop(pts[off[b]:off[b + 1]], R.PILLAR, R.PILLAR["max_points"], R.OVERFLOW_CAP)[2].size for b in range(2)]
+        assert got == sizes
+
+
 def test_faces_follow_the_definition():
     """a lower face is in, an upper face is out, one ulp either side falls as the float32 division says"""
     cfg = R.PILLAR
@@ -329,3 +422,34 @@ def test_lane_level_emulation_of_the_feature_kernel_meets_the_bars(n_layers):
     out = E.kernel(E.pack(sd6, n_layers, C, R.EPS), u, n40, c40, C, T, n_layers, vx, vy, xo, yo)
     j = R.judge(out, R.reader_f64(sd6, u, n40, c40, P["voxel_size"], P["pc_range"]))
     assert j["dead_ok"] and j["tensor"] < 1e-6 and j["chan_max"] < 1e-5, j
+
+
+def _far_module(n_layers):
+    cfg = R.PRODUCTION
+    net = pillars.PillarFeatureNet(num_input_features=cfg["C"], num_filters=(64,) * n_layers, voxel_size=cfg["voxel_size"],
+                                   pc_range=cfg["pc_range"], norm_cfg=dict(type="BN1d", eps=R.EPS, momentum=0.01)).eval()
+    net.load_state_dict({k: torch.as_tensor(v) for k, v in R.reader_weights(n_layers, cfg["C"]).items()}, strict=True)
+    return net
+
+
+@pytest.mark.parametrize("n_layers", [1, 2])
+def test_lane_level_emulation_far_from_the_origin_meets_the_bars(n_layers):
+    """the production grid's corner, centre and far-corner pillars (x and y indices up to 467, where the decoration
+    cancels 74 m against 74 m): the emulation against the float64 truth, the torch-CPU composite as the yardstick, under
+    the GPU test's bars, before a GPU is involved"""
+    import pillars_emu as E
+    cfg = R.PRODUCTION
+    vox, num, co = R.far_pillars()
+    assert sorted(set(co[:, 3].tolist())) == sorted(set(co[:, 2].tolist())) == list(R.FAR_AT) and (num == 1).any() and (num == 20).any()
+    assert np.abs(vox[:, 0, 0]).max() > 74.5 and np.abs(vox[:, 0, 1]).max() > 74.5
+    net = _far_module(n_layers)
+    sd = R.reader_weights(n_layers, cfg["C"])
+    with torch.no_grad():
+        f32 = net.composite(torch.from_numpy(vox), torch.from_numpy(num), torch.from_numpy(co)).numpy()
+    truth = R.reader_f64(sd, vox, num, co, cfg["voxel_size"], cfg["pc_range"])
+    out = E.kernel(E.pack(sd, n_layers, cfg["C"], R.EPS), vox, num, co, cfg["C"], cfg["max_points"], n_layers, net.vx, net.vy,
+                   net.x_offset, net.y_offset)
+    ratio, m, y = R.ratios(out, f32, truth)
+    for k in R.MEASURES:
+        print(f"far/l{n_layers} {k:9s} {m[k]:10.3e}  yardstick {y[k]:10.3e}  ratio {ratio[k]:7.2f}  bar {R.BARS[k]:g}")
+    assert m["dead_ok"] and all(ratio[k] <= R.BARS[k] for k in R.MEASURES), ratio
