@@ -216,6 +216,16 @@ class PillarFeatureArgs(C.Structure):
                 ("canvas_B", C.c_int64), ("ny", C.c_int64), ("nx", C.c_int64), ("max_workgroups", C.c_int64)]
 
 
+CONV2D_3X3, CONV2D_1X1, CONV2D_DECONV2, CONV2D_DECONV4 = range(4)
+
+
+class Conv2dArgs(C.Structure):
+    """dal3_conv2d_args"""
+    _fields_ = [("kind", C.c_int32), ("stride", C.c_int32), ("relu", C.c_int32), ("c_in", C.c_int32), ("c_out", C.c_int32),
+                ("y_channels", C.c_int32), ("y_channel_offset", C.c_int32), ("max_workgroups", C.c_int32), ("B", C.c_int64),
+                ("H", C.c_int64), ("W", C.c_int64), ("x", Map), ("y", Map), ("packed", vp)]
+
+
 # every symbol include/dal3.h declares: (restype, argtypes)
 _i, _i64, _u64, _sz = C.c_int, C.c_int64, C.c_uint64, C.c_size_t
 SIGNATURES = {
@@ -271,6 +281,9 @@ SIGNATURES = {
     "dal3_pillar_features": (_i, [C.POINTER(PillarFeatureArgs), vp]),
     "dal3_pillar_scatter": (_i, [vp, vp, _i64, vp, _i, vp, _i64, _i64, _i64, vp]),
     "dal3_voxel_mean": (_i, [vp, vp, _i64, vp, _i, _i, vp, vp]),
+    "dal3_conv2d_pack_floats": (_sz, [_i, _i, _i]),
+    "dal3_conv2d_pack": (_i, [C.POINTER(Layer), _i, C.c_double, vp, vp]),
+    "dal3_conv2d": (_i, [C.POINTER(Conv2dArgs), vp]),
     "dal3_crop_workspace_bytes": (_sz, [_i64, _i64]),
     "dal3_crop_count": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, _sz, vp]),
     "dal3_crop_fill": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, vp, vp, vp, _i64, vp, _sz, vp]),

@@ -1281,6 +1281,50 @@ extern "C" int dal3_voxel_mean(const float* voxels, const int32_t* num_points, i
     return 0;
 }
 
+// ---------------------------------------------------------------------------------- the detector's dense stage
+static bool conv2d_kind_ok(int kind) { return kind >= DAL3_CONV2D_3X3 && kind <= DAL3_CONV2D_DECONV4; }
+
+extern "C" size_t dal3_conv2d_pack_floats(int kind, int c_in, int c_out) {
+    if (!conv2d_kind_ok(kind) || c_in < 1 || c_in > 4096 || c_out < 1 || c_out > 4096) return 0;
+    return conv2d_pack_floats(kind, c_in, c_out);
+}
+
+extern "C" int dal3_conv2d_pack(const dal3_layer* layer, int kind, double eps, float* out, dal3_stream stream) {
+    if (!layer || !out) return fail(DAL3_EINVAL, "conv2d_pack: null layer / out");
+    if (!conv2d_kind_ok(kind)) return fail(DAL3_EINVAL, "conv2d_pack: kind %d is no DAL3_CONV2D_* form", kind);
+    if (layer->c_in < 1 || layer->c_in > 4096 || layer->c_out < 1 || layer->c_out > 4096)
+        return fail(DAL3_EINVAL, "conv2d_pack: bad c_in / c_out (1 .. 4096)");
+    if (!layer->weight) return fail(DAL3_EINVAL, "conv2d_pack: null weight");
+    const bool bn = layer->bn_weight || layer->bn_bias || layer->bn_mean || layer->bn_var;
+    if (bn && !(layer->bn_weight && layer->bn_bias && layer->bn_mean && layer->bn_var))
+        return fail(DAL3_EINVAL, "conv2d_pack: a BatchNorm needs all four of weight, bias, mean and var");
+    if (bn && !(eps > 0.0)) return fail(DAL3_EINVAL, "conv2d_pack: bad eps (> 0)");
+    if (reinterpret_cast<uintptr_t>(out) & 15) return fail(DAL3_EINVAL, "conv2d_pack: out must be 16-byte aligned");
+    HIP_TRY(launch_conv2d_pack(layer, kind, eps, out, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+extern "C" int dal3_conv2d(const dal3_conv2d_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "conv2d: null args");
+    const dal3_conv2d_args& a = *args;
+    if (!conv2d_kind_ok(a.kind)) return fail(DAL3_EINVAL, "conv2d: kind %d is no DAL3_CONV2D_* form", (int)a.kind);
+    const int want = a.kind == DAL3_CONV2D_DECONV2 ? 2 : a.kind == DAL3_CONV2D_DECONV4 ? 4 : 1;
+    if (a.stride != want && !(a.kind == DAL3_CONV2D_3X3 && a.stride == 2))
+        return fail(DAL3_EINVAL, "conv2d: stride %d (3x3: 1 or 2; 1x1: 1; a transposed convolution: its kernel size, 2 or 4)",
+                    (int)a.stride);
+    if ((a.relu != 0 && a.relu != 1) || a.max_workgroups < 0) return fail(DAL3_EINVAL, "conv2d: bad relu (0 or 1) / max_workgroups (>= 0)");
+    if (a.c_in < 1 || a.c_in > 4096 || a.c_out < 1 || a.c_out > 4096) return fail(DAL3_EINVAL, "conv2d: bad c_in / c_out (1 .. 4096)");
+    if (a.B < 0 || a.H < 0 || a.W < 0 || a.B > 65535 || a.H > 65535 || a.W > 65535)
+        return fail(DAL3_EINVAL, "conv2d: bad B / H / W (0 .. 65535)");
+    if (a.y_channel_offset < 0 || a.y_channels < 1 || (int64_t)a.y_channel_offset + a.c_out > a.y_channels)
+        return fail(DAL3_EINVAL, "conv2d: channels %d .. %lld lie outside the output's %d", (int)a.y_channel_offset,
+                    (long long)a.y_channel_offset + a.c_out, (int)a.y_channels);
+    if (!a.x.data || !a.y.data) return fail(DAL3_EINVAL, "conv2d: null x / y");
+    if (!a.packed || (reinterpret_cast<uintptr_t>(a.packed) & 15)) return fail(DAL3_EINVAL, "conv2d: packed is null or not 16-byte aligned");
+    HIP_TRY(launch_conv2d(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 extern "C" size_t dal3_crop_workspace_bytes(int64_t K_total, int64_t max_points_per_frame) {
     if (K_total <= 0 || max_points_per_frame < 0) return 0;
     return crop_workspace_bytes(K_total, max_points_per_frame);

@@ -297,6 +297,10 @@ hipError_t launch_pillar_scatter(const float* features, const int32_t* coordinat
                                  float* canvas, int64_t canvas_B, int64_t ny, int64_t nx, hipStream_t s);
 hipError_t launch_voxel_mean(const float* voxels, const int32_t* num_points, int64_t P, const int64_t* n_pillars, int max_points,
                              int C, float* out, hipStream_t s);
+// the detector's dense stage (dal3_conv2d.hip): 3x3 / 1x1 / transposed convolutions as one implicit GEMM on the fp32 MFMA
+size_t conv2d_pack_floats(int kind, int c_in, int c_out);
+hipError_t launch_conv2d_pack(const dal3_layer* layer, int kind, double eps, float* out, hipStream_t s);
+hipError_t launch_conv2d(const dal3_conv2d_args* a, hipStream_t s);
 hipError_t launch_points_in_boxes(const void* points, int points_f64, int64_t P, int64_t stride, const double* planes,
                                   int K, int f32_math, uint8_t* inside, hipStream_t s);
 hipError_t launch_writeback(const double* final_boxes, const int32_t* final_idx, const double* pose_best,

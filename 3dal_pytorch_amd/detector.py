@@ -1,0 +1,96 @@
+"""CenterPoint's PointPillars detector, eval mode, on the GPU: `PointPillars` (det3d/models/detectors/point_pillars.py,
+single_stage.py) under the reference's name, constructor signature and state_dict keys (`reader.*`, `neck.*`,
+`bbox_head.*`; the scatter backbone has no parameters), built from the `model` dict of a config such as
+configs/waymo/pp/waymo_centerpoint_pp_two_pfn_stride1_3x.py.
+
+`forward(example, return_loss=False)` takes the reference's collated example (voxels, coordinates, num_points, num_voxels,
+shape, metadata) and returns `CenterHead.predict`'s list. `detect(points, point_offsets, metadata=None)` starts from the
+raw sweep instead: voxelise -> pillar features into the canvas -> RPN -> CenterHead -> decode + NMS, everything enqueued on
+the current stream; the read-back of the kept boxes inside `predict` is the only host synchronisation. The loss is not
+built: `return_loss=True` is refused.
+"""
+import torch
+from torch import nn
+
+from . import pillars, rpn
+from .detect import CenterHeadPost
+
+READERS = {"PillarFeatureNet": pillars.PillarFeatureNet}
+BACKBONES = {"PointPillarsScatter": pillars.PointPillarsScatter}
+NECKS = {"RPN": rpn.RPN}
+HEADS = {"CenterHead": rpn.CenterHead}
+
+
+def _build(cfg, table, what):
+    if isinstance(cfg, nn.Module):
+        return cfg
+    args = dict(cfg)
+    kind = args.pop("type")
+    if kind not in table:
+        raise KeyError(f"{what} type {kind!r} is not built here (known: {sorted(table)})")
+    return table[kind](**args)
+
+
+class PointPillars(nn.Module):
+    """reader / backbone / neck / bbox_head: the config's dicts (with `type`) or modules. max_points / max_voxels: the
+    config's voxel_generator (max_points_in_voxel, max_voxel_num), which `detect` voxelises with."""
+
+    def __init__(self, reader, backbone, neck, bbox_head, train_cfg=None, test_cfg=None, pretrained=None, *, max_points=20,
+                 max_voxels=60000):
+        super().__init__()
+        self.reader = _build(reader, READERS, "reader")
+        self.backbone = _build(backbone, BACKBONES, "backbone")
+        self.neck = _build(neck, NECKS, "neck")
+        self.bbox_head = _build(bbox_head, HEADS, "bbox_head")
+        self.train_cfg, self.test_cfg = train_cfg, test_cfg
+        self.max_points, self.max_voxels = int(max_points), int(max_voxels)
+        if isinstance(reader, dict):
+            self.voxel_size, self.pc_range = list(reader["voxel_size"]), list(reader["pc_range"])
+        else:
+            self.voxel_size, self.pc_range = None, None
+        self.last = None
+        if pretrained is not None:
+            self.init_weights(pretrained)
+
+    @property
+    def with_neck(self):
+        return self.neck is not None
+
+    def init_weights(self, pretrained):
+        """a checkpoint path: its `state_dict` (or the file itself) must hold exactly this model's keys"""
+        ckpt = torch.load(pretrained, map_location="cpu")
+        self.load_state_dict(ckpt.get("state_dict", ckpt), strict=True)
+
+    def extract_feat(self, data):
+        features = self.reader(data["features"], data["num_voxels"], data["coors"])
+        x = self.backbone(features, data["coors"], data["batch_size"], data["input_shape"])
+        return self.neck(x) if self.with_neck else x
+
+    def forward(self, example, return_loss=False, **kwargs):
+        if return_loss:
+            raise NotImplementedError("PointPillars.forward(return_loss=True): the detector's loss is not built; this is the "
+                                      "eval-mode detector (call with return_loss=False)")
+        data = dict(features=example["voxels"], num_voxels=example["num_points"], coors=example["coordinates"],
+                    batch_size=len(example["num_voxels"]), input_shape=example["shape"][0])
+        preds = self.bbox_head(self.extract_feat(data))
+        return self.bbox_head.predict(example, preds, self.test_cfg)
+
+    @torch.no_grad()
+    def detect(self, points, point_offsets, metadata=None, point_offsets_device=None):
+        """points (N, C) float32 CUDA, point_offsets (B + 1) on the host -> the per-sample list of box3d_lidar / scores /
+        label_preds / metadata (CenterHeadPost.to_prediction turns it into the prediction.pkl dictionary). `last` keeps the
+        VoxelizeResult."""
+        if self.training:
+            raise RuntimeError("detect is the eval-mode route: call .eval()")
+        if self.voxel_size is None:
+            raise RuntimeError("detect needs the reader's voxel_size and pc_range: build the model from the config's dicts")
+        r = pillars.voxelize(points, point_offsets, self.voxel_size, self.pc_range, self.max_points, self.max_voxels,
+                             point_offsets_device=point_offsets_device)
+        self.last = r
+        grid = pillars.grid_size(self.voxel_size, self.pc_range)
+        canvas = self.reader.forward_canvas(r.voxels, r.num_points, r.coordinates, r.B, [int(grid[0]), int(grid[1])],
+                                            n_pillars=r.n_pillars)
+        preds = self.bbox_head(self.neck(canvas))
+        return self.bbox_head.predict({"metadata": metadata}, preds, self.test_cfg)
+
+    to_prediction = staticmethod(CenterHeadPost.to_prediction)

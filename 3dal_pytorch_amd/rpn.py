@@ -1,0 +1,414 @@
+"""The detector's dense stage on the GPU through lib3dal_hip.so (dal3_conv2d_pack / dal3_conv2d, include/dal3.h), under
+the reference's names, constructor signatures and state_dict keys: `RPN` (det3d/models/necks/rpn.py), `SepHead` and
+`CenterHead` (det3d/models/bbox_heads/center_head.py:65-110, 167-244).
+
+The modules hold the reference's own children (nn.Conv2d, nn.BatchNorm2d, nn.ConvTranspose2d at the reference's positions
+in their Sequentials), so a checkpoint loads strictly. In eval mode every layer the kernel serves — Conv 3x3 of stride 1
+or 2 with one ring of zero padding, Conv 1x1, ConvTranspose k = s in {2, 4}, each with an optional eval-mode BatchNorm2d
+and ReLU — runs dal3_conv2d on weights folded and packed once (a cache invalidated by load_state_dict / train / _apply
+and the tensors' version stamps); the three upsampled maps are written into channel slices of one tensor, and so are the
+head's maps (they are views, not NCHW-contiguous tensors). `composite()` is the same definition in stock torch ops: it
+runs in train mode and for whatever the kernel does not serve (a strided-convolution deblock, GroupNorm, other kernel
+sizes). There is no quiet fallback on the GPU route: a module that `hip_serves()` raises if its inputs are not on the GPU.
+"""
+import copy
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import _hip
+
+KIND_TAPS = {_hip.CONV2D_3X3: 9, _hip.CONV2D_1X1: 1, _hip.CONV2D_DECONV2: 1, _hip.CONV2D_DECONV4: 1}
+KIND_SUB = {_hip.CONV2D_3X3: 1, _hip.CONV2D_1X1: 1, _hip.CONV2D_DECONV2: 4, _hip.CONV2D_DECONV4: 16}
+
+
+def build_norm_layer(cfg, num_features):
+    """det3d/models/utils/norm.py for the types the neck is configured with: BN -> nn.BatchNorm2d, GN -> nn.GroupNorm"""
+    cfg = dict(cfg)
+    kind = cfg.pop("type")
+    cfg.pop("requires_grad", None)
+    if kind == "BN":
+        return nn.BatchNorm2d(num_features, eps=cfg.get("eps", 1e-5), momentum=cfg.get("momentum", 0.1))
+    if kind == "GN":
+        return nn.GroupNorm(cfg["num_groups"], num_features, eps=cfg.get("eps", 1e-5))
+    raise KeyError(f"norm layer type {kind!r} (BN or GN)")
+
+
+def layer_kind(conv):
+    """(kind, stride) of the dal3_conv2d form that serves this module, or None"""
+    if isinstance(conv, nn.ConvTranspose2d):
+        k, s = conv.kernel_size, conv.stride
+        ok = (k[0] == k[1] == s[0] == s[1] and k[0] in (2, 4) and conv.padding == (0, 0) and conv.output_padding == (0, 0)
+              and conv.dilation == (1, 1) and conv.groups == 1)
+        return ({2: _hip.CONV2D_DECONV2, 4: _hip.CONV2D_DECONV4}[k[0]], k[0]) if ok else None
+    if not isinstance(conv, nn.Conv2d) or conv.groups != 1 or conv.dilation != (1, 1) or conv.padding_mode != "zeros":
+        return None
+    k, s = conv.kernel_size, conv.stride
+    if k == (1, 1) and s == (1, 1) and conv.padding == (0, 0):
+        return _hip.CONV2D_1X1, 1
+    if k == (3, 3) and s[0] == s[1] and s[0] in (1, 2):
+        return _hip.CONV2D_3X3, s[0]             # the caller vouches for the one ring of zeros (padding=1 or a ZeroPad2d(1))
+    return None
+
+
+def _norm_ok(bn):
+    return bn is None or (isinstance(bn, nn.BatchNorm2d) and bn.affine and bn.track_running_stats)
+
+
+def pack_layer(conv, bn, kind):
+    """fold and pack one layer -> a float32 device tensor (dal3_conv2d_pack)"""
+    ts = [conv.weight] + ([conv.bias] if conv.bias is not None else []) + \
+        ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
+    for t in ts:
+        _hip.require_gpu(t, "the layer's parameters")
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError("weights must be contiguous fp32")
+    c_in, c_out = conv.in_channels, conv.out_channels
+    L = _hip.Layer(_hip.ptr(conv.weight), _hip.ptr(conv.bias), None, None, None, None, c_in, c_out)
+    if bn is not None:
+        L.bn_weight, L.bn_bias, L.bn_mean, L.bn_var = (_hip.ptr(t) for t in ts[-4:])
+    lib = _hip.lib()
+    buf = torch.empty(lib.dal3_conv2d_pack_floats(kind, c_in, c_out), dtype=torch.float32, device=conv.weight.device)
+    _hip.check(lib.dal3_conv2d_pack(L, kind, float(bn.eps) if bn is not None else 1e-5, _hip.ptr(buf), _hip.stream()))
+    return buf
+
+
+def out_size(kind, stride, H, W):
+    if kind == _hip.CONV2D_3X3:
+        return (H - 1) // stride + 1, (W - 1) // stride + 1
+    if kind == _hip.CONV2D_1X1:
+        return H, W
+    return H * stride, W * stride
+
+
+def _nchw_map(t):
+    return _hip.Map(_hip.ptr(t), t.stride(0), t.stride(2), t.stride(3), t.stride(1))
+
+
+def conv2d(x, packed, kind, stride, relu, c_out, out=None, channel_offset=0, max_workgroups=0):
+    """one layer: x (B, c_in, H, W) float32 CUDA, any strides -> channels [channel_offset, channel_offset + c_out) of `out`
+    (B, >= channel_offset + c_out, OH, OW) (allocated when None), returned as a view. Enqueued on the current stream."""
+    if not torch.is_tensor(x):
+        raise TypeError("x must be a tensor")
+    _hip.require_gpu(x, "x")
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError(f"x must be float32 (B, C, H, W), got {x.dtype} {tuple(x.shape)}")
+    B, c_in, H, W = x.shape
+    OH, OW = out_size(kind, stride, H, W)
+    if out is None:
+        out = torch.empty((B, channel_offset + c_out, OH, OW), dtype=torch.float32, device=x.device)
+    else:
+        _hip.require_gpu(out, "out")
+        if out.dtype != torch.float32 or out.dim() != 4 or out.shape[0] != B or tuple(out.shape[2:]) != (OH, OW) or out.device != x.device:
+            raise ValueError(f"out must be float32 ({B}, channels, {OH}, {OW}) on {x.device}, got {out.dtype} {tuple(out.shape)}")
+    if packed.numel() != _hip.lib().dal3_conv2d_pack_floats(kind, c_in, c_out) or packed.device != x.device:
+        raise ValueError(f"the packed weights are not those of a {c_in} -> {c_out} layer of kind {kind} on {x.device}")
+    a = _hip.Conv2dArgs(kind=kind, stride=stride, relu=1 if relu else 0, c_in=c_in, c_out=c_out, y_channels=out.shape[1],
+                        y_channel_offset=channel_offset, max_workgroups=int(max_workgroups), B=B, H=H, W=W, x=_nchw_map(x),
+                        y=_nchw_map(out), packed=_hip.ptr(packed))
+    if B and H and W:
+        _hip.check(_hip.lib().dal3_conv2d(a, _hip.stream()))
+    return out[:, channel_offset:channel_offset + c_out]
+
+
+def conv2d_flop(kind, stride, c_in, c_out, H, W, B=1):
+    """(algorithmic, executed) FLOP of one layer: 2 * MACs from the shapes, and what the kernel's tiles (32 GEMM rows,
+    8 x 32 pixels, 8 input channels) execute"""
+    taps, sub = KIND_TAPS[kind], KIND_SUB[kind]
+    ph, pw = out_size(kind, stride, H, W) if kind == _hip.CONV2D_3X3 else (H, W)
+    algo = 2 * B * ph * pw * c_out * sub * c_in * taps
+    rows, k, up = -(-c_out * sub // 32) * 32, -(-c_in // 8) * 8, lambda v, m: -(-v // m) * m
+    return algo, 2 * B * up(ph, 8) * up(pw, 32) * rows * k * taps
+
+
+class _PackedLayers(nn.Module):
+    """the packed-weights cache of a module whose `_plan()` lists its kernel layers as (conv, bn, kind, stride, relu)"""
+
+    def __init__(self):
+        super().__init__()
+        self._packed, self._stamp = None, None
+
+    def invalidate_packed(self):
+        """after writes that bypass the tensors' version counters (`.data` writes, raw pointers)"""
+        self._packed, self._stamp = None, None
+
+    def load_state_dict(self, *a, **k):
+        out = super().load_state_dict(*a, **k)
+        self.invalidate_packed()
+        return out
+
+    def train(self, mode=True):
+        out = super().train(mode)
+        self.invalidate_packed()
+        return out
+
+    def _apply(self, fn, *a, **k):
+        out = super()._apply(fn, *a, **k)
+        self.invalidate_packed()
+        return out
+
+    def packed(self):
+        plan = self._plan()
+        ts = [t for conv, bn, *_ in plan for t in list(conv.parameters()) + (list(bn.parameters()) + list(bn.buffers()) if bn is not None else [])]
+        stamp = tuple((t.data_ptr(), t._version, t.device) for t in ts)
+        if self._packed is None or stamp != self._stamp:
+            self._packed, self._stamp = self._pack(plan), stamp
+        return self._packed
+
+    def _pack(self, plan):
+        return [pack_layer(conv, bn, kind) for conv, bn, kind, _, _ in plan]
+
+
+def _split(seq):
+    """a reference Sequential -> [(conv, norm or None, relu)] by position; padding modules are skipped"""
+    out = []
+    for m in seq:
+        if isinstance(m, (nn.Conv2d, nn.ConvTranspose2d)):
+            out.append([m, None, False])
+        elif isinstance(m, nn.ReLU):
+            out[-1][2] = True
+        elif not isinstance(m, nn.ZeroPad2d):
+            out[-1][1] = m
+    return out
+
+
+class RPN(_PackedLayers):
+    """det3d/models/necks/rpn.py. forward(x (B, num_input_features, H, W)) -> (B, sum(us_num_filters), H', W')."""
+
+    def __init__(self, layer_nums, ds_layer_strides, ds_num_filters, us_layer_strides, us_num_filters, num_input_features,
+                 norm_cfg=None, name="rpn", logger=None, **kwargs):
+        super().__init__()
+        self._layer_strides, self._num_filters, self._layer_nums = ds_layer_strides, ds_num_filters, layer_nums
+        self._upsample_strides, self._num_upsample_filters = us_layer_strides, us_num_filters
+        self._num_input_features = num_input_features
+        self._norm_cfg = dict(type="BN", eps=1e-3, momentum=0.01) if norm_cfg is None else norm_cfg
+        assert len(self._layer_strides) == len(self._layer_nums) == len(self._num_filters)
+        assert len(self._num_upsample_filters) == len(self._upsample_strides)
+        self._upsample_start_idx = len(self._layer_nums) - len(self._upsample_strides)
+        must_equal = [self._upsample_strides[i] / np.prod(self._layer_strides[:i + self._upsample_start_idx + 1])
+                      for i in range(len(self._upsample_strides))]
+        assert all(v == must_equal[0] for v in must_equal)
+        in_filters = [num_input_features, *self._num_filters[:-1]]
+        blocks, deblocks = [], []
+        for i, layer_num in enumerate(self._layer_nums):
+            planes = self._num_filters[i]
+            block = [nn.ZeroPad2d(1), nn.Conv2d(in_filters[i], planes, 3, stride=self._layer_strides[i], bias=False),
+                     build_norm_layer(self._norm_cfg, planes), nn.ReLU()]
+            for _ in range(layer_num):
+                block += [nn.Conv2d(planes, planes, 3, padding=1, bias=False), build_norm_layer(self._norm_cfg, planes), nn.ReLU()]
+            blocks.append(nn.Sequential(*block))
+            j = i - self._upsample_start_idx
+            if j >= 0:
+                stride, up = self._upsample_strides[j], self._num_upsample_filters[j]
+                if stride > 1:
+                    conv = nn.ConvTranspose2d(planes, up, stride, stride=stride, bias=False)
+                else:
+                    stride = int(np.round(1 / stride))
+                    conv = nn.Conv2d(planes, up, stride, stride=stride, bias=False)
+                deblocks.append(nn.Sequential(conv, build_norm_layer(self._norm_cfg, up), nn.ReLU()))
+        self.blocks = nn.ModuleList(blocks)
+        self.deblocks = nn.ModuleList(deblocks)
+        if logger is not None:
+            logger.info("Finish RPN Initialization")
+
+    @property
+    def downsample_factor(self):
+        factor = np.prod(self._layer_strides)
+        if len(self._upsample_strides) > 0:
+            factor /= self._upsample_strides[-1]
+        return factor
+
+    def init_weights(self):
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.xavier_uniform_(m.weight)
+
+    def _plan(self):
+        """[(conv, bn, kind, stride, relu)]: every block's layers, then every deblock's"""
+        return [(conv, bn, *layer_kind(conv), relu) for seq in list(self.blocks) + list(self.deblocks) for conv, bn, relu in _split(seq)]
+
+    def hip_serves(self):
+        """whether the eval-mode forward of this module runs the HIP kernel"""
+        for seq in list(self.blocks) + list(self.deblocks):
+            for conv, bn, _ in _split(seq):
+                kind = layer_kind(conv)
+                if kind is None or not _norm_ok(bn) or (kind[0] == _hip.CONV2D_3X3 and conv.padding not in ((0, 0), (1, 1))):
+                    return False
+        return len(self.deblocks) > 0
+
+    def composite(self, x):
+        """the same definition in stock torch ops (the reference's forward); differentiable, BatchNorm by its mode"""
+        ups = []
+        for i, block in enumerate(self.blocks):
+            x = block(x)
+            if i - self._upsample_start_idx >= 0:
+                ups.append(self.deblocks[i - self._upsample_start_idx](x))
+        return torch.cat(ups, dim=1) if ups else x
+
+    def forward(self, x, max_workgroups=0):
+        if self.training or not self.hip_serves():
+            return self.composite(x)
+        with torch.no_grad():
+            packed, plan = self.packed(), self._plan()
+            at, n_block_layers = 0, sum(len(_split(b)) for b in self.blocks)
+            ups, offset, out = [], 0, None
+            for i, block in enumerate(self.blocks):
+                for _ in _split(block):
+                    conv, _, kind, stride, relu = plan[at]
+                    x = conv2d(x, packed[at], kind, stride, relu, conv.out_channels, max_workgroups=max_workgroups)
+                    at += 1
+                j = i - self._upsample_start_idx
+                if j >= 0:
+                    conv, _, kind, stride, relu = plan[n_block_layers + j]
+                    size = out_size(kind, stride, x.shape[2], x.shape[3])
+                    if out is None:
+                        out = torch.empty((x.shape[0], sum(self._num_upsample_filters), *size), dtype=torch.float32, device=x.device)
+                    elif tuple(out.shape[2:]) != size:
+                        raise RuntimeError(f"the upsampled maps differ in size ({tuple(out.shape[2:])} and {size}): torch.cat would refuse them")
+                    conv2d(x, packed[n_block_layers + j], kind, stride, relu, conv.out_channels, out=out, channel_offset=offset,
+                           max_workgroups=max_workgroups)
+                    offset += conv.out_channels
+            return out
+
+
+class SepHead(nn.Module):
+    """center_head.py:65-110: one Sequential per head, [Conv, (BatchNorm2d), ReLU] * (num_conv - 1) + [Conv]. A parameter
+    container with the reference's forward; CenterHead runs its layers through the kernel."""
+
+    def __init__(self, in_channels, heads, head_conv=64, final_kernel=1, bn=False, init_bias=-2.19, **kwargs):
+        super().__init__(**kwargs)
+        self.heads = heads
+        for head in self.heads:
+            classes, num_conv = self.heads[head]
+            fc = []
+            for _ in range(num_conv - 1):
+                fc.append(nn.Conv2d(in_channels, head_conv, kernel_size=final_kernel, stride=1, padding=final_kernel // 2, bias=True))
+                if bn:
+                    fc.append(nn.BatchNorm2d(head_conv))
+                fc.append(nn.ReLU())
+            fc.append(nn.Conv2d(head_conv, classes, kernel_size=final_kernel, stride=1, padding=final_kernel // 2, bias=True))
+            fc = nn.Sequential(*fc)
+            if "hm" in head:
+                fc[-1].bias.data.fill_(init_bias)
+            else:
+                for m in fc.modules():
+                    if isinstance(m, nn.Conv2d):
+                        nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+                        nn.init.constant_(m.bias, 0)
+            self.__setattr__(head, fc)
+
+    def forward(self, x):
+        return {head: self.__getattr__(head)(x) for head in self.heads}
+
+
+class CenterHead(_PackedLayers):
+    """center_head.py:167-244 and `predict` (through detect.CenterHeadPost). forward(x) -> one dict per task of logical
+    (B, c, H, W) maps; on the kernel route they are channel slices of one tensor per task."""
+
+    def __init__(self, in_channels=[128, ], tasks=[], dataset="nuscenes", weight=0.25, code_weights=[], common_heads=dict(),
+                 logger=None, init_bias=-2.19, share_conv_channel=64, num_hm_conv=2, dcn_head=False):
+        super().__init__()
+        if dcn_head:
+            raise NotImplementedError("dcn_head=True (deformable convolutions in the head) is not supported")
+        num_classes = [len(t["class_names"]) for t in tasks]
+        self.class_names = [t["class_names"] for t in tasks]
+        self.code_weights, self.weight, self.dataset = code_weights, weight, dataset
+        self.in_channels, self.num_classes = in_channels, num_classes
+        self.box_n_dim = 9 if "vel" in common_heads else 7
+        self.use_direction_classifier = False
+        self.shared_conv = nn.Sequential(nn.Conv2d(in_channels, share_conv_channel, kernel_size=3, padding=1, bias=True),
+                                         nn.BatchNorm2d(share_conv_channel), nn.ReLU(inplace=True))
+        self.tasks = nn.ModuleList()
+        for num_cls in num_classes:
+            heads = copy.deepcopy(common_heads)
+            heads.update(dict(hm=(num_cls, num_hm_conv)))
+            self.tasks.append(SepHead(share_conv_channel, heads, bn=True, init_bias=init_bias, final_kernel=3))
+        self._post = None
+
+    def _sequences(self):
+        return [self.shared_conv] + [getattr(task, head) for task in self.tasks for head in task.heads]
+
+    def _plan(self):
+        return [(conv, bn, *layer_kind(conv), relu) for seq in self._sequences() for conv, bn, relu in _split(seq)]
+
+    def hip_serves(self):
+        """whether the eval-mode forward of this module runs the HIP kernel"""
+        for seq in self._sequences():
+            for conv, bn, _ in _split(seq):
+                kind = layer_kind(conv)
+                if kind is None or not _norm_ok(bn) or (kind[0] == _hip.CONV2D_3X3 and conv.padding != (1, 1)):
+                    return False
+        return True
+
+    def _fusable(self, task):
+        """the first convolutions of a task's heads read the same input: they run as one launch when each is one 3x3
+        layer of a multiple of 64 channels (whole row groups of the kernel), which leaves every output's k-order as it is
+        when run alone"""
+        firsts = [_split(getattr(task, head)) for head in task.heads]
+        return all(len(f) == 2 and f[0][0].out_channels % 64 == 0 and f[0][0].kernel_size == (3, 3) for f in firsts)
+
+    def _pack(self, plan):
+        packs = super()._pack(plan)
+        fused, at = [], 1
+        for task in self.tasks:
+            n = [len(_split(getattr(task, head))) for head in task.heads]
+            if self._fusable(task):
+                first = [packs[at + sum(n[:i])] for i in range(len(n))]
+                rows = [plan[at + sum(n[:i])][0].out_channels for i in range(len(n))]
+                # a pack is [bias of every GEMM row | fragments by out tile]: the fused layer's is both parts concatenated
+                fused.append(torch.cat([p[:r] for p, r in zip(first, rows)] + [p[r:] for p, r in zip(first, rows)]))
+            else:
+                fused.append(None)
+            at += sum(n)
+        return packs, fused
+
+    def composite(self, x):
+        """the same definition in stock torch ops (the reference's forward)"""
+        x = self.shared_conv(x)
+        return [task(x) for task in self.tasks]
+
+    def forward(self, x, *kwargs, max_workgroups=0):
+        if self.training or not self.hip_serves():
+            return self.composite(x)
+        with torch.no_grad():
+            (packed, fused), plan = self.packed(), self._plan()
+
+            def run(at, x, **kw):
+                conv, _, kind, stride, relu = plan[at]
+                return conv2d(x, packed[at], kind, stride, relu, conv.out_channels, max_workgroups=max_workgroups, **kw)
+
+            x = run(0, x)
+            at, ret = 1, []
+            for t, task in enumerate(self.tasks):
+                n = [len(_split(getattr(task, head))) for head in task.heads]
+                classes = [task.heads[head][0] for head in task.heads]
+                maps = torch.empty((x.shape[0], sum(classes), x.shape[2], x.shape[3]), dtype=torch.float32, device=x.device)
+                mid = None
+                if fused[t] is not None:
+                    widths = [plan[at + sum(n[:i])][0].out_channels for i in range(len(n))]
+                    mid = conv2d(x, fused[t], _hip.CONV2D_3X3, 1, True, sum(widths), max_workgroups=max_workgroups)
+                d, offset = {}, 0
+                for i, head in enumerate(task.heads):
+                    y = x
+                    if mid is not None:
+                        y = mid[:, sum(widths[:i]):sum(widths[:i + 1])]
+                        at += 1
+                    for k in range(n[i] - (1 if mid is None else 2)):
+                        y = run(at, y)
+                        at += 1
+                    d[head] = run(at, y, out=maps, channel_offset=offset)
+                    at += 1
+                    offset += classes[i]
+                ret.append(d)
+            return ret
+
+    @torch.no_grad()
+    def predict(self, example, preds_dicts, test_cfg, **kwargs):
+        """center_head.py:294 through detect.CenterHeadPost -> the per-sample list of box3d_lidar / scores / label_preds /
+        metadata; one host synchronisation"""
+        from .detect import CenterHeadPost
+        if self._post is None or self._post[0] is not test_cfg:
+            self._post = (test_cfg, CenterHeadPost(test_cfg, self.num_classes))
+        meta = example.get("metadata") if isinstance(example, dict) else None
+        return self._post[1].predict(preds_dicts, metadata=meta)

@@ -870,6 +870,48 @@ int dal3_pillar_scatter(const float* features, const int32_t* coordinates, int64
 int dal3_voxel_mean(const float* voxels, const int32_t* num_points, int64_t P, const int64_t* n_pillars, int max_points, int C,
                     float* out, dal3_stream stream);
 
+/* ---- the detector's dense stage: the 2-D convolutions of RPN (det3d/models/necks/rpn.py) and of CenterHead.forward /
+ * SepHead (det3d/models/bbox_heads/center_head.py:65-110, 167-244), float32, eval mode.
+ *
+ * A layer is Conv + optional BatchNorm2d + optional ReLU with the BatchNorm folded by dal3_conv2d_pack, in float64 and
+ * rounded once to float32, with the layer's own eps (the neck's norm_cfg says 1e-3, the head's nn.BatchNorm2d 1e-5):
+ *   scale = g / sqrt(var + eps),  W' = W * scale,  b' = (bias - mean) * scale + beta     (the product and the sum each
+ * rounded by itself); without BatchNorm scale = 1 and b' = bias; a NULL bias is 0. Three forms, x and y float32 NCHW
+ * tensors read and written through the element strides of a dal3_map, a (B, H, W, C) view:
+ *   DAL3_CONV2D_3X3      y[b,co,oy,ox] = act(b'[co] + sum W'[co,ci,ky,kx] * x[b,ci,oy*s+ky-1,ox*s+kx-1]), zeros outside the
+ *                        image, s = stride 1 or 2, output (floor((H-1)/s)+1, floor((W-1)/s)+1): both ZeroPad2d(1) +
+ *                        Conv2d(3, stride=s) and Conv2d(3, padding=1). weight (c_out, c_in, 3, 3).
+ *   DAL3_CONV2D_1X1      y[b,co,iy,ix] = act(b'[co] + sum W'[co,ci] * x[b,ci,iy,ix]); stride 1. weight (c_out, c_in).
+ *   DAL3_CONV2D_DECONV2 / _DECONV4   ConvTranspose2d(c_in, c_out, s, stride=s), s = 2 / 4 (= args.stride):
+ *                        y[b,co,iy*s+dy,ix*s+dx] = act(b'[co] + sum W'[ci,co,dy,dx] * x[b,ci,iy,ix]), output (H*s, W*s).
+ *                        weight (c_in, c_out, s, s).
+ * act = max(., 0) with relu, the identity without. y.data is channel 0 of a tensor of y_channels channels and the layer
+ * writes channels [y_channel_offset, y_channel_offset + c_out) of it: torch.cat of several layers' outputs is no copy.
+ * The sums run on the fp32 MFMA (output channels on its rows, 32 output pixels on its columns, K = c_in * taps, in
+ * steps of two channels per tap); the accumulator starts at b', and the ORDER of the summation is not part of the
+ * definition: results are judged against a float64 evaluation (tests/rpn_ref.py). Non-finite inputs and weights are
+ * outside the contract. x and y must not overlap. B, H, W <= 65535, c_in, c_out <= 4096; offsets are formed in 64 bits.
+ * packed: dal3_conv2d_pack_floats(kind, c_in, c_out) floats (0 for bad arguments), 16-byte aligned; every pointer of the
+ * layer is a device pointer. Invalid arguments return DAL3_EINVAL and nothing is launched. No workspace. */
+enum { DAL3_CONV2D_3X3 = 0, DAL3_CONV2D_1X1 = 1, DAL3_CONV2D_DECONV2 = 2, DAL3_CONV2D_DECONV4 = 3 };
+
+typedef struct dal3_conv2d_args {
+    int32_t kind;                        /* DAL3_CONV2D_* */
+    int32_t stride;                      /* 3X3: 1 or 2; 1X1: 1; DECONV2: 2; DECONV4: 4 */
+    int32_t relu;                        /* 0 or 1 */
+    int32_t c_in, c_out;
+    int32_t y_channels;                  /* channels of the tensor y.data starts */
+    int32_t y_channel_offset;            /* first channel this layer writes */
+    int32_t max_workgroups;              /* 0: no cap */
+    int64_t B, H, W;                     /* of the INPUT */
+    dal3_map x, y;
+    const float* packed;                 /* dal3_conv2d_pack's */
+} dal3_conv2d_args;
+
+size_t dal3_conv2d_pack_floats(int kind, int c_in, int c_out);
+int dal3_conv2d_pack(const dal3_layer* layer, int kind, double eps, float* out, dal3_stream stream);
+int dal3_conv2d(const dal3_conv2d_args* args, dal3_stream stream);
+
 /* ---- crop extraction from full sweeps: the per-detection loop of _create_pd_detection
  * (det3d/datasets/waymo/waymo_common.py:166-171, 193) for F frames at once. points (P_total,3) f32 vehicle-frame
  * sweeps concatenated, point_offsets (F+1); planes (K_total,6,4) f64 face equations of every frame's detections
