@@ -11,15 +11,24 @@
              within 1e-5 of 0.75 (checked here), so a float32 IoU decides the same way.
     regroup  tools/trackData.py run on a temp `val` dir holding a trackData.pkl built from the tracker's output.
 
+    dense    tracking_dense.npz: PubTracker.step_centertrack driven directly on tests/track_ref.dense_cases() — inputs
+             already in tracker form. A detection is a dict with translation (x, y, 0), velocity = -tracking, fed with
+             time_lag 1.0 (`velocity * -1 * time_lag` is then `tracking` bit for bit), detection_name by its label and
+             its score as a Python float of the same value: the reference compares `score > score_thresh` in float64
+             under the NumPy 1.x it was written for, while NumPy 2 would round the threshold to a float32 score's type.
+             reset() at each sequence start; outputs filtered by `active != 0` as above.
+
 Stored: the reference's outputs only (the inputs are rebuilt from the seed). Run where the reference exists
-(DAL3_REFERENCE, default /root/reference):
-    python tests/golden/gen_tracking.py
+(DAL3_REFERENCE, default /root/reference); an argument names another output directory:
+    python tests/golden/gen_tracking.py [OUT_DIR]
 """
+import io
 import os
 import pickle
 import sys
 import tempfile
 import types
+import zipfile
 
 import numpy as np
 import torch
@@ -87,8 +96,54 @@ def run_tracker(tp, PubTracker, preds, infos, p):
     return out, tracker.id_count, cts, vels, toks
 
 
+def run_dense(PubTracker, inputs, max_age=3, max_dist=(0.8, 0.4, 0.6), score_thresh=0.75):
+    """-> (per frame (box_ids, tracking_ids), id_count) of the reference's tracker on tracker-form inputs"""
+    ct, tracking, label, score, fo, so = inputs
+    names = ["VEHICLE", "PEDESTRIAN", "CYCLIST"]
+    tracker = PubTracker(max_age=max_age, max_dist=dict(zip(names, max_dist)), score_thresh=score_thresh)
+    starts = set(int(x) for x in so[:-1])
+    out = []
+    for f in range(len(fo) - 1):
+        if f in starts:
+            tracker.reset()
+        dets = [{"translation": (ct[k, 0], ct[k, 1], 0.0), "velocity": -tracking[k], "detection_name": names[label[k]],
+                 "score": float(score[k]), "box_id": k - int(fo[f])} for k in range(int(fo[f]), int(fo[f + 1]))]
+        for d in dets:
+            assert np.array_equal(np.array(d["velocity"][:2]) * -1 * 1.0, tracking[d["box_id"] + int(fo[f])])
+        outputs = tracker.step_centertrack(dets, 1.0)
+        keep = [it for it in outputs if it["active"] != 0]
+        out.append((np.array([it["box_id"] for it in keep], np.int64), np.array([it["tracking_id"] for it in keep], np.int64)))
+    return out, tracker.id_count
+
+
+def write_npz(path, rec):
+    """np.savez_compressed with fixed member dates, so that the file regenerates byte for byte"""
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for k, v in rec.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(v), allow_pickle=False)
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            z.writestr(info, buf.getvalue())
+
+
+def dense(PubTracker, out_dir):
+    rec = {}
+    with np.errstate(invalid="ignore"):
+        for name, (inputs, params) in track_ref.dense_cases().items():
+            out, id_count = run_dense(PubTracker, inputs, **params)
+            rec[name + "__box_ids"] = np.concatenate([o[0] for o in out] + [np.zeros(0, np.int64)]).astype(np.int32)
+            rec[name + "__tracking_ids"] = np.concatenate([o[1] for o in out] + [np.zeros(0, np.int64)]).astype(np.int32)
+            rec[name + "__out_count"] = np.array([len(o[0]) for o in out], np.int32)
+            rec[name + "__id_count"] = np.array(id_count, np.int64)
+            print(name, "frames", len(out), "entries", len(rec[name + "__box_ids"]), "ids", id_count)
+    write_npz(os.path.join(out_dir, "tracking_dense.npz"), rec)
+
+
 def main():
+    out_dir = sys.argv[1] if len(sys.argv) > 1 else HERE
     tp, PubTracker = import_test_py()
+    dense(PubTracker, out_dir)
     frames = track_ref.scene(SEED)
     rec = {}
     with tempfile.TemporaryDirectory() as tmp:
@@ -142,7 +197,7 @@ def main():
     for k, v in rec.items():
         print(k, v.shape, v.dtype)
     print("matches:", int((rec["match_obj"] >= 0).sum()), "of", len(flat), "ids:", id_count)
-    np.savez_compressed(os.path.join(HERE, "tracking.npz"), **rec)
+    np.savez_compressed(os.path.join(out_dir, "tracking.npz"), **rec)
 
 
 def regroup_input(out, tokens):

@@ -106,3 +106,153 @@ def test_header_declares_the_tracking_entries():
     for name in ("dal3_track_args", "dal3_track_match_args", "DAL3_TRACK_MAX_CAPACITY", "DAL3_TRACK_OVERFLOW"):
         assert name in text
     assert int(re.search(r"#define DAL3_TRACK_MAX_CAPACITY (\d+)", text).group(1)) == hip.TRACK_MAX_CAPACITY
+
+
+# ------------------------------------------------------------------ the dense scenes (tests/golden/tracking_dense.npz)
+# Recorded from the reference's PubTracker: every case of track_ref.dense_cases(), the 27 (N, M) pairs included.
+# track_ref.many_frames() is NOT recorded (100 k entries of a two-detection pattern): it is held to the restatement alone.
+_CASES = track_ref.dense_cases()
+_STATS = {}
+
+
+def _stats(name):
+    if name not in _STATS:
+        inputs, params = _CASES[name] if name in _CASES else (track_ref.many_frames(), {})
+        _STATS[name] = track_ref.stats(*inputs, **params)
+    return _STATS[name]
+
+
+def _track(name):
+    inputs, params = _CASES[name]
+    with np.errstate(invalid="ignore"):
+        return track_ref.track(*inputs, **params)
+
+
+def test_restated_tracker_equals_the_reference_on_every_dense_scene():
+    g = golden("tracking_dense")
+    assert sorted({k.split("__")[0] for k in g}) == sorted(_CASES)
+    for name in _CASES:
+        out, ids = _track(name)
+        assert np.array_equal([len(b) for b, _ in out], g[name + "__out_count"]), name
+        assert np.array_equal(np.concatenate([b for b, _ in out] + [np.zeros(0, np.int64)]), g[name + "__box_ids"]), name
+        assert np.array_equal(np.concatenate([t for _, t in out] + [np.zeros(0, np.int64)]), g[name + "__tracking_ids"]), name
+        assert ids == int(g[name + "__id_count"]), name
+
+
+def test_crowded_scenes_contend_and_tie():
+    """conditions on the inputs, from the restatement alone: about half of what the scenes give"""
+    for name in ("crowded", "crowded_far", "continuous", "continuous_far"):
+        s = _stats(name)
+        assert s["rescanned"] >= 0.25 * s["rows"], (name, s["rescanned"], s["rows"])
+        assert s["matches"] >= 0.5 * s["rows"], (name, s["matches"], s["rows"])
+        assert s["max_n"] > 256 and s["max_live"] > 256, name
+    for name in ("crowded", "crowded_far"):
+        assert _stats(name)["ties"] >= 0.1 * _stats(name)["rows"], name
+    keys = ("rows", "rescanned", "ties", "max_n", "max_m", "matches", "max_live")
+    assert [_stats("crowded")[k] for k in keys] == [_stats("crowded_far")[k] for k in keys]   # exact at 3e5 m alike
+    assert _stats("continuous")["ties"] == 0
+    assert _stats("continuous_far")["ties"] >= 1
+    # three sequences of different size in one call; the second's list passes 64 and stays below 256
+    ct, tr, lab, sc, fo, so = _CASES["crowded"][0]
+    assert len(so) == 4
+    mid = tuple(a[fo[so[1]]:fo[so[2]]] for a in (ct, tr, lab, sc)) + (fo[so[1]:so[2] + 1] - fo[so[1]], np.array([0, so[2] - so[1]]))
+    assert 64 < track_ref.stats(*mid)["max_live"] < 256
+    # detections are multiples of 1/8 m: exact in float32 at the origin and at 3e5 m
+    far = _CASES["crowded_far"][0][0]
+    assert np.array_equal(ct * 8, np.round(ct * 8)) and np.array_equal(far.astype(np.float32).astype(np.float64), far)
+    assert np.array_equal(far - 300000.0, ct)
+
+
+def test_tie_ring_ties_at_the_designed_columns():
+    s = _stats("tie_ring_default")
+    for pair in track_ref.TIE_RING_PAIRS:
+        assert tuple(pair) in s["tie_sets"], pair
+    assert tuple(track_ref.TIE_RING_MANY) in s["tie_sets"]
+    for k in range(1, len(track_ref.TIE_RING_MANY) - 1):                # every later row: the free columns that remain
+        assert tuple(track_ref.TIE_RING_MANY[k:]) in s["tie_sets"], k
+    assert s["max_m"] >= track_ref.TIE_RING_M and s["rescanned"] >= 15
+    (b1, t1) = _track("tie_ring_default")[0][1]
+    took = dict(zip(b1.tolist(), (t1 - 1).tolist()))                    # frame 1: row -> column (id - 1) where matched
+    M = track_ref.TIE_RING_M
+    assert [took[r] for r in (0, 1, 2)] == [5, 6, 69] and took[3] >= M              # rows at a, b, a; a third at a: none left
+    assert [took[r] for r in (4, 5)] == [63, 64] and took[6] >= M
+    assert [took[r] for r in (7, 10)] == [0, M - 1] and took[11] >= M
+    assert [took[r] for r in (8, 9)] == [31, 32]
+    assert [took[r] for r in range(12, 24)] == list(track_ref.TIE_RING_MANY) and took[24] >= M and took[25] >= M
+    # max_dist exactly the ring distance still matches; the float32 just below it matches nothing on a ring
+    exact, below = _track("tie_ring_exact"), _track("tie_ring_below")
+    assert np.array_equal(exact[0][1][1], t1) and exact[1] == _track("tie_ring_default")[1]
+    assert (below[0][1][1] > M).all() and _stats("tie_ring_below")["ties"] == 0
+    assert track_ref.TIE_RING_MAX_DIST["below"][0] < 0.625 == track_ref.TIE_RING_MAX_DIST["exact"][0]
+
+
+def test_nonfinite_scene_decides_as_its_comment_says():
+    out, ids = _track("nonfinite")
+    rows = lambda f: out[f][0].tolist()         # noqa: E731
+    tids = lambda f: out[f][1].tolist()         # noqa: E731
+    assert (rows(1), tids(1)) == ([0, 1, 2, 3, 6, 4, 5], [1, 2, 3, 4, 6, 9, 10])     # the NaN rows: no match, new tracks
+    for f in (2, 3, 4):                                                             # two NaN tracks live: nothing matches
+        assert rows(f) == [0, 1, 2] and tids(f) == list(range(11 + 3 * (f - 2), 14 + 3 * (f - 2)))
+    assert (rows(5), tids(5)) == ([0, 1, 2, 3, 4, 5], [17, 18, 19, 20, 21, 22])      # gone after max_age frames
+    assert tids(6) == tids(5)
+    assert tids(7) == [23, 24, 25, 26, 27, 28]                                      # 28: the inf track
+    assert (rows(8), tids(8)) == ([0, 3, 4, 5, 6, 1, 2], [23, 24, 25, 26, 27, 29, 30])   # NaN score (row 7): no id
+    assert tids(9) == [23, 24, 25, 26, 27] and ids == 30
+    ct, _, _, sc, fo, so = _CASES["nonfinite"][0]
+    assert np.isnan(ct).sum() == 2 and np.isinf(ct).sum() == 3 and np.isnan(sc).sum() == 1
+    assert _stats("nonfinite")["rescanned"] >= 2                                    # the NaN rows' column 0 was taken
+
+
+def test_threshold_scene_decides_as_its_comment_says():
+    s75, s_next, s6 = track_ref.THRESHOLD_SCORES
+    assert float(s75) == 0.75 and float(s_next) > 0.75 and float(s6) > 0.6 and s6 == np.float32(0.6)
+    first = lambda name, row: [t for b, t in zip(*_track(name)[0][0]) if b == row]   # noqa: E731
+    assert first("threshold_age3", 0) == [] and first("threshold_age3", 1) == [1] and first("threshold_age3", 2) == []
+    assert first("threshold_0.6", 0) == [1] and first("threshold_0.6", 2) == [3]
+    for max_age in (0, 1, 2, 3):
+        out, _ = _track(f"threshold_age{max_age}")
+        born = dict(zip(out[0][0].tolist(), out[0][1].tolist()))        # frame 0: row -> id; object h is row 3 + h
+        for h in track_ref.THRESHOLD_HIDDEN[1:]:
+            b, t = out[h + 1]                                           # the frame object h returns in, as row 3 + (h - 1)... by id
+            kept = born[3 + h] in t.tolist()
+            assert kept == (h < max_age), (max_age, h)
+        for f in range(len(out)):                                       # the two objects always seen keep their ids
+            assert born[8] in out[f][1] and born[9] in out[f][1]
+
+
+def test_edge_layouts_are_what_they_claim():
+    e = track_ref.edge_layouts()
+    assert len(e["S0"][5]) == 1 and len(e["S0"][4]) == 1
+    assert len(e["K0"][2]) == 0 and len(e["K0"][4]) == 4
+    assert e["no_frames"][5].tolist() == [0, 0, 2, 2, 4, 4]
+    counts = lambda k: np.diff(e[k][4]).tolist()        # noqa: E731
+    assert counts("first_empty")[2] == 0 and e["first_empty"][5].tolist() == [0, 2, 5, 6]
+    assert counts("all_empty")[2:4] == [0, 0] and e["all_empty"][5].tolist() == [0, 2, 4, 6]
+    assert counts("single") == [1]
+    c = np.array(counts("pairs")).reshape(-1, 2)
+    assert [(int(n), int(m)) for m, n in c] == list(track_ref.EDGE_NM) and len(track_ref.EDGE_NM) == 27
+    out, _ = _track("edge_pairs")
+    assert all(len(out[2 * q][0]) == m for q, (n, m) in enumerate(track_ref.EDGE_NM))   # frame 0 leaves M tracks
+    assert _stats("edge_pairs")["rescanned"] > 1000
+
+
+def test_many_frames_passes_the_grid_cap():
+    ct, tr, lab, sc, fo, so = track_ref.many_frames()
+    assert len(fo) - 1 == 66000 > 65535 and len(so) - 1 == 33000 > 256
+    assert set(np.diff(fo).tolist()) == {1, 2}
+    s = _stats("many_frames")
+    assert s["matches"] > 10000 and s["rows"] - s["matches"] > 5000
+
+
+def test_capacity_bound_covers_every_dense_scene():
+    for name in list(_CASES) + ["many_frames"]:
+        inputs, params = _CASES[name] if name in _CASES else (track_ref.many_frames(), {})
+        max_age = params.get("max_age", 3)
+        inp = trk.TrackInputs.__new__(trk.TrackInputs)
+        inp.counts, inp.seq_offsets = np.diff(inputs[4]), inputs[5]
+        assert inp.capacity(max_age) >= _stats(name)["max_live"], name
+    for max_age in (0, 1, 2):                   # the crowded scene at every max_age
+        inputs = _CASES["crowded"][0]
+        inp = trk.TrackInputs.__new__(trk.TrackInputs)
+        inp.counts, inp.seq_offsets = np.diff(inputs[4]), inputs[5]
+        assert inp.capacity(max_age) >= track_ref.stats(*inputs, max_age=max_age)["max_live"], max_age
