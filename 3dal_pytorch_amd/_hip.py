@@ -195,6 +195,11 @@ class CenterDecodeArgs(C.Structure):
                 ("workspace", vp), ("workspace_bytes", C.c_size_t)]
 
 
+class CenterDecodeFlip4Args(C.Structure):
+    """dal3_center_decode_flip4_args"""
+    _fields_ = [("decode", CenterDecodeArgs)]
+
+
 PILLAR_OVERFLOW = 128
 PILLAR_PACK_FLOATS = 5120
 
@@ -275,6 +280,9 @@ SIGNATURES = {
     "dal3_nms": (_i, [C.POINTER(NmsArgs), vp]),
     "dal3_center_decode_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "dal3_center_decode": (_i, [C.POINTER(CenterDecodeArgs), vp]),
+    "dal3_center_decode_flip4_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "dal3_center_decode_flip4": (_i, [C.POINTER(CenterDecodeFlip4Args), vp]),
+    "dal3_flip4_points": (_i, [vp, _i64, C.c_int32, vp, _i64, vp, vp, _i64, vp]),
     "dal3_voxelize_workspace_bytes": (_sz, [_i64, _i64]),
     "dal3_voxelize": (_i, [C.POINTER(VoxelizeArgs), vp]),
     "dal3_pillar_pack": (_i, [C.POINTER(Layer), _i, _i, C.c_double, vp, vp]),

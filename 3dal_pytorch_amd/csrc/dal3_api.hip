@@ -1142,28 +1142,62 @@ extern "C" size_t dal3_center_decode_workspace_bytes(int64_t B, int64_t H, int64
     return center_decode_workspace_bytes(B, H, W);
 }
 
-extern "C" int dal3_center_decode(const dal3_center_decode_args* args, dal3_stream stream) {
-    if (!args) return fail(DAL3_EINVAL, "center_decode: null args");
-    const dal3_center_decode_args& a = *args;
+// the checks dal3_center_decode and dal3_center_decode_flip4 share (B: the samples that are written)
+static int check_center_decode(const dal3_center_decode_args& a, const char* who) {
     if (a.B < 0 || a.H <= 0 || a.W <= 0 || a.B > DAL3_MAX_ITEMS || a.H > DAL3_MAX_ITEMS || a.W > DAL3_MAX_ITEMS ||
         a.H * a.W > DAL3_MAX_ITEMS)
-        return fail(DAL3_EINVAL, "center_decode: bad B / H / W (H, W >= 1, B, H W <= DAL3_MAX_ITEMS)");
-    if (a.C < 1 || a.C > 64) return fail(DAL3_EINVAL, "center_decode: bad C (1 <= C <= 64)");
+        return fail(DAL3_EINVAL, "%s: bad B / H / W (H, W >= 1, B, H W <= DAL3_MAX_ITEMS)", who);
+    if (a.C < 1 || a.C > 64) return fail(DAL3_EINVAL, "%s: bad C (1 <= C <= 64)", who);
     if (a.F < 0 || a.K < 0 || a.F > DAL3_MAX_ITEMS || a.K > DAL3_MAX_ITEMS || a.max_workgroups < 0)
-        return fail(DAL3_EINVAL, "center_decode: bad F / K / max_workgroups");
+        return fail(DAL3_EINVAL, "%s: bad F / K / max_workgroups", who);
     if (a.B == 0) return 0;
     const int64_t last = a.seg_first + (a.B - 1) * a.seg_step;
     if (a.seg_first < 0 || a.seg_first >= a.F || last < 0 || last >= a.F || (a.B > 1 && a.seg_step == 0))
-        return fail(DAL3_EINVAL, "center_decode: segments seg_first + b * seg_step must be distinct and lie in [0, F)");
+        return fail(DAL3_EINVAL, "%s: segments seg_first + b * seg_step must be distinct and lie in [0, F)", who);
     if (!a.hm.data || !a.reg.data || !a.height.data || !a.dim.data || !a.rot.data)
-        return fail(DAL3_EINVAL, "center_decode: null hm / reg / height / dim / rot");
+        return fail(DAL3_EINVAL, "%s: null hm / reg / height / dim / rot", who);
     if (!a.seg_offsets || !a.seg_count || !a.status || !a.workspace)
-        return fail(DAL3_EINVAL, "center_decode: null seg_offsets / seg_count / status / workspace");
+        return fail(DAL3_EINVAL, "%s: null seg_offsets / seg_count / status / workspace", who);
     if (a.K > 0 && (!a.boxes || !a.scores || !a.labels || !a.cell))
-        return fail(DAL3_EINVAL, "center_decode: null boxes / scores / labels / cell");
+        return fail(DAL3_EINVAL, "%s: null boxes / scores / labels / cell", who);
     if (a.workspace_bytes < center_decode_workspace_bytes(a.B, a.H, a.W))
-        return fail(DAL3_EWORKSPACE, "center_decode: workspace too small (dal3_center_decode_workspace_bytes)");
+        return fail(DAL3_EWORKSPACE, "%s: workspace too small (dal3_%s_workspace_bytes)", who, who);
+    return 0;
+}
+
+extern "C" int dal3_center_decode(const dal3_center_decode_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "center_decode: null args");
+    TRY(check_center_decode(*args, "center_decode"));
+    if (args->B == 0) return 0;
     HIP_TRY(launch_center_decode(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+// the merged samples share dal3_center_decode's chunks, so its workspace
+extern "C" size_t dal3_center_decode_flip4_workspace_bytes(int64_t B, int64_t H, int64_t W) {
+    return dal3_center_decode_workspace_bytes(B, H, W);
+}
+
+extern "C" int dal3_center_decode_flip4(const dal3_center_decode_flip4_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "center_decode_flip4: null args");
+    if (args->decode.B > DAL3_MAX_ITEMS / 4)
+        return fail(DAL3_EINVAL, "center_decode_flip4: bad B (the maps hold 4 B <= DAL3_MAX_ITEMS samples)");
+    TRY(check_center_decode(args->decode, "center_decode_flip4"));
+    if (args->decode.B == 0) return 0;
+    HIP_TRY(launch_center_decode_flip4(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+extern "C" int dal3_flip4_points(const float* points, int64_t N, int32_t C, const int64_t* offsets, int64_t B, float* out,
+                                 int64_t* out_offsets, int64_t max_workgroups, dal3_stream stream) {
+    if (B < 0 || N < 0 || B > DAL3_MAX_ITEMS / 4 || N > DAL3_MAX_ITEMS / 4)
+        return fail(DAL3_EINVAL, "flip4_points: bad B / N (0 <= B, N <= DAL3_MAX_ITEMS / 4)");
+    if (C < 2 || C > 64) return fail(DAL3_EINVAL, "flip4_points: bad C (2 <= C <= 64)");
+    if (max_workgroups < 0) return fail(DAL3_EINVAL, "flip4_points: negative max_workgroups");
+    if (B == 0) return 0;
+    if (!offsets || !out_offsets) return fail(DAL3_EINVAL, "flip4_points: null offsets / out_offsets");
+    if (N > 0 && (!points || !out)) return fail(DAL3_EINVAL, "flip4_points: null points / out");
+    HIP_TRY(launch_flip4_points(points, N, C, offsets, B, out, out_offsets, max_workgroups, static_cast<hipStream_t>(stream)));
     return 0;
 }
 

@@ -288,6 +288,10 @@ size_t nms_workspace_bytes(int64_t K, int boxes_f64);
 hipError_t launch_nms(const dal3_nms_args* a, hipStream_t s);
 size_t center_decode_workspace_bytes(int64_t B, int64_t H, int64_t W);
 hipError_t launch_center_decode(const dal3_center_decode_args* a, hipStream_t s);
+// double_flip: the four views' un-flip, merge and decode in the same three launches; DoubleFlip's copies of the points
+hipError_t launch_center_decode_flip4(const dal3_center_decode_flip4_args* a, hipStream_t s);
+hipError_t launch_flip4_points(const float* points, int64_t N, int C, const int64_t* offsets, int64_t B, float* out,
+                               int64_t* out_offsets, int64_t max_workgroups, hipStream_t s);
 // the PointPillars reader (dal3_pillars.hip): voxelisation as a stable radix sort over chunks, the fused feature kernel
 size_t voxelize_workspace_bytes(int64_t B, int64_t N);
 hipError_t launch_voxelize(const dal3_voxelize_args* a, hipStream_t s);

@@ -1,4 +1,5 @@
-// dal3_nms.hip — the detector's post-processing (dal3_nms / dal3_center_decode, include/dal3.h): the non-maximum
+// dal3_nms.hip — the detector's post-processing (dal3_nms / dal3_center_decode / dal3_center_decode_flip4 /
+// dal3_flip4_points, include/dal3.h): the non-maximum
 // suppression of det3d/core/bbox/box_torch_ops.py:248-277 (rotate_nms_pcdet -> iou3d_nms_cuda.nms_gpu) and of
 // det3d/core/utils/circle_nms_jit.py, and the decode of det3d/models/bbox_heads/center_head.py:342-419, 459-471.
 //
@@ -26,7 +27,9 @@
 //
 // The decode is an ordered compaction in three launches: per chunk of DEC_CHUNK cells the number of survivors, one
 // exclusive scan per sample, then each chunk again with ballot ranks. A cell's mask and values come from one function
-// (cell_eval) in both passes.
+// (cell_eval) in both passes. The count and fill kernels are instantiated twice on the cell's evaluator: one view
+// (dal3_center_decode) and the four flipped views of test_cfg.double_flip merged as they are read (dal3_center_decode_flip4,
+// center_head.py:318-414: no un-flipped or merged map is written); scan, ranks and workspace are the same code.
 #include "dal3_block.h"
 #include "dal3_kernels.h"
 
@@ -242,19 +245,73 @@ __device__ __forceinline__ float map_at(const dal3_map& mp, int64_t b, int64_t r
     return mp.data[b * mp.stride_b + row * mp.stride_h + col * mp.stride_w + c * mp.stride_c];
 }
 
+// The maps of one output cell. V = 1: the cell itself in sample b (dal3_center_decode). V = 4: the four views of merged
+// sample b (dal3_center_decode_flip4), view v in map 4 b + v at the mirrored cell: rows reversed for v & 1 (y = -y), columns
+// for v & 2 (x = -x). A reversed row or column is still a run of neighbouring addresses across the wave.
+template <int V>
+struct Views {
+    int64_t b, row[2], col[2];                  // [0] as it is, [1] mirrored (V = 4 only)
+    __device__ __forceinline__ Views(const dal3_center_decode_args& a, int64_t b_, int64_t r, int64_t c) : b(b_) {
+        row[0] = r;
+        col[0] = c;
+        row[1] = a.H - 1 - r;
+        col[1] = a.W - 1 - c;
+    }
+    // view v's value of channel c
+    __device__ __forceinline__ float at(const dal3_map& mp, int v, int c) const {
+        return map_at(mp, V * b + v, row[v & 1], col[(v >> 1) & 1], c);
+    }
+};
+
+// torch.mean(dim=1) over the four views on the CPU: a running sum in view order, then one division
+__device__ __forceinline__ float mean4(float a0, float a1, float a2, float a3) { return (((a0 + a1) + a2) + a3) / 4.f; }
+
+// channel c of a two-channel map after the un-flip of its values, merged: channel 0 belongs to x and changes under the
+// x-flips (views 2, 3), channel 1 to y and changes under the y-flips (views 1, 3). ONE_MINUS: reg (1 - r), else rot / vel (-r).
+template <int V, bool ONE_MINUS>
+__device__ __forceinline__ float merged_xy(const Views<V>& w, const dal3_map& mp, int c) {
+    if constexpr (V == 1) {
+        return w.at(mp, 0, c);
+    } else {
+        float r[4];
+        for (int v = 0; v < 4; ++v) {
+            const float x = w.at(mp, v, c);
+            const bool flipped = c == 0 ? (v & 2) != 0 : (v & 1) != 0;
+            r[v] = !flipped ? x : ONE_MINUS ? 1.f - x : -x;
+        }
+        return mean4(r[0], r[1], r[2], r[3]);
+    }
+}
+
+// a channel no flip changes (height), merged
+template <int V>
+__device__ __forceinline__ float merged(const Views<V>& w, const dal3_map& mp, int c) {
+    if constexpr (V == 1) return w.at(mp, 0, c);
+    else return mean4(w.at(mp, 0, c), w.at(mp, 1, c), w.at(mp, 2, c), w.at(mp, 3, c));
+}
+
+__device__ __forceinline__ float sigmoid_of(float h) {
+    const float e = expf(-h);
+    return 1.f / (1.f + e);
+}
+
 struct Cell {
     float x, y, z, score;
     int32_t label;
 };
 
-// post_processing's mask of one cell and the values it is taken on (center_head.py:342, 397-401, 459-465)
-__device__ __forceinline__ bool cell_eval(const dal3_center_decode_args& a, int64_t b, int64_t row, int64_t col, Cell& o) {
+// post_processing's mask of one cell and the values it is taken on (center_head.py:342-362, 397-401, 459-465)
+template <int V>
+__device__ __forceinline__ bool cell_eval(const dal3_center_decode_args& a, const Views<V>& w, int64_t row, int64_t col,
+                                          Cell& o) {
     float best = 0.f;
     int32_t label = 0;
     for (int c = 0; c < a.C; ++c) {
-        const float h = map_at(a.hm, b, row, col, c);
-        const float e = expf(-h);
-        const float s = 1.f / (1.f + e);
+        float s;
+        if constexpr (V == 1) s = sigmoid_of(w.at(a.hm, 0, c));
+        else
+            s = mean4(sigmoid_of(w.at(a.hm, 0, c)), sigmoid_of(w.at(a.hm, 1, c)), sigmoid_of(w.at(a.hm, 2, c)),
+                      sigmoid_of(w.at(a.hm, 3, c)));
         // torch.max: the first maximum, a NaN wins and stays
         if (c == 0 || (best == best && (s > best || s != s))) {
             best = s;
@@ -263,13 +320,13 @@ __device__ __forceinline__ bool cell_eval(const dal3_center_decode_args& a, int6
     }
     o.score = best;
     o.label = label;
-    const float fx = (float)col + map_at(a.reg, b, row, col, 0);
-    const float fy = (float)row + map_at(a.reg, b, row, col, 1);
+    const float fx = (float)col + merged_xy<V, true>(w, a.reg, 0);
+    const float fy = (float)row + merged_xy<V, true>(w, a.reg, 1);
     const float sx = fx * a.out_size_factor, sy = fy * a.out_size_factor;
     const float vx = sx * a.voxel_size[0], vy = sy * a.voxel_size[1];
     o.x = vx + a.pc_range[0];
     o.y = vy + a.pc_range[1];
-    o.z = map_at(a.height, b, row, col, 0);
+    o.z = merged<V>(w, a.height, 0);
     bool ok = best > a.score_threshold;
     if (a.has_range)
         ok = ok && o.x >= a.range[0] && o.y >= a.range[1] && o.z >= a.range[2] && o.x <= a.range[3] && o.y <= a.range[4] &&
@@ -277,6 +334,21 @@ __device__ __forceinline__ bool cell_eval(const dal3_center_decode_args& a, int6
     return ok;
 }
 
+// the columns of a survivor's row that the mask does not need: dim, vel, rot (center_head.py:344, 364-382, 403-414)
+template <int V>
+__device__ __forceinline__ void cell_rest(const dal3_center_decode_args& a, const Views<V>& w, float* q, int cols) {
+    for (int j = 0; j < 3; ++j) {
+        if constexpr (V == 1) q[3 + j] = expf(w.at(a.dim, 0, j));
+        else q[3 + j] = mean4(expf(w.at(a.dim, 0, j)), expf(w.at(a.dim, 1, j)), expf(w.at(a.dim, 2, j)), expf(w.at(a.dim, 3, j)));
+    }
+    if (a.vel.data) {
+        q[6] = merged_xy<V, false>(w, a.vel, 0);
+        q[7] = merged_xy<V, false>(w, a.vel, 1);
+    }
+    q[cols - 1] = atan2f(merged_xy<V, false>(w, a.rot, 0), merged_xy<V, false>(w, a.rot, 1));
+}
+
+template <int V>
 __global__ __launch_bounds__(DEC_BLOCK) void decode_count_kernel(const dal3_center_decode_args a, int32_t* counts,
                                                                  int64_t chunks) {
     __shared__ int32_t s_cnt;
@@ -290,7 +362,7 @@ __global__ __launch_bounds__(DEC_BLOCK) void decode_count_kernel(const dal3_cent
             const int64_t cell = c * DEC_CHUNK + (int64_t)r * DEC_BLOCK + threadIdx.x;
             Cell o;
             const uint32_t row = (uint32_t)cell / (uint32_t)a.W, col = (uint32_t)cell - row * (uint32_t)a.W;   // H W <= 2^24
-            const bool ok = cell < HW && cell_eval(a, b, row, col, o);
+            const bool ok = cell < HW && cell_eval<V>(a, Views<V>(a, b, row, col), row, col, o);
             mine += __popcll(__ballot(ok));
         }
         if ((threadIdx.x & 63) == 0) atomicAdd(&s_cnt, mine);   // integers: the order does not matter
@@ -322,6 +394,7 @@ __global__ __launch_bounds__(DEC_BLOCK) void decode_scan_kernel(const dal3_cente
     }
 }
 
+template <int V>
 __global__ __launch_bounds__(DEC_BLOCK) void decode_fill_kernel(const dal3_center_decode_args a, const int32_t* counts,
                                                                 int64_t chunks) {
     __shared__ int32_t s_wave[DEC_WAVES];
@@ -338,7 +411,8 @@ __global__ __launch_bounds__(DEC_BLOCK) void decode_fill_kernel(const dal3_cente
             const int64_t cell = c * DEC_CHUNK + (int64_t)r * DEC_BLOCK + t;
             const uint32_t row = (uint32_t)cell / (uint32_t)a.W, col = (uint32_t)cell - row * (uint32_t)a.W;
             Cell o;
-            const bool ok = cell < HW && cell_eval(a, b, row, col, o);
+            const Views<V> w(a, b, row, col);
+            const bool ok = cell < HW && cell_eval<V>(a, w, row, col, o);
             int32_t tile;
             const int64_t pos = base + block_rank<DEC_WAVES>(ok, s_wave, tile);
             if (ok && pos >= 0 && pos < cap) {
@@ -347,20 +421,48 @@ __global__ __launch_bounds__(DEC_BLOCK) void decode_fill_kernel(const dal3_cente
                 q[0] = o.x;
                 q[1] = o.y;
                 q[2] = o.z;
-                q[3] = expf(map_at(a.dim, b, row, col, 0));
-                q[4] = expf(map_at(a.dim, b, row, col, 1));
-                q[5] = expf(map_at(a.dim, b, row, col, 2));
-                if (a.vel.data) {
-                    q[6] = map_at(a.vel, b, row, col, 0);
-                    q[7] = map_at(a.vel, b, row, col, 1);
-                }
-                q[cols - 1] = atan2f(map_at(a.rot, b, row, col, 0), map_at(a.rot, b, row, col, 1));
+                cell_rest<V>(a, w, q, cols);
                 a.scores[k] = o.score;
                 a.labels[k] = o.label;
                 a.cell[k] = (int32_t)cell;
             }
             base += tile;
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------- DoubleFlip's points
+constexpr int FLIP_BLOCK = 256;
+
+// one thread per input element: read once, written to the sample's four views; then out_offsets
+__global__ __launch_bounds__(FLIP_BLOCK) void flip4_points_kernel(const uint32_t* __restrict__ points, int64_t N, int C,
+                                                                  const int64_t* __restrict__ offsets, int64_t B,
+                                                                  uint32_t* __restrict__ out, int64_t* __restrict__ out_offsets) {
+    const int64_t stride = (int64_t)gridDim.x * FLIP_BLOCK, first = (int64_t)blockIdx.x * FLIP_BLOCK + threadIdx.x;
+    for (int64_t i = first; i < N * C; i += stride) {
+        const int64_t r = i / C;
+        const int c = (int)(i - r * C);
+        // the sample of row r: the last b with offsets[b] <= r
+        int64_t lo = 0, hi = B;
+        while (hi - lo > 1) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (offsets[mid] <= r) lo = mid;
+            else hi = mid;
+        }
+        const int64_t o0 = offsets[lo], o1 = offsets[lo + 1];
+        if (r < o0 || r >= o1) continue;        // a row of no sample
+        const int64_t n = o1 - o0;
+        const uint32_t x = points[i];
+        for (int v = 0; v < 4; ++v) {
+            const int64_t row = 4 * o0 + v * n + (r - o0);
+            if (row < 0 || row >= 4 * N) continue;   // only offsets that are no CSR of [0, N] get here
+            const bool neg = (c == 0 && (v & 2)) || (c == 1 && (v & 1));
+            out[row * C + c] = neg ? x ^ 0x80000000u : x;
+        }
+    }
+    for (int64_t j = first; j <= 4 * B; j += stride) {
+        const int64_t b = j >> 2, v = j & 3;
+        out_offsets[j] = b == B ? 4 * offsets[B] : 4 * offsets[b] + v * (offsets[b + 1] - offsets[b]);
     }
 }
 
@@ -407,8 +509,8 @@ size_t center_decode_workspace_bytes(int64_t B, int64_t H, int64_t W) {
     return c.off;
 }
 
-hipError_t launch_center_decode(const dal3_center_decode_args* args, hipStream_t s) {
-    const dal3_center_decode_args& a = *args;
+template <int V>
+static hipError_t launch_decode(const dal3_center_decode_args& a, hipStream_t s) {
     if (a.B <= 0) return hipSuccess;
     const int64_t chunks = decode_chunks(a.H, a.W);
     Carver c(a.workspace, a.workspace_bytes);
@@ -416,8 +518,28 @@ hipError_t launch_center_decode(const dal3_center_decode_args* args, hipStream_t
     int64_t jobs = a.B * chunks, samples = a.B;
     if (a.max_workgroups > 0 && jobs > a.max_workgroups) jobs = a.max_workgroups;
     if (a.max_workgroups > 0 && samples > a.max_workgroups) samples = a.max_workgroups;
-    if (jobs > 0) hipLaunchKernelGGL(decode_count_kernel, dim3((unsigned)jobs), dim3(DEC_BLOCK), 0, s, a, counts, chunks);
+    if (jobs > 0) hipLaunchKernelGGL(decode_count_kernel<V>, dim3((unsigned)jobs), dim3(DEC_BLOCK), 0, s, a, counts, chunks);
     hipLaunchKernelGGL(decode_scan_kernel, dim3((unsigned)samples), dim3(DEC_BLOCK), 0, s, a, counts, chunks);
-    if (jobs > 0) hipLaunchKernelGGL(decode_fill_kernel, dim3((unsigned)jobs), dim3(DEC_BLOCK), 0, s, a, counts, chunks);
+    if (jobs > 0) hipLaunchKernelGGL(decode_fill_kernel<V>, dim3((unsigned)jobs), dim3(DEC_BLOCK), 0, s, a, counts, chunks);
+    return hipGetLastError();
+}
+
+hipError_t launch_center_decode(const dal3_center_decode_args* args, hipStream_t s) { return launch_decode<1>(*args, s); }
+
+// the merged samples' chunks: the same array, scan and ranks as the one-view decode
+hipError_t launch_center_decode_flip4(const dal3_center_decode_flip4_args* args, hipStream_t s) {
+    return launch_decode<4>(args->decode, s);
+}
+
+hipError_t launch_flip4_points(const float* points, int64_t N, int C, const int64_t* offsets, int64_t B, float* out,
+                               int64_t* out_offsets, int64_t max_workgroups, hipStream_t s) {
+    if (B <= 0) return hipSuccess;
+    const int64_t work = N * C > 4 * B + 1 ? N * C : 4 * B + 1;
+    int64_t grid = (work + FLIP_BLOCK - 1) / FLIP_BLOCK;
+    if (grid > 65536) grid = 65536;
+    if (max_workgroups > 0 && grid > max_workgroups) grid = max_workgroups;
+    hipLaunchKernelGGL(flip4_points_kernel, dim3((unsigned)grid), dim3(FLIP_BLOCK), 0, s,
+                       reinterpret_cast<const uint32_t*>(points), N, C, offsets, B, reinterpret_cast<uint32_t*>(out),
+                       out_offsets);
     return hipGetLastError();
 }

@@ -1,11 +1,12 @@
 """CenterPoint's head post-processing on the GPU: `CenterHead.predict` / `post_processing`
 (det3d/models/bbox_heads/center_head.py:294-506) through dal3_center_decode and dal3_nms (include/dal3.h), from the
 network's `preds_dicts` to the `prediction.pkl` dictionary tools/dist_test.py pickles and `track.py` reads.
+`CenterHeadPost` is the plain route; `DoubleFlipPost` is the one for `test_cfg.double_flip` (test-time augmentation: the
+batch holds every sample four times, flipped), whose un-flip, merge and decode are one pass of dal3_center_decode_flip4.
 
 Every sample and task is decoded and suppressed on the device first (one decode enqueue per task, one NMS enqueue for all
 segments, or one per task for circle NMS with its per-task radius); the kept rows are gathered once at the end, which is
-the only host synchronisation. `double_flip` (test-time augmentation) and `per_class_nms` (a `pass` in the reference)
-are refused.
+the only host synchronisation. `per_class_nms` (a `pass` in the reference) is refused.
 """
 import numpy as np
 import torch
@@ -46,9 +47,11 @@ class CenterHeadPost:
     task, as CenterHead.num_classes. capacity: rows kept per (sample, task) before NMS (default: every cell, which cannot
     overflow; a smaller one saves memory and raises when a sample needs more)."""
 
+    VIEWS = 1                                   # maps per sample
+
     def __init__(self, test_cfg, num_classes, capacity=None):
-        if _get(test_cfg, "double_flip", False):
-            raise ValueError("double_flip (test-time augmentation) is not supported")
+        if self.VIEWS == 1 and _get(test_cfg, "double_flip", False):
+            raise ValueError("double_flip (test-time augmentation) merges four views per sample: use DoubleFlipPost")
         if _get(test_cfg, "per_class_nms", False):
             raise ValueError("per_class_nms is not supported (the reference's branch is a `pass`)")
         self.num_classes = [int(c) for c in num_classes]
@@ -84,8 +87,7 @@ class CenterHeadPost:
         if layout not in ("NCHW", "NHWC"):
             raise ValueError("layout must be 'NCHW' (the network's outputs) or 'NHWC' (after the reference's permute)")
         T = len(self.num_classes)
-        if len(preds_dicts) != T:
-            raise ValueError(f"{len(preds_dicts)} prediction dicts for {T} tasks")
+        self._samples(preds_dicts)
         tasks = []
         for t, pd in enumerate(preds_dicts):
             hm = _map(pd["hm"], layout, self.num_classes[t], f"preds_dicts[{t}]['hm']")
@@ -97,11 +99,12 @@ class CenterHeadPost:
                 if maps[key].shape[:3] != hm.shape[:3] or maps[key].device != hm.device:
                     raise ValueError(f"preds_dicts[{t}]['{key}'] does not match hm's batch / size / device")
             tasks.append(maps)
-        B, dev = tasks[0]["hm"].shape[0], tasks[0]["hm"].device
+        n_maps, dev = tasks[0]["hm"].shape[0], tasks[0]["hm"].device
         has_vel = "vel" in tasks[0]
         for maps in tasks:
-            if maps["hm"].shape[0] != B or ("vel" in maps) != has_vel or maps["hm"].device != dev:
+            if maps["hm"].shape[0] != n_maps or ("vel" in maps) != has_vel or maps["hm"].device != dev:
                 raise ValueError("the tasks differ in batch size, device or in having 'vel'")
+        B = n_maps // self.VIEWS
         cols = 9 if has_vel else 7
         caps = []
         for maps in tasks:
@@ -122,7 +125,7 @@ class CenterHeadPost:
             _, H, W, C = maps["hm"].shape
             if B == 0:
                 break
-            nbytes = lib.dal3_center_decode_workspace_bytes(B, H, W)
+            nbytes = self._workspace_bytes(lib, B, H, W)
             ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
             a = _hip.CenterDecodeArgs(B=B, H=H, W=W, C=C, has_range=1 if self.range else 0, hm=_map_struct(maps["hm"]),
                                       reg=_map_struct(maps["reg"]), height=_map_struct(maps["height"]),
@@ -137,9 +140,30 @@ class CenterHeadPost:
             a.pc_range[:] = self.pc_range
             if self.range:
                 a.range[:] = self.range
-            _hip.check(lib.dal3_center_decode(a, _hip.stream()))
+            self._launch(lib, a)
         return {"boxes": boxes, "scores": scores, "labels": labels, "cell": cell, "seg_count": seg_count, "status": status,
                 "seg_offsets": off, "seg_offsets_device": off_dev, "B": B}
+
+    def _samples(self, preds_dicts):
+        """the samples that come out: the maps' batch over the views per sample, checked before anything is enqueued"""
+        if len(preds_dicts) != len(self.num_classes):
+            raise ValueError(f"{len(preds_dicts)} prediction dicts for {len(self.num_classes)} tasks")
+        hm = preds_dicts[0]["hm"]
+        if not torch.is_tensor(hm):
+            raise TypeError("preds_dicts[0]['hm'] must be a tensor")
+        if hm.dim() != 4:
+            raise ValueError(f"preds_dicts[0]['hm'] must be 4-D, got {tuple(hm.shape)}")
+        if hm.shape[0] % self.VIEWS:
+            raise ValueError(f"double_flip needs {self.VIEWS} views per sample: a batch of {hm.shape[0]} is no multiple of it")
+        return hm.shape[0] // self.VIEWS
+
+    @staticmethod
+    def _workspace_bytes(lib, B, H, W):
+        return lib.dal3_center_decode_workspace_bytes(B, H, W)
+
+    @staticmethod
+    def _launch(lib, a):
+        _hip.check(lib.dal3_center_decode(a, _hip.stream()))
 
     def suppress(self, r):
         """the NMS of a decode() result, added to it as keep / keep_count"""
@@ -183,12 +207,14 @@ class CenterHeadPost:
         """center_head.py:294: -> ret_list, per sample {'box3d_lidar' (n, 9 or 7) float32, 'scores' (n) float32,
         'label_preds' (n) int64 with the cumulative class offset of its task, 'metadata'}; tasks in order, within a task
         in keep order. preds_dicts are not modified (the reference permutes them in place)."""
-        r = self.decode_nms(preds_dicts, layout)
-        B, T = r["B"], len(self.num_classes)
-        F = T * B
-        dev = r["boxes"].device
+        B, T = self._samples(preds_dicts), len(self.num_classes)
+        if metadata is not None and self.VIEWS > 1 and B > 0 and len(metadata) == self.VIEWS * B:
+            metadata = metadata[::self.VIEWS]                       # one entry per view: the sample's first (center_head.py:340)
         if metadata is not None and len(metadata) != B:
             raise ValueError(f"{len(metadata)} metadata entries for {B} samples")
+        r = self.decode_nms(preds_dicts, layout)
+        F = T * B
+        dev = r["boxes"].device
         counts = r["keep_count"].cpu().numpy().astype(np.int64)    # the one synchronisation
         self.check_status(r["status"])
         # segments sample-major, tasks in order: one gather for everything
@@ -219,3 +245,20 @@ class CenterHeadPost:
                 raise ValueError("to_prediction needs metadata with a 'token' for every sample")
             out[meta["token"]] = {k: (v if k == "metadata" else v.cpu()) for k, v in output.items()}
         return out
+
+
+class DoubleFlipPost(CenterHeadPost):
+    """CenterHeadPost for `test_cfg.double_flip` (center_head.py:318-414): `preds_dicts` hold 4 B samples, sample b's views
+    at 4 b .. 4 b + 3 in the order Reformat returns them (the sweep, y = -y, x = -x, both). `decode` un-flips, merges and
+    decodes them in one pass (dal3_center_decode_flip4, whose header comment is the arithmetic) into B samples; everything
+    after it is CenterHeadPost's. `predict` takes the metadata of the 4 B views (every fourth is kept) or of the B samples."""
+
+    VIEWS = 4
+
+    @staticmethod
+    def _workspace_bytes(lib, B, H, W):
+        return lib.dal3_center_decode_flip4_workspace_bytes(B, H, W)
+
+    @staticmethod
+    def _launch(lib, a):
+        _hip.check(lib.dal3_center_decode_flip4(_hip.CenterDecodeFlip4Args(decode=a), _hip.stream()))

@@ -6,14 +6,15 @@ configs/waymo/pp/waymo_centerpoint_pp_two_pfn_stride1_3x.py.
 `forward(example, return_loss=False)` takes the reference's collated example (voxels, coordinates, num_points, num_voxels,
 shape, metadata) and returns `CenterHead.predict`'s list. `detect(points, point_offsets, metadata=None)` starts from the
 raw sweep instead: voxelise -> pillar features into the canvas -> RPN -> CenterHead -> decode + NMS, everything enqueued on
-the current stream; the read-back of the kept boxes inside `predict` is the only host synchronisation. The loss is not
-built: `return_loss=True` is refused.
+the current stream; the read-back of the kept boxes inside `predict` is the only host synchronisation. A `test_cfg` with
+`double_flip` (test-time augmentation) is served by both: `forward` takes the reference's batch of four views per sample,
+`detect` makes the views itself. The loss is not built: `return_loss=True` is refused.
 """
 import torch
 from torch import nn
 
 from . import pillars, rpn
-from .detect import CenterHeadPost
+from .detect import CenterHeadPost, _get
 
 READERS = {"PillarFeatureNet": pillars.PillarFeatureNet}
 BACKBONES = {"PointPillarsScatter": pillars.PointPillarsScatter}
@@ -79,11 +80,15 @@ class PointPillars(nn.Module):
     def detect(self, points, point_offsets, metadata=None, point_offsets_device=None):
         """points (N, C) float32 CUDA, point_offsets (B + 1) on the host -> the per-sample list of box3d_lidar / scores /
         label_preds / metadata (CenterHeadPost.to_prediction turns it into the prediction.pkl dictionary). `last` keeps the
-        VoxelizeResult."""
+        VoxelizeResult. With test_cfg.double_flip the sweep is first copied into its four flipped views (pillars.double_flip),
+        everything up to the head runs on 4 B samples (`last` is theirs) and the post-processing merges them into B."""
         if self.training:
             raise RuntimeError("detect is the eval-mode route: call .eval()")
         if self.voxel_size is None:
             raise RuntimeError("detect needs the reader's voxel_size and pc_range: build the model from the config's dicts")
+        if _get(self.test_cfg, "double_flip", False):
+            # four views per sample (the sweep, y = -y, x = -x, both), merged again by DoubleFlipPost inside predict
+            points, point_offsets, point_offsets_device = pillars.double_flip(points, point_offsets, point_offsets_device)
         r = pillars.voxelize(points, point_offsets, self.voxel_size, self.pc_range, self.max_points, self.max_voxels,
                              point_offsets_device=point_offsets_device)
         self.last = r

@@ -153,6 +153,38 @@ def voxelize(points, point_offsets, voxel_size, pc_range, max_points, max_voxels
     return VoxelizeResult(voxels, coords, num, vo, status, B)
 
 
+def double_flip(points, point_offsets, point_offsets_device=None, *, max_workgroups=0):
+    """DoubleFlip (det3d/datasets/pipelines/test_aug.py) on the device: points (N, C) float32 CUDA, C >= 2, point_offsets
+    (B + 1) on the HOST -> (out (4 N, C), out_offsets (4 B + 1) host int64, out_offsets_device): the batch of 4 B samples
+    CenterHead.predict's double_flip expects, sample b's views at 4 b .. 4 b + 3: its rows as they are, with y = -y, with
+    x = -x, with both (a sign-bit flip, as NumPy's unary minus). One enqueue (dal3_flip4_points), no synchronisation: the
+    host offsets come from the host's, the device offsets from the kernel."""
+    if not torch.is_tensor(points):
+        raise TypeError("points must be a tensor")
+    _hip.require_gpu(points, "points")
+    if points.dim() != 2 or points.shape[1] < 2:
+        raise ValueError(f"points must be (N, C >= 2), got {tuple(points.shape)}")
+    if points.dtype != torch.float32:
+        raise TypeError(f"points must be float32, got {points.dtype}")
+    points = points.contiguous()
+    N, C = points.shape
+    off = _host_offsets(point_offsets, N)
+    B, dev = off.size - 1, points.device
+    n = np.diff(off)
+    out_off = np.empty(4 * B + 1, np.int64)
+    out_off[:-1] = (4 * off[:-1, None] + np.arange(4, dtype=np.int64)[None, :] * n[:, None]).reshape(-1)
+    out_off[-1] = 4 * off[-1]
+    off_dev = _device_ints(point_offsets_device, "point_offsets_device", torch.int64, B + 1, dev)
+    if off_dev is None:
+        off_dev = torch.from_numpy(off).to(dev)
+    out = torch.empty((4 * N, C), dtype=torch.float32, device=dev)
+    out_off_dev = torch.zeros(4 * B + 1, dtype=torch.int64, device=dev) if B == 0 else \
+        torch.empty(4 * B + 1, dtype=torch.int64, device=dev)
+    _hip.check(_hip.lib().dal3_flip4_points(_hip.ptr(points), N, C, _hip.ptr(off_dev), B, _hip.ptr(out), _hip.ptr(out_off_dev),
+                                            int(max_workgroups), _hip.stream()))
+    return out, out_off, out_off_dev
+
+
 class VoxelGenerator:
     """det3d/core/input/voxel_generator.py: the reference's constructor and properties; `generate` takes one sample's
     points (a CUDA tensor) and returns its voxels, coordinates (M, 3) [z, y, x] and num_points as device tensors."""

@@ -405,10 +405,12 @@ class CenterHead(_PackedLayers):
 
     @torch.no_grad()
     def predict(self, example, preds_dicts, test_cfg, **kwargs):
-        """center_head.py:294 through detect.CenterHeadPost -> the per-sample list of box3d_lidar / scores / label_preds /
-        metadata; one host synchronisation"""
-        from .detect import CenterHeadPost
+        """center_head.py:294 through detect.CenterHeadPost, or detect.DoubleFlipPost when test_cfg has double_flip (the batch
+        then holds four views per sample) -> the per-sample list of box3d_lidar / scores / label_preds / metadata; one host
+        synchronisation"""
+        from . import detect
         if self._post is None or self._post[0] is not test_cfg:
-            self._post = (test_cfg, CenterHeadPost(test_cfg, self.num_classes))
+            post = detect.DoubleFlipPost if detect._get(test_cfg, "double_flip", False) else detect.CenterHeadPost
+            self._post = (test_cfg, post(test_cfg, self.num_classes))
         meta = example.get("metadata") if isinstance(example, dict) else None
         return self._post[1].predict(preds_dicts, metadata=meta)

@@ -721,10 +721,10 @@ typedef struct dal3_nms_args {
 size_t dal3_nms_workspace_bytes(int64_t K, int boxes_f64);
 int dal3_nms(const dal3_nms_args* args, dal3_stream stream);
 
-/* dal3_center_decode: CenterHead.predict's arithmetic for one task (center_head.py:342-419 without double_flip) and
- * post_processing's masks (center_head.py:459-469), B samples in one enqueue. The maps are float32 views (B, H, W, C)
- * with ELEMENT strides: NHWC as the reference's permute(0, 2, 3, 1).contiguous() leaves them, or the network's NCHW as
- * it is. Per cell (row, col), every operation a separately rounded float32, in this order:
+/* dal3_center_decode: CenterHead.predict's arithmetic for one task (center_head.py:342-419; with double_flip:
+ * dal3_center_decode_flip4 below) and post_processing's masks (center_head.py:459-469), B samples in one enqueue. The
+ * maps are float32 views (B, H, W, C) with ELEMENT strides: NHWC as the reference's permute(0, 2, 3, 1).contiguous()
+ * leaves them, or the network's NCHW as it is. Per cell (row, col), every operation a separately rounded float32, in this order:
  *   score = max over classes of sigmoid(hm) = 1 / (1 + exp(-hm)), label = the FIRST maximum (torch.max);
  *   x = ((col + reg[0]) * out_size_factor) * voxel_size[0] + pc_range[0], y likewise from row and reg[1]; z = height;
  *   dim = exp(dim); rot = atan2(rot[0], rot[1]).
@@ -767,6 +767,43 @@ typedef struct dal3_center_decode_args {
 
 size_t dal3_center_decode_workspace_bytes(int64_t B, int64_t H, int64_t W);
 int dal3_center_decode(const dal3_center_decode_args* args, dal3_stream stream);
+
+/* dal3_center_decode_flip4: CenterHead.predict with test_cfg.double_flip (center_head.py:318-414) for one task: the
+ * un-flip of the four views' maps, their merge and the decode above in one pass, no intermediate map written.
+ * decode.B is the number of MERGED samples; every map holds 4 * decode.B samples, sample b's view v at map index
+ * 4 b + v in the order Reformat returns them (formating.py:78): v = 0 the sweep as it is, 1 with y = -y, 2 with x = -x,
+ * 3 with both. Output cell (row, col) reads view v at
+ *   v = 0: (row, col)   v = 1: (H-1-row, col)   v = 2: (row, W-1-col)   v = 3: (H-1-row, W-1-col),
+ * and with a_v the value there and mean(a0, a1, a2, a3) = (((a0 + a1) + a2) + a3) / 4, every operation a separately
+ * rounded float32 in exactly this order (torch.mean(dim=1) on a CPU tensor):
+ *   score_k = mean over v of sigmoid(hm_v[k]) (the mean of the sigmoids); score = the max over k, label = the FIRST
+ *             maximum, a NaN wins and stays;
+ *   reg_x   = mean(r0, r1, 1 - r2, 1 - r3) of reg[0], reg_y = mean(r0, 1 - r1, r2, 1 - r3) of reg[1]; x and y from
+ *             col + reg_x and row + reg_y as dal3_center_decode forms them;
+ *   z       = mean of height; dim_j = mean of exp(dim_v[j]);
+ *   rot     = atan2(mean(s0, s1, -s2, -s3), mean(c0, -c1, c2, -c3)), s = rot[0], c = rot[1];
+ *   vel     = (mean(vx0, vx1, -vx2, -vx3), mean(vy0, -vy1, vy2, -vy3)).
+ * The score and range masks, the ordered compaction, boxes / scores / labels / cell / seg_count of segment
+ * seg_first + b * seg_step, the status bits and every bound are dal3_center_decode's, with B the merged samples.
+ * workspace: dal3_center_decode_flip4_workspace_bytes(B, H, W) (B merged samples). */
+typedef struct dal3_center_decode_flip4_args {
+    dal3_center_decode_args decode;      /* B: MERGED samples; the maps hold 4 B */
+} dal3_center_decode_flip4_args;
+
+size_t dal3_center_decode_flip4_workspace_bytes(int64_t B, int64_t H, int64_t W);
+int dal3_center_decode_flip4(const dal3_center_decode_flip4_args* args, dal3_stream stream);
+
+/* dal3_flip4_points: DoubleFlip's three copies (det3d/datasets/pipelines/test_aug.py) of B samples' points, laid out
+ * as the batch of 4 B samples the detector then runs on. points (N, C) float32 contiguous, C >= 2; sample b is rows
+ * [offsets[b], offsets[b+1]) (device, non-decreasing within [0, N]). out (4 N, C): sample b's four views are consecutive,
+ * view v at rows [out_offsets[4 b + v], out_offsets[4 b + v + 1]) with out_offsets[4 b + v] = 4 offsets[b] + v n_b,
+ * n_b the sample's rows, out_offsets[4 B] = 4 offsets[B]; each view holds the sample's rows in their order with column 1
+ * negated for v = 1, column 0 for v = 2, both for v = 3. The negation flips the sign bit (0.0 -> -0.0, a NaN keeps its
+ * payload: NumPy's unary minus); columns >= 2 are copied. One enqueue, every input element read once, nothing read
+ * back; a row that device offsets would send outside out is not written. B == 0 succeeds with nothing launched.
+ * B, N <= DAL3_MAX_ITEMS / 4. */
+int dal3_flip4_points(const float* points, int64_t N, int32_t C, const int64_t* offsets, int64_t B, float* out,
+                      int64_t* out_offsets, int64_t max_workgroups, dal3_stream stream);
 
 /* ---- the PointPillars reader: points_to_voxel (det3d/ops/point_cloud/point_cloud_ops.py:7-184, through
  * VoxelGenerator.generate and collate_kitti's batch column), PillarFeatureNet and PointPillarsScatter

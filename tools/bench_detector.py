@@ -11,6 +11,15 @@ and records beside them the algorithmic FLOP (2 x MACs from the shapes, `flop` b
 the two routes' outputs, and the compiler's register / scratch / LDS counts of every kernel. One JSON line; --out writes it
 to a file (after every batch size, so that an interrupted run leaves what it measured).
     python tools/bench_detector.py [--batches 1 4 --window 1.0 --out profiles/bench_detector.json]
+
+--double-flip measures the test-time augmentation instead (profiles/bench_tta.json): `PointPillars.detect` on one seeded
+sweep of --points points over the same 468 x 468 grid, with and without test_cfg.double_flip, and the merge of the four
+views alone two ways on the head's own outputs:
+  fused      DoubleFlipPost.decode: dal3_center_decode_flip4 reads the four views' NCHW channel slices and writes rows
+  composite  the reference's formulation in stock PyTorch-ROCm ops (permute + contiguous, three flips written back in
+             place, sigmoid / exp, the sign and 1 - x rules, six means), then logit / log of the merged hm / dim so that
+             the existing dal3_center_decode can take the merged maps through NHWC views
+    python tools/bench_detector.py --double-flip --out profiles/bench_tta.json
 """
 import argparse
 import importlib
@@ -102,6 +111,118 @@ def kernel_resources():
     return out or None
 
 
+TTA_VOXEL, TTA_RANGE = (0.32, 0.32, 6.0), (-74.88, -74.88, -2.0, 74.88, 74.88, 4.0)      # 468 x 468 pillars
+TTA_CFG = dict(post_center_limit_range=[-80, -80, -10.0, 80, 80, 10.0],
+               nms=dict(nms_pre_max_size=4096, nms_post_max_size=500, nms_iou_threshold=0.7), score_threshold=0.1,
+               pc_range=[TTA_RANGE[0], TTA_RANGE[1]], out_size_factor=1, voxel_size=[0.32, 0.32])
+
+
+def composite_merge(preds_dicts):
+    """center_head.py:311-414's merge of the four views in stock ops -> NHWC maps of the merged samples that
+    dal3_center_decode reproduces the merged values from (hm as the logit of the mean score, dim as the log of the mean)"""
+    out = []
+    for pd in preds_dicts:
+        m = {}
+        for k, v in pd.items():
+            v = v.permute(0, 2, 3, 1).contiguous()
+            _, H, W, C = v.shape
+            v = v.reshape(-1, 4, H, W, C)
+            v[:, 1] = torch.flip(v[:, 1], dims=[1])
+            v[:, 2] = torch.flip(v[:, 2], dims=[2])
+            v[:, 3] = torch.flip(v[:, 3], dims=[1, 2])
+            m[k] = v
+        hm = torch.sigmoid(m["hm"]).mean(dim=1)
+        dim = torch.exp(m["dim"]).mean(dim=1)
+        reg = m["reg"]
+        reg[:, 1, ..., 1] = 1 - reg[:, 1, ..., 1]
+        reg[:, 2, ..., 0] = 1 - reg[:, 2, ..., 0]
+        reg[:, 3] = 1 - reg[:, 3]
+        rot = m["rot"]
+        rot[:, 1, ..., 1] *= -1
+        rot[:, 2, ..., 0] *= -1
+        rot[:, 3] *= -1
+        d = {"hm": torch.logit(hm), "dim": torch.log(dim), "reg": reg.mean(dim=1), "height": m["height"].mean(dim=1),
+             "rot": rot.mean(dim=1)}
+        if "vel" in m:
+            vel = m["vel"]
+            vel[:, 1, ..., 1] *= -1
+            vel[:, 2, ..., 0] *= -1
+            vel[:, 3] *= -1
+            d["vel"] = vel.mean(dim=1)
+        out.append(d)
+    return out
+
+
+def double_flip_bench(a):
+    """--double-flip: see the module's docstring"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import pillars_ref as P
+    import rpn_ref as R
+    detector = importlib.import_module("3dal_pytorch_amd.detector")
+    detect = importlib.import_module("3dal_pytorch_amd.detect")
+    pillars = importlib.import_module("3dal_pytorch_amd.pillars")
+    dev = torch.device("cuda")
+    model = detector.PointPillars(
+        reader=dict(type="PillarFeatureNet", num_filters=[64, 64], num_input_features=5, with_distance=False,
+                    voxel_size=TTA_VOXEL, pc_range=TTA_RANGE),
+        backbone=dict(type="PointPillarsScatter", ds_factor=1), neck=dict(type="RPN", **R.NECK),
+        bbox_head=dict(type="CenterHead", **R.HEAD), test_cfg=TTA_CFG, max_points=20, max_voxels=60000)
+    sd = {"reader." + k: v for k, v in P.reader_weights(2, 5).items()}
+    sd.update({"neck." + k: v for k, v in R.neck_weights().items()})
+    sd.update({"bbox_head." + k: v for k, v in R.head_weights().items()})
+    model.load_state_dict({k: torch.as_tensor(np.asarray(v)) for k, v in sd.items()}, strict=True)
+    model = model.to(dev).eval()
+    rng = np.random.default_rng(0)
+    n = a.points
+    pts = np.concatenate([np.clip(rng.normal(0, 30, (n, 2)), -74.8, 74.8), rng.uniform(-2, 4, (n, 1)), rng.uniform(0, 1, (n, 2))],
+                         1).astype(np.float32)
+    dpts, off = torch.from_numpy(pts).to(dev), np.asarray([0, n], np.int64)
+    off_dev = torch.from_numpy(off).to(dev)
+    flip_cfg = dict(TTA_CFG, double_flip=True)
+    res = {"bench": "double_flip", "size": a.size, "points": n, "device": torch.cuda.get_device_name(0), "window_s": a.window}
+
+    def run_detect(cfg):
+        model.test_cfg = cfg
+        return model.detect(dpts, off, point_offsets_device=off_dev)
+
+    with torch.no_grad():
+        plain, flipped = run_detect(TTA_CFG), run_detect(flip_cfg)
+        res["occupied"] = float(model.last.voxel_offsets[1]) / (a.size * a.size)
+        res["kept_plain"], res["kept_double_flip"] = int(plain[0]["scores"].numel()), int(flipped[0]["scores"].numel())
+        # the head's outputs of the four views, for the merge alone
+        r = pillars.voxelize(*pillars.double_flip(dpts, off, off_dev)[:2], TTA_VOXEL, TTA_RANGE, 20, 60000)
+        canvas = model.reader.forward_canvas(r.voxels, r.num_points, r.coordinates, 4, [a.size, a.size], n_pillars=r.n_pillars)
+        preds = model.bbox_head(model.neck(canvas))
+        fused_post = detect.DoubleFlipPost(flip_cfg, model.bbox_head.num_classes)
+        plain_post = detect.CenterHeadPost(TTA_CFG, model.bbox_head.num_classes)
+
+        def fused():
+            return fused_post.decode(preds)
+
+        def composite():
+            return plain_post.decode(composite_merge(preds), layout="NHWC")
+
+        x, y = fused(), composite()
+        res["candidates_fused"], res["candidates_composite"] = x["seg_count"].cpu().tolist(), y["seg_count"].cpu().tolist()
+        torch.cuda.synchronize()
+        rows = {"detect_ms": lambda: run_detect(TTA_CFG), "detect_double_flip_ms": lambda: run_detect(flip_cfg),
+                "merge_fused_ms": fused, "merge_composite_ms": composite}
+        times = {k: [] for k in rows}
+        for _ in range(a.windows):
+            for k, fn in rows.items():
+                times[k].append(window(fn, a.window))
+    for k, w in times.items():
+        res[k] = float(np.median([t for t, _ in w]))
+        res[k.replace("_ms", "_windows")] = [[round(t, 3), c] for t, c in w]
+    res["double_flip_over_plain"] = res["detect_double_flip_ms"] / res["detect_ms"]
+    res["fused_over_composite_time"] = res["merge_fused_ms"] / res["merge_composite_ms"]
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res) + "\n")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 4])
@@ -110,7 +231,11 @@ def main():
     ap.add_argument("--size", type=int, default=SIZE)
     ap.add_argument("--skip_composite", action="store_true")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--double-flip", action="store_true", help="time the test-time augmentation instead (see above)")
+    ap.add_argument("--points", type=int, default=180000, help="points of the --double-flip sweep")
     a = ap.parse_args()
+    if a.double_flip:
+        return double_flip_bench(a)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import rpn_ref as R
     dev = torch.device("cuda")
