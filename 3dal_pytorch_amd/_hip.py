@@ -8,6 +8,7 @@ loading raises if it has not been built (python -c "import __graft_entry__ as g;
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -415,6 +416,28 @@ def require_gpu(t, what):
         raise RuntimeError(
             f"{what} lives on {t.device}: the eval-mode forward runs only on an MI355X through "
             "lib3dal_hip.so (no CPU fallback). Move the model and its inputs to the GPU.")
+
+
+def workspace(nbytes, device):
+    """a run kernel's workspace of `nbytes` bytes on `device`; never empty: 8 bytes cover the 8-byte alignment checks of
+    dal3_api.hip"""
+    return torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=device)
+
+
+def host_offsets(offsets, n, name, sized_by, count):
+    """the HOST offsets `name` of a run (a list, an array or a CPU tensor; `count` + 1 of them) checked against [0, n]
+    -> contiguous int64 array. `sized_by`: what the message says the host needs them for."""
+    if torch.is_tensor(offsets):
+        if offsets.is_cuda:
+            raise TypeError(f"{name} must be on the host (a list, an array or a CPU tensor): {sized_by} from it, and "
+                            "reading a device tensor back would be the synchronisation this call avoids")
+        offsets = offsets.numpy()
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
+    if off.size < 1:
+        raise ValueError(f"{name} needs {count} + 1 entries")
+    if off[0] < 0 or off[-1] > n or np.any(np.diff(off) < 0):
+        raise ValueError(f"{name} must be non-decreasing within [0, {n}]")
+    return off
 
 
 STORAGE = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}

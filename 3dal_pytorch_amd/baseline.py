@@ -123,7 +123,7 @@ def score_tracks(boxes, box_row, frame, pose_inv, gt, has_gt, types, thr=THR_TYP
         out = (vb, v3, pb, lb)
     if acc is not None:
         need = _hip.lib().dal3_score_workspace_bytes(S)
-        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+        ws = _hip.workspace(need, dev)
         a.acc, a.workspace, a.workspace_bytes = _hip.ptr(acc.acc), _hip.ptr(ws), need
     with torch.cuda.device(dev):
         _hip.check(_hip.lib().dal3_score_tracks(a, _hip.stream()))

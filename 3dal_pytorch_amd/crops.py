@@ -114,7 +114,7 @@ class CropPlan:
                 raise ValueError("CropPlan: order must be a permutation of the detections")
             self.d_order = torch.from_numpy(order).to(dev)
         lib = _hip.lib()
-        self.ws = torch.empty(max(int(lib.dal3_crop_workspace_bytes(K, self.max_pts)), 4), dtype=torch.uint8, device=dev)
+        self.ws = _hip.workspace(lib.dal3_crop_workspace_bytes(K, self.max_pts), dev)
         self.counts = torch.zeros(max(K, 1), dtype=torch.int64, device=dev)
         self.start = torch.zeros(K + 1, dtype=torch.int64, device=dev)           # by detection; [K] = total
         self.offsets = torch.zeros(K + 1, dtype=torch.int64, device=dev)         # by output position

@@ -1,10 +1,14 @@
-// dal3_block.h — what the run kernels (dal3_motion.hip, dal3_track.hip, dal3_nms.hip) share: the workspace carver
-// and the integer workgroup primitives of their ordered compactions, radix sorts and scans. Everything here is used
-// at two or more call sites; a building block with one user stays in its file. A run kernel's workspace size is
-// its carve on a null base (Carver::off), never a formula of its own.
+// dal3_block.h — what the run kernels (dal3_motion.hip, dal3_track.hip, dal3_nms.hip, dal3_pillars.hip) share: the
+// workspace carver, the grid clamp, the integer workgroup primitives of their ordered compactions, radix sorts and
+// scans, the two binary searches, and the chunked radix sort of (key, position) pairs that the grouping run and the
+// voxeliser both stand on. Everything here is used at two or more call sites; a building block with one user stays in
+// its file. A run kernel's workspace size is its carve on a null base (Carver::off), never a formula of its own.
 //
 // The block primitives take their LDS arrays from the caller, must be called by every thread of the workgroup
 // (they hold barriers) and index by threadIdx.x; waves are 64 lanes.
+//
+// dal3_nms.hip's sort is deliberately not the chunked sort: it is one workgroup per segment with the histogram in LDS,
+// a different shape. It shares radix_tile_step and nothing above it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -28,6 +32,37 @@ struct Carver {
         return reinterpret_cast<T*>(p);
     }
 };
+
+// The grid of a launch that wants `want` workgroups: at least one, at most the site's `ceiling`, and at most
+// max_workgroups when that is positive (the run kernels' argument; 0 leaves the grid to the site).
+constexpr int64_t GRID_MAX = 0x7fffffff;        // the ceiling of a site that has none of its own: the launch limit
+inline unsigned grid_clamp(int64_t want, int64_t ceiling, int64_t max_workgroups) {
+    int64_t g = want < ceiling ? want : ceiling;
+    if (g < 1) g = 1;
+    if (max_workgroups > 0 && g > max_workgroups) g = max_workgroups;
+    return (unsigned)g;
+}
+
+// The first index in [lo, hi) with v[i] >= x, and the first with v[i] > x; hi when there is none. v ascends.
+template <typename T, typename X>
+__device__ __forceinline__ int64_t lower_bound(const T* v, int64_t lo, int64_t hi, X x) {
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (v[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+template <typename T, typename X>
+__device__ __forceinline__ int64_t upper_bound(const T* v, int64_t lo, int64_t hi, X x) {
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (v[mid] <= x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
 
 // Ordered compaction: the exclusive rank of `flag` among the workgroup's WAVES * 64 threads, in thread order, and
 // the workgroup's count. s_cnt[WAVES] is free again on return.
@@ -120,3 +155,122 @@ __device__ __forceinline__ int64_t block_scan_spans(int32_t* data, int64_t n, in
     }
     return s_part[BLOCK - 1];
 }
+
+// ---------------------------------------------------------------------------------- chunked radix sort
+// A stable least-significant-digit radix sort of n (key, position) pairs by their non-negative 32-bit keys, 8 bits a
+// pass, over many workgroups. The input is cut into chunks of RADIX_CHUNK consecutive entries, whatever the grid; per pass
+//   hist     each chunk's digit counts (LDS integer adds), stored digit-major (256, chunks);
+//   scan     one exclusive scan over that table: where each (digit, chunk) run starts in the output;
+//   scatter  each chunk again, tile by tile of RADIX_BLOCK consecutive entries on radix_tile_step: equal digits keep
+//            their input order, so the pass is stable and the passes together sort by key with the positions ascending
+//            inside a key.
+// Every count is an integer and every output slot is a function of the input alone: no result depends on the grid,
+// on which workgroup ran which chunk, or on the order atomics arrive in.
+//
+// The kernels are templates (on the key type; the scan on its block) in an unnamed namespace: a translation unit that
+// sorts instantiates its own device copy, one that does not has none, and the objects link without relocatable device
+// code.
+namespace {
+
+constexpr int RADIX_BLOCK = 256;
+constexpr int RADIX_WAVES = RADIX_BLOCK / 64;
+constexpr int RADIX_TILES = 16;
+constexpr int64_t RADIX_CHUNK = (int64_t)RADIX_BLOCK * RADIX_TILES;     // 4096 entries
+constexpr int RADIX_SCAN_BLOCK = 1024;
+
+__host__ __device__ inline int64_t radix_chunks(int64_t n) { return (n + RADIX_CHUNK - 1) / RADIX_CHUNK; }
+
+inline int radix_passes(int64_t max_key) {      // keys lie in [0, max_key]
+    int bits = 1;
+    while (bits < 32 && (max_key >> bits) != 0) ++bits;
+    return (bits + 7) / 8;
+}
+
+template <typename K>
+struct RadixBufs {
+    K* key[2];                                  // (n) each: the pairs' keys, ping-pong; the input is key[0]
+    int32_t* pos[2];                            // (n) each: the pairs' positions, ping-pong
+    int32_t* hist;                              // (256, chunks)
+};
+
+// key[0], key[1], the first n_pos position buffers, hist, in this order. The position buffers it does not take
+// (null here) are the caller's to set.
+template <typename K>
+inline RadixBufs<K> carve_radix(Carver& c, int64_t n, int n_pos) {
+    RadixBufs<K> b = {};
+    for (int i = 0; i < 2; ++i) b.key[i] = c.take<K>((size_t)n);
+    for (int i = 0; i < n_pos; ++i) b.pos[i] = c.take<int32_t>((size_t)n);
+    b.hist = c.take<int32_t>((size_t)256 * (size_t)radix_chunks(n));
+    return b;
+}
+
+template <typename K>
+__global__ __launch_bounds__(RADIX_BLOCK) void radix_hist_kernel(const K* key, int64_t E, int shift, int32_t* hist) {
+    __shared__ int32_t s_hist[256];
+    const int64_t chunks = radix_chunks(E);
+    for (int64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
+        s_hist[threadIdx.x] = 0;
+        __syncthreads();
+        const int64_t e0 = c * RADIX_CHUNK;
+        for (int r = 0; r < RADIX_TILES; ++r) {
+            const int64_t i = e0 + (int64_t)r * RADIX_BLOCK + threadIdx.x;
+            if (i < E) atomicAdd(&s_hist[(key[i] >> shift) & 255], 1);   // an integer count: the order does not matter
+        }
+        __syncthreads();
+        hist[(int64_t)threadIdx.x * chunks + c] = s_hist[threadIdx.x];
+        __syncthreads();
+    }
+}
+
+// in-place exclusive scan of n int32 by ONE workgroup; total (optional) gets the sum
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void scan_kernel(int32_t* data, int64_t n, int64_t* total) {
+    __shared__ int64_t s_part[BLOCK];
+    const int64_t sum = block_scan_spans<BLOCK>(data, n, s_part);
+    if (total && threadIdx.x == BLOCK - 1) *total = sum;
+}
+
+// pos_in == nullptr: the first pass, the position is the index itself
+template <typename K>
+__global__ __launch_bounds__(RADIX_BLOCK) void radix_scatter_kernel(const K* key_in, const int32_t* pos_in, int64_t E, int shift,
+                                                                    const int32_t* hist, K* key_out, int32_t* pos_out) {
+    __shared__ int32_t s_base[256];             // where the chunk's next entry of each digit goes
+    __shared__ int32_t s_wave[RADIX_WAVES][256];    // the tile's count of each digit, per wave
+    const int t = threadIdx.x;
+    const int64_t chunks = radix_chunks(E);
+    for (int64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
+        s_base[t] = hist[(int64_t)t * chunks + c];
+        const int64_t e0 = c * RADIX_CHUNK;
+        for (int r = 0; r < RADIX_TILES; ++r) {
+            const int64_t i = e0 + (int64_t)r * RADIX_BLOCK + t;
+            const bool live = i < E;
+            const K k = live ? key_in[i] : 0;
+            const int64_t o = radix_tile_step<RADIX_WAVES>(live, (k >> shift) & 255, s_base, s_wave);
+            if (o >= 0 && o < E) {              // live; the bound always holds for a table hist/scan made from these keys
+                key_out[o] = k;
+                pos_out[o] = pos_in ? pos_in[i] : (int32_t)i;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// Sorts the n > 0 keys in b.key[0], each paired with its index, in `passes` passes on `grid` workgroups. The sorted
+// pairs end in key[passes & 1] / pos[passes & 1]: pass p reads buffer p & 1 and writes the other one. The first pass
+// takes the index itself as the position, so pos[0] is never read before it is written.
+template <typename K>
+inline hipError_t radix_sort_pairs(const RadixBufs<K>& b, int64_t n, int passes, unsigned grid, hipStream_t s) {
+    const int64_t chunks = radix_chunks(n);
+    for (int p = 0; p < passes; ++p) {
+        const int in = p & 1, out = in ^ 1;
+        hipLaunchKernelGGL(radix_hist_kernel<K>, dim3(grid), dim3(RADIX_BLOCK), 0, s, b.key[in], n, 8 * p, b.hist);
+        hipLaunchKernelGGL(scan_kernel<RADIX_SCAN_BLOCK>, dim3(1), dim3(RADIX_SCAN_BLOCK), 0, s, b.hist, 256 * chunks, (int64_t*)nullptr);
+        hipLaunchKernelGGL(radix_scatter_kernel<K>, dim3(grid), dim3(RADIX_BLOCK), 0, s, b.key[in],
+                           p ? b.pos[in] : (const int32_t*)nullptr, n, 8 * p, b.hist, b.key[out], b.pos[out]);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+}  // namespace

@@ -2,17 +2,8 @@
 // dal3_motion_classify, include/dal3.h): the regrouping of tools/trackData.py as a stable sort, trackFeature of
 // tools/motionState.py:30-67, the static flag of tools/trackGT.py:60-66 and the linear decision of SVC(kernel='linear').
 //
-// Grouping is a least-significant-digit radix sort of (key, input position) pairs, 8 bits a pass. An entry that is not
-// part of the input (the unused tail of a frame's slots) or whose key is outside [0, T) gets the key T and so sorts
-// behind every group. The input is cut into chunks of MO_CHUNK consecutive entries, whatever the grid; per pass
-//   hist     each chunk's digit counts (LDS integer adds), stored digit-major (256, chunks);
-//   scan     one exclusive scan over that table: where each (digit, chunk) run starts in the output;
-//   scatter  each chunk again, tile by tile of 256 consecutive entries, thread t = entry t of the tile: an entry's rank
-//            among the tile's equal digits comes from wave ballots and the waves' counts in wave order, so equal digits
-//            keep their input order — the pass is stable, and three stable passes sort by key with the positions ascending
-//            inside a key.
-// Every count is an integer and every output slot is a function of the input alone: no result depends on the grid,
-// on which workgroup ran which chunk, or on the order atomics arrive in.
+// Grouping is dal3_block.h's chunked radix sort of (key, input position) pairs. An entry that is not part of the input
+// (the unused tail of a frame's slots) or whose key is outside [0, T) gets the key T and so sorts behind every group.
 //
 // Features are one wave per group: the float64 sums are the sequential sums NumPy forms along axis 0, taken in two
 // passes (mean, then squared deviations); the integer reductions run across the lanes.
@@ -26,27 +17,11 @@ namespace {
 
 constexpr int MO_BLOCK = 256;
 constexpr int MO_WAVES = MO_BLOCK / 64;
-constexpr int MO_TILES = 16;
-constexpr int64_t MO_CHUNK = (int64_t)MO_BLOCK * MO_TILES;       // 4096 entries
-constexpr int MO_SCAN_BLOCK = 1024;
 constexpr int64_t MO_FLAG_TILE = 1024;                           // groups per compaction tile (4 per thread)
 
-__host__ __device__ inline int64_t mo_chunks(int64_t E) { return (E + MO_CHUNK - 1) / MO_CHUNK; }
-
-struct GroupWs {
-    int32_t* key[2];                            // (E) each: the pairs' keys, ping-pong
-    int32_t* pos;                               // (E) the pairs' positions, ping-pong with args.entry
-    int32_t* hist;                              // (256, chunks)
-};
-
-inline GroupWs carve_group(Carver& c, int64_t E) {
-    GroupWs w;
-    w.key[0] = c.take<int32_t>((size_t)E);
-    w.key[1] = c.take<int32_t>((size_t)E);
-    w.pos = c.take<int32_t>((size_t)E);
-    w.hist = c.take<int32_t>((size_t)256 * (size_t)mo_chunks(E));
-    return w;
-}
+// key[2] and hist are the sort's; of the positions' ping-pong one buffer is the workspace's (pos[0] after the carve), the
+// other is args.entry, which saves E words
+inline RadixBufs<int32_t> carve_group(Carver& c, int64_t E) { return carve_radix<int32_t>(c, E, 1); }
 
 struct ClassifyWs {
     int32_t* stat;                              // (tiles) each: the tiles' kept static / dynamic groups
@@ -94,65 +69,11 @@ __global__ __launch_bounds__(MO_BLOCK) void group_keys_kernel(const dal3_group_a
     }
 }
 
-__global__ __launch_bounds__(MO_BLOCK) void radix_hist_kernel(const int32_t* key, int64_t E, int shift, int32_t* hist) {
-    __shared__ int32_t s_hist[256];
-    const int64_t chunks = mo_chunks(E);
-    for (int64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
-        s_hist[threadIdx.x] = 0;
-        __syncthreads();
-        const int64_t e0 = c * MO_CHUNK;
-        for (int r = 0; r < MO_TILES; ++r) {
-            const int64_t i = e0 + (int64_t)r * MO_BLOCK + threadIdx.x;
-            if (i < E) atomicAdd(&s_hist[(key[i] >> shift) & 255], 1);
-        }
-        __syncthreads();
-        hist[(int64_t)threadIdx.x * chunks + c] = s_hist[threadIdx.x];
-        __syncthreads();
-    }
-}
-
-// in-place exclusive scan of n int32 by ONE workgroup
-__global__ __launch_bounds__(MO_SCAN_BLOCK) void scan_kernel(int32_t* data, int64_t n, int64_t* total) {
-    __shared__ int64_t s_part[MO_SCAN_BLOCK];
-    const int64_t sum = block_scan_spans<MO_SCAN_BLOCK>(data, n, s_part);
-    if (total && threadIdx.x == MO_SCAN_BLOCK - 1) *total = sum;
-}
-
-// pos_in == nullptr: the first pass, the position is the index itself
-__global__ __launch_bounds__(MO_BLOCK) void radix_scatter_kernel(const int32_t* key_in, const int32_t* pos_in, int64_t E,
-                                                                 int shift, const int32_t* hist, int32_t* key_out,
-                                                                 int32_t* pos_out) {
-    __shared__ int32_t s_base[256];             // where the chunk's next entry of each digit goes
-    __shared__ int32_t s_wave[MO_WAVES][256];   // the tile's count of each digit, per wave
-    const int t = threadIdx.x;
-    const int64_t chunks = mo_chunks(E);
-    for (int64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
-        s_base[t] = hist[(int64_t)t * chunks + c];
-        const int64_t e0 = c * MO_CHUNK;
-        for (int r = 0; r < MO_TILES; ++r) {
-            const int64_t i = e0 + (int64_t)r * MO_BLOCK + t;
-            const bool live = i < E;
-            const int32_t k = live ? key_in[i] : 0;
-            const int64_t o = radix_tile_step<MO_WAVES>(live, (k >> shift) & 255, s_base, s_wave);
-            if (o >= 0 && o < E) {              // live; the bound always holds for a table hist/scan made from these keys
-                key_out[o] = k;
-                pos_out[o] = pos_in ? pos_in[i] : (int32_t)i;
-            }
-            __syncthreads();
-        }
-    }
-}
-
 // group_start[j] = the first sorted position whose key is >= j (a binary search per group: empty groups cost the same as
 // full ones); group_start[T] = the number of entries, and the key in front of it + 1 = the number of groups
 __global__ __launch_bounds__(MO_BLOCK) void group_bounds_kernel(const dal3_group_args a, const int32_t* key) {
     for (int64_t j = (int64_t)blockIdx.x * MO_BLOCK + threadIdx.x; j <= a.T; j += (int64_t)gridDim.x * MO_BLOCK) {
-        int64_t lo = 0, hi = a.E;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (key[mid] < j) lo = mid + 1;
-            else hi = mid;
-        }
+        const int64_t lo = lower_bound(key, 0, a.E, j);
         a.group_start[j] = lo;
         if (j == a.T && a.n_groups) *a.n_groups = lo > 0 ? (int64_t)key[lo - 1] + 1 : 0;
     }
@@ -404,18 +325,8 @@ __global__ __launch_bounds__(MO_BLOCK) void classify_fill_kernel(const dal3_moti
     }
 }
 
-inline unsigned mo_grid(int64_t work_items, int64_t max_workgroups) {
-    int64_t g = work_items < 1 ? 1 : work_items;
-    if (g > 2048) g = 2048;                     // grid-stride beyond 8 workgroups per CU
-    if (max_workgroups > 0 && g > max_workgroups) g = max_workgroups;
-    return (unsigned)g;
-}
-
-inline int radix_passes(int64_t T) {            // keys lie in [0, T]
-    int bits = 1;
-    while (bits < 32 && (T >> bits) != 0) ++bits;
-    return (bits + 7) / 8;
-}
+// grid-stride beyond 8 workgroups per CU
+inline unsigned mo_grid(int64_t work_items, int64_t max_workgroups) { return grid_clamp(work_items, 2048, max_workgroups); }
 
 }  // namespace
 
@@ -434,27 +345,19 @@ size_t motion_classify_workspace_bytes(int64_t T) {
 
 hipError_t launch_group_by_key(const dal3_group_args* a, hipStream_t s) {
     Carver c(a->workspace, a->workspace_bytes);
-    const GroupWs ws = carve_group(c, a->E);
-    const int64_t E = a->E, chunks = mo_chunks(E);
+    RadixBufs<int32_t> ws = carve_group(c, a->E);
+    const int64_t E = a->E;
     const int passes = radix_passes(a->T);
     const int32_t* sorted = ws.key[0];
     if (E > 0) {
         const int64_t key_items = a->frame_offsets ? (a->F > (E + MO_BLOCK - 1) / MO_BLOCK ? a->F : (E + MO_BLOCK - 1) / MO_BLOCK)
                                                    : (E + MO_BLOCK - 1) / MO_BLOCK;
         hipLaunchKernelGGL(group_keys_kernel, dim3(mo_grid(key_items, a->max_workgroups)), dim3(MO_BLOCK), 0, s, *a, ws.key[0]);
-        const unsigned grid = mo_grid(chunks, a->max_workgroups);
-        for (int p = 0; p < passes; ++p) {
-            const int32_t* kin = ws.key[p & 1];
-            int32_t* kout = ws.key[(p + 1) & 1];
-            // the last pass writes the positions to args.entry
-            int32_t* pout = ((passes - 1 - p) & 1) ? ws.pos : a->entry;
-            const int32_t* pin = p == 0 ? nullptr : (((passes - p) & 1) ? ws.pos : a->entry);
-            hipLaunchKernelGGL(radix_hist_kernel, dim3(grid), dim3(MO_BLOCK), 0, s, kin, E, 8 * p, ws.hist);
-            hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(MO_SCAN_BLOCK), 0, s, ws.hist, 256 * chunks, (int64_t*)nullptr);
-            hipLaunchKernelGGL(radix_scatter_kernel, dim3(grid), dim3(MO_BLOCK), 0, s, kin, pin, E, 8 * p, ws.hist, kout, pout);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return e;
-        }
+        int32_t* const own = ws.pos[0];
+        ws.pos[passes & 1] = a->entry;          // where the sorted positions land
+        ws.pos[~passes & 1] = own;
+        const hipError_t e = radix_sort_pairs(ws, E, passes, mo_grid(radix_chunks(E), a->max_workgroups), s);
+        if (e != hipSuccess) return e;
         sorted = ws.key[passes & 1];
     }
     hipLaunchKernelGGL(group_bounds_kernel, dim3(mo_grid((a->T + MO_BLOCK) / MO_BLOCK, a->max_workgroups)), dim3(MO_BLOCK), 0, s, *a,
@@ -487,8 +390,8 @@ hipError_t launch_motion_classify(const dal3_motion_classify_args* a, hipStream_
     if (tiles > 0)
         hipLaunchKernelGGL(classify_count_kernel, dim3(mo_grid(tiles, a->max_workgroups)), dim3(MO_BLOCK), 0, s, *a, stat, dyn);
     // with T == 0 the scans only write the two zero totals
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(MO_SCAN_BLOCK), 0, s, stat, tiles, a->counts);
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(MO_SCAN_BLOCK), 0, s, dyn, tiles, a->counts + 1);
+    hipLaunchKernelGGL(scan_kernel<RADIX_SCAN_BLOCK>, dim3(1), dim3(RADIX_SCAN_BLOCK), 0, s, stat, tiles, a->counts);
+    hipLaunchKernelGGL(scan_kernel<RADIX_SCAN_BLOCK>, dim3(1), dim3(RADIX_SCAN_BLOCK), 0, s, dyn, tiles, a->counts + 1);
     if (tiles > 0)
         hipLaunchKernelGGL(classify_fill_kernel, dim3(mo_grid(tiles, a->max_workgroups)), dim3(MO_BLOCK), 0, s, *a, stat, dyn);
     return hipGetLastError();

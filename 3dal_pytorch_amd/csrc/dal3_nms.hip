@@ -12,10 +12,11 @@
 //
 // NMS is two launches, each one workgroup per segment (a (frame, task) pair), whatever the grid:
 //   sort      a stable least-significant-digit radix sort of the segment's (key, row) pairs, 8 bits a pass, key =
-//             ~orderable(score) with every NaN mapped to 0 (first) and -0 to +0. It is dal3_motion.hip's chunk
-//             histogram -> scan -> ballot-rank scatter with the segment as the one chunk: equal digits keep their
-//             input order, so equal scores end by ascending row. Then the candidates' IouBox (sin / cos once per box)
-//             are written in sorted order to the workspace: the one table the scan reads. It is O(K); no mask exists.
+//             ~orderable(score) with every NaN mapped to 0 (first) and -0 to +0. It is the histogram -> scan ->
+//             ballot-rank scatter of dal3_block.h's chunked sort with the segment as the one chunk and the histogram
+//             in LDS (its own kernel, on the shared radix_tile_step): equal digits keep their input order, so equal
+//             scores end by ascending row. Then the candidates' IouBox (sin / cos once per box) are written in sorted
+//             order to the workspace: the one table the scan reads. It is O(K); no mask exists.
 //   suppress  walks the candidates in blocks of 64, lane = candidate. (1) The block's 64 boxes are tested against the
 //             boxes KEPT so far, the kept list split over the waves (each kept box is one broadcast load); a wave stops
 //             when all its lanes are suppressed. (2) The block's own 64 x 64 triangle: wave w takes rows w, w + 4, ...,
@@ -477,11 +478,9 @@ size_t nms_workspace_bytes(int64_t K, int boxes_f64) {
 hipError_t launch_nms(const dal3_nms_args* args, hipStream_t s) {
     const dal3_nms_args& a = *args;
     if (a.F <= 0) return hipSuccess;
-    int64_t grid = a.F;
-    if (a.max_workgroups > 0 && grid > a.max_workgroups) grid = a.max_workgroups;
     Carver c(a.workspace, a.workspace_bytes);
     const NmsWs ws = carve_nms(c, a.K, a.boxes_f64);
-    const dim3 g((unsigned)grid), blk(NMS_BLOCK);
+    const dim3 g(grid_clamp(a.F, GRID_MAX, a.max_workgroups)), blk(NMS_BLOCK);
     if (a.K > 0) {
         if (a.boxes_f64) hipLaunchKernelGGL(nms_sort_kernel<double>, g, blk, 0, s, a, ws);
         else hipLaunchKernelGGL(nms_sort_kernel<float>, g, blk, 0, s, a, ws);
@@ -515,12 +514,10 @@ static hipError_t launch_decode(const dal3_center_decode_args& a, hipStream_t s)
     const int64_t chunks = decode_chunks(a.H, a.W);
     Carver c(a.workspace, a.workspace_bytes);
     int32_t* counts = carve_decode(c, a.B, a.H, a.W);
-    int64_t jobs = a.B * chunks, samples = a.B;
-    if (a.max_workgroups > 0 && jobs > a.max_workgroups) jobs = a.max_workgroups;
-    if (a.max_workgroups > 0 && samples > a.max_workgroups) samples = a.max_workgroups;
-    if (jobs > 0) hipLaunchKernelGGL(decode_count_kernel<V>, dim3((unsigned)jobs), dim3(DEC_BLOCK), 0, s, a, counts, chunks);
-    hipLaunchKernelGGL(decode_scan_kernel, dim3((unsigned)samples), dim3(DEC_BLOCK), 0, s, a, counts, chunks);
-    if (jobs > 0) hipLaunchKernelGGL(decode_fill_kernel<V>, dim3((unsigned)jobs), dim3(DEC_BLOCK), 0, s, a, counts, chunks);
+    const dim3 jobs(grid_clamp(a.B * chunks, GRID_MAX, a.max_workgroups)), samples(grid_clamp(a.B, GRID_MAX, a.max_workgroups));
+    if (chunks > 0) hipLaunchKernelGGL(decode_count_kernel<V>, jobs, dim3(DEC_BLOCK), 0, s, a, counts, chunks);
+    hipLaunchKernelGGL(decode_scan_kernel, samples, dim3(DEC_BLOCK), 0, s, a, counts, chunks);
+    if (chunks > 0) hipLaunchKernelGGL(decode_fill_kernel<V>, jobs, dim3(DEC_BLOCK), 0, s, a, counts, chunks);
     return hipGetLastError();
 }
 
@@ -535,10 +532,8 @@ hipError_t launch_flip4_points(const float* points, int64_t N, int C, const int6
                                int64_t* out_offsets, int64_t max_workgroups, hipStream_t s) {
     if (B <= 0) return hipSuccess;
     const int64_t work = N * C > 4 * B + 1 ? N * C : 4 * B + 1;
-    int64_t grid = (work + FLIP_BLOCK - 1) / FLIP_BLOCK;
-    if (grid > 65536) grid = 65536;
-    if (max_workgroups > 0 && grid > max_workgroups) grid = max_workgroups;
-    hipLaunchKernelGGL(flip4_points_kernel, dim3((unsigned)grid), dim3(FLIP_BLOCK), 0, s,
+    const unsigned grid = grid_clamp((work + FLIP_BLOCK - 1) / FLIP_BLOCK, 65536, max_workgroups);
+    hipLaunchKernelGGL(flip4_points_kernel, dim3(grid), dim3(FLIP_BLOCK), 0, s,
                        reinterpret_cast<const uint32_t*>(points), N, C, offsets, B, reinterpret_cast<uint32_t*>(out),
                        out_offsets);
     return hipGetLastError();

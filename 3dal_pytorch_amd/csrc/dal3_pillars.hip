@@ -5,9 +5,8 @@
 //
 // Voxelisation restates the reference's sequential loop as an ordered compaction. Every point gets the 32-bit key
 // sample * cells + cell (a point outside the range, with a NaN coordinate or outside every sample: B * cells, behind
-// every real key). A stable least-significant-digit radix sort of (key, point index) pairs, 8 bits a pass over chunks of
-// PL_CHUNK points (histogram, scan, scatter: dal3_motion.hip's passes, on dal3_block.h's tile step), leaves the points
-// of a cell together and by ascending index. Then
+// every real key). dal3_block.h's chunked radix sort of (key, point index) pairs, stable, leaves the points of a cell
+// together and by ascending index. Then
 //   heads   the first entry of a run is the cell's first point: flagged at its ORIGINAL position; every entry learns
 //           where its run starts (a binary search over the sorted keys);
 //   ranks   an exclusive scan of the flags in point order (per 256-point tile: count, scan of the counts, ballot ranks)
@@ -28,17 +27,10 @@ namespace {
 
 constexpr int PL_BLOCK = 256;
 constexpr int PL_WAVES = PL_BLOCK / 64;
-constexpr int PL_TILES = 16;
-constexpr int64_t PL_CHUNK = (int64_t)PL_BLOCK * PL_TILES;       // 4096 points
-constexpr int PL_SCAN_BLOCK = 1024;
-
-__host__ __device__ inline int64_t pl_chunks(int64_t N) { return (N + PL_CHUNK - 1) / PL_CHUNK; }
 __host__ __device__ inline int64_t pl_tiles(int64_t N) { return (N + PL_BLOCK - 1) / PL_BLOCK; }
 
 struct VoxWs {
-    int32_t* key[2];                            // (N) each: the pairs' keys, ping-pong
-    int32_t* pos[2];                            // (N) each: the pairs' point indices
-    int32_t* hist;                              // (256, chunks)
+    RadixBufs<int32_t> sort;                    // the (key, point index) pairs; both position buffers are the workspace's
     int32_t* start;                             // (N) where the run of sorted entry r starts
     int32_t* rank;                              // (N) by point: the head's rank among all heads, -1 for the others
     int32_t* tile;                              // (tiles) heads per 256-point tile, then their exclusive scan
@@ -48,9 +40,7 @@ struct VoxWs {
 
 inline VoxWs carve_vox(Carver& c, int64_t B, int64_t N) {
     VoxWs w;
-    for (int i = 0; i < 2; ++i) w.key[i] = c.take<int32_t>((size_t)N);
-    for (int i = 0; i < 2; ++i) w.pos[i] = c.take<int32_t>((size_t)N);
-    w.hist = c.take<int32_t>((size_t)256 * (size_t)pl_chunks(N));
+    w.sort = carve_radix<int32_t>(c, N, 2);
     w.start = c.take<int32_t>((size_t)N);
     w.rank = c.take<int32_t>((size_t)N);
     w.tile = c.take<int32_t>((size_t)pl_tiles(N));
@@ -65,12 +55,7 @@ __host__ __device__ inline int64_t vox_cells(const dal3_voxelize_args& a) {
 
 // the sample of point i by the device offsets: the last b with offsets[b] <= i, -1 when i is in no sample
 __device__ __forceinline__ int64_t sample_of(const int64_t* off, int64_t B, int64_t i) {
-    int64_t lo = 0, hi = B + 1;                 // first b with off[b] > i
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (off[mid] <= i) lo = mid + 1;
-        else hi = mid;
-    }
+    const int64_t lo = upper_bound(off, 0, B + 1, i);       // first b with off[b] > i
     return lo >= 1 && lo <= B ? lo - 1 : -1;
 }
 
@@ -92,54 +77,6 @@ __global__ __launch_bounds__(PL_BLOCK) void vox_keys_kernel(const dal3_voxelize_
     }
 }
 
-__global__ __launch_bounds__(PL_BLOCK) void vox_hist_kernel(const int32_t* key, int64_t N, int shift, int32_t* hist) {
-    __shared__ int32_t s_hist[256];
-    const int64_t chunks = pl_chunks(N);
-    for (int64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
-        s_hist[threadIdx.x] = 0;
-        __syncthreads();
-        const int64_t e0 = c * PL_CHUNK;
-        for (int r = 0; r < PL_TILES; ++r) {
-            const int64_t i = e0 + (int64_t)r * PL_BLOCK + threadIdx.x;
-            if (i < N) atomicAdd(&s_hist[(key[i] >> shift) & 255], 1);   // an integer count: the order does not matter
-        }
-        __syncthreads();
-        hist[(int64_t)threadIdx.x * chunks + c] = s_hist[threadIdx.x];
-        __syncthreads();
-    }
-}
-
-// in-place exclusive scan of n int32 by ONE workgroup
-__global__ __launch_bounds__(PL_SCAN_BLOCK) void vox_scan_kernel(int32_t* data, int64_t n, int64_t* total) {
-    __shared__ int64_t s_part[PL_SCAN_BLOCK];
-    const int64_t sum = block_scan_spans<PL_SCAN_BLOCK>(data, n, s_part);
-    if (total && threadIdx.x == PL_SCAN_BLOCK - 1) *total = sum;
-}
-
-// pos_in == nullptr: the first pass, the position is the index itself
-__global__ __launch_bounds__(PL_BLOCK) void vox_scatter_kernel(const int32_t* key_in, const int32_t* pos_in, int64_t N, int shift,
-                                                               const int32_t* hist, int32_t* key_out, int32_t* pos_out) {
-    __shared__ int32_t s_base[256];
-    __shared__ int32_t s_wave[PL_WAVES][256];
-    const int t = threadIdx.x;
-    const int64_t chunks = pl_chunks(N);
-    for (int64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
-        s_base[t] = hist[(int64_t)t * chunks + c];
-        const int64_t e0 = c * PL_CHUNK;
-        for (int r = 0; r < PL_TILES; ++r) {
-            const int64_t i = e0 + (int64_t)r * PL_BLOCK + t;
-            const bool live = i < N;
-            const int32_t k = live ? key_in[i] : 0;
-            const int64_t o = radix_tile_step<PL_WAVES>(live, (k >> shift) & 255, s_base, s_wave);
-            if (o >= 0 && o < N) {
-                key_out[o] = k;
-                pos_out[o] = pos_in ? pos_in[i] : (int32_t)i;
-            }
-            __syncthreads();
-        }
-    }
-}
-
 // per sorted entry: where its run starts, and the head's flag at the head's own point (rank 0 / -1 until vox_rank_kernel)
 __global__ __launch_bounds__(PL_BLOCK) void vox_heads_kernel(const int32_t* key, const int32_t* pos, int64_t N, int32_t none,
                                                              int32_t* start, int32_t* rank) {
@@ -152,12 +89,7 @@ __global__ __launch_bounds__(PL_BLOCK) void vox_heads_kernel(const int32_t* key,
             start[r] = (int32_t)r;
             continue;
         }
-        int64_t lo = 0, hi = r;                 // the first entry with this key
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (key[mid] < k) lo = mid + 1;
-            else hi = mid;
-        }
+        const int64_t lo = lower_bound(key, 0, r, k);      // the first entry with this key
         start[r] = (int32_t)lo;
         rank[p] = lo == r ? 0 : -1;
     }
@@ -237,13 +169,7 @@ __global__ __launch_bounds__(PL_BLOCK) void vox_fill_kernel(const dal3_voxelize_
         float* o = a.voxels + (slot * a.max_points + row) * a.C;
         for (int c = 0; c < a.C; ++c) o[c] = p[c];
         if (row == 0) {
-            int64_t lo = r, hi = a.N;           // the first entry behind the run
-            while (lo < hi) {
-                const int64_t mid = (lo + hi) >> 1;
-                if (key[mid] <= k) lo = mid + 1;
-                else hi = mid;
-            }
-            const int64_t n = lo - s;
+            const int64_t n = upper_bound(key, r, a.N, k) - s;      // the first entry behind the run
             a.num_points[slot] = (int32_t)(n < a.max_points ? n : a.max_points);
             const int64_t cell = k - b * cells;
             const int32_t x = (int32_t)(cell % a.grid[0]), y = (int32_t)((cell / a.grid[0]) % a.grid[1]);
@@ -257,11 +183,7 @@ __global__ __launch_bounds__(PL_BLOCK) void vox_fill_kernel(const dal3_voxelize_
     }
 }
 
-int64_t capped(int64_t want, int64_t max_workgroups) {
-    if (want < 1) want = 1;
-    if (want > 65535 * 16) want = 65535 * 16;
-    return max_workgroups > 0 && want > max_workgroups ? max_workgroups : want;
-}
+inline unsigned pl_grid(int64_t want, int64_t max_workgroups) { return grid_clamp(want, 65535 * 16, max_workgroups); }
 
 // ---------------------------------------------------------------------------------- pillar features
 // the packed blob, in floats (include/dal3.h DAL3_PILLAR_PACK_FLOATS)
@@ -501,28 +423,18 @@ hipError_t launch_voxelize(const dal3_voxelize_args* args, hipStream_t s) {
     Carver c(a.workspace, a.workspace_bytes);
     const VoxWs w = carve_vox(c, a.B, a.N);
     const int64_t cells = vox_cells(a), none = a.B * cells;
-    int bits = 0;
-    while (bits < 32 && ((int64_t)1 << bits) <= none) ++bits;
-    const int passes = (bits + 7) / 8;
+    const int passes = radix_passes(none);
     const dim3 blk(PL_BLOCK);
-    const dim3 g_pts((unsigned)capped(pl_tiles(a.N), a.max_workgroups)), g_chunk((unsigned)capped(pl_chunks(a.N), a.max_workgroups));
-    hipLaunchKernelGGL(vox_keys_kernel, g_pts, blk, 0, s, a, w.key[0]);
-    int cur = 0;
-    for (int pass = 0; pass < passes; ++pass) {
-        const int shift = 8 * pass;
-        hipLaunchKernelGGL(vox_hist_kernel, g_chunk, blk, 0, s, w.key[cur], a.N, shift, w.hist);
-        hipLaunchKernelGGL(vox_scan_kernel, dim3(1), dim3(PL_SCAN_BLOCK), 0, s, w.hist, (int64_t)256 * pl_chunks(a.N),
-                           (int64_t*)nullptr);
-        hipLaunchKernelGGL(vox_scatter_kernel, g_chunk, blk, 0, s, w.key[cur], pass ? w.pos[cur] : (const int32_t*)nullptr, a.N,
-                           shift, w.hist, w.key[cur ^ 1], w.pos[cur ^ 1]);
-        cur ^= 1;
-    }
-    hipLaunchKernelGGL(vox_heads_kernel, g_pts, blk, 0, s, w.key[cur], w.pos[cur], a.N, (int32_t)none, w.start, w.rank);
+    const dim3 g_pts(pl_grid(pl_tiles(a.N), a.max_workgroups));
+    hipLaunchKernelGGL(vox_keys_kernel, g_pts, blk, 0, s, a, w.sort.key[0]);
+    if ((e = radix_sort_pairs(w.sort, a.N, passes, pl_grid(radix_chunks(a.N), a.max_workgroups), s)) != hipSuccess) return e;
+    const int32_t *key = w.sort.key[passes & 1], *pos = w.sort.pos[passes & 1];
+    hipLaunchKernelGGL(vox_heads_kernel, g_pts, blk, 0, s, key, pos, a.N, (int32_t)none, w.start, w.rank);
     hipLaunchKernelGGL(vox_tile_count_kernel, g_pts, blk, 0, s, w.rank, a.N, w.tile);
-    hipLaunchKernelGGL(vox_scan_kernel, dim3(1), dim3(PL_SCAN_BLOCK), 0, s, w.tile, pl_tiles(a.N), w.total);
+    hipLaunchKernelGGL(scan_kernel<RADIX_SCAN_BLOCK>, dim3(1), dim3(RADIX_SCAN_BLOCK), 0, s, w.tile, pl_tiles(a.N), w.total);
     hipLaunchKernelGGL(vox_rank_kernel, g_pts, blk, 0, s, w.rank, a.N, w.tile);
     hipLaunchKernelGGL(vox_offsets_kernel, dim3(1), blk, 0, s, a, w);
-    hipLaunchKernelGGL(vox_fill_kernel, g_pts, blk, 0, s, a, w, w.key[cur], w.pos[cur]);
+    hipLaunchKernelGGL(vox_fill_kernel, g_pts, blk, 0, s, a, w, key, pos);
     return hipGetLastError();
 }
 
@@ -543,7 +455,7 @@ hipError_t launch_pillar_features(const dal3_pillar_feature_args* args, hipStrea
         if (e != hipSuccess) return e;
     }
     if (a.P <= 0) return hipSuccess;
-    const dim3 g((unsigned)capped((a.P + PL_WAVES - 1) / PL_WAVES, a.max_workgroups > 0 ? a.max_workgroups : 4096)), blk(PL_BLOCK);
+    const dim3 g(pl_grid((a.P + PL_WAVES - 1) / PL_WAVES, a.max_workgroups > 0 ? a.max_workgroups : 4096)), blk(PL_BLOCK);
     const bool two = a.max_points > 32;
     if (a.n_layers == 2) {
         if (two) hipLaunchKernelGGL((pillar_feature_kernel<1, 2>), g, blk, 0, s, a);
@@ -560,7 +472,7 @@ hipError_t launch_pillar_scatter(const float* features, const int32_t* coordinat
     const hipError_t e = launch_fill_words(canvas, (size_t)(canvas_B * c_out * ny * nx), 0, s);
     if (e != hipSuccess) return e;
     if (P <= 0) return hipSuccess;
-    hipLaunchKernelGGL(pillar_scatter_kernel, dim3((unsigned)capped((P * c_out + PL_BLOCK - 1) / PL_BLOCK, 0)), dim3(PL_BLOCK), 0, s,
+    hipLaunchKernelGGL(pillar_scatter_kernel, dim3(pl_grid((P * c_out + PL_BLOCK - 1) / PL_BLOCK, 0)), dim3(PL_BLOCK), 0, s,
                        features, coordinates, P, n_pillars, c_out, canvas, canvas_B, ny, nx);
     return hipGetLastError();
 }
@@ -568,7 +480,7 @@ hipError_t launch_pillar_scatter(const float* features, const int32_t* coordinat
 hipError_t launch_voxel_mean(const float* voxels, const int32_t* num_points, int64_t P, const int64_t* n_pillars, int max_points,
                              int C, float* out, hipStream_t s) {
     if (P <= 0) return hipSuccess;
-    hipLaunchKernelGGL(voxel_mean_kernel, dim3((unsigned)capped((P * C + PL_BLOCK - 1) / PL_BLOCK, 0)), dim3(PL_BLOCK), 0, s, voxels,
+    hipLaunchKernelGGL(voxel_mean_kernel, dim3(pl_grid((P * C + PL_BLOCK - 1) / PL_BLOCK, 0)), dim3(PL_BLOCK), 0, s, voxels,
                        num_points, P, n_pillars, max_points, C, out);
     return hipGetLastError();
 }

@@ -384,20 +384,18 @@ size_t track_match_workspace_bytes(int64_t K) {
 }
 
 hipError_t launch_track(const dal3_track_args* a, hipStream_t s) {
-    int64_t grid = a->S;
-    if (a->max_workgroups > 0 && grid > a->max_workgroups) grid = a->max_workgroups;
-    if (grid > 0) hipLaunchKernelGGL(track_kernel, dim3((unsigned)grid), dim3(TK_BLOCK), 0, s, *a);
+    const dim3 grid(grid_clamp(a->S, GRID_MAX, a->max_workgroups));
+    if (a->S > 0) hipLaunchKernelGGL(track_kernel, grid, dim3(TK_BLOCK), 0, s, *a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(track_finalize_kernel, dim3((unsigned)(grid > 0 ? grid : 1)), dim3(TK_BLOCK), 0, s, *a);
+    hipLaunchKernelGGL(track_finalize_kernel, grid, dim3(TK_BLOCK), 0, s, *a);
     return hipGetLastError();
 }
 
 hipError_t launch_track_match(const dal3_track_match_args* a, hipStream_t s) {
     if (a->K == 0 || a->F == 0) return hipSuccess;
-    const int64_t gk = (a->K + TK_BLOCK - 1) / TK_BLOCK;
-    hipLaunchKernelGGL(match_init_kernel, dim3((unsigned)(gk < 65535 ? gk : 65535)), dim3(TK_BLOCK), 0, s, *a);
-    const unsigned gf = (unsigned)(a->F < 65535 ? a->F : 65535);
+    hipLaunchKernelGGL(match_init_kernel, dim3(grid_clamp((a->K + TK_BLOCK - 1) / TK_BLOCK, 65535, 0)), dim3(TK_BLOCK), 0, s, *a);
+    const unsigned gf = grid_clamp(a->F, 65535, 0);
     hipLaunchKernelGGL(match_candidates_kernel, dim3(gf), dim3(TK_BLOCK), 0, s, *a);
     hipLaunchKernelGGL(match_fill_kernel, dim3(gf), dim3(TK_BLOCK), 0, s, *a);
     return hipGetLastError();

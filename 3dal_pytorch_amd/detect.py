@@ -126,7 +126,7 @@ class CenterHeadPost:
             if B == 0:
                 break
             nbytes = self._workspace_bytes(lib, B, H, W)
-            ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+            ws = _hip.workspace(nbytes, dev)
             a = _hip.CenterDecodeArgs(B=B, H=H, W=W, C=C, has_range=1 if self.range else 0, hm=_map_struct(maps["hm"]),
                                       reg=_map_struct(maps["reg"]), height=_map_struct(maps["height"]),
                                       dim=_map_struct(maps["dim"]), rot=_map_struct(maps["rot"]),

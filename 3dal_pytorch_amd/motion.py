@@ -74,7 +74,7 @@ def group_by_key(keys, T, key_base=None, key_bias=0, frame_offsets=None, out_cou
     E, T = int(keys.numel()), int(T)
     F = int(out_count.numel()) if out_count is not None else 0
     lib = _hip.lib()
-    ws = torch.empty(max(int(lib.dal3_group_workspace_bytes(E, T)), 4), dtype=torch.uint8, device=dev)
+    ws = _hip.workspace(lib.dal3_group_workspace_bytes(E, T), dev)
     group_start = torch.empty(T + 1, dtype=torch.int64, device=dev)
     entry = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
     n_groups = torch.empty(1, dtype=torch.int64, device=dev)
@@ -199,7 +199,7 @@ def classify(features, keep, model, max_workgroups=0):
     T = int(features.shape[0])
     w, b = model
     lib = _hip.lib()
-    ws = torch.empty(max(int(lib.dal3_motion_classify_workspace_bytes(T)), 4), dtype=torch.uint8, device=dev)
+    ws = _hip.workspace(lib.dal3_motion_classify_workspace_bytes(T), dev)
     n = max(T, 1)
     out = Classes(torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.uint8, device=dev),
                   torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev),

@@ -42,20 +42,6 @@ def _scores(t, n, device):
     return t.to(torch.float32).contiguous()
 
 
-def _host_offsets(seg_offsets, K):
-    if torch.is_tensor(seg_offsets):
-        if seg_offsets.is_cuda:
-            raise TypeError("seg_offsets must be on the host (a list, an array or a CPU tensor): the sizes of the outputs come "
-                            "from it, and reading a device tensor back would be the synchronisation this call avoids")
-        seg_offsets = seg_offsets.numpy()
-    off = np.ascontiguousarray(np.asarray(seg_offsets, dtype=np.int64).reshape(-1))
-    if off.size < 1:
-        raise ValueError("seg_offsets needs F + 1 entries")
-    if off[0] < 0 or off[-1] > K or np.any(np.diff(off) < 0):
-        raise ValueError(f"seg_offsets must be non-decreasing within [0, {K}]")
-    return off
-
-
 def keep_stride(seg_offsets, post_max):
     """the row length batched_nms gives `keep`: min(post_max or N, N), N the largest segment"""
     off = np.asarray(seg_offsets, dtype=np.int64).reshape(-1)
@@ -80,7 +66,7 @@ def batched_nms(boxes, scores, seg_offsets, mode, thresh, pre_max=0, post_max=0,
     boxes = _boxes(boxes, "boxes")
     K, cols = boxes.shape
     scores = _scores(scores, K, boxes.device)
-    off = _host_offsets(seg_offsets, K)
+    off = _hip.host_offsets(seg_offsets, K, "seg_offsets", "the sizes of the outputs come", "F")
     F = off.size - 1
     pre_max, post_max = int(pre_max or 0), int(post_max or 0)
     if pre_max < 0 or post_max < 0:
@@ -109,7 +95,7 @@ def batched_nms(boxes, scores, seg_offsets, mode, thresh, pre_max=0, post_max=0,
         off_dev = seg_offsets_device if seg_offsets_device is not None else torch.from_numpy(off).to(dev)
         lib = _hip.lib()
         nbytes = lib.dal3_nms_workspace_bytes(K, _F64[boxes.dtype])
-        ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+        ws = _hip.workspace(nbytes, dev)
         a = _hip.NmsArgs(F=F, K=K, seg_offsets=_hip.ptr(off_dev), seg_offsets_host=off.ctypes.data, seg_count=_hip.ptr(seg_count),
                          boxes=_hip.ptr(boxes), scores=_hip.ptr(scores), box_stride=boxes.stride(0) if K else cols, yaw_col=yaw,
                          boxes_f64=_F64[boxes.dtype], mode=MODES[mode], thresh=float(thresh), pre_max=pre_max,

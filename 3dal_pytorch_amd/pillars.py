@@ -26,20 +26,6 @@ def grid_size(voxel_size, pc_range):
     return np.round((r[3:] - r[:3]) / v).astype(np.int64)
 
 
-def _host_offsets(point_offsets, N):
-    if torch.is_tensor(point_offsets):
-        if point_offsets.is_cuda:
-            raise TypeError("point_offsets must be on the host (a list, an array or a CPU tensor): the capacity of the outputs "
-                            "comes from it, and reading a device tensor back would be the synchronisation this call avoids")
-        point_offsets = point_offsets.numpy()
-    off = np.ascontiguousarray(np.asarray(point_offsets, dtype=np.int64).reshape(-1))
-    if off.size < 1:
-        raise ValueError("point_offsets needs B + 1 entries")
-    if off[0] < 0 or off[-1] > N or np.any(np.diff(off) < 0):
-        raise ValueError(f"point_offsets must be non-decreasing within [0, {N}]")
-    return off
-
-
 def capacity_of(point_offsets, max_voxels, grid):
     """rows the packed outputs need: the samples' min(points, max_voxels, cells) summed"""
     n = np.diff(np.asarray(point_offsets, dtype=np.int64).reshape(-1))
@@ -53,7 +39,7 @@ def _alloc(allocator, nbytes, device):
         if ws.dtype != torch.uint8 or ws.numel() < nbytes or not ws.is_contiguous():
             raise ValueError(f"the allocator must return a contiguous uint8 tensor of at least {nbytes} bytes")
         return ws
-    return torch.empty(max(nbytes, 8), dtype=torch.uint8, device=device)
+    return _hip.workspace(nbytes, device)
 
 
 def _device_ints(t, what, dtype, count, device):
@@ -111,7 +97,7 @@ def voxelize(points, point_offsets, voxel_size, pc_range, max_points, max_voxels
     N, C = points.shape
     if N and (points.stride(1) != 1 or points.stride(0) < C):
         points = points.contiguous()
-    off = _host_offsets(point_offsets, N)
+    off = _hip.host_offsets(point_offsets, N, "point_offsets", "the capacity of the outputs comes", "B")
     B = off.size - 1
     max_points, max_voxels = int(max_points), int(max_voxels)
     if max_points < 1 or max_voxels < 1:
@@ -168,7 +154,7 @@ def double_flip(points, point_offsets, point_offsets_device=None, *, max_workgro
         raise TypeError(f"points must be float32, got {points.dtype}")
     points = points.contiguous()
     N, C = points.shape
-    off = _host_offsets(point_offsets, N)
+    off = _hip.host_offsets(point_offsets, N, "point_offsets", "the capacity of the outputs comes", "B")
     B, dev = off.size - 1, points.device
     n = np.diff(off)
     out_off = np.empty(4 * B + 1, np.int64)

@@ -213,7 +213,7 @@ def _mask_and_gather(pts, logits, n_obj, n_ch, model=None):
         idx = torch.empty((B, n_obj), dtype=torch.int32, device=pts.device)
         obj = torch.empty((B, n_obj, n_ch), dtype=torch.float32, device=pts.device)
         need = lib.dal3_gather_workspace_bytes(B, N)
-        ws = torch.empty(max(int(need), 8), dtype=torch.uint8, device=pts.device)
+        ws = _hip.workspace(need, pts.device)
         # a fresh draw per training step, as the reference's np.random gives: the key carries a draw counter that
         # lives in DEVICE memory and is bumped by an ordinary op — captured into a hipGraph (graph.CapturedTrainStep)
         # it still advances on every replay, where a host-computed seed would be frozen into the kernel's arguments

@@ -170,7 +170,7 @@ def track_sequences(seq_offsets, frame_offsets, ct, tracking, label, score, max_
         capacity = min(b.capacity(max_age), _hip.TRACK_MAX_CAPACITY)
     cap = int(capacity)
     lib = _hip.lib()
-    ws = torch.empty(max(int(lib.dal3_track_workspace_bytes(S, K, cap)), 4), dtype=torch.uint8, device=dev)
+    ws = _hip.workspace(lib.dal3_track_workspace_bytes(S, K, cap), dev)
     box_ids = torch.empty(max(K, 1), dtype=torch.int32, device=dev)
     tracking_ids = torch.empty(max(K, 1), dtype=torch.int64, device=dev)
     out_count = torch.empty(max(F, 1), dtype=torch.int32, device=dev)
@@ -199,7 +199,7 @@ def match_ground_truth(result, boxes, gt_offsets, gt_boxes, thr=0.75):
     dev = boxes.device
     F, K = result.out_count.numel(), boxes.shape[0]
     lib = _hip.lib()
-    ws = torch.empty(max(int(lib.dal3_track_match_workspace_bytes(K)), 4), dtype=torch.uint8, device=dev)
+    ws = _hip.workspace(lib.dal3_track_match_workspace_bytes(K), dev)
     mf = torch.full((max(K, 1),), -1, dtype=torch.int32, device=dev)
     mo = torch.full((max(K, 1),), -1, dtype=torch.int32, device=dev)
     gt = gt_boxes if gt_boxes.numel() else torch.zeros((1, 7), dtype=torch.float32, device=dev)

@@ -86,6 +86,25 @@ def test_group_by_key_at_the_tile_chunk_and_pass_edges(E, T):
         assert int(g.n_groups.item()) == int(keys.max()) + 1
 
 
+@pytest.mark.parametrize("E", (257, 4097))
+def test_group_by_key_at_four_passes(E):
+    """T = 2^24 (DAL3_MAX_ITEMS) is the one T whose keys take four radix passes: the positions swap buffers an even number
+    of times and must still end in `entry`. The keys differ in every digit; E is just past the tile and just past the
+    chunk. Kept apart from the edges above: group_start is 128 MiB at this T."""
+    T = 1 << 24
+    rng = np.random.default_rng(E)
+    keys = np.array([0, 255, 256, 65536, T - 1], np.int64)[rng.integers(0, 5, E)]
+    want = np.argsort(keys, kind="stable").astype(np.int32)
+    sizes = np.bincount(keys, minlength=T)
+    d = dev(keys)
+    for wg in (0, 1):
+        g = motion.group_by_key(d, T, max_workgroups=wg)
+        g.check()
+        assert np.array_equal(g.entry.cpu().numpy(), want), wg
+        assert np.array_equal(np.diff(g.group_start.cpu().numpy()), sizes), wg
+        assert int(g.n_groups.item()) == int(keys.max()) + 1
+
+
 @pytest.mark.parametrize("T", (1023, 1024, 1025, 2049))
 def test_classify_ids_at_the_compaction_tile_edges(T):
     """a compaction tile is 1024 groups, ranked 256 at a time: one tile short of full, full, one group into the second,

@@ -1,6 +1,7 @@
-"""The six run-kernel workspace sizes, pinned. Each dal3_*_workspace_bytes is its carve (dal3_block.h's Carver) run on a
+"""The seven run-kernel workspace sizes, pinned. Each dal3_*_workspace_bytes is its carve (dal3_block.h's Carver) run on a
 null base; the numbers below are what the closed formulas returned before the carves replaced them, recorded from that
-library over the grid, so a carve that drifts from the layout the kernels were written against fails here. No GPU."""
+library over the grid (VOXELIZE: from the library before its sort's buffers became dal3_block.h's carve), so a carve
+that drifts from the layout the kernels were written against fails here. No GPU."""
 import importlib
 
 hip = importlib.import_module("3dal_pytorch_amd._hip")
@@ -50,6 +51,11 @@ NMS = {                                                         # [boxes_f64] ->
     1: (0, 1536, 5888, 5888, 7424, 376832, 376832, 378368, 6029312, 92001536),
 }
 DECODE = (256, 256, 3584)
+VOXELIZE = {                                                    # [B] -> per N
+    1: (512, 3328, 3328, 3328, 4864, 100096, 100096, 102656, 1590784, 24268800),
+    2: (512, 3328, 3328, 3328, 4864, 100096, 100096, 102656, 1590784, 24268800),
+    300: (2816, 5632, 5632, 5632, 7168, 102400, 102400, 104960, 1593088, 24271104),
+}
 
 
 def test_workspace_sizes_are_the_recorded_ones():
@@ -64,6 +70,8 @@ def test_workspace_sizes_are_the_recorded_ones():
         for S in SEQS:
             for c, cap in enumerate(CAPACITIES):
                 assert lib.dal3_track_workspace_bytes(S, n, cap) == TRACK[S][i][c], (S, n, cap)
+        for B in VOXELIZE:
+            assert lib.dal3_voxelize_workspace_bytes(B, n) == VOXELIZE[B][i], (B, n)
     for i, (B, H, W) in enumerate(MAPS):
         assert lib.dal3_center_decode_workspace_bytes(B, H, W) == DECODE[i], (B, H, W)
 
