@@ -232,6 +232,41 @@ class Conv2dArgs(C.Structure):
                 ("H", C.c_int64), ("W", C.c_int64), ("x", Map), ("y", Map), ("packed", vp)]
 
 
+SP_OVERFLOW, SP_BAD_COORD, SP_DUPLICATE, SP_BAD_WEIGHT = 256, 512, 1024, 2048
+_i3 = C.c_int32 * 3
+
+
+class SpSortArgs(C.Structure):
+    """dal3_sp_sort_args"""
+    _fields_ = [("B", C.c_int64), ("shape", _i3), ("reserved", C.c_int32), ("capacity", C.c_int64), ("n", vp), ("indices", vp),
+                ("sorted_key", vp), ("sorted_pos", vp), ("status", vp), ("max_workgroups", C.c_int64), ("workspace", vp),
+                ("workspace_bytes", C.c_size_t)]
+
+
+class SpDownsampleArgs(C.Structure):
+    """dal3_sp_downsample_args"""
+    _fields_ = [("B", C.c_int64), ("in_shape", _i3), ("out_shape", _i3), ("kernel", _i3), ("stride", _i3), ("padding", _i3),
+                ("reserved", C.c_int32), ("in_capacity", C.c_int64), ("n_in", vp), ("in_indices", vp), ("out_capacity", C.c_int64),
+                ("out_indices", vp), ("out_key", vp), ("n_out", vp), ("status", vp), ("max_workgroups", C.c_int64),
+                ("workspace", vp), ("workspace_bytes", C.c_size_t)]
+
+
+class SpTableArgs(C.Structure):
+    """dal3_sp_table_args"""
+    _fields_ = [("B", C.c_int64), ("in_shape", _i3), ("out_shape", _i3), ("kernel", _i3), ("stride", _i3), ("padding", _i3),
+                ("reserved", C.c_int32), ("out_capacity", C.c_int64), ("n_out", vp), ("out_indices", vp), ("in_capacity", C.c_int64),
+                ("n_in", vp), ("in_key", vp), ("in_pos", vp), ("table", vp), ("max_workgroups", C.c_int64)]
+
+
+class SpConvArgs(C.Structure):
+    """dal3_sp_conv_args"""
+    _fields_ = [("taps", C.c_int32), ("c_in", C.c_int32), ("c_out", C.c_int32), ("relu", C.c_int32), ("center_tap", C.c_int32),
+                ("reserved", C.c_int32), ("in_capacity", C.c_int64), ("x", vp), ("out_capacity", C.c_int64), ("n_out", vp),
+                ("table", vp), ("packed", vp), ("residual", vp), ("y", vp), ("canvas", vp), ("out_indices", vp),
+                ("canvas_B", C.c_int64), ("canvas_shape", _i3), ("reserved2", C.c_int32), ("status", vp),
+                ("max_workgroups", C.c_int64)]
+
+
 # every symbol include/dal3.h declares: (restype, argtypes)
 _i, _i64, _u64, _sz = C.c_int, C.c_int64, C.c_uint64, C.c_size_t
 SIGNATURES = {
@@ -293,6 +328,14 @@ SIGNATURES = {
     "dal3_conv2d_pack_floats": (_sz, [_i, _i, _i]),
     "dal3_conv2d_pack": (_i, [C.POINTER(Layer), _i, C.c_double, vp, vp]),
     "dal3_conv2d": (_i, [C.POINTER(Conv2dArgs), vp]),
+    "dal3_sp_sort_workspace_bytes": (_sz, [_i64]),
+    "dal3_sp_sort": (_i, [C.POINTER(SpSortArgs), vp]),
+    "dal3_sp_downsample_workspace_bytes": (_sz, [_i64, _i]),
+    "dal3_sp_downsample": (_i, [C.POINTER(SpDownsampleArgs), vp]),
+    "dal3_sp_table": (_i, [C.POINTER(SpTableArgs), vp]),
+    "dal3_sp_conv_pack_floats": (_sz, [_i, _i, _i]),
+    "dal3_sp_conv_pack": (_i, [C.POINTER(Layer), _i, C.c_double, vp, vp, vp]),
+    "dal3_sp_conv": (_i, [C.POINTER(SpConvArgs), vp]),
     "dal3_crop_workspace_bytes": (_sz, [_i64, _i64]),
     "dal3_crop_count": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, _sz, vp]),
     "dal3_crop_fill": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, vp, vp, vp, _i64, vp, _sz, vp]),

@@ -1359,6 +1359,141 @@ extern "C" int dal3_conv2d(const dal3_conv2d_args* args, dal3_stream stream) {
     return 0;
 }
 
+// ---------------------------------------------------------------------------------- the sparse 3-D middle
+static int sp_grid_ok(const char* who, int64_t B, const int32_t* shape) {
+    if (B < 1 || B > 65535) return fail(DAL3_EINVAL, "%s: bad B (1 .. 65535)", who);
+    for (int j = 0; j < 3; ++j)
+        if (shape[j] < 1 || shape[j] > 65536) return fail(DAL3_EINVAL, "%s: every axis of a grid needs 1 .. 65536 cells", who);
+    const int64_t cells = (int64_t)shape[0] * shape[1] * shape[2];
+    if (cells >= 2147483647 || cells >= 2147483647 / B)
+        return fail(DAL3_EINVAL, "%s: the (sample, cell) key needs B * D * H * W < 2^31 - 1 (split the batch)", who);
+    return 0;
+}
+
+static int sp_window_ok(const char* who, const int32_t* in, const int32_t* out, const int32_t* k, const int32_t* s, const int32_t* p) {
+    for (int j = 0; j < 3; ++j) {
+        if (k[j] < 1 || k[j] > 3 || s[j] < 1 || s[j] > 3 || p[j] < 0 || p[j] > 2)
+            return fail(DAL3_EINVAL, "%s: kernel 1 .. 3, stride 1 .. 3, padding 0 .. 2 per axis", who);
+        if (in[j] + 2 * p[j] < k[j] || out[j] != (in[j] + 2 * p[j] - k[j]) / s[j] + 1)
+            return fail(DAL3_EINVAL, "%s: out_shape[%d] must be floor((in + 2 padding - kernel) / stride) + 1", who, j);
+    }
+    return 0;
+}
+
+static bool sp_cap_ok(int64_t c) { return c >= 0 && c <= ((int64_t)1 << 28); }
+
+extern "C" size_t dal3_sp_sort_workspace_bytes(int64_t capacity) { return sp_cap_ok(capacity) ? sp_sort_workspace_bytes(capacity) : 0; }
+
+extern "C" int dal3_sp_sort(const dal3_sp_sort_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "sp_sort: null args");
+    const dal3_sp_sort_args& a = *args;
+    TRY(sp_grid_ok("sp_sort", a.B, a.shape));
+    if (!sp_cap_ok(a.capacity) || a.max_workgroups < 0 || a.reserved) return fail(DAL3_EINVAL, "sp_sort: bad capacity / max_workgroups / reserved");
+    if (!a.status) return fail(DAL3_EINVAL, "sp_sort: null status");
+    if (a.capacity > 0) {
+        if (!a.indices || !a.sorted_key || !a.sorted_pos || !a.workspace) return fail(DAL3_EINVAL, "sp_sort: null indices / sorted_key / sorted_pos / workspace");
+        if (a.workspace_bytes < sp_sort_workspace_bytes(a.capacity)) return fail(DAL3_EWORKSPACE, "sp_sort: workspace too small (dal3_sp_sort_workspace_bytes)");
+        if (reinterpret_cast<uintptr_t>(a.workspace) & 7) return fail(DAL3_EINVAL, "sp_sort: workspace must be 8-byte aligned");
+    }
+    HIP_TRY(launch_sp_sort(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+extern "C" size_t dal3_sp_downsample_workspace_bytes(int64_t in_capacity, int candidates) {
+    if (!sp_cap_ok(in_capacity) || candidates < 1 || candidates > 27 || !sp_cap_ok(in_capacity * candidates)) return 0;
+    return sp_downsample_workspace_bytes(in_capacity, candidates);
+}
+
+extern "C" int dal3_sp_downsample(const dal3_sp_downsample_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "sp_downsample: null args");
+    const dal3_sp_downsample_args& a = *args;
+    TRY(sp_grid_ok("sp_downsample", a.B, a.in_shape));
+    TRY(sp_window_ok("sp_downsample", a.in_shape, a.out_shape, a.kernel, a.stride, a.padding));
+    TRY(sp_grid_ok("sp_downsample", a.B, a.out_shape));
+    const int cand = sp_candidates(a.kernel, a.stride);
+    if (!sp_cap_ok(a.in_capacity) || !sp_cap_ok(a.out_capacity) || !sp_cap_ok(a.in_capacity * cand) || a.max_workgroups < 0 || a.reserved)
+        return fail(DAL3_EINVAL, "sp_downsample: bad capacity / max_workgroups / reserved");
+    if (!a.status || !a.n_out) return fail(DAL3_EINVAL, "sp_downsample: null status / n_out");
+    if (a.out_capacity > 0 && (!a.out_indices || !a.out_key)) return fail(DAL3_EINVAL, "sp_downsample: null out_indices / out_key");
+    if (a.in_capacity > 0) {
+        if (!a.in_indices || !a.workspace) return fail(DAL3_EINVAL, "sp_downsample: null in_indices / workspace");
+        if (a.workspace_bytes < sp_downsample_workspace_bytes(a.in_capacity, cand))
+            return fail(DAL3_EWORKSPACE, "sp_downsample: workspace too small (dal3_sp_downsample_workspace_bytes)");
+        if (reinterpret_cast<uintptr_t>(a.workspace) & 7) return fail(DAL3_EINVAL, "sp_downsample: workspace must be 8-byte aligned");
+    }
+    HIP_TRY(launch_sp_downsample(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+extern "C" int dal3_sp_table(const dal3_sp_table_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "sp_table: null args");
+    const dal3_sp_table_args& a = *args;
+    TRY(sp_grid_ok("sp_table", a.B, a.in_shape));
+    TRY(sp_window_ok("sp_table", a.in_shape, a.out_shape, a.kernel, a.stride, a.padding));
+    TRY(sp_grid_ok("sp_table", a.B, a.out_shape));
+    if (!sp_cap_ok(a.in_capacity) || !sp_cap_ok(a.out_capacity) || !sp_cap_ok(a.out_capacity * 27) || a.max_workgroups < 0 || a.reserved)
+        return fail(DAL3_EINVAL, "sp_table: bad capacity / max_workgroups / reserved");
+    if (a.out_capacity > 0 && (!a.out_indices || !a.table)) return fail(DAL3_EINVAL, "sp_table: null out_indices / table");
+    if (a.out_capacity > 0 && a.in_capacity > 0 && !a.in_key) return fail(DAL3_EINVAL, "sp_table: null in_key");
+    HIP_TRY(launch_sp_table(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+static bool sp_channels_ok(int c_in, int c_out) {
+    const bool in = (c_in >= 1 && c_in <= 8) || c_in == 16 || c_in == 32 || c_in == 64 || c_in == 128;
+    return in && (c_out == 16 || c_out == 32 || c_out == 64 || c_out == 128);
+}
+
+extern "C" size_t dal3_sp_conv_pack_floats(int taps, int c_in, int c_out) {
+    if (taps < 1 || taps > 27 || !sp_channels_ok(c_in, c_out)) return 0;
+    return sp_conv_pack_floats(taps, c_in, c_out);
+}
+
+extern "C" int dal3_sp_conv_pack(const dal3_layer* layer, int taps, double eps, float* out, int32_t* status, dal3_stream stream) {
+    if (!layer || !out) return fail(DAL3_EINVAL, "sp_conv_pack: null layer / out");
+    if (taps < 1 || taps > 27) return fail(DAL3_EINVAL, "sp_conv_pack: %d taps (1 .. 27)", taps);
+    if (!sp_channels_ok(layer->c_in, layer->c_out))
+        return fail(DAL3_EINVAL, "sp_conv_pack: %d -> %d channels (c_in 1 .. 8, 16, 32, 64, 128; c_out 16, 32, 64, 128)", (int)layer->c_in,
+                    (int)layer->c_out);
+    if (!layer->weight) return fail(DAL3_EINVAL, "sp_conv_pack: null weight");
+    const bool bn = layer->bn_weight || layer->bn_bias || layer->bn_mean || layer->bn_var;
+    if (bn && !(layer->bn_weight && layer->bn_bias && layer->bn_mean && layer->bn_var))
+        return fail(DAL3_EINVAL, "sp_conv_pack: a BatchNorm needs all four of weight, bias, mean and var");
+    if (bn && !(eps > 0.0)) return fail(DAL3_EINVAL, "sp_conv_pack: bad eps (> 0)");
+    if (reinterpret_cast<uintptr_t>(out) & 15) return fail(DAL3_EINVAL, "sp_conv_pack: out must be 16-byte aligned");
+    HIP_TRY(launch_sp_conv_pack(layer, taps, eps, out, status, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+extern "C" int dal3_sp_conv(const dal3_sp_conv_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "sp_conv: null args");
+    const dal3_sp_conv_args& a = *args;
+    if (a.taps < 1 || a.taps > 27 || !sp_channels_ok(a.c_in, a.c_out))
+        return fail(DAL3_EINVAL, "sp_conv: %d taps, %d -> %d channels (taps 1 .. 27; c_in 1 .. 8, 16, 32, 64, 128; c_out 16, 32, 64, 128)", (int)a.taps,
+                    (int)a.c_in, (int)a.c_out);
+    if ((a.relu != 0 && a.relu != 1) || a.center_tap < -1 || a.center_tap >= a.taps || a.max_workgroups < 0 || a.reserved || a.reserved2)
+        return fail(DAL3_EINVAL, "sp_conv: bad relu (0 or 1) / center_tap (-1 .. taps - 1) / max_workgroups (>= 0) / reserved");
+    if (!sp_cap_ok(a.in_capacity) || !sp_cap_ok(a.out_capacity) || !sp_cap_ok(a.out_capacity * 27)) return fail(DAL3_EINVAL, "sp_conv: bad capacity");
+    if (!a.status) return fail(DAL3_EINVAL, "sp_conv: null status");
+    if (!a.packed || (reinterpret_cast<uintptr_t>(a.packed) & 15)) return fail(DAL3_EINVAL, "sp_conv: packed is null or not 16-byte aligned");
+    if (a.canvas) {
+        if (!a.out_indices && a.out_capacity > 0) return fail(DAL3_EINVAL, "sp_conv: a canvas needs out_indices");
+        if (a.canvas_B < 1 || a.canvas_B > 65535 || a.canvas_shape[0] < 1 || a.canvas_shape[1] < 1 || a.canvas_shape[2] < 1 ||
+            a.canvas_shape[0] > 65536 || a.canvas_shape[1] > 65536 || a.canvas_shape[2] > 65536 ||
+            a.canvas_B * a.c_out * a.canvas_shape[0] * a.canvas_shape[1] * a.canvas_shape[2] > ((int64_t)1 << 40))
+            return fail(DAL3_EINVAL, "sp_conv: bad canvas shape (canvas_B, D, H, W >= 1)");
+    } else if (a.out_capacity > 0 && !a.y) {
+        return fail(DAL3_EINVAL, "sp_conv: no output (y and canvas are NULL)");
+    }
+    if (a.out_capacity > 0) {
+        if (!a.table || (a.in_capacity > 0 && !a.x)) return fail(DAL3_EINVAL, "sp_conv: null table / x");
+        if (((a.c_in > 8 ? reinterpret_cast<uintptr_t>(a.x) : 0) | reinterpret_cast<uintptr_t>(a.y) | reinterpret_cast<uintptr_t>(a.residual)) & 15)
+            return fail(DAL3_EINVAL, "sp_conv: x (with 16 or more channels), y and residual must be 16-byte aligned");
+    }
+    HIP_TRY(launch_sp_conv(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 extern "C" size_t dal3_crop_workspace_bytes(int64_t K_total, int64_t max_points_per_frame) {
     if (K_total <= 0 || max_points_per_frame < 0) return 0;
     return crop_workspace_bytes(K_total, max_points_per_frame);

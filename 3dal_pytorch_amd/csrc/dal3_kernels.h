@@ -305,6 +305,16 @@ hipError_t launch_voxel_mean(const float* voxels, const int32_t* num_points, int
 size_t conv2d_pack_floats(int kind, int c_in, int c_out);
 hipError_t launch_conv2d_pack(const dal3_layer* layer, int kind, double eps, float* out, hipStream_t s);
 hipError_t launch_conv2d(const dal3_conv2d_args* a, hipStream_t s);
+// the VoxelNet detector's sparse 3-D middle (dal3_spconv.hip): site bookkeeping on the chunked radix sort, gather-GEMM convolutions
+size_t sp_sort_workspace_bytes(int64_t capacity);
+hipError_t launch_sp_sort(const dal3_sp_sort_args* a, hipStream_t s);
+int sp_candidates(const int32_t* kernel, const int32_t* stride);
+size_t sp_downsample_workspace_bytes(int64_t in_capacity, int candidates);
+hipError_t launch_sp_downsample(const dal3_sp_downsample_args* a, hipStream_t s);
+hipError_t launch_sp_table(const dal3_sp_table_args* a, hipStream_t s);
+size_t sp_conv_pack_floats(int taps, int c_in, int c_out);
+hipError_t launch_sp_conv_pack(const dal3_layer* layer, int taps, double eps, float* out, int32_t* status, hipStream_t s);
+hipError_t launch_sp_conv(const dal3_sp_conv_args* a, hipStream_t s);
 hipError_t launch_points_in_boxes(const void* points, int points_f64, int64_t P, int64_t stride, const double* planes,
                                   int K, int f32_math, uint8_t* inside, hipStream_t s);
 hipError_t launch_writeback(const double* final_boxes, const int32_t* final_idx, const double* pose_best,

@@ -1,23 +1,26 @@
-"""CenterPoint's PointPillars detector, eval mode, on the GPU: `PointPillars` (det3d/models/detectors/point_pillars.py,
-single_stage.py) under the reference's name, constructor signature and state_dict keys (`reader.*`, `neck.*`,
-`bbox_head.*`; the scatter backbone has no parameters), built from the `model` dict of a config such as
-configs/waymo/pp/waymo_centerpoint_pp_two_pfn_stride1_3x.py.
+"""CenterPoint's one-stage detectors, eval mode, on the GPU: `PointPillars` (det3d/models/detectors/point_pillars.py,
+single_stage.py) and `VoxelNet` (det3d/models/detectors/voxelnet.py) under the reference's names, constructor signatures
+and state_dict keys (`reader.*`, `backbone.*`, `neck.*`, `bbox_head.*`; the scatter backbone and the voxel-mean reader have
+no parameters), built from the `model` dict of a config such as configs/waymo/pp/waymo_centerpoint_pp_two_pfn_stride1_3x.py
+or configs/waymo/voxelnet/waymo_centerpoint_voxelnet_3x.py.
 
 `forward(example, return_loss=False)` takes the reference's collated example (voxels, coordinates, num_points, num_voxels,
 shape, metadata) and returns `CenterHead.predict`'s list. `detect(points, point_offsets, metadata=None)` starts from the
 raw sweep instead: voxelise -> pillar features into the canvas -> RPN -> CenterHead -> decode + NMS, everything enqueued on
 the current stream; the read-back of the kept boxes inside `predict` is the only host synchronisation. A `test_cfg` with
 `double_flip` (test-time augmentation) is served by both: `forward` takes the reference's batch of four views per sample,
-`detect` makes the views itself. The loss is not built: `return_loss=True` is refused.
+`detect` makes the views itself. The loss is not built: `return_loss=True` is refused. `VoxelNet` has the same two doors
+with the 3-D grid, VoxelFeatureExtractorV3 and the sparse middle (sparse.SpMiddleResNetFHD) in front of the neck; its
+second stage (`forward_two_stage`) is not built.
 """
 import torch
 from torch import nn
 
-from . import pillars, rpn
+from . import pillars, rpn, sparse
 from .detect import CenterHeadPost, _get
 
-READERS = {"PillarFeatureNet": pillars.PillarFeatureNet}
-BACKBONES = {"PointPillarsScatter": pillars.PointPillarsScatter}
+READERS = {"PillarFeatureNet": pillars.PillarFeatureNet, "VoxelFeatureExtractorV3": pillars.VoxelFeatureExtractorV3}
+BACKBONES = {"PointPillarsScatter": pillars.PointPillarsScatter, "SpMiddleResNetFHD": sparse.SpMiddleResNetFHD}
 NECKS = {"RPN": rpn.RPN}
 HEADS = {"CenterHead": rpn.CenterHead}
 
@@ -32,12 +35,11 @@ def _build(cfg, table, what):
     return table[kind](**args)
 
 
-class PointPillars(nn.Module):
-    """reader / backbone / neck / bbox_head: the config's dicts (with `type`) or modules. max_points / max_voxels: the
-    config's voxel_generator (max_points_in_voxel, max_voxel_num), which `detect` voxelises with."""
+class SingleStageDetector(nn.Module):
+    """what the one-stage detectors share (det3d/models/detectors/single_stage.py): the four stages built from the config's
+    dicts (with `type`) or given as modules, the checkpoint door, and the start of `detect`."""
 
-    def __init__(self, reader, backbone, neck, bbox_head, train_cfg=None, test_cfg=None, pretrained=None, *, max_points=20,
-                 max_voxels=60000):
+    def __init__(self, reader, backbone, neck, bbox_head, train_cfg, test_cfg, max_points, max_voxels, voxel_size, pc_range):
         super().__init__()
         self.reader = _build(reader, READERS, "reader")
         self.backbone = _build(backbone, BACKBONES, "backbone")
@@ -45,13 +47,8 @@ class PointPillars(nn.Module):
         self.bbox_head = _build(bbox_head, HEADS, "bbox_head")
         self.train_cfg, self.test_cfg = train_cfg, test_cfg
         self.max_points, self.max_voxels = int(max_points), int(max_voxels)
-        if isinstance(reader, dict):
-            self.voxel_size, self.pc_range = list(reader["voxel_size"]), list(reader["pc_range"])
-        else:
-            self.voxel_size, self.pc_range = None, None
+        self.voxel_size, self.pc_range = voxel_size, pc_range
         self.last = None
-        if pretrained is not None:
-            self.init_weights(pretrained)
 
     @property
     def with_neck(self):
@@ -62,15 +59,47 @@ class PointPillars(nn.Module):
         ckpt = torch.load(pretrained, map_location="cpu")
         self.load_state_dict(ckpt.get("state_dict", ckpt), strict=True)
 
+    def _refuse_loss(self, return_loss):
+        if return_loss:
+            raise NotImplementedError(f"{type(self).__name__}.forward(return_loss=True): the detector's loss is not built; this is "
+                                      "the eval-mode detector (call with return_loss=False)")
+
+    def _voxelize(self, points, point_offsets, point_offsets_device):
+        """the start of `detect`: the checks, the four flipped views of test_cfg.double_flip, the voxelisation (kept in `last`)"""
+        if self.training:
+            raise RuntimeError("detect is the eval-mode route: call .eval()")
+        if self.voxel_size is None:
+            raise RuntimeError("detect needs the reader's voxel_size and pc_range: build the model from the config's dicts")
+        if _get(self.test_cfg, "double_flip", False):
+            # four views per sample (the sweep, y = -y, x = -x, both), merged again by DoubleFlipPost inside predict
+            points, point_offsets, point_offsets_device = pillars.double_flip(points, point_offsets, point_offsets_device)
+        r = pillars.voxelize(points, point_offsets, self.voxel_size, self.pc_range, self.max_points, self.max_voxels,
+                             point_offsets_device=point_offsets_device)
+        self.last = r
+        return r
+
+    to_prediction = staticmethod(CenterHeadPost.to_prediction)
+
+
+class PointPillars(SingleStageDetector):
+    """reader / backbone / neck / bbox_head: the config's dicts (with `type`) or modules. max_points / max_voxels: the
+    config's voxel_generator (max_points_in_voxel, max_voxel_num), which `detect` voxelises with."""
+
+    def __init__(self, reader, backbone, neck, bbox_head, train_cfg=None, test_cfg=None, pretrained=None, *, max_points=20,
+                 max_voxels=60000):
+        super().__init__(reader, backbone, neck, bbox_head, train_cfg, test_cfg, max_points, max_voxels, None, None)
+        if isinstance(reader, dict):
+            self.voxel_size, self.pc_range = list(reader["voxel_size"]), list(reader["pc_range"])
+        if pretrained is not None:
+            self.init_weights(pretrained)
+
     def extract_feat(self, data):
         features = self.reader(data["features"], data["num_voxels"], data["coors"])
         x = self.backbone(features, data["coors"], data["batch_size"], data["input_shape"])
         return self.neck(x) if self.with_neck else x
 
     def forward(self, example, return_loss=False, **kwargs):
-        if return_loss:
-            raise NotImplementedError("PointPillars.forward(return_loss=True): the detector's loss is not built; this is the "
-                                      "eval-mode detector (call with return_loss=False)")
+        self._refuse_loss(return_loss)
         data = dict(features=example["voxels"], num_voxels=example["num_points"], coors=example["coordinates"],
                     batch_size=len(example["num_voxels"]), input_shape=example["shape"][0])
         preds = self.bbox_head(self.extract_feat(data))
@@ -82,20 +111,55 @@ class PointPillars(nn.Module):
         label_preds / metadata (CenterHeadPost.to_prediction turns it into the prediction.pkl dictionary). `last` keeps the
         VoxelizeResult. With test_cfg.double_flip the sweep is first copied into its four flipped views (pillars.double_flip),
         everything up to the head runs on 4 B samples (`last` is theirs) and the post-processing merges them into B."""
-        if self.training:
-            raise RuntimeError("detect is the eval-mode route: call .eval()")
-        if self.voxel_size is None:
-            raise RuntimeError("detect needs the reader's voxel_size and pc_range: build the model from the config's dicts")
-        if _get(self.test_cfg, "double_flip", False):
-            # four views per sample (the sweep, y = -y, x = -x, both), merged again by DoubleFlipPost inside predict
-            points, point_offsets, point_offsets_device = pillars.double_flip(points, point_offsets, point_offsets_device)
-        r = pillars.voxelize(points, point_offsets, self.voxel_size, self.pc_range, self.max_points, self.max_voxels,
-                             point_offsets_device=point_offsets_device)
-        self.last = r
+        r = self._voxelize(points, point_offsets, point_offsets_device)
         grid = pillars.grid_size(self.voxel_size, self.pc_range)
         canvas = self.reader.forward_canvas(r.voxels, r.num_points, r.coordinates, r.B, [int(grid[0]), int(grid[1])],
                                             n_pillars=r.n_pillars)
         preds = self.bbox_head(self.neck(canvas))
         return self.bbox_head.predict({"metadata": metadata}, preds, self.test_cfg)
 
-    to_prediction = staticmethod(CenterHeadPost.to_prediction)
+
+class VoxelNet(SingleStageDetector):
+    """det3d/models/detectors/voxelnet.py, one stage: VoxelFeatureExtractorV3 -> SpMiddleResNetFHD -> RPN -> CenterHead.
+    max_points / max_voxels / voxel_size / pc_range: the config's voxel_generator (max_points_in_voxel, max_voxel_num,
+    voxel_size, range), which `detect` voxelises with on the 3-D grid. sparse_capacities: the rows of the backbone's
+    strided levels ({"conv2": ..}, see sparse.SpMiddleResNetFHD; None: the safe bounds)."""
+
+    def __init__(self, reader, backbone, neck, bbox_head, train_cfg=None, test_cfg=None, pretrained=None, *, max_points=5,
+                 max_voxels=150000, voxel_size=None, pc_range=None, sparse_capacities=None):
+        super().__init__(reader, backbone, neck, bbox_head, train_cfg, test_cfg, max_points, max_voxels,
+                         None if voxel_size is None else list(voxel_size), None if pc_range is None else list(pc_range))
+        self.sparse_capacities = sparse_capacities
+        if pretrained is not None:
+            self.init_weights(pretrained)
+
+    def extract_feat(self, data, n_voxels=None):
+        """-> (x, voxel_feature): the neck's map and the backbone's {conv1 .. conv4} sparse tensors"""
+        input_features = self.reader(data["features"], data["num_voxels"], n_pillars=n_voxels)
+        x, voxel_feature = self.backbone(input_features, data["coors"], data["batch_size"], data["input_shape"],
+                                         n_voxels=n_voxels, capacities=self.sparse_capacities)
+        if self.with_neck:
+            x = self.neck(x)
+        return x, voxel_feature
+
+    def forward(self, example, return_loss=False, **kwargs):
+        self._refuse_loss(return_loss)
+        data = dict(features=example["voxels"], num_voxels=example["num_points"], coors=example["coordinates"],
+                    batch_size=len(example["num_voxels"]), input_shape=example["shape"][0])
+        x, _ = self.extract_feat(data)
+        return self.bbox_head.predict(example, self.bbox_head(x), self.test_cfg)
+
+    def forward_two_stage(self, example, return_loss=False, **kwargs):
+        raise NotImplementedError("VoxelNet.forward_two_stage: the second stage is not built")
+
+    @torch.no_grad()
+    def detect(self, points, point_offsets, metadata=None, point_offsets_device=None):
+        """PointPillars.detect's contract on the 3-D grid: voxelise -> voxel mean -> sparse backbone -> RPN -> CenterHead ->
+        decode + NMS on the current stream; the read-back inside `predict` is the only host synchronisation. `last` keeps the
+        VoxelizeResult; the backbone's `last_status` holds the sparse levels' status word."""
+        r = self._voxelize(points, point_offsets, point_offsets_device)
+        grid = pillars.grid_size(self.voxel_size, self.pc_range)
+        data = dict(features=r.voxels, num_voxels=r.num_points, coors=r.coordinates, batch_size=r.B,
+                    input_shape=[int(g) for g in grid])
+        x, _ = self.extract_feat(data, n_voxels=r.n_pillars)
+        return self.bbox_head.predict({"metadata": metadata}, self.bbox_head(x), self.test_cfg)

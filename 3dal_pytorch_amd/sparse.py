@@ -1,0 +1,399 @@
+"""The sparse 3-D middle of the VoxelNet detector on the GPU through lib3dal_hip.so (dal3_sp_* of include/dal3.h), under the
+reference's names, constructor signatures and state_dict keys: `SparseBasicBlock` and `SpMiddleResNetFHD`
+(det3d/models/backbones/scn.py), and what they take from spconv 1.x: `SparseConvTensor`, `SubMConv3d`, `SparseConv3d`.
+
+Weights are spconv 1.x's (kD, kH, kW, c_in, c_out) and the operation is a cross-correlation: output site p sums
+in[p * stride - padding + k] @ W[k] over the taps whose input site is active. A submanifold layer (kernel 3) keeps its input's
+sites and row order; a SparseConv3d's sites are emitted in ascending (b, z, y, x) order. Site counts stay on the device
+(`SparseConvTensor.n`, an int64 (1) tensor the later kernels read): the forward never synchronises, every buffer is
+capacity-sized, and a level that would exceed its capacity sets _hip.SP_OVERFLOW in `status` and stays in bounds. Eval mode,
+float32; a train-mode forward is refused. There is no CPU route.
+"""
+import numpy as np
+import torch
+from torch import nn
+
+from . import _hip
+from .pillars import _device_ints
+from .rpn import _PackedLayers
+
+
+def _triple(v):
+    return tuple(int(x) for x in v) if isinstance(v, (tuple, list)) else (int(v),) * 3
+
+
+def out_shape(shape, kernel, stride, padding):
+    """floor((in + 2 pad - k) / s) + 1 per axis"""
+    return tuple((int(n) + 2 * p - k) // s + 1 for n, k, s, p in zip(shape, kernel, stride, padding))
+
+
+def candidates(kernel, stride):
+    """output sites one input site can belong to: ceil(k / s) per axis"""
+    return int(np.prod([-(-k // s) for k, s in zip(kernel, stride)]))
+
+
+def safe_capacity(in_capacity, batch_size, shape, kernel, stride, padding):
+    """the bound no input exceeds: min(candidates per input x input capacity, B x output cells)"""
+    return int(min(candidates(kernel, stride) * in_capacity, batch_size * int(np.prod(out_shape(shape, kernel, stride, padding)))))
+
+
+def _check_grid(batch_size, shape):
+    if batch_size < 1 or any(n < 1 for n in shape):
+        raise ValueError(f"batch_size {batch_size} and spatial_shape {tuple(shape)} must be positive")
+    if batch_size * int(np.prod([int(n) for n in shape], dtype=np.int64)) >= 2 ** 31 - 1:
+        raise ValueError(f"B * D * H * W = {batch_size} * {int(np.prod(shape, dtype=np.int64))} does not fit the 31-bit (sample, cell) "
+                         "key: split the batch")
+
+
+class SparseConvTensor:
+    """features (capacity, C) float32 and indices (capacity, 4) int32 rows [b, z, y, x] on the GPU, spatial_shape (D, H, W),
+    batch_size. n: a device int64 (1) tensor, the rows in use (None: all of them). status: the int32 (1) word the kernels OR
+    problems into (_hip.SP_*). `sorted` (keys, rows; rows None = the identity) and `indice_dict` are the bookkeeping the
+    layers share."""
+
+    def __init__(self, features, indices, spatial_shape, batch_size, n=None, status=None):
+        for t, what in ((features, "features"), (indices, "indices")):
+            if not torch.is_tensor(t):
+                raise TypeError(f"{what} must be a tensor")
+        if features.dim() != 2 or features.dtype != torch.float32:
+            raise ValueError(f"features must be float32 (n, C), got {features.dtype} {tuple(features.shape)}")
+        if indices.shape != (features.shape[0], 4) or indices.dtype != torch.int32:
+            raise ValueError(f"indices must be int32 ({features.shape[0]}, 4), got {indices.dtype} {tuple(indices.shape)}")
+        _hip.require_gpu(features, "features")
+        _hip.require_gpu(indices, "indices")
+        self.features, self.indices = features.contiguous(), indices.contiguous()
+        self.spatial_shape, self.batch_size = tuple(int(v) for v in spatial_shape), int(batch_size)
+        if len(self.spatial_shape) != 3:
+            raise ValueError("spatial_shape must be (D, H, W)")
+        _check_grid(self.batch_size, self.spatial_shape)
+        dev = features.device
+        self.n = _device_ints(n, "n", torch.int64, 1, dev)
+        self.status = _device_ints(status, "status", torch.int32, 1, dev)
+        if self.status is None:
+            self.status = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.sorted, self.indice_dict = None, {}
+
+    @property
+    def capacity(self):
+        return self.features.shape[0]
+
+    def like(self, features):
+        """the same sites with other features (what a submanifold layer returns)"""
+        out = SparseConvTensor(features, self.indices, self.spatial_shape, self.batch_size, self.n, self.status)
+        out.sorted, out.indice_dict = self.sorted, self.indice_dict
+        return out
+
+    def dense(self):
+        """(B, C, D, H, W), inactive cells +0; stock torch ops, no synchronisation (rows that are no site go to a spare cell)"""
+        D, H, W = self.spatial_shape
+        cells = self.batch_size * D * H * W
+        i = self.indices.long()
+        ok = (i[:, 0] >= 0) & (i[:, 0] < self.batch_size) & (i[:, 1] >= 0) & (i[:, 1] < D) & (i[:, 2] >= 0) & (i[:, 2] < H) & \
+            (i[:, 3] >= 0) & (i[:, 3] < W)
+        if self.n is not None:
+            ok = ok & (torch.arange(self.capacity, device=i.device) < self.n)
+        flat = torch.where(ok, ((i[:, 0] * D + i[:, 1]) * H + i[:, 2]) * W + i[:, 3], torch.full_like(i[:, 0], cells))
+        out = torch.zeros((cells + 1, self.features.shape[1]), dtype=torch.float32, device=i.device)
+        out.index_copy_(0, flat, self.features)
+        return out[:cells].reshape(self.batch_size, D, H, W, -1).permute(0, 4, 1, 2, 3).contiguous()
+
+
+# ------------------------------------------------------------------------------------- the bookkeeping
+def _i3(v):
+    return (_hip.C.c_int32 * 3)(*[int(x) for x in v])
+
+
+def sort_sites(x, max_workgroups=0):
+    """x.sorted = (keys, rows) of the tensor's sites by ascending key (dal3_sp_sort); flags bad and duplicate rows"""
+    if x.sorted is None:
+        cap, dev = x.capacity, x.features.device
+        key = torch.empty(cap, dtype=torch.int32, device=dev)
+        pos = torch.empty(cap, dtype=torch.int32, device=dev)
+        lib = _hip.lib()
+        nbytes = lib.dal3_sp_sort_workspace_bytes(cap)
+        ws = _hip.workspace(nbytes, dev)
+        a = _hip.SpSortArgs(B=x.batch_size, shape=_i3(x.spatial_shape), capacity=cap, n=_hip.ptr(x.n), indices=_hip.ptr(x.indices),
+                            sorted_key=_hip.ptr(key), sorted_pos=_hip.ptr(pos), status=_hip.ptr(x.status),
+                            max_workgroups=int(max_workgroups), workspace=_hip.ptr(ws), workspace_bytes=nbytes)
+        _hip.check(lib.dal3_sp_sort(a, _hip.stream()))
+        x.sorted = (key, pos)
+    return x.sorted
+
+
+def neighbour_table(x, out_indices, out_n, out_capacity, shape_out, kernel, stride, padding, max_workgroups=0, table=None):
+    """(taps, out_capacity) int32, tap-major: the input row under each tap of each output site, -1 for none (dal3_sp_table)"""
+    key, pos = sort_sites(x, max_workgroups)
+    taps = int(np.prod(kernel))
+    if table is None:
+        table = torch.empty((taps, out_capacity), dtype=torch.int32, device=x.features.device)
+    a = _hip.SpTableArgs(B=x.batch_size, in_shape=_i3(x.spatial_shape), out_shape=_i3(shape_out), kernel=_i3(kernel),
+                         stride=_i3(stride), padding=_i3(padding), out_capacity=out_capacity, n_out=_hip.ptr(out_n),
+                         out_indices=_hip.ptr(out_indices), in_capacity=x.capacity, n_in=_hip.ptr(x.n), in_key=_hip.ptr(key),
+                         in_pos=_hip.ptr(pos), table=_hip.ptr(table), max_workgroups=int(max_workgroups))
+    _hip.check(_hip.lib().dal3_sp_table(a, _hip.stream()))
+    return table
+
+
+def subm_table(x, indice_key=None, max_workgroups=0):
+    """the 27-tap table of a submanifold kernel-3 layer, shared by every layer with the same indice_key"""
+    if indice_key is not None and indice_key in x.indice_dict:
+        return x.indice_dict[indice_key]
+    t = neighbour_table(x, x.indices, x.n, x.capacity, x.spatial_shape, (3, 3, 3), (1, 1, 1), (1, 1, 1), max_workgroups)
+    if indice_key is not None:
+        x.indice_dict[indice_key] = t
+    return t
+
+
+def downsample(x, kernel, stride, padding, capacity=None, max_workgroups=0, indices=None, keys=None):
+    """the output sites of a SparseConv3d -> (an empty-featured description: indices, keys, n, capacity, shape)
+    (dal3_sp_downsample). capacity None: the safe bound. indices / keys: caller's buffers (tests put guard rows around them)."""
+    shape = out_shape(x.spatial_shape, kernel, stride, padding)
+    if any(n < 1 for n in shape):
+        raise ValueError(f"a {tuple(kernel)} kernel with stride {tuple(stride)} and padding {tuple(padding)} leaves no cell of {x.spatial_shape}")
+    _check_grid(x.batch_size, shape)
+    cand = candidates(kernel, stride)
+    cap = safe_capacity(x.capacity, x.batch_size, x.spatial_shape, kernel, stride, padding) if capacity is None else int(capacity)
+    if cap < 0:
+        raise ValueError("capacity must be >= 0")
+    dev = x.features.device
+    if indices is None:
+        indices = torch.empty((cap, 4), dtype=torch.int32, device=dev)
+    if keys is None:
+        keys = torch.empty(cap, dtype=torch.int32, device=dev)
+    n_out = torch.empty(1, dtype=torch.int64, device=dev)
+    lib = _hip.lib()
+    nbytes = lib.dal3_sp_downsample_workspace_bytes(x.capacity, cand)
+    ws = _hip.workspace(nbytes, dev)
+    a = _hip.SpDownsampleArgs(B=x.batch_size, in_shape=_i3(x.spatial_shape), out_shape=_i3(shape), kernel=_i3(kernel),
+                              stride=_i3(stride), padding=_i3(padding), in_capacity=x.capacity, n_in=_hip.ptr(x.n),
+                              in_indices=_hip.ptr(x.indices), out_capacity=cap, out_indices=_hip.ptr(indices),
+                              out_key=_hip.ptr(keys), n_out=_hip.ptr(n_out), status=_hip.ptr(x.status),
+                              max_workgroups=int(max_workgroups), workspace=_hip.ptr(ws), workspace_bytes=nbytes)
+    _hip.check(lib.dal3_sp_downsample(a, _hip.stream()))
+    return indices, keys, n_out, cap, shape
+
+
+# ------------------------------------------------------------------------------------- the convolution
+def pack_layer(conv, bn, status=None):
+    """fold and pack one layer -> a float32 device tensor (dal3_sp_conv_pack). conv: SubMConv3d / SparseConv3d; bn:
+    nn.BatchNorm1d or None"""
+    ts = [conv.weight] + ([conv.bias] if conv.bias is not None else []) + \
+        ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
+    for t in ts:
+        _hip.require_gpu(t, "the layer's parameters")
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError("weights must be contiguous fp32")
+    if bn is not None and not (isinstance(bn, nn.BatchNorm1d) and bn.affine and bn.track_running_stats):
+        raise RuntimeError("the norm layer must be an affine nn.BatchNorm1d with running statistics")
+    L = _hip.Layer(_hip.ptr(conv.weight), _hip.ptr(conv.bias), None, None, None, None, conv.in_channels, conv.out_channels)
+    if bn is not None:
+        L.bn_weight, L.bn_bias, L.bn_mean, L.bn_var = (_hip.ptr(t) for t in ts[-4:])
+    lib = _hip.lib()
+    taps = int(np.prod(conv.kernel_size))
+    floats = lib.dal3_sp_conv_pack_floats(taps, conv.in_channels, conv.out_channels)
+    if not floats:
+        raise ValueError(f"the kernel serves c_in 1 .. 8, 16, 32, 64, 128 and c_out 16, 32, 64, 128, not {conv.in_channels} -> "
+                         f"{conv.out_channels}")
+    buf = torch.empty(floats, dtype=torch.float32, device=conv.weight.device)
+    _hip.check(lib.dal3_sp_conv_pack(L, taps, float(bn.eps) if bn is not None else 1e-3, _hip.ptr(buf), _hip.ptr(status), _hip.stream()))
+    return buf
+
+
+def conv(features, table, n_out, packed, c_in, c_out, status, relu=False, residual=None, center_tap=-1, canvas=None,
+         out_indices=None, canvas_shape=None, out=None, max_workgroups=0):
+    """one dal3_sp_conv launch: features (in_capacity, c_in), table (taps, out_capacity) -> (out_capacity, c_out) rows, or, with
+    `canvas` (B, c_out * D, H, W), the BEV store (the rows are then not kept)"""
+    taps, out_cap = table.shape
+    dev = features.device
+    if packed.numel() != _hip.lib().dal3_sp_conv_pack_floats(taps, c_in, c_out) or packed.device != dev:
+        raise ValueError(f"the packed weights are not those of a {taps}-tap {c_in} -> {c_out} layer on {dev}")
+    if features.shape[1] != c_in or features.dtype != torch.float32 or not features.is_contiguous():
+        raise ValueError(f"features must be contiguous float32 (n, {c_in}), got {features.dtype} {tuple(features.shape)}")
+    if residual is not None and (residual.shape != (out_cap, c_out) or not residual.is_contiguous() or residual.dtype != torch.float32):
+        raise ValueError(f"residual must be contiguous float32 ({out_cap}, {c_out})")
+    if canvas is None and out is None:
+        out = torch.empty((out_cap, c_out), dtype=torch.float32, device=dev)
+    a = _hip.SpConvArgs(taps=taps, c_in=c_in, c_out=c_out, relu=1 if relu else 0, center_tap=center_tap,
+                        in_capacity=features.shape[0], x=_hip.ptr(features), out_capacity=out_cap, n_out=_hip.ptr(n_out),
+                        table=_hip.ptr(table), packed=_hip.ptr(packed), residual=_hip.ptr(residual), y=_hip.ptr(out),
+                        canvas=_hip.ptr(canvas), out_indices=_hip.ptr(out_indices), status=_hip.ptr(status),
+                        max_workgroups=int(max_workgroups))
+    if canvas is not None:
+        a.canvas_B = canvas.shape[0]
+        a.canvas_shape[:] = [int(v) for v in canvas_shape]
+    _hip.check(_hip.lib().dal3_sp_conv(a, _hip.stream()))
+    return canvas if canvas is not None else out
+
+
+class _SparseConv(_PackedLayers):
+    """a parameter container with spconv 1.x's shapes: weight (kD, kH, kW, c_in, c_out), bias (c_out) or None"""
+    subm = False
+
+    def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, padding=0, dilation=1, groups=1, bias=True,
+                 indice_key=None, **kwargs):
+        super().__init__()
+        if _triple(dilation) != (1, 1, 1) or groups != 1:
+            raise NotImplementedError("dilation and groups other than 1 are not served")
+        self.in_channels, self.out_channels = int(in_channels), int(out_channels)
+        self.kernel_size, self.stride, self.padding = _triple(kernel_size), _triple(stride), _triple(padding)
+        self.indice_key = indice_key
+        self.weight = nn.Parameter(torch.empty(*self.kernel_size, self.in_channels, self.out_channels))
+        self.bias = nn.Parameter(torch.empty(self.out_channels)) if bias else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        fan_in = self.in_channels * int(np.prod(self.kernel_size))
+        bound = 1.0 / np.sqrt(fan_in)
+        nn.init.uniform_(self.weight, -bound * np.sqrt(3.0), bound * np.sqrt(3.0))
+        if self.bias is not None:
+            nn.init.uniform_(self.bias, -bound, bound)
+
+    def _plan(self):
+        return [(self, None)]
+
+    def _pack(self, plan):
+        return [pack_layer(c, bn) for c, bn in plan]
+
+    def run(self, x, packed, relu=False, residual=None, capacity=None, max_workgroups=0, canvas=False):
+        """the layer on x with the given pack (its own, or one with a BatchNorm folded in) -> SparseConvTensor, or the
+        (B, c_out * D, H, W) BEV map with canvas=True"""
+        if self.subm:
+            if self.kernel_size != (3, 3, 3) or self.stride != (1, 1, 1):
+                raise NotImplementedError("SubMConv3d is served with kernel 3 and stride 1")
+            table = subm_table(x, self.indice_key, max_workgroups)
+            indices, n_out, shape, center = x.indices, x.n, x.spatial_shape, 13
+        else:
+            indices, keys, n_out, cap, shape = downsample(x, self.kernel_size, self.stride, self.padding, capacity, max_workgroups)
+            table = neighbour_table(x, indices, n_out, cap, shape, self.kernel_size, self.stride, self.padding, max_workgroups)
+            center = -1
+        kw = dict(relu=relu, residual=residual, center_tap=center, max_workgroups=max_workgroups)
+        if canvas:
+            D, H, W = shape
+            bev = torch.empty((x.batch_size, self.out_channels * D, H, W), dtype=torch.float32, device=x.features.device)
+            return conv(x.features, table, n_out, packed, self.in_channels, self.out_channels, x.status, canvas=bev,
+                        out_indices=indices, canvas_shape=shape, **kw)
+        y = conv(x.features, table, n_out, packed, self.in_channels, self.out_channels, x.status, **kw)
+        if self.subm:
+            return x.like(y)
+        out = SparseConvTensor(y, indices, shape, x.batch_size, n_out, x.status)
+        out.sorted = (keys, None)               # emitted in key order
+        return out
+
+    def forward(self, x, capacity=None, max_workgroups=0):
+        _refuse_training(self)
+        with torch.no_grad():
+            return self.run(x, self.packed()[0], capacity=capacity, max_workgroups=max_workgroups)
+
+
+class SubMConv3d(_SparseConv):
+    """spconv.SubMConv3d, kernel 3: the output sites are the input sites in the same row order; `padding` plays no part"""
+    subm = True
+
+
+class SparseConv3d(_SparseConv):
+    """spconv.SparseConv3d: forward(x, capacity=None) — capacity: rows of the output (None: the safe bound)"""
+
+
+def _refuse_training(m):
+    if m.training:
+        raise RuntimeError(f"{type(m).__name__} is the eval-mode forward (call .eval()): training and the backward are not built")
+
+
+def _norm(cfg, c):
+    """det3d/models/utils/norm.py for BN1d"""
+    cfg = dict(type="BN1d", eps=1e-3, momentum=0.01) if cfg is None else dict(cfg)
+    kind = cfg.pop("type")
+    cfg.pop("requires_grad", None)
+    if kind not in ("BN1d", "BN"):
+        raise KeyError(f"norm layer type {kind!r} (BN1d)")
+    return nn.BatchNorm1d(c, eps=cfg.get("eps", 1e-5), momentum=cfg.get("momentum", 0.1))
+
+
+class SparseBasicBlock(_PackedLayers):
+    """scn.py:37-80: relu(bn2(conv2(relu(bn1(conv1(x))))) + x); both convolutions are submanifold and have a bias"""
+    expansion = 1
+
+    def __init__(self, inplanes, planes, stride=1, norm_cfg=None, downsample=None, indice_key=None):
+        super().__init__()
+        if downsample is not None or stride != 1 or inplanes != planes:
+            raise NotImplementedError("SparseBasicBlock is served with stride 1, equal widths and no downsample")
+        self.conv1 = SubMConv3d(inplanes, planes, 3, stride=1, padding=1, bias=True, indice_key=indice_key)
+        self.bn1 = _norm(norm_cfg, planes)
+        self.relu = nn.ReLU()
+        self.conv2 = SubMConv3d(planes, planes, 3, padding=1, bias=True, indice_key=indice_key)
+        self.bn2 = _norm(norm_cfg, planes)
+        self.downsample, self.stride = downsample, stride
+
+    def _plan(self):
+        return [(self.conv1, self.bn1), (self.conv2, self.bn2)]
+
+    def _pack(self, plan):
+        return [pack_layer(c, bn) for c, bn in plan]
+
+    def forward(self, x, max_workgroups=0):
+        _refuse_training(self)
+        with torch.no_grad():
+            p1, p2 = self.packed()
+            out = self.conv1.run(x, p1, relu=True, max_workgroups=max_workgroups)
+            return self.conv2.run(out, p2, relu=True, residual=x.features, max_workgroups=max_workgroups)
+
+
+class SpMiddleResNetFHD(_PackedLayers):
+    """scn.py:83-177. forward(voxel_features, coors, batch_size, input_shape, n_voxels=None) -> (bev (B, 128 * D', H', W'),
+    {conv1 .. conv4: SparseConvTensor}). n_voxels: a device int64 (1) tensor (VoxelizeResult.n_pillars), the rows in use;
+    without it every row is a voxel. `capacities`: {"conv2" | "conv3" | "conv4" | "extra_conv": rows} for the strided
+    levels (default: the safe bound of sparse.safe_capacity). `last_status` is the status word of the last forward."""
+
+    def __init__(self, num_input_features=128, norm_cfg=None, name="SpMiddleResNetFHD", **kwargs):
+        super().__init__()
+        self.name = name
+        self.dcn, self.zero_init_residual = None, False
+        self.capacities = kwargs.pop("capacities", None)         # ds_factor and the like are swallowed
+        c = int(num_input_features)
+
+        def block(w, key):
+            return SparseBasicBlock(w, w, norm_cfg=norm_cfg, indice_key=key)
+
+        self.conv_input = nn.Sequential(SubMConv3d(c, 16, 3, bias=False, indice_key="res0"), _norm(norm_cfg, 16), nn.ReLU(inplace=True))
+        self.conv1 = nn.Sequential(block(16, "res0"), block(16, "res0"))
+        self.conv2 = nn.Sequential(SparseConv3d(16, 32, 3, 2, padding=1, bias=False), _norm(norm_cfg, 32), nn.ReLU(inplace=True),
+                                   block(32, "res1"), block(32, "res1"))
+        self.conv3 = nn.Sequential(SparseConv3d(32, 64, 3, 2, padding=1, bias=False), _norm(norm_cfg, 64), nn.ReLU(inplace=True),
+                                   block(64, "res2"), block(64, "res2"))
+        self.conv4 = nn.Sequential(SparseConv3d(64, 128, 3, 2, padding=[0, 1, 1], bias=False), _norm(norm_cfg, 128),
+                                   nn.ReLU(inplace=True), block(128, "res3"), block(128, "res3"))
+        self.extra_conv = nn.Sequential(SparseConv3d(128, 128, (3, 1, 1), (2, 1, 1), bias=False), _norm(norm_cfg, 128), nn.ReLU())
+        self.last_status = None
+
+    STEMS = ("conv_input", "conv2", "conv3", "conv4", "extra_conv")
+
+    def _plan(self):
+        return [(getattr(self, s)[0], getattr(self, s)[1]) for s in self.STEMS]
+
+    def _pack(self, plan):
+        return [pack_layer(c, bn) for c, bn in plan]
+
+    def forward(self, voxel_features, coors, batch_size, input_shape, n_voxels=None, capacities=None, max_workgroups=0):
+        _refuse_training(self)
+        with torch.no_grad():
+            sparse_shape = tuple(int(v) for v in (np.array(input_shape[::-1]) + [1, 0, 0]))
+            if not torch.is_tensor(coors) or not torch.is_tensor(voxel_features):
+                raise TypeError("voxel_features and coors must be tensors")
+            x = SparseConvTensor(voxel_features, coors.int(), sparse_shape, batch_size, n=n_voxels)
+            self.last_status = x.status
+            caps = dict(self.capacities or {}, **(capacities or {}))
+            packs = dict(zip(self.STEMS, self.packed()))
+            kw = dict(max_workgroups=max_workgroups)
+            x = self.conv_input[0].run(x, packs["conv_input"], relu=True, **kw)
+            out = {}
+            for name in ("conv1", "conv2", "conv3", "conv4"):
+                seq = getattr(self, name)
+                blocks = list(seq)
+                if name != "conv1":
+                    x = seq[0].run(x, packs[name], relu=True, capacity=caps.get(name), **kw)
+                    blocks = blocks[3:]
+                for b in blocks:
+                    x = b(x, **kw)
+                out[name] = x
+            bev = self.extra_conv[0].run(x, packs["extra_conv"], relu=True, capacity=caps.get("extra_conv"), canvas=True, **kw)
+            return bev, out

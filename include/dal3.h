@@ -949,6 +949,133 @@ size_t dal3_conv2d_pack_floats(int kind, int c_in, int c_out);
 int dal3_conv2d_pack(const dal3_layer* layer, int kind, double eps, float* out, dal3_stream stream);
 int dal3_conv2d(const dal3_conv2d_args* args, dal3_stream stream);
 
+/* ---- the VoxelNet detector's sparse 3-D middle: SpMiddleResNetFHD (det3d/models/backbones/scn.py), which the reference
+ * delegates to spconv 1.x: SubMConv3d (kernel 3), SparseConv3d, BatchNorm1d (folded), ReLU, SparseBasicBlock's residual and
+ * the .dense().view(N, C * D, H, W) at the end. float32, eval mode. (Additions only; DAL3_VERSION stays, as for the entries
+ * above.)
+ *
+ * A sparse tensor is features (capacity, C) float32 and indices (capacity, 4) int32 rows [b, z, y, x] on a grid
+ * shape = (D, H, W) with B samples; an optional device count n (int64, 1) says that only the first min(*n, capacity) rows
+ * exist. Nothing here synchronises: counts stay on the device and later kernels read them. B * D * H * W < 2^31 - 1.
+ *
+ * Definition. weight (kD, kH, kW, c_in, c_out), spconv 1.x's layout; a cross-correlation: output site p sums
+ * in[p * stride - padding + k] @ weight[k] over the taps k whose input site is active. A submanifold layer's output sites
+ * are its input sites in the same row order (kernel 3, stride 1, padding 1 in these terms). A SparseConv3d's output grid is
+ * floor((in + 2 * padding - kernel) / stride) + 1 per axis; an output site is active iff an active input site lies in its
+ * receptive field, and the active output sites are emitted in ascending ((b * D + z) * H + y) * W + x order.
+ *
+ * dal3_sp_sort: the level's (key, row) pairs sorted by key into sorted_key / sorted_pos (capacity each); rows that are no
+ * site carry the key B * D * H * W at the end. A row of the first *n whose coordinates lie outside the grid or the batch
+ * sets DAL3_SP_BAD_COORD and is treated as absent; equal keys set DAL3_SP_DUPLICATE (the result is then unspecified, in
+ * bounds). dal3_sp_downsample: the output sites of a SparseConv3d: out_indices (out_capacity, 4) and out_key
+ * (out_capacity), rows [0, *n_out) written, *n_out = min(active output sites, out_capacity); more sites than out_capacity
+ * set DAL3_SP_OVERFLOW and the sites beyond it are dropped (nothing is written out of bounds and later levels stay in
+ * bounds). out_capacity = min(candidates * in_capacity, B * output cells) always suffices; candidates = the product over
+ * the axes of ceil(kernel / stride). dal3_sp_table: table (taps, out_capacity) int32, tap-major, tap = (kz * kH + ky) * kW
+ * + kx: the row of the input site under that tap of output site i, -1 when there is none; columns [0, *n_out) are
+ * written. in_key / in_pos are dal3_sp_sort's of the input (in_pos NULL: the input rows are in key order, as
+ * dal3_sp_downsample emits them: its out_key). The status words are OR-ed. No atomic decides a position or a count; the
+ * bytes are the same for every max_workgroups.
+ *
+ * dal3_sp_conv_pack folds Conv (+ optional bias) + optional eval-mode BatchNorm1d in float64, every operation rounded
+ * by itself, one rounding to float32: scale = g / sqrt(var + eps), W' = W * scale, b' = (bias - mean) * scale + beta
+ * (without BatchNorm scale = 1, b' = bias; a NULL bias is 0). c_in 1 .. 8, 16, 32, 64 or 128; c_out 16, 32, 64 or 128;
+ * 1 <= taps <= 27. out: dal3_sp_conv_pack_floats(taps, c_in, c_out) floats (0 for bad arguments), 16-byte aligned. A
+ * folded weight that is not finite marks the pack and sets DAL3_SP_BAD_WEIGHT in *status (optional): dal3_sp_conv on
+ * such a pack writes nothing and sets the same bit.
+ *
+ * dal3_sp_conv: y[i] = act(b' + sum over taps with table[tap][i] >= 0 of W'[tap]^T x[table[tap][i]] (+ residual[i])) for
+ * i < min(*n_out, out_capacity), on the fp32 MFMA (output channels on its rows, 32 sites on its columns). An absent
+ * neighbour contributes exactly zero; taps are summed in ascending order, each tap's products from zero first, so the
+ * bits depend on neither the grid nor max_workgroups; there are no floating-point atomics. IEEE NaN semantics: a NaN or
+ * Inf feature reaches exactly the outputs whose receptive field holds it, and act = relu keeps a NaN. center_tap >= 0
+ * (a submanifold layer: 13): a row whose table entry under that tap is -1 is no site and its output row is +0. x, y and
+ * residual are row-major with exactly c_in / c_out floats a row, 16-byte aligned (x: when c_in >= 16); y may be NULL with a canvas. With
+ * `canvas` (canvas_B, c_out * D, H, W), canvas_shape = (D, H, W), the call first fills it with +0 on the stream and then
+ * writes feature c of site (b, d, y, x) = out_indices[i] to canvas[b, c * D + d, y, x]: .dense().view(N, C * D, H, W) as a
+ * store pattern. Rows whose indices fall outside the canvas are not written. Invalid arguments return DAL3_EINVAL and
+ * nothing is launched. */
+enum { DAL3_SP_OVERFLOW = 256, DAL3_SP_BAD_COORD = 512, DAL3_SP_DUPLICATE = 1024, DAL3_SP_BAD_WEIGHT = 2048 };  /* status bits */
+
+typedef struct dal3_sp_sort_args {
+    int64_t B;
+    int32_t shape[3];                    /* D, H, W */
+    int32_t reserved;                    /* 0 */
+    int64_t capacity;                    /* rows of indices */
+    const int64_t* n;                    /* optional device (1): rows in use */
+    const int32_t* indices;              /* (capacity, 4) [b, z, y, x] */
+    int32_t* sorted_key;                 /* (capacity) */
+    int32_t* sorted_pos;                 /* (capacity) */
+    int32_t* status;                     /* (1) OR-ed */
+    int64_t max_workgroups;              /* 0: no cap */
+    void* workspace;
+    size_t workspace_bytes;
+} dal3_sp_sort_args;
+
+typedef struct dal3_sp_downsample_args {
+    int64_t B;
+    int32_t in_shape[3], out_shape[3];   /* D, H, W */
+    int32_t kernel[3], stride[3], padding[3];
+    int32_t reserved;                    /* 0 */
+    int64_t in_capacity;
+    const int64_t* n_in;                 /* optional device (1) */
+    const int32_t* in_indices;           /* (in_capacity, 4) */
+    int64_t out_capacity;
+    int32_t* out_indices;                /* (out_capacity, 4) */
+    int32_t* out_key;                    /* (out_capacity) */
+    int64_t* n_out;                      /* device (1) */
+    int32_t* status;                     /* (1) OR-ed */
+    int64_t max_workgroups;
+    void* workspace;
+    size_t workspace_bytes;
+} dal3_sp_downsample_args;
+
+typedef struct dal3_sp_table_args {
+    int64_t B;
+    int32_t in_shape[3], out_shape[3];
+    int32_t kernel[3], stride[3], padding[3];
+    int32_t reserved;                    /* 0 */
+    int64_t out_capacity;
+    const int64_t* n_out;                /* optional device (1) */
+    const int32_t* out_indices;          /* (out_capacity, 4) */
+    int64_t in_capacity;
+    const int64_t* n_in;                 /* optional device (1) */
+    const int32_t* in_key;               /* (in_capacity) ascending */
+    const int32_t* in_pos;               /* (in_capacity), or NULL: the identity */
+    int32_t* table;                      /* (taps, out_capacity) */
+    int64_t max_workgroups;
+} dal3_sp_table_args;
+
+typedef struct dal3_sp_conv_args {
+    int32_t taps, c_in, c_out, relu;
+    int32_t center_tap;                  /* -1, or the tap whose absence makes a row +0 */
+    int32_t reserved;                    /* 0 */
+    int64_t in_capacity;
+    const float* x;                      /* (in_capacity, c_in) */
+    int64_t out_capacity;
+    const int64_t* n_out;                /* optional device (1) */
+    const int32_t* table;                /* (taps, out_capacity) */
+    const float* packed;                 /* dal3_sp_conv_pack's */
+    const float* residual;               /* optional (out_capacity, c_out) */
+    float* y;                            /* (out_capacity, c_out); may be NULL with a canvas */
+    float* canvas;                       /* optional (canvas_B, c_out * D, H, W) */
+    const int32_t* out_indices;          /* (out_capacity, 4), with a canvas */
+    int64_t canvas_B;
+    int32_t canvas_shape[3];             /* D, H, W */
+    int32_t reserved2;                   /* 0 */
+    int32_t* status;                     /* (1) OR-ed */
+    int64_t max_workgroups;
+} dal3_sp_conv_args;
+
+size_t dal3_sp_sort_workspace_bytes(int64_t capacity);
+int dal3_sp_sort(const dal3_sp_sort_args* args, dal3_stream stream);
+size_t dal3_sp_downsample_workspace_bytes(int64_t in_capacity, int candidates);
+int dal3_sp_downsample(const dal3_sp_downsample_args* args, dal3_stream stream);
+int dal3_sp_table(const dal3_sp_table_args* args, dal3_stream stream);
+size_t dal3_sp_conv_pack_floats(int taps, int c_in, int c_out);
+int dal3_sp_conv_pack(const dal3_layer* layer, int taps, double eps, float* out, int32_t* status, dal3_stream stream);
+int dal3_sp_conv(const dal3_sp_conv_args* args, dal3_stream stream);
+
 /* ---- crop extraction from full sweeps: the per-detection loop of _create_pd_detection
  * (det3d/datasets/waymo/waymo_common.py:166-171, 193) for F frames at once. points (P_total,3) f32 vehicle-frame
  * sweeps concatenated, point_offsets (F+1); planes (K_total,6,4) f64 face equations of every frame's detections
