@@ -114,6 +114,12 @@ static PointHeadW point_head_walk(Cursor& cur, int head_kind) {
         w.fc.w[i] = i < n_fc ? cur.take((size_t)fi[i] * fo[i]) : nullptr;
         w.fc.b[i] = i < n_fc ? cur.take((fo[i] + 31) / 32 * 32) : nullptr;
     }
+    // the screened conv4's copies (heads with conv4 256 -> 512): fp32 rows, fp16 fragments, bound coefficients, flag
+    const bool scr = c[2] == 256 && c[3] == 512;
+    w.w4row = scr ? cur.take((size_t)512 * 256) : nullptr;
+    w.w4h = scr ? cur.take4((size_t)16 * 8 * 2 * 256) : nullptr;
+    w.scr_pq = scr ? cur.take(2 * 512) : nullptr;
+    w.scr_flag = scr ? reinterpret_cast<const int32_t*>(cur.take(64)) : nullptr;
     return w;
 }
 size_t point_head_packed_floats(int head_kind) {
@@ -481,6 +487,11 @@ extern "C" int dal3_pack_weights(int head_kind, const dal3_layer* L, int n_layer
     TRY(pack_frag(L[1], PACK_FRAG_MT_MAJOR, 0, c[0], w.stream, 0, w.b2, s));
     TRY(pack_frag(L[2], PACK_FRAG_MT_MAJOR, 0, c[1], w.stream, f3, w.b3, s));
     TRY(pack_frag(L[3], PACK_FRAG_MT_MAJOR, 0, c[2], w.stream, f4, w.b4, s));
+    if (w.w4row) {
+        HIP_TRY(launch_pack_weight(L[3], PACK_ROWMAJOR, 0, 256, 0, 0, mut(w.w4row), s));
+        HIP_TRY(launch_pack_weight_lp(L[3], DAL3_F16, 0, 0, 256, 16, 8, reinterpret_cast<uint16_t*>(mut(w.w4h)), s));
+        HIP_TRY(launch_pack_head_screen(L[3], mut(w.scr_pq), reinterpret_cast<int32_t*>(mut(w.scr_flag)), s));
+    }
     return pack_fc(L + 4, w.fc, s);
 }
 
@@ -785,6 +796,9 @@ extern "C" int dal3_point_head_pool(int head_kind, const void* packed, int dtype
     HIP_TRY(launch_point_head(head_kind, w, to_bcn(x), c_in, B, M, feat, n_distinct, s, workspace, workspace_bytes));
     return 0;
 }
+
+extern "C" int dal3_point_head_screen_min_tiles(void) { return DAL3_HEAD_SCREEN ? DAL3_HEAD_SCR_MIN_TILES : 0x7fffffff; }
+extern "C" int dal3_point_head_screen_stride(void) { return DAL3_HEAD_SCR_STRIDE; }
 
 extern "C" int dal3_dynamic_box_est_forward(const void* packed, const float* embedding, int B, float* box_pred,
                                             void* workspace, size_t workspace_bytes, dal3_stream stream) {

@@ -1,0 +1,337 @@
+// dal3_head_screen.hip — the fp32 point heads with conv4 SCREENED (DESIGN.md "Screened conv4 of the point heads").
+//
+// The box head is conv1..conv4 (3 -> 128 -> 128 -> 256 -> 512) and a max over the item's object points; conv4 is 73 %
+// of the multiply-adds and only its 512 channel maxima are kept. For large jobs the head is two launches over two
+// worklists (nonfinite_rows_kernel, dal3_misc.hip):
+//   seed launch      point_head_pers_kernel, UNCHANGED and dense, over each item's SEED tiles (the live tiles whose index
+//                    is a multiple of DAL3_HEAD_SCR_STRIDE; tile 0 always): exact values in `feat`;
+//   screened launch  this kernel over the other live tiles: conv1..conv3 in fp32 exactly as the dense kernel does, conv4
+//                    on the fp16 MFMA with the encoder's proved bound restated for K = 256,
+//                        |s16(c,p) - chain32(c,p)| <= E_c = X * P_c + Q_c     (X >= ||x_p||_2 for every point of the tile),
+//                    (c,p) is a candidate iff s16 > thr = fl(fl(G - b_c) - fl(E + 2^-22 (|G| + |b_c|))); every candidate is
+//                    recomputed with the exact k-ordered fmaf chain on the VALU, then + b, ReLU on the bits, into the
+//                    run's LDS row, which is flushed to `feat` as the dense kernel's is.
+// G is any value that is <= the final feat[item][c]: the seed's exact maximum as read when the run enters the item
+// (possibly raised by other waves already), and the run's own exact maxima so far. A pair that is not a candidate has
+// fl(chain + b_c) <= G, so it cannot change the result: the bits are the dense kernel's. Unlike the encoder there is no
+// lower-bound pass: conv1..conv3 are 27 % of the head, and a pass that recomputes them costs more than it saves.
+// Whatever does not fit the proof or the list takes the dense conv_max_layer, per tile: activations beyond fp16's range,
+// conv4 weights beyond it (blob flag), more than HEAD_SCR_CAP candidates in the tile.
+#include "dal3_device.h"
+#include "dal3_kernels.h"
+#include "dal3_lp.h"
+
+#ifndef HEAD_SCR_CAP
+#define HEAD_SCR_CAP 1024               // candidate entries per 32-point tile (CPU model, bench crops: at most 856 at stride 4)
+#endif
+#define HEAD_SCR_XLD 132                // floats per point row of the LDS copy of HALF of x3: 128 + 4, rows start 4 banks apart
+#define HEAD_SCR_XMAX_BITS 0x476A6000   // 60000.0f: activations up to here round to a FINITE fp16
+#ifndef HEAD_RUN
+#define HEAD_RUN 6                      // as point_head_pers_kernel
+#endif
+
+// Diagnostic build only (-DDAL3_SCREEN_COUNT): [0] tiles, [1] tiles dense for range or flag, [2] tiles dense for list
+// overflow, [3] candidates, [4] recompute rounds (64 candidates, both halves of k). No counter executes in the shipped library.
+#ifdef DAL3_SCREEN_COUNT
+__device__ unsigned long long g_head_scr_count[8];
+extern "C" int dal3_debug_head_screen_counts(unsigned long long* out, int reset) {
+    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_head_scr_count), sizeof(g_head_scr_count));
+    if (e == hipSuccess && reset) {
+        unsigned long long z[8] = {};
+        e = hipMemcpyToSymbol(HIP_SYMBOL(g_head_scr_count), z, sizeof(z));
+    }
+    return (int)e;
+}
+#define HSCR_COUNT(k, v)                                                    \
+    do {                                                                    \
+        if (lane == 0) atomicAdd(&g_head_scr_count[k], (unsigned long long)(v)); \
+    } while (0)
+#else
+#define HSCR_COUNT(k, v)
+#endif
+
+template <int KS, int C1, int C2, int C3>
+__global__ __launch_bounds__(64) void point_head_screen_kernel(PointHeadW w, BCN x, int c_in, float* __restrict__ feat,
+                                                               uint32_t* __restrict__ ctl, const u32x4* __restrict__ list) {
+    constexpr int T = 1;
+    constexpr int KT = C3 / 32;                        // k-tiles of conv4
+    static_assert(C3 == 256, "the bound, the two halves of k and the fp16 fragments are laid out for conv4 256 -> 512");
+    const int lane = threadIdx.x & 63;
+    const int h = lane >> 5;
+    __shared__ float s_b4[512];                        // conv4's folded bias
+    __shared__ int s_run[512];                         // the current item's channel maxima (bit patterns, >= 0)
+    __shared__ int s_g[512];                           // feat[item] as read when the run entered the item
+    __shared__ f32x2 s_pq[512];                        // (P_c, Q_c)
+    __shared__ uint32_t s_list[HEAD_SCR_CAP];          // the tile's candidates: channel << 8 | point
+    __shared__ float s_part[HEAD_SCR_CAP];             // their chains after the first half of k
+    __shared__ __attribute__((aligned(16))) float s_x[32 * HEAD_SCR_XLD];   // half of x3, point-major
+    // Four one-wave workgroups per CU (one wave per SIMD at this register count) must fit the CU's 160 KiB: the four
+    // tables, the list, the partial chains and HALF of x3 (a whole point-major x3 is 33 KiB per wave and does not fit).
+    static_assert(4 * (3 * 512 * 4 + 512 * 8 + HEAD_SCR_CAP * 8 + 32 * HEAD_SCR_XLD * 4) <= 160 * 1024,
+                  "the screened head's LDS exceeds a quarter of a CU's 160 KiB: lower HEAD_SCR_CAP or HEAD_SCR_XLD");
+    for (int i = threadIdx.x; i < 512; i += 64) {
+        s_b4[i] = w.b4[i];
+        s_run[i] = 0;
+        s_pq[i] = reinterpret_cast<const f32x2*>(w.scr_pq)[i];
+    }
+    __syncthreads();
+    const uint32_t n_live = ctl[0];
+    uint32_t run0 = n_live / (2u * gridDim.x);         // the guided schedule of point_head_pers_kernel
+    run0 = run0 < 1u ? 1u : (run0 > HEAD_RUN ? HEAD_RUN : run0);
+    const uint32_t first_free = gridDim.x * run0;
+    uint32_t cur = blockIdx.x * run0, run_end = cur + run0;
+    if (cur >= n_live) return;
+    const bool blob_dense = *w.scr_flag != 0;          // a folded conv4 weight is not finite in fp16: every tile is dense
+
+    constexpr uint32_t FRAGS23 = ((C2 / 32) * (C1 / 32) + (C3 / 32) * (C2 / 32)) * 4u;   // conv2 | conv3 fragments
+    WRing<DAL3_PF, true> ring;                         // conv2 | conv3, cyclic: conv4's fp32 fragments are the fallback's
+    ring.init(w.stream, lane, FRAGS23 * 1024u);
+    WRing<8, true> r16;                                // conv4's fp16 fragments [16 out-tiles][8 kt][2 s] of 1 KiB, cyclic
+    r16.init(w.w4h, lane, 16u * KT * 2u * 1024u);
+    f32x16 bias = tile_from_channels(w.b2, h);
+    u32x4 e = list[cur];
+    float in[T][KS];
+    load_points<KS, T>(x, (int64_t)e[0], (int)e[1] * 32, (int)e[2], c_in, in, lane);
+    auto enter = [&](int64_t b) {                      // the item's thresholds (other waves may be raising them: any value read is <= the final one)
+        const int* gi = reinterpret_cast<const int*>(feat + b * 512);
+#pragma unroll
+        for (int c = lane; c < 512; c += 64) s_g[c] = __hip_atomic_load(gi + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    auto flush = [&](int64_t b) {                      // the finished item's maxima -> feat (nothing where the value is 0)
+        int* gi = reinterpret_cast<int*>(feat + b * 512);
+#pragma unroll
+        for (int c = lane; c < 512; c += 64) {
+            const int v = s_run[c];
+            if (v > 0) atomicMax(gi + c, v);
+            s_run[c] = 0;
+        }
+    };
+    auto dense_tile = [&](const f32x16 (&x3)[T][KT]) {  // the dense kernel's conv4 + max on this tile, from a ring of its own
+        WRing<DAL3_PF> r32;
+        r32.init(w.stream + FRAGS23 * 64, lane);
+        conv_max_layer<KT, T>(r32, s_b4, x3, reinterpret_cast<float*>(s_run), 16, lane);
+    };
+    enter((int64_t)e[0]);
+    for (;;) {
+        const int64_t b = (int64_t)e[0];
+        const int e_t = (int)e[1], e_n = (int)e[2];    // this tile's index and the item's distinct points
+        const bool last_of_run = cur + 1 >= run_end || cur + 1 >= n_live;
+        uint32_t nxt = 0, take = 1;
+        if (last_of_run) {
+            const uint32_t left = n_live > run_end ? n_live - run_end : 0u;
+            take = left / (2u * gridDim.x);
+            take = take < 1u ? 1u : (take > HEAD_RUN ? HEAD_RUN : take);
+            if (lane == 0) nxt = atomicAdd(&ctl[1], take);
+        }
+        f32x16 x3[T][KT];
+        float in_n[T][KS];
+        uint32_t ncur, nend;
+        {
+            f32x16 x1[T][C1 / 32], x2[T][C2 / 32];
+            first_layer<KS, C1 / 32, T>(w.w1, w.b1, in, x1, lane);
+            mlp_layer_ring<C1 / 32, C2 / 32, T>(ring, w.b2, w.b3, bias, x1, x2, lane);
+            if (last_of_run) {
+                ncur = (uint32_t)__builtin_amdgcn_readfirstlane((int)nxt) + first_free;
+                nend = ncur + take;
+            } else {
+                ncur = cur + 1;
+                nend = run_end;
+            }
+            const uint32_t nclamp = ncur < n_live ? ncur : cur;
+            e = list[nclamp];
+            mlp_layer_ring<C2 / 32, C3 / 32, T>(ring, w.b3, w.b2, bias, x2, x3, lane);   // leaves bias = conv2's tile 0
+            load_points<KS, T>(x, (int64_t)e[0], (int)e[1] * 32, (int)e[2], c_in, in_n, lane);
+        }
+        HSCR_COUNT(0, 1);
+
+        // fp16 holds every activation of the tile? (x3 >= +0 after the ReLU: the integer order of the bit patterns is the
+        // order of the values, and a NaN / Inf pattern lies above the limit.)
+        int xm = 0;
+#pragma unroll
+        for (int kt = 0; kt < KT; ++kt) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int v = __float_as_int(x3[0][kt][r]);
+                xm = v > xm ? v : xm;
+            }
+        }
+        if (blob_dense || __builtin_amdgcn_ballot_w64(xm > HEAD_SCR_XMAX_BITS) != 0) {
+            HSCR_COUNT(1, 1);
+            dense_tile(x3);
+        } else {
+            // X >= ||x_p||_2 for every point of the tile (lane half h holds 128 of a point's 256 channels)
+            float ss = 0.0f;
+#pragma unroll
+            for (int kt = 0; kt < KT; ++kt) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) ss = fmaf(x3[0][kt][r], x3[0][kt][r], ss);
+            }
+            ss += __shfl_xor(ss, 32);
+#pragma unroll
+            for (int d = 16; d >= 1; d >>= 1) ss = __builtin_fmaxf(ss, __shfl_xor(ss, d));
+            const float X = sqrtf(ss) * (1.0f + 0x1p-15f);             // (margin: 256 roundings of the sum, the root, the products below)
+
+            ActTile<FP16> xh[KT];
+#pragma unroll
+            for (int kt = 0; kt < KT; ++kt) xh[kt] = pack_relu<FP16>(x3[0][kt]);
+
+            uint32_t cnt = 0;
+            // the ragged last tile of an item repeats the item's last point (load_points): a copy is never listed, the
+            // point itself is in this tile. Bit r of vmask: accumulator register r of this lane half is a point of its own.
+            uint32_t vmask = 0;
+            {
+                const int left = e_n - e_t * 32;                         // >= 1
+#pragma unroll
+                for (int r = 0; r < 16; ++r) vmask |= ((r & 3) + 8 * (r >> 2) + 4 * h) < left ? (1u << r) : 0u;
+            }
+            // Per 32-channel block one constant per lane (= channel): the threshold on the fp16 score.
+            // chain32 <= s16 + E; s16 <= thr <= G - b - E  ==>  chain32 + b <= G  ==>  fl(chain32 + b) <= G.
+            auto block_const = [&](int mt) -> float {
+                const int c = 32 * mt + (lane & 31);
+                const f32x2 pq = s_pq[c];
+                float E = fmaf(X, pq[0], pq[1]);
+                E = fmaf(E, 0x1p-20f, E);
+                const int gs = s_g[c], gr = s_run[c];                  // both exact values of this item, both patterns >= 0
+                const float G = __int_as_float(gs > gr ? gs : gr), bb = s_b4[c];
+                if (bits_nonfinite(G)) return 3.0e38f;                 // above every finite score: no candidate (decided on the bit pattern)
+                return (G - bb) - fmaf(__builtin_fabsf(G) + __builtin_fabsf(bb), 0x1p-22f, E);
+            };
+            // one hit bit per accumulator register (= point), collected in 8 slices behind the NEXT block's first MFMAs
+            uint32_t hb = 0;
+            auto ep_slice = [&](const f32x16& acc, int i, float k) {
+                hb |= acc[2 * i] > k ? (1u << (2 * i)) : 0u;
+                hb |= acc[2 * i + 1] > k ? (2u << (2 * i)) : 0u;
+            };
+            auto ep_finish = [&](int mt) {
+                const int c = 32 * mt + (lane & 31);
+                uint32_t bits = hb & vmask;            // the block's hits of this lane: one (channel, point) pair per bit
+                hb = 0;
+                while (__builtin_amdgcn_ballot_w64(bits != 0)) {
+                    const bool act = bits != 0;
+                    const int r = act ? __builtin_ctz(bits) : 0;
+                    const uint32_t ent = ((uint32_t)c << 8) | (uint32_t)((r & 3) + 8 * (r >> 2) + 4 * h);   // tile_chan(r, h)
+                    const unsigned long long mask = __builtin_amdgcn_ballot_w64(act);
+                    const uint32_t pos = cnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+                    if (act && pos < HEAD_SCR_CAP) s_list[pos] = ent;
+                    cnt += (uint32_t)__builtin_popcountll(mask);
+                    bits &= bits - 1;
+                }
+            };
+            // transposed tile, as conv_max_layer: points on the registers, channels on the lanes
+            auto mm = [&](f32x16& acc, auto side) {
+                acc = f32x16{};
+#pragma unroll
+                for (int i = 0; i < 2 * KT; ++i) {
+                    const f16x8_t a = __builtin_bit_cast(f16x8_t, r16.slot[i & 7]);
+                    r16.slot[i & 7] = r16.fetch();
+                    acc = FP16::mfma(xh[i >> 1].k[i & 1], a, acc);
+                    DAL3_SCHED_FENCE();
+                    side(i);
+                    DAL3_SCHED_FENCE();
+                }
+            };
+            f32x16 accA, accB;
+            float kA = block_const(0), kB;
+            mm(accA, NoSide());                                                    // block 0
+            int mt = 1;
+            for (; mt + 1 < 16; mt += 2) {             // (two whole blocks per trip and nothing else: see conv_max_layer)
+                kB = block_const(mt);
+                mm(accB, [&](int i) { if (i < 8) ep_slice(accA, i, kA); });
+                ep_finish(mt - 1);
+                kA = block_const(mt + 1);
+                mm(accA, [&](int i) { if (i < 8) ep_slice(accB, i, kB); });
+                ep_finish(mt);
+            }
+            kB = block_const(mt);                                                  // mt == 15
+            mm(accB, [&](int i) { if (i < 8) ep_slice(accA, i, kA); });
+            ep_finish(mt - 1);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) ep_slice(accB, i, kB);                     // last block: nothing left to hide under
+            ep_finish(mt);
+            HSCR_COUNT(3, cnt);
+
+            if (cnt > HEAD_SCR_CAP) {                  // the list does not hold the tile's candidates: the dense layer, exact
+                HSCR_COUNT(2, 1);
+                dense_tile(x3);
+            } else {
+                // One candidate per lane: the dense kernel's chain. v_mfma_f32_32x32x2_f32 from a zero accumulator is, per
+                // output, fma(a1, b1, fma(a0, b0, acc)) over its k-steps in issue order, k = 0 from lane half 0: channels
+                // 8i, 8i+4, 8i+1, 8i+5, ... for i = 4 kt + q. The operands are staged in TWO HALVES of k (channels
+                // 0..127, then 128..255); the chain crosses the halves through s_part, its order unchanged.
+#pragma unroll
+                for (int half = 0; half < 2; ++half) {
+                    // this half of x3 in fp32, point-major, channels in natural order: registers 4q..4q+3 of k-tile kt
+                    // are channels 32kt + 8q + 4h .. +3 of point lane&31
+                    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                    for (int kt = 0; kt < 4; ++kt) {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            f32x4 v;
+                            v[0] = x3[0][4 * half + kt][4 * q + 0];
+                            v[1] = x3[0][4 * half + kt][4 * q + 1];
+                            v[2] = x3[0][4 * half + kt][4 * q + 2];
+                            v[3] = x3[0][4 * half + kt][4 * q + 3];
+                            *reinterpret_cast<f32x4*>(s_x + (lane & 31) * HEAD_SCR_XLD + 32 * kt + 8 * q + 4 * h) = v;
+                        }
+                    }
+                    __builtin_amdgcn_wave_barrier();
+                    for (uint32_t base = 0; base < cnt; base += 64) {
+                        if (half == 1) HSCR_COUNT(4, 1);
+                        const uint32_t idx = base + lane;
+                        const bool live = idx < cnt;
+                        const uint32_t li = live ? idx : 0u;
+                        const uint32_t ent = s_list[li];
+                        const int c = (int)(ent >> 8), p = (int)(ent & 31u);
+                        const f32x4* wr = reinterpret_cast<const f32x4*>(w.w4row + c * 256 + 128 * half);
+                        const f32x4* xr = reinterpret_cast<const f32x4*>(s_x + p * HEAD_SCR_XLD);
+                        float a = half == 0 ? 0.0f : s_part[li];
+#pragma unroll
+                        for (int i = 0; i < 16; ++i) {
+                            const f32x4 w0 = wr[2 * i], w1 = wr[2 * i + 1];
+                            const f32x4 x0 = xr[2 * i], x1 = xr[2 * i + 1];
+#pragma unroll
+                            for (int q = 0; q < 4; ++q) {
+                                a = fmaf(x0[q], w0[q], a);
+                                a = fmaf(x1[q], w1[q], a);
+                            }
+                        }
+                        if (half == 0) {
+                            if (live) s_part[li] = a;
+                        } else {
+                            int bits = __float_as_int(a + s_b4[c]);
+                            bits = bits > 0 ? bits : 0;
+                            if (live && bits > 0) atomicMax(&s_run[c], bits);
+                        }
+                    }
+                }
+            }
+        }
+        const bool more = ncur < n_live;
+        const bool leave = !more || (int64_t)e[0] != b;
+        if (leave) flush(b);                           // (the wave's own LDS operations are in order: no barrier)
+        if (!more) break;
+        if (leave) enter((int64_t)e[0]);
+        cur = ncur;
+        run_end = nend;
+#pragma unroll
+        for (int k = 0; k < KS; ++k) in[0][k] = in_n[0][k];
+    }
+}
+
+hipError_t launch_point_head_screen(int head_kind, const PointHeadW& w, BCN x, int c_in, float* feat, uint32_t* ctl,
+                                    const u32x4* list, int64_t max_tiles, int64_t slots, hipStream_t s) {
+    if (!w.w4row || !w.w4h || !w.scr_pq || !w.scr_flag) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(max_tiles < slots ? max_tiles : slots)), block(64);
+    switch (head_kind) {
+        case 1:
+            hipLaunchKernelGGL((point_head_screen_kernel<2, 128, 128, 256>), grid, block, 0, s, w, x, c_in, feat, ctl, list);
+            break;
+        case 2:
+            hipLaunchKernelGGL((point_head_screen_kernel<2, 64, 128, 256>), grid, block, 0, s, w, x, c_in, feat, ctl, list);
+            break;
+        default:
+            return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}

@@ -102,6 +102,12 @@ struct PointHeadW {
     const float* b4;
     const f32x4* stream; // conv2 | conv3 | conv4 fragment blocks, out-tile major, back to back
     FcW fc;
+    // the screened conv4 (dal3_head_screen.hip, DESIGN.md "Screened conv4 of the point heads"); heads with conv4 256 -> 512
+    // only (static box_est, point_emb), NULL for box_emb
+    const float* w4row;       // row-major (512,256) fp32, folded: one candidate's weights in natural channel order
+    const f32x4* w4h;         // fp16 MFMA fragments [16 out-tiles][8 kt][2 s] of 1 KiB, the 16-bit family's layout
+    const float* scr_pq;      // (512,2): E(c) = X * P_c + Q_c bounds |fp16 score - fp32 chain| for ||x||_2 <= X
+    const int32_t* scr_flag;  // nonzero: a folded conv4 weight is not finite in fp16 -> every tile runs the dense layer
 };
 
 // ---- 16-bit (bf16 / fp16) packed heads: fp32 first layer, biases and FC; MFMA weights as one stream of
@@ -214,6 +220,30 @@ hipError_t launch_ins_seg_decode(const InsSegW& w, BCN pts, int c_in, int B, int
 size_t point_head_worklist_bytes(int B, int M);
 hipError_t launch_point_head(int head_kind, const PointHeadW& w, BCN x, int c_in, int B, int M, float* feat,
                              const int32_t* distinct, hipStream_t s, void* worklist = nullptr, size_t worklist_bytes = 0);
+// The screened route of launch_point_head (dal3_head_screen.hip): the tiles of `list` (ctl[0] entries, ctl[1] = cursor)
+// with conv4 screened against the exact values that the seed launch has left in feat.
+// Seed tiles are the live tiles of an item whose index is a multiple of DAL3_HEAD_SCR_STRIDE. Measured at 4096 x 512
+// object points, the bench mix of distinct counts (profiles/LEDGER_r10.md): the head takes 3.42 / 3.22 / 3.23 / 3.11 ms
+// at 2 / 3 / 4 / 8 against 3.97 ms dense. 8 was the fastest there, but its lists overflow in about 1 % of the tiles (CPU
+// model; capacity 1024 holds the model's maximum up to 4) and the dispatch minimum below was swept at 4 only.
+#ifndef DAL3_HEAD_SCR_STRIDE
+#define DAL3_HEAD_SCR_STRIDE 4
+#endif
+// 0: the dense persistent kernel for every job (A/B builds: make OUT=... EXTRA=-DDAL3_HEAD_SCREEN=0)
+#ifndef DAL3_HEAD_SCREEN
+#define DAL3_HEAD_SCREEN 1
+#endif
+// The screened route is taken from this many 32-point tiles (B * ceil(M / 32)) upward. Measured at stride 4
+// (profiles/LEDGER_r10.md, B x 512 object points, bench mix / every point distinct, us dense -> screened): 4096 tiles
+// 343 -> 348 / 354 -> 383, 6144 tiles 426 -> 482 / 510 -> 545, 8192 tiles 576 -> 523 / 671 -> 669, 16384 tiles
+// 1129 -> 938 / 1376 -> 1325. Below 8192 the second launch and the seed launch's own tail cost more than the screen saves.
+#ifndef DAL3_HEAD_SCR_MIN_TILES
+#define DAL3_HEAD_SCR_MIN_TILES 8192
+#endif
+static_assert(DAL3_HEAD_SCR_STRIDE >= 2, "stride 1 leaves no tile to screen");
+hipError_t launch_point_head_screen(int head_kind, const PointHeadW& w, BCN x, int c_in, float* feat, uint32_t* ctl,
+                                    const u32x4* list, int64_t max_tiles, int64_t slots, hipStream_t s);
+hipError_t launch_pack_head_screen(const dal3_layer& L, float* pq, int32_t* flag, hipStream_t s);
 hipError_t launch_generic_layer(const f32x4* wf, const float* w1, const float* bias, int kt_n, int ks_n, int mt_n,
                                 int relu, BCN x, int c_in, int B, int N, float* y, hipStream_t s);
 
@@ -327,9 +357,10 @@ hipError_t launch_segment_counts(const uint8_t* mask, int B, int N, int32_t* cou
 // captured into a hipGraph (see dal3_misc.hip)
 hipError_t launch_fill_words(void* p, size_t n_words, uint32_t value, hipStream_t s);
 // dst (B, C) = 0, or the quiet-NaN pattern in the rows of items whose input x (B, c_in, n_pts) holds a NaN / Inf
-// distinct / worklist (optional): also build the point heads' worklist (ctl at worklist, entries at worklist + 256)
+// distinct / worklist (optional): also build the point heads' worklist (ctl at worklist, entries at worklist + 256);
+// seed_stride > 0: as two lists, the seed tiles and the others (the screened heads, dal3_head_screen.hip)
 hipError_t launch_nonfinite_rows(BCN x, int B, int n_pts, int c_in, float* dst, int C, hipStream_t s,
-                                 const int32_t* distinct = nullptr, void* worklist = nullptr);
+                                 const int32_t* distinct = nullptr, void* worklist = nullptr, int seed_stride = 0);
 hipError_t launch_compact_sample(const uint8_t* mask, BCN pts, int B, int N, int C, int M, int sampler,
                                  const int32_t* choice, uint64_t seed, int64_t item_offset, int32_t* counts,
                                  int32_t* pos, int32_t* obj_idx, float* obj_pts, hipStream_t s, const int64_t* step = nullptr);

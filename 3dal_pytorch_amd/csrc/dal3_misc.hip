@@ -162,6 +162,29 @@ hipError_t launch_pack_enc_screen(const dal3_layer& L, float* pq, int32_t* flag,
     return hipGetLastError();
 }
 
+// The same coefficients for conv4 (256 -> 512) of the point heads (DESIGN.md "Screened conv4 of the point heads"): K = 256,
+//   P_c = kappa ||w_c||_2 + 2^-24 sqrt(256),  Q_c = 2^-24 ||w_c||_1 + 2^-40,  kappa = 1.02 * 2^-10 + 256 * 2^-23.
+__global__ void pack_head_screen_kernel(dal3_layer L, float* __restrict__ pq, int32_t* __restrict__ flag) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= 512) return;
+    double s2 = 0.0, s1 = 0.0;
+    bool bad = false;
+    for (int k = 0; k < 256; ++k) {
+        const float v = folded_w(L, c, k, 0, 256);
+        bad |= !(fabsf(v) < 65504.0f);
+        s2 += (double)v * (double)v;
+        s1 += fabs((double)v);
+    }
+    const double kappa = 1.02 * 0x1p-10 + 256.0 * 0x1p-23;
+    pq[2 * c] = (float)((kappa * sqrt(s2) + 0x1p-24 * 16.0) * (1.0 + 1e-6));
+    pq[2 * c + 1] = (float)((0x1p-24 * s1 + 0x1p-40) * (1.0 + 1e-6));
+    if (bad) atomicOr(flag, 1);
+}
+hipError_t launch_pack_head_screen(const dal3_layer& L, float* pq, int32_t* flag, hipStream_t s) {
+    hipLaunchKernelGGL(pack_head_screen_kernel, dim3(2), dim3(256), 0, s, L, pq, flag);
+    return hipGetLastError();
+}
+
 // The compacted dconv2's weight copy (dal3_kernels.h::InsSegW::dw2c) and its guard: skipping a dead channel's term is
 // exact only while 0 * w is a zero (w finite) and no accumulator chain starts from -0 (DESIGN.md "Compacted dconv2").
 __global__ void pack_dec_sparse_kernel(dal3_layer L, const float* __restrict__ db2, float* __restrict__ out,
@@ -802,7 +825,8 @@ __global__ __launch_bounds__(256) void fill_words_kernel(uint32_t* __restrict__ 
 // thread at B = 4096) — deterministic, no atomics, nothing to zero beforehand, and no launch of its own.
 __global__ __launch_bounds__(256) void nonfinite_rows_kernel(BCN x, int n_pts, int c_in, uint32_t* __restrict__ dst, int C,
                                                              const int32_t* __restrict__ distinct,
-                                                             uint32_t* __restrict__ ctl, u32x4* __restrict__ list) {
+                                                             uint32_t* __restrict__ ctl, u32x4* __restrict__ list,
+                                                             int seed_stride) {
     __shared__ int lds_wave[8];
     const int64_t b = blockIdx.x;
     if (list) {
@@ -811,21 +835,56 @@ __global__ __launch_bounds__(256) void nonfinite_rows_kernel(BCN x, int n_pts, i
             const int d = distinct[i];
             return d <= 0 ? 1 : (d < n_pts ? d : n_pts);
         };
-        int before = 0;
-        for (int i = threadIdx.x; i < (int)b; i += 256) before += (eff(i) + 31) >> 5;
-        before = block_sum(before, lds_wave);
         const int n_eff = eff((int)b), n_t = (n_eff + 31) >> 5;
-        for (int t = threadIdx.x; t < n_t; t += 256) {
-            u32x4 e;
-            e[0] = (uint32_t)b;
-            e[1] = (uint32_t)t;
-            e[2] = (uint32_t)n_eff;
-            e[3] = 0u;
-            list[before + t] = e;
-        }
-        if (b == gridDim.x - 1 && threadIdx.x == 0) {
-            ctl[0] = (uint32_t)(before + n_t);
-            ctl[1] = 0u;
+        if (seed_stride <= 0) {
+            int before = 0;
+            for (int i = threadIdx.x; i < (int)b; i += 256) before += (eff(i) + 31) >> 5;
+            before = block_sum(before, lds_wave);
+            for (int t = threadIdx.x; t < n_t; t += 256) {
+                u32x4 e;
+                e[0] = (uint32_t)b;
+                e[1] = (uint32_t)t;
+                e[2] = (uint32_t)n_eff;
+                e[3] = 0u;
+                list[before + t] = e;
+            }
+            if (b == gridDim.x - 1 && threadIdx.x == 0) {
+                ctl[0] = (uint32_t)(before + n_t);
+                ctl[1] = 0u;
+            }
+        } else {
+            // TWO lists for the screened heads (dal3_head_screen.hip): the SEED tiles of an item — index a multiple of
+            // seed_stride, tile 0 always — from list[0], every other live tile from list[B * ceil(tiles / stride)], the
+            // most seeds the batch can have: both fit the bytes point_head_worklist_bytes reserves. Both item-major.
+            // ctl[0], ctl[1]: seed entries and their cursor; ctl[2], ctl[3]: the others'.
+            const int S = seed_stride;
+            int seeds = 0, others = 0;
+            for (int i = threadIdx.x; i < (int)b; i += 256) {
+                const int t = (eff(i) + 31) >> 5, sd = (t + S - 1) / S;
+                seeds += sd;
+                others += t - sd;
+            }
+            seeds = block_sum(seeds, lds_wave);
+            __syncthreads();                               // (lds_wave is used again)
+            others = block_sum(others, lds_wave);
+            const int tiles_max = (n_pts + 31) >> 5;
+            u32x4* const list2 = list + (size_t)gridDim.x * ((tiles_max + S - 1) / S);
+            const int n_s = (n_t + S - 1) / S;
+            for (int t = threadIdx.x; t < n_t; t += 256) {
+                u32x4 e;
+                e[0] = (uint32_t)b;
+                e[1] = (uint32_t)t;
+                e[2] = (uint32_t)n_eff;
+                e[3] = 0u;
+                if (t % S == 0) list[seeds + t / S] = e;
+                else list2[others + t - t / S - 1] = e;
+            }
+            if (b == gridDim.x - 1 && threadIdx.x == 0) {
+                ctl[0] = (uint32_t)(seeds + n_s);
+                ctl[1] = 0u;
+                ctl[2] = (uint32_t)(others + n_t - n_s);
+                ctl[3] = 0u;
+            }
         }
     }
     const int64_t base = b * x.sb;
@@ -873,11 +932,11 @@ __global__ __launch_bounds__(256) void nonfinite_rows_kernel(BCN x, int n_pts, i
     for (int c = threadIdx.x; c < C; c += 256) dst[b * C + c] = v;
 }
 hipError_t launch_nonfinite_rows(BCN x, int B, int n_pts, int c_in, float* dst, int C, hipStream_t s, const int32_t* distinct,
-                                 void* worklist) {
+                                 void* worklist, int seed_stride) {
     uint32_t* ctl = static_cast<uint32_t*>(worklist);
     u32x4* list = worklist ? reinterpret_cast<u32x4*>(static_cast<char*>(worklist) + 256) : nullptr;
     hipLaunchKernelGGL(nonfinite_rows_kernel, dim3((unsigned)B), dim3(256), 0, s, x, n_pts, c_in,
-                       reinterpret_cast<uint32_t*>(dst), C, distinct, ctl, list);
+                       reinterpret_cast<uint32_t*>(dst), C, distinct, ctl, list, seed_stride);
     return hipGetLastError();
 }
 

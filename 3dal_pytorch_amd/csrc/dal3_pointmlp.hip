@@ -710,15 +710,22 @@ hipError_t launch_point_head(int head_kind, const PointHeadW& w, BCN x, int c_in
     const int tpi = (M + 32 * T - 1) / (32 * T);       // one-wave workgroups
     const bool lat = lat_use((int64_t)B * ((M + 31) / 32), x.flags, DAL3_LAT_MAX_TILES_HEAD);
     const bool pers = !lat && worklist && worklist_bytes >= point_head_worklist_bytes(B, M) && !(x.flags & DAL3_BCN_NO_WORKLIST) && T == 1;
+    // conv4 screened (dal3_head_screen.hip): the persistent route of a head with conv4 256 -> 512 from
+    // DAL3_HEAD_SCR_MIN_TILES tiles upward, and items of more than one seed's worth of tiles
+    const bool screen = DAL3_HEAD_SCREEN && pers && (head_kind == 1 || head_kind == 2) && w.w4row &&
+                        (int64_t)B * tpi >= DAL3_HEAD_SCR_MIN_TILES && tpi > 1;
     // feat = 0 (NaN rows for items with a non-finite input, dal3.h) and, for the persistent kernel, the worklist
-    hipError_t e0 = launch_nonfinite_rows(x, B, M, c_in, feat, 512, s, distinct, pers ? worklist : nullptr);
+    hipError_t e0 = launch_nonfinite_rows(x, B, M, c_in, feat, 512, s, distinct, pers ? worklist : nullptr,
+                                          screen ? DAL3_HEAD_SCR_STRIDE : 0);
     if (e0 != hipSuccess) return e0;
     if (lat) return launch_point_head_lat(head_kind, w, x, c_in, B, M, feat, distinct, s);
     if (pers) {
         uint32_t* ctl = static_cast<uint32_t*>(worklist);
         u32x4* list = reinterpret_cast<u32x4*>(static_cast<char*>(worklist) + 256);
-        const int64_t tiles = (int64_t)B * tpi;            // (an upper bound: the list holds the live tiles only; a wave beyond it exits)
         const int64_t slots = head_slots();
+        // (tile counts are upper bounds: the lists hold the live tiles only; a wave beyond its list exits)
+        const int64_t seed_tpi = (tpi + DAL3_HEAD_SCR_STRIDE - 1) / DAL3_HEAD_SCR_STRIDE;
+        const int64_t tiles = screen ? (int64_t)B * seed_tpi : (int64_t)B * tpi;
         const dim3 grid((unsigned)(tiles < slots ? tiles : slots)), block(64);
         switch (head_kind) {
             case 1:
@@ -733,7 +740,11 @@ hipError_t launch_point_head(int head_kind, const PointHeadW& w, BCN x, int c_in
             default:
                 return hipErrorInvalidValue;
         }
-        return hipGetLastError();
+        hipError_t e1 = hipGetLastError();
+        if (e1 != hipSuccess || !screen) return e1;
+        // the seed launch above has left exact maxima in feat (same stream): the other live tiles, screened against them
+        return launch_point_head_screen(head_kind, w, x, c_in, feat, ctl + 2, list + (size_t)B * seed_tpi,
+                                        (int64_t)B * (tpi - seed_tpi), slots, s);
     }
     const dim3 grid((unsigned)((int64_t)B * tpi)), block(64);
     switch (head_kind) {

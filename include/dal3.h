@@ -206,6 +206,11 @@ size_t dal3_point_head_pool_workspace_bytes(int B, int M);
 int dal3_point_head_pool(int head_kind, const void* packed, int dtype, dal3_bcn x, int B, int M,
                          const int32_t* n_distinct, float* feat, void* workspace, size_t workspace_bytes,
                          dal3_stream stream);
+/* How the fp32 static box_est / point_emb heads take their screened route (conv4 on the fp16 MFMA, candidates
+ * recomputed exactly: same bits): with a workspace, from this many 32-point tiles (B * ceil(M / 32)) upward; every
+ * `stride`-th live tile of an item is its dense seed. Dispatch facts for tests and measurements. */
+int dal3_point_head_screen_min_tiles(void);
+int dal3_point_head_screen_stride(void);
 
 /* ---- dynamic PointNetEstimation.forward (dynamic_model.py:300-312): (B,384) -> (B,39). */
 int dal3_dynamic_box_est_forward(const void* packed, const float* embedding, int B, float* box_pred,
