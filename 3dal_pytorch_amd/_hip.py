@@ -267,6 +267,36 @@ class SpConvArgs(C.Structure):
                 ("max_workgroups", C.c_int64)]
 
 
+ROI_OVERFLOW = 4096
+ROI_MAX_TASKS, ROI_MAX_WIDTH = 16, 256
+_f2 = C.c_float * 2
+
+
+class BevGatherArgs(C.Structure):
+    """dal3_bev_gather_args"""
+    _fields_ = [("B", C.c_int64), ("H", C.c_int64), ("W", C.c_int64), ("C", C.c_int32), ("sample_index", C.c_int32), ("map", Map),
+                ("n", C.c_int64), ("xy", vp), ("xy_stride", C.c_int64), ("sample", vp), ("pc_start", _f2), ("voxel_size", _f2),
+                ("out_stride", C.c_float), ("points_per_row", C.c_int32), ("out", vp), ("out_row_stride", C.c_int64),
+                ("out_col_offset", C.c_int64)]
+
+
+class RoiShape(C.Structure):
+    """dal3_roi_shape"""
+    _fields_ = [("c_in", C.c_int32), ("n_shared", C.c_int32), ("n_cls", C.c_int32), ("n_reg", C.c_int32), ("shared", _i3),
+                ("cls", _i3), ("reg", _i3), ("num_class", C.c_int32), ("code_size", C.c_int32)]
+
+
+class RoiHeadArgs(C.Structure):
+    """dal3_roi_head_args"""
+    _fields_ = [("shape", RoiShape), ("packed", vp), ("B", C.c_int64), ("M", C.c_int64), ("num_point", C.c_int32), ("C", C.c_int32),
+                ("T", C.c_int32), ("box_cols", C.c_int32), ("K", C.c_int64), ("keep_stride", C.c_int64), ("boxes", vp), ("scores", vp),
+                ("labels", vp), ("keep", vp), ("keep_count", vp), ("seg_offsets", vp), ("label_base", C.c_int32 * ROI_MAX_TASKS),
+                ("bev", Map), ("H", C.c_int64), ("W", C.c_int64), ("pc_start", _f2), ("voxel_size", _f2), ("out_stride", C.c_float),
+                ("rois", vp), ("roi_scores", vp), ("roi_features", vp), ("out_boxes", vp), ("out_scores", vp), ("out_labels", vp),
+                ("out_counts", vp), ("out_features", vp), ("box_preds", vp), ("cls_preds", vp), ("status", vp), ("workspace", vp),
+                ("workspace_bytes", C.c_size_t)]
+
+
 # every symbol include/dal3.h declares: (restype, argtypes)
 _i, _i64, _u64, _sz = C.c_int, C.c_int64, C.c_uint64, C.c_size_t
 SIGNATURES = {
@@ -338,6 +368,13 @@ SIGNATURES = {
     "dal3_sp_conv_pack_floats": (_sz, [_i, _i, _i]),
     "dal3_sp_conv_pack": (_i, [C.POINTER(Layer), _i, C.c_double, vp, vp, vp]),
     "dal3_sp_conv": (_i, [C.POINTER(SpConvArgs), vp]),
+    "dal3_bev_gather": (_i, [C.POINTER(BevGatherArgs), vp]),
+    "dal3_box_points": (_i, [vp, _i64, _i, _i, vp, vp]),
+    "dal3_roi_pack_floats": (_sz, [C.POINTER(RoiShape)]),
+    "dal3_roi_pack": (_i, [C.POINTER(RoiShape), C.POINTER(Layer), _i, C.POINTER(C.c_double), vp, vp]),
+    "dal3_roi_head_workspace_bytes": (_sz, [_i64, _i64, _i, _i, _i]),
+    "dal3_roi_head": (_i, [C.POINTER(RoiHeadArgs), vp]),
+    "dal3_roi_post": (_i, [vp, vp, vp, _i64, _i, vp, vp, vp]),
     "dal3_crop_workspace_bytes": (_sz, [_i64, _i64]),
     "dal3_crop_count": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, _sz, vp]),
     "dal3_crop_fill": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, vp, vp, vp, _i64, vp, _sz, vp]),

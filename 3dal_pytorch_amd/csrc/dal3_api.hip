@@ -2369,3 +2369,107 @@ extern "C" int dal3_dynamic_forward(const dal3_dynamic_args* a, int phases, dal3
                  ws.head.t1, ws.head.t2, s, &dd));
     return 0;
 }
+
+// ---------------------------------------------------------------------------------- CenterPoint's second stage
+static bool map_dims_ok(int64_t B, int64_t H, int64_t W) { return B >= 0 && H >= 1 && W >= 1 && B <= 65535 && H <= 65535 && W <= 65535; }
+
+extern "C" int dal3_bev_gather(const dal3_bev_gather_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "bev_gather: null args");
+    const dal3_bev_gather_args& a = *args;
+    if (!map_dims_ok(a.B, a.H, a.W) || a.C < 1 || a.C > 65535) return fail(DAL3_EINVAL, "bev_gather: bad B / H / W (<= 65535) / C (1 .. 65535)");
+    if (a.n < 0 || a.n > DAL3_MAX_ITEMS) return fail(DAL3_EINVAL, "bev_gather: bad n (0 .. DAL3_MAX_ITEMS)");
+    if (a.points_per_row < 1 || a.points_per_row > 5) return fail(DAL3_EINVAL, "bev_gather: points_per_row %d (1 .. 5)", (int)a.points_per_row);
+    if (a.xy_stride < 2 || a.out_col_offset < 0 || a.out_row_stride < a.out_col_offset + (int64_t)a.points_per_row * a.C)
+        return fail(DAL3_EINVAL, "bev_gather: xy_stride < 2, or the sections do not fit into a row of out_row_stride floats");
+    if (!a.sample && (a.sample_index < 0 || (a.sample_index >= a.B && a.n > 0)))
+        return fail(DAL3_EINVAL, "bev_gather: sample_index %d outside the %lld samples", (int)a.sample_index, (long long)a.B);
+    if (a.n > 0 && (!a.map.data || !a.xy || !a.out)) return fail(DAL3_EINVAL, "bev_gather: null map / xy / out");
+    if (!(a.voxel_size[0] > 0.f) || !(a.voxel_size[1] > 0.f) || !(a.out_stride > 0.f))
+        return fail(DAL3_EINVAL, "bev_gather: voxel_size and out_stride must be positive");
+    HIP_TRY(launch_bev_gather(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+extern "C" int dal3_box_points(const float* boxes, int64_t n, int cols, int num_point, float* out, dal3_stream stream) {
+    if (n < 0 || n > DAL3_MAX_ITEMS || (cols != 7 && cols != 9) || (num_point != 1 && num_point != 5))
+        return fail(DAL3_EINVAL, "box_points: bad n / cols (7 or 9) / num_point (1 or 5)");
+    if (n > 0 && (!boxes || !out)) return fail(DAL3_EINVAL, "box_points: null boxes / out");
+    HIP_TRY(launch_box_points(boxes, n, cols, num_point, out, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+extern "C" size_t dal3_roi_pack_floats(const dal3_roi_shape* shape) { return shape ? roi_pack_floats(shape) : 0; }
+
+extern "C" int dal3_roi_pack(const dal3_roi_shape* shape, const dal3_layer* layers, int n_layers, const double* eps, float* out,
+                             dal3_stream stream) {
+    if (!shape || !layers || !out) return fail(DAL3_EINVAL, "roi_pack: null shape / layers / out");
+    const int want = roi_layers(shape);
+    if (want == 0)
+        return fail(DAL3_EINVAL, "roi_pack: the shape is not served (1 .. 3 layers a list, widths multiples of 16 up to %d, "
+                    "num_class 1, code_size 7 or 9)", DAL3_ROI_MAX_WIDTH);
+    if (n_layers != want) return fail(DAL3_EINVAL, "roi_pack: %d layers given, the shape has %d", n_layers, want);
+    if (reinterpret_cast<uintptr_t>(out) & 15) return fail(DAL3_EINVAL, "roi_pack: out must be 16-byte aligned");
+    for (int i = 0; i < n_layers; ++i) {
+        const dal3_layer& L = layers[i];
+        int c_in, c_out;
+        roi_layer_dims(shape, i, &c_in, &c_out);
+        if (L.c_in != c_in || L.c_out != c_out)
+            return fail(DAL3_EINVAL, "roi_pack: layer %d is %d -> %d, the shape says %d -> %d", i, (int)L.c_in, (int)L.c_out, c_in, c_out);
+        if (!L.weight) return fail(DAL3_EINVAL, "roi_pack: layer %d has no weight", i);
+        const bool bn = L.bn_weight || L.bn_bias || L.bn_mean || L.bn_var;
+        if (bn && !(L.bn_weight && L.bn_bias && L.bn_mean && L.bn_var))
+            return fail(DAL3_EINVAL, "roi_pack: a BatchNorm needs all four of weight, bias, mean and var");
+        if (bn && !(eps && eps[i] > 0.0)) return fail(DAL3_EINVAL, "roi_pack: layer %d needs its BatchNorm's eps (> 0)", i);
+    }
+    HIP_TRY(launch_roi_pack(shape, layers, eps, out, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+static bool roi_dims_ok(int64_t B, int64_t M, int num_point, int C, int code_size) {
+    return B >= 0 && M >= 0 && B <= 65535 && B * M <= (1 << 24) && (num_point == 1 || num_point == 5) && C >= 1 && C <= 65535 &&
+           (code_size == 7 || code_size == 9);
+}
+
+extern "C" size_t dal3_roi_head_workspace_bytes(int64_t B, int64_t M, int num_point, int C, int code_size) {
+    if (!roi_dims_ok(B, M, num_point, C, code_size)) return 0;
+    return roi_head_workspace_bytes(B, M, num_point, C, code_size);
+}
+
+extern "C" int dal3_roi_head(const dal3_roi_head_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "roi_head: null args");
+    const dal3_roi_head_args& a = *args;
+    if (roi_layers(&a.shape) == 0) return fail(DAL3_EINVAL, "roi_head: the shape is not served (see dal3_roi_pack)");
+    const int code = a.shape.code_size;
+    if (!roi_dims_ok(a.B, a.M, a.num_point, a.C, code)) return fail(DAL3_EINVAL, "roi_head: bad B / M (B * M <= 2^24) / num_point (1 or 5) / C");
+    if ((int64_t)a.num_point * a.C != a.shape.c_in)
+        return fail(DAL3_EINVAL, "roi_head: num_point * C = %lld, the head takes %d inputs", (long long)a.num_point * a.C, (int)a.shape.c_in);
+    if (!a.packed || (reinterpret_cast<uintptr_t>(a.packed) & 15)) return fail(DAL3_EINVAL, "roi_head: packed is null or not 16-byte aligned");
+    const bool any = a.B > 0 && a.M > 0;
+    if (a.keep) {
+        if (a.T < 1 || a.T > DAL3_ROI_MAX_TASKS) return fail(DAL3_EINVAL, "roi_head: T %d (1 .. %d)", (int)a.T, DAL3_ROI_MAX_TASKS);
+        if (a.box_cols != code) return fail(DAL3_EINVAL, "roi_head: boxes of %d columns for code_size %d", (int)a.box_cols, code);
+        if (a.K < 0 || a.keep_stride < 0) return fail(DAL3_EINVAL, "roi_head: bad K / keep_stride");
+        if (!map_dims_ok(a.B, a.H, a.W)) return fail(DAL3_EINVAL, "roi_head: bad H / W (1 .. 65535)");
+        if (!(a.voxel_size[0] > 0.f) || !(a.voxel_size[1] > 0.f) || !(a.out_stride > 0.f))
+            return fail(DAL3_EINVAL, "roi_head: voxel_size and out_stride must be positive");
+        if (!a.keep_count || !a.seg_offsets || !a.status || (any && (!a.bev.data || (a.K > 0 && (!a.boxes || !a.scores || !a.labels)))))
+            return fail(DAL3_EINVAL, "roi_head: null pointer in the fused form");
+        if (any && (!a.workspace || (reinterpret_cast<uintptr_t>(a.workspace) & 7))) return fail(DAL3_EINVAL, "roi_head: workspace is null or misaligned");
+    } else if (any && (!a.rois || !a.roi_scores || !a.roi_features)) {
+        return fail(DAL3_EINVAL, "roi_head: the direct form needs rois, roi_scores and roi_features");
+    }
+    hipError_t e = hipSuccess;
+    if (!launch_roi_head(args, static_cast<hipStream_t>(stream), &e))
+        return fail(DAL3_EWORKSPACE, "roi_head: workspace of %zu bytes, %zu needed", a.workspace_bytes,
+                    roi_head_workspace_bytes(a.B, a.M, a.num_point, a.C, code));
+    HIP_TRY(e);
+    return 0;
+}
+
+extern "C" int dal3_roi_post(const float* box_preds, const float* cls_preds, const float* roi_scores, int64_t n, int code_size,
+                             float* out_boxes, float* out_scores, dal3_stream stream) {
+    if (n < 0 || n > (1 << 24) || (code_size != 7 && code_size != 9)) return fail(DAL3_EINVAL, "roi_post: bad n / code_size (7 or 9)");
+    if (n > 0 && (!box_preds || !cls_preds || !roi_scores)) return fail(DAL3_EINVAL, "roi_post: null input");
+    HIP_TRY(launch_roi_post(box_preds, cls_preds, roi_scores, n, code_size, out_boxes, out_scores, static_cast<hipStream_t>(stream)));
+    return 0;
+}

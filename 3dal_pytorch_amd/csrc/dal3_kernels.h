@@ -547,4 +547,14 @@ hipError_t launch_tr_act_dropout(const float* x, int64_t M, int C, int64_t ldx, 
 hipError_t launch_tr_segmax(const float* z, int64_t ldz, int64_t seg, int C, const float* scale, const float* shift,
                             float* g, int32_t* arg, int64_t n_seg, unsigned long long* packed, hipStream_t s);
 hipError_t launch_tr_segsum(const float* x, int64_t ldx, int64_t seg, int C, float* out, int64_t n_seg, hipStream_t s);
-
+// CenterPoint's second stage (dal3_roi.hip): BEV point features, the RoI head's fused MLP and box prediction
+hipError_t launch_bev_gather(const dal3_bev_gather_args* a, hipStream_t s);
+hipError_t launch_box_points(const float* boxes, int64_t n, int cols, int num_point, float* out, hipStream_t s);
+size_t roi_pack_floats(const dal3_roi_shape* shape);
+int roi_layers(const dal3_roi_shape* shape);
+void roi_layer_dims(const dal3_roi_shape* shape, int i, int* c_in, int* c_out);
+hipError_t launch_roi_pack(const dal3_roi_shape* shape, const dal3_layer* layers, const double* eps, float* out, hipStream_t s);
+size_t roi_head_workspace_bytes(int64_t B, int64_t M, int num_point, int C, int code_size);
+hipError_t launch_roi_post(const float* box_preds, const float* cls_preds, const float* roi_scores, int64_t n, int code_size,
+                           float* out_boxes, float* out_scores, hipStream_t s);
+bool launch_roi_head(const dal3_roi_head_args* a, hipStream_t s, hipError_t* err);

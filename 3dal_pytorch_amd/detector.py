@@ -10,8 +10,9 @@ raw sweep instead: voxelise -> pillar features into the canvas -> RPN -> CenterH
 the current stream; the read-back of the kept boxes inside `predict` is the only host synchronisation. A `test_cfg` with
 `double_flip` (test-time augmentation) is served by both: `forward` takes the reference's batch of four views per sample,
 `detect` makes the views itself. The loss is not built: `return_loss=True` is refused. `VoxelNet` has the same two doors
-with the 3-D grid, VoxelFeatureExtractorV3 and the sparse middle (sparse.SpMiddleResNetFHD) in front of the neck; its
-second stage (`forward_two_stage`) is not built.
+with the 3-D grid, VoxelFeatureExtractorV3 and the sparse middle (sparse.SpMiddleResNetFHD) in front of the neck.
+`forward_two_stage` stays refused: the two-stage model is two_stage.TwoStageDetector, which wraps either detector, runs
+its stages up to the head itself and keeps the kept boxes on the device for the RoI head.
 """
 import torch
 from torch import nn
@@ -150,7 +151,8 @@ class VoxelNet(SingleStageDetector):
         return self.bbox_head.predict(example, self.bbox_head(x), self.test_cfg)
 
     def forward_two_stage(self, example, return_loss=False, **kwargs):
-        raise NotImplementedError("VoxelNet.forward_two_stage: the second stage is not built")
+        raise NotImplementedError("VoxelNet.forward_two_stage: the second stage is not built into this method: two_stage."
+                                  "TwoStageDetector runs the first stage through extract_feat and bbox_head itself")
 
     @torch.no_grad()
     def detect(self, points, point_offsets, metadata=None, point_offsets_device=None):

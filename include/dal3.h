@@ -1523,6 +1523,138 @@ size_t dal3_dynamic_workspace_bytes(int B, int N, int n_box);
 /* DynamicModel.forward (dynamic_model.py:121-155) + decode (dynamic_eval.py:226-242) */
 int dal3_dynamic_forward(const dal3_dynamic_args* args, int phases, dal3_stream stream);
 
+/* ---- CenterPoint's second stage (det3d/models/detectors/two_stage.py, second_stage/bird_eye_view.py,
+ * roi_heads/roi_head.py, roi_head_template.py): the BEV point features and the RoI head, float32, eval mode.
+ * (Additions only; DAL3_VERSION stays, as for the entries above.)
+ *
+ * dal3_bev_gather: bilinear_interpolate_torch (det3d/core/utils/center_utils.py:92) of a BEV map at n points. The map is
+ * a float32 (B, H, W, C) view by ELEMENT strides (dal3_map): the neck's NCHW tensor as it is, or an NHWC one; no copy of
+ * the map is made. Point i has the absolute coordinates xy[i * xy_stride + {0, 1}] and lies in sample sample[i]
+ * (sample NULL: every point in sample_index). Every operation a separately rounded float32 one, in this order:
+ *   x = ((abs_x - pc_start[0]) / voxel_size[0]) / out_stride   (IEEE divisions, no reciprocal, no contraction), y likewise;
+ *   x0 = floor(x), x1 = x0 + 1, both clamped to [0, W - 1]; y0, y1 likewise to [0, H - 1] (the clamp is done in float
+ *   before the conversion to an index, fmax first: a NaN lands on index 0, so no coordinate reads outside the map);
+ *   wa = (x1 - x) * (y1 - y), wb = (x1 - x) * (y - y0), wc = (x - x0) * (y1 - y), wd = (x - x0) * (y - y0) from the
+ *   CLAMPED x0, x1, y0, y1;
+ *   out[c] = ((map[y0, x0, c] * wa + map[y1, x0, c] * wb) + map[y0, x1, c] * wc) + map[y1, x1, c] * wd.
+ * Everything outside the map, and on the lines x = W - 1 and y = H - 1, therefore comes out as 0 * I (two equal clamped
+ * neighbours), and the result is discontinuous at coordinate 0 and at W - 1 (H - 1): the reference's behaviour, kept.
+ * Point i writes C floats at out[(i / points_per_row) * out_row_stride + out_col_offset + (i % points_per_row) * C]:
+ * with points_per_row 1 a call fills one section of a wider row, so the five points' sections land side by side without
+ * a cat. A point whose sample lies outside [0, B) writes nothing. Outside the contract: non-finite coordinates (their
+ * values; the reads stay in bounds) and relative coordinates beyond +-2^31 (the reference converts to int64 first).
+ * H, W <= 65535, 1 <= C <= 65535, 1 <= points_per_row <= 5. Invalid arguments return DAL3_EINVAL and nothing is launched.
+ *
+ * dal3_box_points: TwoStageDetector.get_box_center for n boxes of `cols` (7 or 9) columns [x, y, z, dx, dy, ..., rot]
+ * (the rotation is the LAST column): out (num_point * n, 3), section p at rows [p * n, (p + 1) * n): the centre, then
+ * the front, back, left and right mid-edges ((c0 + c1) / 2, (c2 + c3) / 2, (c0 + c3) / 2, (c1 + c2) / 2) of
+ * center_to_corner_box2d's corners c_k = rotation_2d((dx, dy) * ((-,-), (-,+), (+,+), (+,-)) / 2, rot) + (x, y), with
+ * rotation_2d(p) = (p.x cos + p.y sin, -p.x sin + p.y cos); z is the box's. num_point 1 or 5.
+ *
+ * The RoI head. A dal3_roi_shape names the network: c_in = num_point * C inputs; n_shared / n_cls / n_reg (1 .. 3 each)
+ * layers Conv1d(k = 1, no bias) + BatchNorm1d + ReLU of the widths shared[] / cls[] / reg[] (multiples of 16, <= 256), and
+ * the two final biased Conv1d to num_class (1) and code_size (7 or 9) outputs; Dropout is the identity. dal3_roi_pack
+ * takes the layers in the order shared, cls (its final layer last), reg (likewise), n_layers = n_shared + n_cls + n_reg
+ * + 2, with eps[i] the BatchNorm's own (ignored for a layer without one), and folds in float64, every operation
+ * rounded by itself, one rounding to float32, by the formula of dal3_conv2d_pack above: scale = g / sqrt(var + eps),
+ * W' = W * scale, b' = (bias - mean) * scale + beta. out: dal3_roi_pack_floats(shape) floats (0 for a shape that is not
+ * served), 16-byte aligned.
+ *
+ * dal3_roi_head, the fused form (keep != NULL): from CenterHeadPost's device results (dal3_center_decode + dal3_nms: boxes
+ * (K, box_cols), scores, labels, keep (F, keep_stride), keep_count (F), seg_offsets (F + 1), segment f = task * B +
+ * sample, F = T * B) to the refined boxes, enqueued on the stream, nothing read back. Per sample b and slot m < M:
+ *   (a) the slot's kept row: tasks in order, keep order within a task (row = seg_offsets[f] + keep[f][j]);
+ *       out_counts[b] = min(kept, M); a sample with more kept rows than M sets DAL3_ROI_OVERFLOW in *status and nothing is
+ *       written past M. A keep_count beyond keep_stride or a row outside [0, K) sets DAL3_NMS_BAD_SEGMENT and the slot is
+ *       treated as empty. out_labels[b][m] = labels[row] + label_base[task]. Slots past the count are not computed and
+ *       their outputs are not written.
+ *   (b) the num_point points of dal3_box_points;  (c) dal3_bev_gather of them into the (num_point * C) feature row
+ *       (out_features (B, M, num_point * C), optional: NULL keeps the rows in the workspace);
+ *   (d) the MLP on the fp32 MFMA (output channels on its rows, 32 RoIs on its columns; the first layer's sum in chunks
+ *       of 64 inputs, each chunk from zero; the summation order is not part of the definition, results are judged
+ *       against a float64 evaluation, tests/roi_ref.py). Activations stay in LDS between the layers;
+ *   (e) generate_predicted_boxes: roi = the box with the rotation moved to column 6 (code 9: columns [0..5, 8, 6, 7]);
+ *       pred = reg + roi with its xyz zeroed; columns 0:3 rotated about z by roi[6] (x' = x cos + y sin, y' = -x sin +
+ *       y cos, the reference's matrix); + the roi's xyz; the velocity is not rotated, the heading not wrapped;
+ *   (f) post_process: out_scores = sqrt(sigmoid(cls) * score), out_boxes (B, M, code_size) with the rotation moved back
+ *       to the last column (code 9: [0..5, 7, 8, 6]).
+ * box_preds (B, M, code_size) / cls_preds (B, M), optional, receive (e)'s boxes before (f)'s reordering and the raw cls.
+ * The direct form (keep == NULL) is RoIHead.forward: rois (B, M, code_size), roi_scores (B, M) and roi_features (B, M,
+ * num_point * C) are given, every slot is computed, and steps (d) .. (f) write whichever of the outputs are not NULL.
+ * dal3_roi_post is step (f) alone on n rows. box_cols must equal code_size; T <= DAL3_ROI_MAX_TASKS; B * M <= 2^24.
+ * workspace: dal3_roi_head_workspace_bytes (0 for bad arguments). Anything else returns DAL3_EINVAL and launches nothing. */
+enum { DAL3_ROI_OVERFLOW = 4096 };       /* status bit, numbered beside DAL3_SP_* */
+#define DAL3_ROI_MAX_TASKS 16
+#define DAL3_ROI_MAX_WIDTH 256
+
+typedef struct dal3_bev_gather_args {
+    int64_t B, H, W;
+    int32_t C;
+    int32_t sample_index;                /* every point's sample when `sample` is NULL */
+    dal3_map map;
+    int64_t n;                           /* points */
+    const float* xy;
+    int64_t xy_stride;                   /* floats between two points (>= 2) */
+    const int32_t* sample;               /* (n) or NULL */
+    float pc_start[2], voxel_size[2], out_stride;
+    int32_t points_per_row;              /* 1 .. 5 */
+    float* out;
+    int64_t out_row_stride, out_col_offset;   /* in floats */
+} dal3_bev_gather_args;
+
+typedef struct dal3_roi_shape {
+    int32_t c_in;                        /* num_point * C */
+    int32_t n_shared, n_cls, n_reg;      /* 1 .. 3 */
+    int32_t shared[3], cls[3], reg[3];
+    int32_t num_class;                   /* 1 */
+    int32_t code_size;                   /* 7 or 9 */
+} dal3_roi_shape;
+
+typedef struct dal3_roi_head_args {
+    dal3_roi_shape shape;
+    const float* packed;                 /* dal3_roi_pack's */
+    int64_t B, M;
+    int32_t num_point, C;
+    /* the fused form */
+    int32_t T, box_cols;
+    int64_t K, keep_stride;
+    const float* boxes;
+    const float* scores;
+    const int32_t* labels;
+    const int32_t* keep;
+    const int32_t* keep_count;
+    const int64_t* seg_offsets;          /* device */
+    int32_t label_base[DAL3_ROI_MAX_TASKS];
+    dal3_map bev;
+    int64_t H, W;
+    float pc_start[2], voxel_size[2], out_stride;
+    /* the direct form */
+    const float* rois;
+    const float* roi_scores;
+    const float* roi_features;
+    /* outputs, each optional */
+    float* out_boxes;                    /* (B, M, code_size) */
+    float* out_scores;                   /* (B, M) */
+    int32_t* out_labels;                 /* (B, M); fused form */
+    int32_t* out_counts;                 /* (B); fused form */
+    float* out_features;                 /* (B, M, num_point * C); fused form */
+    float* box_preds;                    /* (B, M, code_size) */
+    float* cls_preds;                    /* (B, M) */
+    int32_t* status;                     /* (1) OR-ed; fused form */
+    void* workspace;
+    size_t workspace_bytes;
+} dal3_roi_head_args;
+
+int dal3_bev_gather(const dal3_bev_gather_args* args, dal3_stream stream);
+int dal3_box_points(const float* boxes, int64_t n, int cols, int num_point, float* out, dal3_stream stream);
+size_t dal3_roi_pack_floats(const dal3_roi_shape* shape);
+int dal3_roi_pack(const dal3_roi_shape* shape, const dal3_layer* layers, int n_layers, const double* eps, float* out,
+                  dal3_stream stream);
+size_t dal3_roi_head_workspace_bytes(int64_t B, int64_t M, int num_point, int C, int code_size);
+int dal3_roi_head(const dal3_roi_head_args* args, dal3_stream stream);
+int dal3_roi_post(const float* box_preds, const float* cls_preds, const float* roi_scores, int64_t n, int code_size,
+                  float* out_boxes, float* out_scores, dal3_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
