@@ -297,6 +297,24 @@ class RoiHeadArgs(C.Structure):
                 ("workspace_bytes", C.c_size_t)]
 
 
+ROI_NO_SAMPLE = 8192
+ROI_CLS_SCORE = {"roi_iou": 0, "cls": 1}
+ROI_TRAIN_MAX_M, ROI_TRAIN_MAX_R, ROI_TRAIN_MAX_G = 512, 512, 1024
+
+
+class RoiTargetsArgs(C.Structure):
+    """dal3_roi_targets_args"""
+    _fields_ = [("B", C.c_int64), ("M", C.c_int64), ("R", C.c_int64), ("G", C.c_int64), ("code_size", C.c_int32),
+                ("reserved0", C.c_int32), ("T", C.c_int32), ("reserved", C.c_int32), ("K", C.c_int64), ("keep_stride", C.c_int64),
+                ("boxes", vp), ("scores", vp), ("labels", vp), ("keep", vp), ("keep_count", vp), ("seg_offsets", vp),
+                ("label_base", C.c_int32 * ROI_MAX_TASKS), ("rois", vp), ("roi_scores", vp), ("roi_labels", vp), ("gt", vp),
+                ("draws", vp), ("fg_per_image", C.c_int32), ("cls_score_type", C.c_int32), ("reg_fg_thresh", C.c_float),
+                ("cls_fg_thresh", C.c_float), ("cls_bg_thresh", C.c_float), ("cls_bg_thresh_lo", C.c_float),
+                ("cls_thresh_span", C.c_float), ("reserved2", C.c_float), ("hard_bg_ratio", C.c_double), ("slot", vp), ("sample", vp),
+                ("out_rois", vp), ("out_labels", vp), ("out_scores", vp), ("gt_iou", vp), ("gt_src", vp), ("reg_valid", vp),
+                ("cls_labels", vp), ("gt_of_rois", vp), ("out_boxes", vp), ("status", vp)]
+
+
 # every symbol include/dal3.h declares: (restype, argtypes)
 _i, _i64, _u64, _sz = C.c_int, C.c_int64, C.c_uint64, C.c_size_t
 SIGNATURES = {
@@ -375,6 +393,8 @@ SIGNATURES = {
     "dal3_roi_head_workspace_bytes": (_sz, [_i64, _i64, _i, _i, _i]),
     "dal3_roi_head": (_i, [C.POINTER(RoiHeadArgs), vp]),
     "dal3_roi_post": (_i, [vp, vp, vp, _i64, _i, vp, vp, vp]),
+    "dal3_roi_targets": (_i, [C.POINTER(RoiTargetsArgs), vp]),
+    "dal3_roi_loss": (_i, [vp, vp, _i64, _i, vp, vp, vp, C.POINTER(C.c_float), C.c_float, C.c_float, vp, vp, vp, vp]),
     "dal3_crop_workspace_bytes": (_sz, [_i64, _i64]),
     "dal3_crop_count": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, _sz, vp]),
     "dal3_crop_fill": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, vp, vp, vp, _i64, vp, _sz, vp]),

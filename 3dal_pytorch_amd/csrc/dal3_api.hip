@@ -2473,3 +2473,41 @@ extern "C" int dal3_roi_post(const float* box_preds, const float* cls_preds, con
     HIP_TRY(launch_roi_post(box_preds, cls_preds, roi_scores, n, code_size, out_boxes, out_scores, static_cast<hipStream_t>(stream)));
     return 0;
 }
+
+extern "C" int dal3_roi_targets(const dal3_roi_targets_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "roi_targets: null args");
+    const dal3_roi_targets_args& a = *args;
+    if (a.B < 0 || a.B > 65535 || a.M < 1 || a.M > DAL3_ROI_TRAIN_MAX_M || a.R < 1 || a.R > DAL3_ROI_TRAIN_MAX_R || a.G < 1 ||
+        a.G > DAL3_ROI_TRAIN_MAX_G || (a.code_size != 7 && a.code_size != 9))
+        return fail(DAL3_EINVAL, "roi_targets: bad B / M (1 .. %d) / R (1 .. %d) / G (1 .. %d) / code_size (7 or 9)",
+                    DAL3_ROI_TRAIN_MAX_M, DAL3_ROI_TRAIN_MAX_R, DAL3_ROI_TRAIN_MAX_G);
+    if (a.cls_score_type != DAL3_ROI_CLS_SCORE_ROI_IOU && a.cls_score_type != DAL3_ROI_CLS_SCORE_CLS)
+        return fail(DAL3_EINVAL, "roi_targets: cls_score_type %d", (int)a.cls_score_type);
+    if (a.fg_per_image < 0 || !(a.hard_bg_ratio >= 0.0 && a.hard_bg_ratio <= 1.0) || !(a.cls_thresh_span > 0.f))
+        return fail(DAL3_EINVAL, "roi_targets: bad fg_per_image / hard_bg_ratio (0 .. 1) / cls_thresh_span (> 0)");
+    if (a.B == 0) return 0;
+    if (a.keep) {
+        if (a.T < 1 || a.T > DAL3_ROI_MAX_TASKS) return fail(DAL3_EINVAL, "roi_targets: T %d (1 .. %d)", (int)a.T, DAL3_ROI_MAX_TASKS);
+        if (a.K < 0 || a.keep_stride < 0) return fail(DAL3_EINVAL, "roi_targets: bad K / keep_stride");
+        if (!a.boxes || !a.scores || !a.labels || !a.keep_count || !a.seg_offsets)
+            return fail(DAL3_EINVAL, "roi_targets: null pointer in the fused form");
+    } else if (!a.rois || !a.roi_scores || !a.roi_labels) {
+        return fail(DAL3_EINVAL, "roi_targets: the direct form needs rois, roi_scores and roi_labels");
+    }
+    if (!a.gt || !a.draws || !a.slot || !a.sample || !a.out_rois || !a.out_labels || !a.out_scores || !a.gt_iou || !a.gt_src ||
+        !a.reg_valid || !a.cls_labels || !a.gt_of_rois || !a.out_boxes || !a.status)
+        return fail(DAL3_EINVAL, "roi_targets: null gt / draws / output / status");
+    HIP_TRY(launch_roi_targets(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+extern "C" int dal3_roi_loss(const float* rcnn_cls, const float* rcnn_reg, int64_t N, int code_size, const float* cls_labels,
+                             const int32_t* reg_valid, const float* gt_of_rois, const float* code_weights, float cls_weight,
+                             float reg_weight, float* loss, float* d_cls, float* d_reg, dal3_stream stream) {
+    if (N < 0 || N > (1 << 24) || (code_size != 7 && code_size != 9)) return fail(DAL3_EINVAL, "roi_loss: bad N / code_size (7 or 9)");
+    if (!rcnn_cls || !rcnn_reg || !cls_labels || !reg_valid || !gt_of_rois || !code_weights || !loss || !d_cls || !d_reg)
+        return fail(DAL3_EINVAL, "roi_loss: null argument");
+    HIP_TRY(launch_roi_loss(rcnn_cls, rcnn_reg, N, code_size, cls_labels, reg_valid, gt_of_rois, code_weights, cls_weight, reg_weight,
+                            loss, d_cls, d_reg, static_cast<hipStream_t>(stream)));
+    return 0;
+}

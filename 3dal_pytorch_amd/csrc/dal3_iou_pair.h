@@ -74,15 +74,19 @@ __device__ __forceinline__ void clip_slab(const float (&u)[N], const float (&v)[
 }
 
 template <typename T>
-__device__ __forceinline__ void box_iou_pair(const IouBox<T>& a, const IouBox<T>& b, float& iou_bev, float& iou_3d) {
+__device__ __forceinline__ void box_iou_pair(const IouBox<T>& a, const IouBox<T>& b, float& iou_bev, float& iou_3d,
+                                             float* clamped_3d = nullptr) {
+    // clamped_3d (optional): the reference's boxes_iou3d_gpu, the 3-D intersection over max(union, 1e-6)
     if (a.bad | b.bad) {
         iou_bev = iou_3d = __builtin_nanf("");
+        if (clamped_3d) *clamped_3d = iou_3d;
         return;
     }
     const float dx = (float)(a.cx - b.cx), dy = (float)(a.cy - b.cy);
     const float reach = (a.rad + b.rad) * 1.000001f;
     if (dx * dx + dy * dy > reach * reach) {    // bounding circles disjoint
         iou_bev = iou_3d = 0.f;
+        if (clamped_3d) *clamped_3d = 0.f;
         return;
     }
     // a in b's frame: centre, then the half-length and half-width axes rotated by yaw_a - yaw_b
@@ -106,4 +110,5 @@ __device__ __forceinline__ void box_iou_pair(const IouBox<T>& a, const IouBox<T>
     const float zo = fmaxf(fminf(dz + a.hh, b.hh) - fmaxf(dz - a.hh, -b.hh), 0.f);
     const float inter3 = inter * zo, u3 = a.vol + b.vol - inter3;
     iou_3d = u3 > 0.f ? inter3 / u3 : 0.f;
+    if (clamped_3d) *clamped_3d = inter3 / fmaxf(u3, 1e-6f);
 }

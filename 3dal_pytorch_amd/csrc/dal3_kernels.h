@@ -558,3 +558,8 @@ size_t roi_head_workspace_bytes(int64_t B, int64_t M, int num_point, int C, int 
 hipError_t launch_roi_post(const float* box_preds, const float* cls_preds, const float* roi_scores, int64_t n, int code_size,
                            float* out_boxes, float* out_scores, hipStream_t s);
 bool launch_roi_head(const dal3_roi_head_args* a, hipStream_t s, hipError_t* err);
+// the second stage's training (dal3_roi_train.hip): target assignment, the RoI losses and their gradients
+hipError_t launch_roi_targets(const dal3_roi_targets_args* a, hipStream_t s);
+hipError_t launch_roi_loss(const float* rcnn_cls, const float* rcnn_reg, int64_t N, int code_size, const float* cls_labels,
+                           const int32_t* reg_valid, const float* gt_of_rois, const float* code_weights, float cls_weight,
+                           float reg_weight, float* loss, float* d_cls, float* d_reg, hipStream_t s);

@@ -20,6 +20,7 @@
 // and the direct form agree bit for bit.
 #include "dal3_block.h"
 #include "dal3_kernels.h"
+#include "dal3_roi_slots.h"
 
 namespace {
 
@@ -143,23 +144,7 @@ __global__ __launch_bounds__(256) void roi_prepare_kernel(const PrepareGeom g) {
     const int b = (int)(i / g.M), m = (int)(i % g.M);
     int64_t before = 0, row = -1;
     int task = 0, bad = 0;
-    for (int t = 0; t < g.T; ++t) {
-        const int64_t f = (int64_t)t * g.B + b;
-        int64_t c = g.keep_count[f];
-        if (c < 0 || c > g.keep_stride) {
-            bad = 1;
-            c = c < 0 ? 0 : g.keep_stride;
-        }
-        if (row < 0 && m < before + c) {
-            row = g.seg_offsets[f] + g.keep[f * g.keep_stride + (m - before)];
-            task = t;
-            if (row < 0 || row >= g.K) {
-                bad = 1;
-                row = -2;                // found, unusable: the slot is empty
-            }
-        }
-        before += c;
-    }
+    roi_slot_row(g.keep, g.keep_count, g.seg_offsets, g.T, g.B, g.K, g.keep_stride, b, m, before, row, task, bad);
     if (m == 0) {
         const int32_t n = (int32_t)(before < g.M ? before : g.M);
         g.counts[b] = n;

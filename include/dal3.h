@@ -1655,6 +1655,105 @@ int dal3_roi_head(const dal3_roi_head_args* args, dal3_stream stream);
 int dal3_roi_post(const float* box_preds, const float* cls_preds, const float* roi_scores, int64_t n, int code_size,
                   float* out_boxes, float* out_scores, dal3_stream stream);
 
+/* ---- The second stage's training (det3d/models/roi_heads/target_assigner/proposal_target_layer.py, roi_head_template.py):
+ * target assignment and the RoI losses, float32. (Additions only; DAL3_VERSION stays.)
+ *
+ * dal3_roi_targets: ProposalTargetLayer.forward (SAMPLE_ROI_BY_EACH_CLASS) + RoIHeadTemplate.assign_targets for all B
+ * samples in one launch, one workgroup a sample, nothing read back. Two input forms, like dal3_roi_head:
+ *   fused (keep != NULL): CenterHeadPost's device results; slot m of sample b is dal3_roi_head's step (a), with the same
+ *       status bits (DAL3_ROI_OVERFLOW, DAL3_NMS_BAD_SEGMENT); its label is labels[row] + label_base[task] + 1;
+ *   direct: rois (B, M, code_size) with the rotation at column 6, roi_scores (B, M), roi_labels (B, M) int32.
+ * A slot at or past the sample's count (direct form: a slot whose label is 0) is the reference's zero-padded RoI: zero
+ * box, label 0, score 0. It takes part in the sampling as background; its sample[] is -1 and its feature row zero.
+ * Per sample:
+ *   GT trim: gt (B, G, code_size + 1), the box in columns 0:7, the class in the last one; trailing rows without a non-zero
+ *       entry are dropped down to row 0 (rows whose non-zero entries cancel are outside the contract);
+ *   overlap of RoI m: the maximum over the kept GT rows g whose class (truncated to an integer) equals the RoI's label
+ *       of the 3-D intersection / max(union, 1e-6) of dal3_iou_pair.h, the LOWEST g among the maxima; (0, 0) when the
+ *       class has no GT row. A NaN overlap wins, as in torch.max;
+ *   subsample_rois / sample_bg_inds: fg_thresh = min(reg_fg_thresh, cls_fg_thresh); fg: overlap >= fg_thresh, easy bg:
+ *       < cls_bg_thresh_lo, hard bg: < reg_fg_thresh and >= cls_bg_thresh_lo, each list ascending in m. With key =
+ *       draws[b, :M] and pick = draws[b, M:] (draws (B, M + R) float32 in [0, 1)):
+ *         fg and bg: the first min(fg_per_image, n_fg) of the fg list's positions p ordered by (key[p], p), then R - that
+ *             many background rows; fg only: R draws from the fg list; bg only: R background rows;
+ *         n background rows: hard and easy present: min((int)(n * hard_bg_ratio) [a float64 product], n_hard) hard draws,
+ *             then easy draws; else n draws from the list that is not empty. Row c of the n takes pick[c];
+ *         the draw from a list of n with pick v: list[min((int)(v * n), n - 1)], the product a float32 one;
+ *         neither fg nor bg (NaN overlaps; the reference raises): DAL3_ROI_NO_SAMPLE in *status, the sample's rows zero,
+ *             sample[] -1.
+ *   Row j < R, m its sampled slot: slot[b][j] = m; sample[b][j] = b, or -1 for an empty slot; out_rois, out_labels,
+ *       out_scores: the slot's; gt_iou: its overlap; gt_src: its GT row (code_size + 1); reg_valid = overlap >
+ *       reg_fg_thresh; cls_labels (float): DAL3_ROI_CLS_SCORE_ROI_IOU: 1 above cls_fg_thresh, 0 below cls_bg_thresh,
+ *       (overlap - cls_bg_thresh) / cls_thresh_span between; DAL3_ROI_CLS_SCORE_CLS: 1 / 0 by cls_fg_thresh, -1 strictly
+ *       between the two thresholds; gt_of_rois (code_size + 1), every operation a float32 one in this order:
+ *       ry = roi[6] - floor(roi[6] / 2pi + 0.5) * 2pi; e[0:6] = gt[0:6] - roi[0:6]; e[6] = gt[6] - ry; (e0, e1) rotated
+ *       by -ry (x' = x cos + y sin, y' = -x sin + y cos); code 9: e[7:9] = gt[7:9] - roi[7:9], not rotated; h = e[6] mod
+ *       2pi (the divisor's sign); pi/2 < h < 3pi/2: h = (h + pi) mod 2pi; h > pi: h -= 2pi; h clamped to [-pi/2, pi/2];
+ *       the class column is copied. out_boxes (B, R, code_size): out_rois with the rotation back in the last column (code
+ *       9: [0..5, 7, 8, 6]), the layout dal3_box_points takes: dal3_box_points on it and dal3_bev_gather with sample[]
+ *       over a zeroed (B, R, num_point * C) output give the bits of dal3_roi_head's feature row of that slot.
+ * M <= DAL3_ROI_TRAIN_MAX_M, 1 <= R <= DAL3_ROI_TRAIN_MAX_R, 1 <= G <= DAL3_ROI_TRAIN_MAX_G, code_size 7 or 9; non-finite boxes are outside the contract (no access leaves its array). Anything else returns DAL3_EINVAL and
+ * launches nothing.
+ *
+ * dal3_roi_loss: get_box_cls_layer_loss (BinaryCrossEntropy) and get_box_reg_layer_loss (L1) on N rows and their gradients
+ * in one launch of one workgroup, every sum in a fixed order (float64), nothing read back:
+ *   cls: p = sigmoid(x); -(y max(log p, -100) + (1 - y) max(log(1 - p), -100)) summed over the rows with cls_labels >= 0,
+ *       / max(count, 1), * cls_weight;
+ *   reg: |reg - gt_of_rois[:, :code_size]| * code_weights over the rows with reg_valid > 0, / max(their count, 1),
+ *       * reg_weight; the gradient of |.| is 0 at 0;
+ *   loss[3] = (cls, reg, cls + reg); d_cls (N) and d_reg (N, code_size): the gradients of loss[2]. */
+enum { DAL3_ROI_NO_SAMPLE = 8192 };      /* status bit */
+enum { DAL3_ROI_CLS_SCORE_ROI_IOU = 0, DAL3_ROI_CLS_SCORE_CLS = 1 };
+#define DAL3_ROI_TRAIN_MAX_M 512
+#define DAL3_ROI_TRAIN_MAX_R 512
+#define DAL3_ROI_TRAIN_MAX_G 1024
+
+typedef struct dal3_roi_targets_args {
+    int64_t B, M, R, G;
+    int32_t code_size, reserved0;
+    /* the fused form */
+    int32_t T, reserved;
+    int64_t K, keep_stride;
+    const float* boxes;                  /* (K, code_size), the rotation last */
+    const float* scores;
+    const int32_t* labels;
+    const int32_t* keep;
+    const int32_t* keep_count;
+    const int64_t* seg_offsets;          /* device */
+    int32_t label_base[DAL3_ROI_MAX_TASKS];
+    /* the direct form */
+    const float* rois;
+    const float* roi_scores;
+    const int32_t* roi_labels;
+    /* both */
+    const float* gt;                     /* (B, G, code_size + 1) */
+    const float* draws;                  /* (B, M + R) */
+    int32_t fg_per_image;                /* int(round(FG_RATIO * ROI_PER_IMAGE)) */
+    int32_t cls_score_type;
+    float reg_fg_thresh, cls_fg_thresh, cls_bg_thresh, cls_bg_thresh_lo;
+    float cls_thresh_span;               /* (float)(CLS_FG_THRESH - CLS_BG_THRESH) */
+    float reserved2;
+    double hard_bg_ratio;
+    /* outputs */
+    int32_t* slot;                       /* (B, R) */
+    int32_t* sample;                     /* (B, R) */
+    float* out_rois;                     /* (B, R, code_size) */
+    int32_t* out_labels;                 /* (B, R) */
+    float* out_scores;                   /* (B, R) */
+    float* gt_iou;                       /* (B, R) */
+    float* gt_src;                       /* (B, R, code_size + 1) */
+    int32_t* reg_valid;                  /* (B, R) */
+    float* cls_labels;                   /* (B, R) */
+    float* gt_of_rois;                   /* (B, R, code_size + 1) */
+    float* out_boxes;                    /* (B, R, code_size): the rotation last */
+    int32_t* status;                     /* (1) OR-ed */
+} dal3_roi_targets_args;
+
+int dal3_roi_targets(const dal3_roi_targets_args* args, dal3_stream stream);
+int dal3_roi_loss(const float* rcnn_cls, const float* rcnn_reg, int64_t N, int code_size, const float* cls_labels,
+                  const int32_t* reg_valid, const float* gt_of_rois, const float* code_weights /* host, code_size */,
+                  float cls_weight, float reg_weight, float* loss, float* d_cls, float* d_reg, dal3_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
