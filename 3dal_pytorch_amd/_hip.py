@@ -185,6 +185,11 @@ class Map(C.Structure):
                 ("stride_c", C.c_int64)]
 
 
+def nchw_map(t):
+    """a logical (B, C, H, W) float32 tensor of any strides -> dal3_map (no copy)"""
+    return Map(ptr(t), t.stride(0), t.stride(2), t.stride(3), t.stride(1))
+
+
 class CenterDecodeArgs(C.Structure):
     """dal3_center_decode_args"""
     _fields_ = [("B", C.c_int64), ("H", C.c_int64), ("W", C.c_int64), ("C", C.c_int32), ("has_range", C.c_int32),
@@ -315,6 +320,28 @@ class RoiTargetsArgs(C.Structure):
                 ("cls_labels", vp), ("gt_of_rois", vp), ("out_boxes", vp), ("status", vp)]
 
 
+CENTER_OVERFLOW = 16384
+CENTER_MAX_OBJS, CENTER_MAX_CLASSES, CENTER_MAX_COLS = 1024, 64, 10
+_pT = vp * ROI_MAX_TASKS
+
+
+class CenterTargetsArgs(C.Structure):
+    """dal3_center_targets_args"""
+    _fields_ = [("B", C.c_int64), ("G", C.c_int64), ("H", C.c_int64), ("W", C.c_int64), ("T", C.c_int32), ("max_objs", C.c_int32),
+                ("num_class", C.c_int32 * ROI_MAX_TASKS), ("gt", vp), ("pc_start", _f2), ("voxel_size", _f2),
+                ("out_size_factor", C.c_float), ("min_radius", C.c_int32), ("gaussian_overlap", C.c_double), ("hm", _pT),
+                ("anno_box", _pT), ("ind", _pT), ("mask", _pT), ("cat", _pT), ("status", vp)]
+
+
+class CenterLossArgs(C.Structure):
+    """dal3_center_loss_args"""
+    _fields_ = [("B", C.c_int64), ("H", C.c_int64), ("W", C.c_int64), ("C", C.c_int32), ("n_cols", C.c_int32), ("max_objs", C.c_int32),
+                ("reserved", C.c_int32), ("hm", Map), ("reg", Map), ("height", Map), ("dim", Map), ("rot", Map), ("vel", Map),
+                ("target_hm", vp), ("anno_box", vp), ("ind", vp), ("mask", vp), ("cat", vp),
+                ("code_weights", C.c_float * CENTER_MAX_COLS), ("weight", C.c_float), ("reserved2", C.c_float), ("out", vp),
+                ("grad", vp), ("workspace", vp), ("workspace_bytes", C.c_size_t)]
+
+
 # every symbol include/dal3.h declares: (restype, argtypes)
 _i, _i64, _u64, _sz = C.c_int, C.c_int64, C.c_uint64, C.c_size_t
 SIGNATURES = {
@@ -395,6 +422,9 @@ SIGNATURES = {
     "dal3_roi_post": (_i, [vp, vp, vp, _i64, _i, vp, vp, vp]),
     "dal3_roi_targets": (_i, [C.POINTER(RoiTargetsArgs), vp]),
     "dal3_roi_loss": (_i, [vp, vp, _i64, _i, vp, vp, vp, C.POINTER(C.c_float), C.c_float, C.c_float, vp, vp, vp, vp]),
+    "dal3_center_targets": (_i, [C.POINTER(CenterTargetsArgs), vp]),
+    "dal3_center_loss_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "dal3_center_loss": (_i, [C.POINTER(CenterLossArgs), vp]),
     "dal3_crop_workspace_bytes": (_sz, [_i64, _i64]),
     "dal3_crop_count": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, _sz, vp]),
     "dal3_crop_fill": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, vp, vp, vp, _i64, vp, _sz, vp]),

@@ -2511,3 +2511,53 @@ extern "C" int dal3_roi_loss(const float* rcnn_cls, const float* rcnn_reg, int64
                             loss, d_cls, d_reg, static_cast<hipStream_t>(stream)));
     return 0;
 }
+
+static bool center_dims_ok(int64_t B, int64_t H, int64_t W) { return B >= 0 && B <= 65535 && H >= 1 && H <= 65535 && W >= 1 && W <= 65535; }
+
+extern "C" int dal3_center_targets(const dal3_center_targets_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "center_targets: null args");
+    const dal3_center_targets_args& a = *args;
+    if (!center_dims_ok(a.B, a.H, a.W) || a.G < 1 || a.G > (1 << 20)) return fail(DAL3_EINVAL, "center_targets: bad B / G (1 .. 2^20) / H / W (1 .. 65535)");
+    if (a.T < 1 || a.T > DAL3_ROI_MAX_TASKS) return fail(DAL3_EINVAL, "center_targets: T %d (1 .. %d)", (int)a.T, DAL3_ROI_MAX_TASKS);
+    if (a.max_objs < 1 || a.max_objs > DAL3_CENTER_MAX_OBJS) return fail(DAL3_EINVAL, "center_targets: max_objs %d (1 .. %d)", (int)a.max_objs, DAL3_CENTER_MAX_OBJS);
+    if (!(a.voxel_size[0] > 0.f) || !(a.voxel_size[1] > 0.f) || !(a.out_size_factor > 0.f))
+        return fail(DAL3_EINVAL, "center_targets: voxel_size and out_size_factor must be positive");
+    if (!(a.gaussian_overlap >= 0.0 && a.gaussian_overlap < 1.0) || a.min_radius < 0 || a.min_radius > 65535)
+        return fail(DAL3_EINVAL, "center_targets: bad gaussian_overlap (0 <= . < 1) / min_radius (0 .. 65535)");
+    for (int t = 0; t < a.T; ++t) {
+        if (a.num_class[t] < 1 || a.num_class[t] > DAL3_CENTER_MAX_CLASSES)
+            return fail(DAL3_EINVAL, "center_targets: task %d has %d classes (1 .. %d)", t, (int)a.num_class[t], DAL3_CENTER_MAX_CLASSES);
+        if (a.num_class[t] * a.H * a.W >= ((int64_t)1 << 31)) return fail(DAL3_EINVAL, "center_targets: task %d's map has 2^31 elements or more", t);
+        if (!a.hm[t] || !a.anno_box[t] || !a.ind[t] || !a.mask[t] || !a.cat[t]) return fail(DAL3_EINVAL, "center_targets: null output of task %d", t);
+    }
+    if (!a.gt || !a.status) return fail(DAL3_EINVAL, "center_targets: null gt / status");
+    HIP_TRY(launch_center_targets(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+extern "C" size_t dal3_center_loss_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W) {
+    if (!center_dims_ok(B, H, W) || C < 1 || C > DAL3_CENTER_MAX_CLASSES) return 0;
+    return center_loss_workspace_bytes(B, C, H, W);
+}
+
+extern "C" int dal3_center_loss(const dal3_center_loss_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "center_loss: null args");
+    const dal3_center_loss_args& a = *args;
+    if (!center_dims_ok(a.B, a.H, a.W) || a.C < 1 || a.C > DAL3_CENTER_MAX_CLASSES) return fail(DAL3_EINVAL, "center_loss: bad B / H / W (1 .. 65535) / C (1 .. %d)", DAL3_CENTER_MAX_CLASSES);
+    if (a.n_cols != 8 && a.n_cols != 10) return fail(DAL3_EINVAL, "center_loss: n_cols %d (8 or 10)", (int)a.n_cols);
+    if (a.max_objs < 1 || a.max_objs > DAL3_CENTER_MAX_OBJS) return fail(DAL3_EINVAL, "center_loss: max_objs %d (1 .. %d)", (int)a.max_objs, DAL3_CENTER_MAX_OBJS);
+    if (a.B * (a.C + a.n_cols) * a.H * a.W >= ((int64_t)1 << 31)) return fail(DAL3_EINVAL, "center_loss: B * (C + n_cols) * H * W must stay below 2^31");
+    if ((a.vel.data != nullptr) != (a.n_cols == 10)) return fail(DAL3_EINVAL, "center_loss: the vel map goes with n_cols 10, and only with it");
+    if (!a.out) return fail(DAL3_EINVAL, "center_loss: null out");
+    if (a.B == 0) return fail(DAL3_EINVAL, "center_loss: an empty batch has no loss");
+    if (!a.hm.data || !a.reg.data || !a.height.data || !a.dim.data || !a.rot.data || !a.target_hm || !a.anno_box || !a.ind || !a.mask ||
+        !a.cat || !a.grad)
+        return fail(DAL3_EINVAL, "center_loss: null map / target / grad");
+    if (!a.workspace || (reinterpret_cast<uintptr_t>(a.workspace) & 7)) return fail(DAL3_EINVAL, "center_loss: workspace is null or misaligned");
+    hipError_t e = hipSuccess;
+    if (!launch_center_loss(args, static_cast<hipStream_t>(stream), &e))
+        return fail(DAL3_EWORKSPACE, "center_loss: workspace of %zu bytes, %zu needed", a.workspace_bytes,
+                    center_loss_workspace_bytes(a.B, a.C, a.H, a.W));
+    HIP_TRY(e);
+    return 0;
+}

@@ -563,3 +563,7 @@ hipError_t launch_roi_targets(const dal3_roi_targets_args* a, hipStream_t s);
 hipError_t launch_roi_loss(const float* rcnn_cls, const float* rcnn_reg, int64_t N, int code_size, const float* cls_labels,
                            const int32_t* reg_valid, const float* gt_of_rois, const float* code_weights, float cls_weight,
                            float reg_weight, float* loss, float* d_cls, float* d_reg, hipStream_t s);
+// the first stage's training (dal3_center_loss.hip): AssignLabel's targets, the head's loss and its gradients
+hipError_t launch_center_targets(const dal3_center_targets_args* a, hipStream_t s);
+size_t center_loss_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W);
+bool launch_center_loss(const dal3_center_loss_args* a, hipStream_t s, hipError_t* err);

@@ -82,8 +82,7 @@ def out_size(kind, stride, H, W):
     return H * stride, W * stride
 
 
-def _nchw_map(t):
-    return _hip.Map(_hip.ptr(t), t.stride(0), t.stride(2), t.stride(3), t.stride(1))
+_nchw_map = _hip.nchw_map
 
 
 def conv2d(x, packed, kind, stride, relu, c_out, out=None, channel_offset=0, max_workgroups=0):
@@ -402,6 +401,49 @@ class CenterHead(_PackedLayers):
                     offset += classes[i]
                 ret.append(d)
             return ret
+
+    def _loss_heads(self, preds_dict):
+        """what `loss` serves, refused in words otherwise -> the number of regression columns"""
+        from . import center_loss
+        if self.dataset not in ("waymo", "nuscenes"):
+            raise NotImplementedError(f"dataset {self.dataset!r}: the loss is built for 'waymo' and 'nuscenes' (the reference "
+                                      "raises for every other one)")
+        if len(self.code_weights) == 0:
+            raise ValueError("code_weights is empty: the loss needs one weight per regression column (8, or 10 with vel)")
+        heads = set(preds_dict)
+        if "hm" not in heads or not {"reg", "height", "dim", "rot"} <= heads or not heads <= {"hm", *center_loss.REG_HEADS}:
+            raise NotImplementedError(f"heads {sorted(heads)}: the loss is built for hm, reg, height, dim, rot and an optional vel")
+        n_cols = 10 if "vel" in heads else 8
+        if len(self.code_weights) != n_cols:
+            raise ValueError(f"code_weights has {len(self.code_weights)} entries, the heads make {n_cols} regression columns")
+        return n_cols
+
+    def loss(self, example, preds_dicts, **kwargs):
+        """center_head.py's loss: example holds the lists hm, anno_box, ind, mask, cat (center_loss.center_targets makes
+        them), preds_dicts is forward's list -> the merged dictionary of lists loss, hm_loss, loc_loss, loc_loss_elem,
+        num_positive, one entry per task. One dal3_center_loss call per task reads the raw maps in place (the kernel
+        route's channel slices as well as the composite route's tensors) and yields the gradients with the loss; `loss`
+        carries the graph, the other entries are detached, as the reference's hm_loss and loc_loss_elem are.
+        Differences from the reference: every value stays a device tensor and nothing is read back (the reference's
+        .detach().cpu() is a host synchronisation per task); preds_dicts is not changed (no in-place sigmoid, no
+        anno_box key); and `loc_loss`, which the reference returns with its graph, is returned detached: the gradients
+        the kernel writes are those of `loss`, so backward goes through `loss` alone."""
+        from . import center_loss
+        merged = {k: [] for k in ("loss", "hm_loss", "loc_loss", "loc_loss_elem", "num_positive")}
+        if len(preds_dicts) != len(self.tasks):
+            raise ValueError(f"{len(preds_dicts)} prediction dictionaries for {len(self.tasks)} tasks")
+        for t, preds in enumerate(preds_dicts):
+            self._loss_heads(preds)
+            vals = center_loss.head_loss(preds, example["hm"][t], example["anno_box"][t], example["ind"][t], example["mask"][t],
+                                         example["cat"][t], self.code_weights, self.weight)
+            for k, v in zip(merged, vals):
+                merged[k].append(v)
+        return merged
+
+    def loss_from_gt(self, preds_dicts, gt_boxes_and_cls, assigner, voxels=None):
+        """targets and loss chained on the current stream: `assigner` is a center_loss.AssignLabel (`voxels`: the
+        voxeliser's entry, when the assigner was built without it) -> loss(...)'s dictionary"""
+        return self.loss(assigner(gt_boxes_and_cls, voxels), preds_dicts)
 
     @torch.no_grad()
     def predict(self, example, preds_dicts, test_cfg, **kwargs):

@@ -1754,6 +1754,90 @@ int dal3_roi_loss(const float* rcnn_cls, const float* rcnn_reg, int64_t N, int c
                   const int32_t* reg_valid, const float* gt_of_rois, const float* code_weights /* host, code_size */,
                   float cls_weight, float reg_weight, float* loss, float* d_cls, float* d_reg, dal3_stream stream);
 
+/* ---- The first stage's training (det3d/datasets/pipelines/preprocess.py AssignLabel, det3d/models/losses/centernet_loss.py,
+ * CenterHead.loss): the head's targets and its loss with the gradients, float32. (Additions only; DAL3_VERSION stays.)
+ *
+ * dal3_center_targets: AssignLabel's train branch for all B samples and T tasks in one launch, nothing read back.
+ *   gt (B, G, 10) is the collated gt_boxes_and_cls: x, y, z, w, l, h, rot, vx, vy, class; the class is 1-based over all
+ *   tasks, a zero row is padding. Task t holds the classes (base_t, base_t + num_class[t]], base_t the sum of the counts
+ *   before it. The rows of a task are taken in row order (the pipeline's flattening leaves them in the reference's per-task
+ *   order); row's slot k is its rank among them. A task with more than max_objs rows sets DAL3_CENTER_OVERFLOW in *status
+ *   and keeps the first max_objs (the reference asserts).
+ *   A row is skipped, its slot left zero, when w <= 0 or l <= 0 in cells, or when a centre coordinate is not finite, beyond
+ *   int32, or truncates (toward zero) outside [0, W) x [0, H). In float32, one operation after the other, as on the
+ *   reference's float32 range and size arrays: w_c = w / voxel_size[0] / out_size_factor, l_c alike with voxel_size[1],
+ *   ct = ((x, y) - pc_start) / voxel_size / out_size_factor. In float64 from those: radius = max(min_radius,
+ *   (int)gaussian_radius((l_c, w_c), gaussian_overlap)), and the heat map
+ *       hm[b, class, y, x] = max over the task's live objects with |x - ct_x| <= r and |y - ct_y| <= r of
+ *                            (float)exp(-(dx^2 + dy^2) / (2 sigma^2)), sigma = (2 r + 1) / 6; 0 where there is none.
+ *   Every pixel is written (no zero fill is needed) and is a maximum over a set: the bits do not depend on scheduling.
+ *   Slot k: anno_box = ct - ct_int (2), z, log(w, l, h), vx, vy, sin(rot), cos(rot), the three functions in float64
+ *   rounded once; ind = ct_y * W + ct_x; mask = 1; cat = the class within the task. Other slots are zero.
+ * B <= 65535, 1 <= T <= DAL3_ROI_MAX_TASKS, 1 <= G <= 2^20, 1 <= H, W <= 65535, 1 <= max_objs <= DAL3_CENTER_MAX_OBJS,
+ * 1 <= num_class <= DAL3_CENTER_MAX_CLASSES, positive voxel_size and out_size_factor, 0 <= gaussian_overlap < 1.
+ * The radius must stay below 65536 cells (a box of some 10^5 cells a side; no map here is wider than 65535): a larger one,
+ * or a NaN, is taken as 65536, which still covers the whole map but gives sigma, and so the values, of that radius.
+ *
+ * dal3_center_loss: FastFocalLoss and RegLoss of ONE task and CenterHead.loss's combination, with the gradients of `loss`
+ * in every head map, from one call (three launches on the stream), nothing read back. The head maps are read in place by
+ * strides. p = clamp(sigmoid(hm), 1e-4, 1 - 1e-4), its derivative zero where the clamp binds; a NaN stays a NaN.
+ *   neg = sum over the map of log(1 - p) p^2 (1 - target_hm)^4; pos = sum over the slots of log(p) (1 - p)^2 mask at
+ *   (ind, cat); num_pos = sum of mask over the batch; hm_loss = -(pos + neg) / num_pos, or -neg when num_pos == 0.
+ *   Column c of n_cols (10 with vel, else 8: the target's velocity columns 6, 7 are dropped) over the heads reg, height,
+ *   dim, [vel], rot gathered at ind: elem[c] = sum |pred mask - anno_box mask| / (num_pos + 1e-4);
+ *   loc_loss = sum elem[c] code_weights[c]; loss = hm_loss + weight * loc_loss.
+ *   out (4 + n_cols): loss, hm_loss, loc_loss, num_pos, elem. Elementwise terms are float32, every sum float64 in a fixed
+ *   order (per-workgroup partials, then one workgroup): no floating-point atomic.
+ *   grad (B, C + n_cols, H, W), every element written: d loss / d [hm | reg, height, dim, (vel), rot]. Slots that share a
+ *   pixel each count once; their gradients are added in ascending slot order by one thread. sign(0) = 0.
+ *   A slot whose ind or cat lies outside the map / the classes is outside the contract and is left out.
+ * B, H, W as above with B * (C + n_cols) * H * W < 2^31; workspace: dal3_center_loss_workspace_bytes(B, C, H, W). */
+enum { DAL3_CENTER_OVERFLOW = 16384 };   /* status bit */
+#define DAL3_CENTER_MAX_OBJS 1024
+#define DAL3_CENTER_MAX_CLASSES 64
+#define DAL3_CENTER_MAX_COLS 10
+
+typedef struct dal3_center_targets_args {
+    int64_t B, G, H, W;
+    int32_t T, max_objs;
+    int32_t num_class[DAL3_ROI_MAX_TASKS];
+    const float* gt;                     /* (B, G, 10) */
+    float pc_start[2], voxel_size[2];
+    float out_size_factor;
+    int32_t min_radius;
+    double gaussian_overlap;
+    /* outputs, one per task */
+    float* hm[DAL3_ROI_MAX_TASKS];       /* (B, num_class[t], H, W) */
+    float* anno_box[DAL3_ROI_MAX_TASKS]; /* (B, max_objs, 10) */
+    int64_t* ind[DAL3_ROI_MAX_TASKS];    /* (B, max_objs) */
+    uint8_t* mask[DAL3_ROI_MAX_TASKS];   /* (B, max_objs) */
+    int64_t* cat[DAL3_ROI_MAX_TASKS];    /* (B, max_objs) */
+    int32_t* status;                     /* (1) OR-ed */
+} dal3_center_targets_args;
+
+typedef struct dal3_center_loss_args {
+    int64_t B, H, W;
+    int32_t C;                           /* classes of this task (hm's channels) */
+    int32_t n_cols;                      /* 10 with vel, else 8 */
+    int32_t max_objs, reserved;
+    dal3_map hm, reg, height, dim, rot, vel;   /* logical (B, c, H, W); vel.data NULL without vel */
+    const float* target_hm;              /* (B, C, H, W) */
+    const float* anno_box;               /* (B, max_objs, 10) */
+    const int64_t* ind;                  /* (B, max_objs) */
+    const uint8_t* mask;                 /* (B, max_objs) */
+    const int64_t* cat;                  /* (B, max_objs) */
+    float code_weights[DAL3_CENTER_MAX_COLS];
+    float weight, reserved2;
+    float* out;                          /* (4 + n_cols) */
+    float* grad;                         /* (B, C + n_cols, H, W) */
+    void* workspace;
+    size_t workspace_bytes;
+} dal3_center_loss_args;
+
+int dal3_center_targets(const dal3_center_targets_args* args, dal3_stream stream);
+size_t dal3_center_loss_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W);
+int dal3_center_loss(const dal3_center_loss_args* args, dal3_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
