@@ -272,6 +272,23 @@ class SpConvArgs(C.Structure):
                 ("max_workgroups", C.c_int64)]
 
 
+SP_WGRAD_SLICE = 1024                           # DAL3_SP_WGRAD_SLICE: the sites of one partial sum of dal3_sp_wgrad
+
+
+class SpTableTransposedArgs(C.Structure):
+    """dal3_sp_table_transposed_args"""
+    _fields_ = [("B", C.c_int64), ("in_shape", _i3), ("out_shape", _i3), ("kernel", _i3), ("stride", _i3), ("padding", _i3),
+                ("reserved", C.c_int32), ("in_capacity", C.c_int64), ("n_in", vp), ("in_indices", vp), ("out_capacity", C.c_int64),
+                ("n_out", vp), ("out_key", vp), ("table", vp), ("max_workgroups", C.c_int64)]
+
+
+class SpWgradArgs(C.Structure):
+    """dal3_sp_wgrad_args"""
+    _fields_ = [("taps", C.c_int32), ("c_in", C.c_int32), ("c_out", C.c_int32), ("reserved", C.c_int32), ("in_capacity", C.c_int64),
+                ("x", vp), ("out_capacity", C.c_int64), ("n_out", vp), ("table", vp), ("dy", vp), ("dw", vp), ("db", vp),
+                ("max_workgroups", C.c_int64), ("workspace", vp), ("workspace_bytes", C.c_size_t)]
+
+
 ROI_OVERFLOW = 4096
 ROI_MAX_TASKS, ROI_MAX_WIDTH = 16, 256
 _f2 = C.c_float * 2
@@ -413,6 +430,9 @@ SIGNATURES = {
     "dal3_sp_conv_pack_floats": (_sz, [_i, _i, _i]),
     "dal3_sp_conv_pack": (_i, [C.POINTER(Layer), _i, C.c_double, vp, vp, vp]),
     "dal3_sp_conv": (_i, [C.POINTER(SpConvArgs), vp]),
+    "dal3_sp_table_transposed": (_i, [C.POINTER(SpTableTransposedArgs), vp]),
+    "dal3_sp_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i64]),
+    "dal3_sp_wgrad": (_i, [C.POINTER(SpWgradArgs), vp]),
     "dal3_bev_gather": (_i, [C.POINTER(BevGatherArgs), vp]),
     "dal3_box_points": (_i, [vp, _i64, _i, _i, vp, vp]),
     "dal3_roi_pack_floats": (_sz, [C.POINTER(RoiShape)]),

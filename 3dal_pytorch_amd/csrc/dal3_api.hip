@@ -1508,6 +1508,45 @@ extern "C" int dal3_sp_conv(const dal3_sp_conv_args* args, dal3_stream stream) {
     return 0;
 }
 
+extern "C" int dal3_sp_table_transposed(const dal3_sp_table_transposed_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "sp_table_transposed: null args");
+    const dal3_sp_table_transposed_args& a = *args;
+    TRY(sp_grid_ok("sp_table_transposed", a.B, a.in_shape));
+    TRY(sp_window_ok("sp_table_transposed", a.in_shape, a.out_shape, a.kernel, a.stride, a.padding));
+    TRY(sp_grid_ok("sp_table_transposed", a.B, a.out_shape));
+    if (!sp_cap_ok(a.in_capacity) || !sp_cap_ok(a.out_capacity) || !sp_cap_ok(a.in_capacity * 27) || a.max_workgroups < 0 || a.reserved)
+        return fail(DAL3_EINVAL, "sp_table_transposed: bad capacity / max_workgroups / reserved");
+    if (a.in_capacity > 0 && (!a.in_indices || !a.table)) return fail(DAL3_EINVAL, "sp_table_transposed: null in_indices / table");
+    if (a.in_capacity > 0 && a.out_capacity > 0 && !a.out_key) return fail(DAL3_EINVAL, "sp_table_transposed: null out_key");
+    HIP_TRY(launch_sp_table_transposed(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+extern "C" size_t dal3_sp_wgrad_workspace_bytes(int taps, int c_in, int c_out, int64_t out_capacity) {
+    if (taps < 1 || taps > 27 || !sp_channels_ok(c_in, c_out) || !sp_cap_ok(out_capacity)) return 0;
+    return sp_wgrad_workspace_bytes(taps, c_in, c_out, out_capacity);
+}
+
+extern "C" int dal3_sp_wgrad(const dal3_sp_wgrad_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "sp_wgrad: null args");
+    const dal3_sp_wgrad_args& a = *args;
+    if (a.taps < 1 || a.taps > 27 || !sp_channels_ok(a.c_in, a.c_out))
+        return fail(DAL3_EINVAL, "sp_wgrad: %d taps, %d -> %d channels (taps 1 .. 27; c_in 1 .. 8, 16, 32, 64, 128; c_out 16, 32, 64, 128)",
+                    (int)a.taps, (int)a.c_in, (int)a.c_out);
+    if (a.max_workgroups < 0 || a.reserved) return fail(DAL3_EINVAL, "sp_wgrad: bad max_workgroups (>= 0) / reserved");
+    if (!sp_cap_ok(a.in_capacity) || !sp_cap_ok(a.out_capacity) || !sp_cap_ok(a.out_capacity * 27)) return fail(DAL3_EINVAL, "sp_wgrad: bad capacity");
+    if (!a.dw) return fail(DAL3_EINVAL, "sp_wgrad: null dw");
+    if (a.out_capacity > 0) {
+        if (!a.table || !a.dy || (a.in_capacity > 0 && !a.x)) return fail(DAL3_EINVAL, "sp_wgrad: null table / dy / x");
+        if (!a.workspace) return fail(DAL3_EINVAL, "sp_wgrad: null workspace");
+        if (a.workspace_bytes < sp_wgrad_workspace_bytes(a.taps, a.c_in, a.c_out, a.out_capacity))
+            return fail(DAL3_EWORKSPACE, "sp_wgrad: workspace too small (dal3_sp_wgrad_workspace_bytes)");
+        if (reinterpret_cast<uintptr_t>(a.workspace) & 7) return fail(DAL3_EINVAL, "sp_wgrad: workspace must be 8-byte aligned");
+    }
+    HIP_TRY(launch_sp_wgrad(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 extern "C" size_t dal3_crop_workspace_bytes(int64_t K_total, int64_t max_points_per_frame) {
     if (K_total <= 0 || max_points_per_frame < 0) return 0;
     return crop_workspace_bytes(K_total, max_points_per_frame);

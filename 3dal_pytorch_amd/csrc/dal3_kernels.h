@@ -345,6 +345,9 @@ hipError_t launch_sp_table(const dal3_sp_table_args* a, hipStream_t s);
 size_t sp_conv_pack_floats(int taps, int c_in, int c_out);
 hipError_t launch_sp_conv_pack(const dal3_layer* layer, int taps, double eps, float* out, int32_t* status, hipStream_t s);
 hipError_t launch_sp_conv(const dal3_sp_conv_args* a, hipStream_t s);
+hipError_t launch_sp_table_transposed(const dal3_sp_table_transposed_args* a, hipStream_t s);
+size_t sp_wgrad_workspace_bytes(int taps, int c_in, int c_out, int64_t out_capacity);
+hipError_t launch_sp_wgrad(const dal3_sp_wgrad_args* a, hipStream_t s);
 hipError_t launch_points_in_boxes(const void* points, int points_f64, int64_t P, int64_t stride, const double* planes,
                                   int K, int f32_math, uint8_t* inside, hipStream_t s);
 hipError_t launch_writeback(const double* final_boxes, const int32_t* final_idx, const double* pose_best,

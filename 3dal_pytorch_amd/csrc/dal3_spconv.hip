@@ -495,3 +495,224 @@ hipError_t launch_sp_conv(const dal3_sp_conv_args* args, hipStream_t s) {
     }
     return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------------- the backward pass
+// The data gradient is launch_sp_conv itself with the roles swapped (include/dal3.h); what it needs beyond the forward's
+// bookkeeping is the inverse table of a SparseConv3d. The weight gradient is the one new GEMM: per tap
+// dW[k] (c_in x c_out) = X_k^T (c_in x sites) . dY (sites x c_out) on v_mfma_f32_32x32x2_f32 with the SITES as the
+// contraction: input channels on the MFMA rows (A), output channels on its columns (B), lane half h supplies site 2 s + h
+// of k-step s, so both operand loads are 32 consecutive floats of one row per half-wave. A wave owns one (tap, slice of
+// SP_WGRAD_SLICE sites, group of CT x OT tiles): every loaded x fragment feeds OT MFMAs and every dy fragment CT. The
+// slice's sites are taken 64 at a time: lane l reads table[tap][i0 + l] (one coalesced load), a chunk without a present
+// neighbour is skipped by ballot and a k-step whose two sites are both absent by a scalar branch: adding the +0 products
+// of absent sites never changes an accumulator, so the bits are those of the k-ordered fma chain over the present pairs.
+// The partial of every (slice, tap) goes to the workspace in the parameter's layout; sp_wgrad_reduce_kernel adds the live
+// slices in ascending order. The bias gradient takes the same two steps with plain column sums in a fixed order.
+namespace {
+
+constexpr int WG_SLICE = DAL3_SP_WGRAD_SLICE;
+inline int64_t wg_slices(int64_t out_cap) { return (out_cap + WG_SLICE - 1) / WG_SLICE; }
+
+__global__ __launch_bounds__(SP_BLOCK) void sp_table_transposed_kernel(const int32_t* in_idx, int64_t in_cap, const int64_t* n_in_ptr,
+                                                                       SpShape in, SpShape out, SpWindow w, const int32_t* out_key,
+                                                                       int64_t out_cap, const int64_t* n_out_ptr, int32_t* table) {
+    const int64_t n_in = sp_live(n_in_ptr, in_cap), n_out = sp_live(n_out_ptr, out_cap);
+    const int taps = w.k[0] * w.k[1] * w.k[2];
+    const int64_t total = (int64_t)taps * in_cap;
+    for (int64_t e = (int64_t)blockIdx.x * SP_BLOCK + threadIdx.x; e < total; e += (int64_t)gridDim.x * SP_BLOCK) {
+        const int64_t j = e % in_cap;
+        const int tap = (int)(e / in_cap);
+        if (j >= n_in) continue;
+        int32_t found = -1;
+        if (sp_key_of(in_idx, j, in) >= 0) {
+            const int kk[3] = {tap / (w.k[1] * w.k[2]), (tap / w.k[2]) % w.k[1], tap % w.k[2]};
+            const int32_t ext[3] = {out.D, out.H, out.W};
+            int32_t o[3];
+            bool ok = true;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                const int32_t t = in_idx[4 * j + 1 + a] + w.p[a] - kk[a];      // = o * stride
+                o[a] = t / w.s[a];
+                if (t < 0 || o[a] * w.s[a] != t || o[a] >= ext[a]) ok = false;
+            }
+            if (ok) {
+                const int32_t k = (int32_t)((((int64_t)in_idx[4 * j] * out.D + o[0]) * out.H + o[1]) * out.W + o[2]);
+                const int64_t lo = lower_bound(out_key, 0, n_out, k);
+                if (lo < n_out && out_key[lo] == k) found = (int32_t)lo;
+            }
+        }
+        table[e] = found;
+    }
+}
+
+struct SpWgradGeom {
+    int taps, c_in, c_out, ci_tiles, co_tiles, ci_groups, co_groups;
+    int64_t in_cap, out_cap, n_work;
+    const int64_t* n_out;
+    const int32_t* table;
+    const float *x, *dy;
+    float *part, *part_b;               // (slices, taps, c_in, c_out), (slices, c_out)
+    float *dw, *db;
+};
+
+// CT x OT tiles of 32 x 32 per wave
+template <int CT, int OT>
+__global__ __launch_bounds__(SP_BLOCK) void sp_wgrad_kernel(const SpWgradGeom g) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+    const int64_t n_out = sp_live(g.n_out, g.out_cap);
+    const int groups = g.ci_groups * g.co_groups;
+    for (int64_t work = (int64_t)blockIdx.x * SP_WAVES + wave; work < g.n_work; work += (int64_t)gridDim.x * SP_WAVES) {
+        const int grp = (int)(work % groups);
+        const int tap = (int)((work / groups) % g.taps);
+        const int64_t slice = work / ((int64_t)groups * g.taps);
+        const int64_t s0 = slice * WG_SLICE;
+        if (s0 >= n_out) continue;                          // a dead slice: neither written nor summed
+        const int64_t s1 = s0 + WG_SLICE < n_out ? s0 + WG_SLICE : n_out;
+        const int ci0 = (grp / g.co_groups) * CT * 32 + r, co0 = (grp % g.co_groups) * OT * 32 + r;
+
+        f32x16 acc[CT][OT];
+#pragma unroll
+        for (int a = 0; a < CT; ++a)
+#pragma unroll
+            for (int b = 0; b < OT; ++b) acc[a][b] = f32x16{};
+
+        for (int64_t i0 = s0; i0 < s1; i0 += 64) {
+            int32_t tidx = -1;
+            if (i0 + lane < s1) {
+                tidx = g.table[(int64_t)tap * g.out_cap + i0 + lane];
+                if (tidx >= g.in_cap) tidx = -1;
+            }
+            if (__ballot(tidx >= 0) == 0ull) continue;
+#pragma unroll 4
+            for (int s = 0; s < 32; ++s) {
+                const int32_t e0 = __builtin_amdgcn_readlane(tidx, 2 * s), e1 = __builtin_amdgcn_readlane(tidx, 2 * s + 1);
+                if (e0 < 0 && e1 < 0) continue;             // scalar: neither site of the k-step has the tap
+                const int32_t idx = h ? e1 : e0;
+                const float* xr = g.x + (int64_t)(idx < 0 ? 0 : idx) * g.c_in;
+                const float* dr = g.dy + (i0 + 2 * s + h) * g.c_out;
+                float a[CT], b[OT];
+#pragma unroll
+                for (int t = 0; t < CT; ++t) a[t] = (idx >= 0 && ci0 + 32 * t < g.c_in) ? xr[ci0 + 32 * t] : 0.f;
+#pragma unroll
+                for (int t = 0; t < OT; ++t) b[t] = (idx >= 0 && co0 + 32 * t < g.c_out) ? dr[co0 + 32 * t] : 0.f;
+#pragma unroll
+                for (int ta = 0; ta < CT; ++ta)
+#pragma unroll
+                    for (int tb = 0; tb < OT; ++tb) acc[ta][tb] = mfma32(a[ta], b[tb], acc[ta][tb]);
+            }
+        }
+
+        // register q of lane half h is input channel tile_chan(q, h) of the tile, the lane's column its output channel
+        float* out = g.part + ((int64_t)slice * g.taps + tap) * g.c_in * g.c_out;
+#pragma unroll
+        for (int ta = 0; ta < CT; ++ta)
+#pragma unroll
+            for (int tb = 0; tb < OT; ++tb) {
+                const int co = co0 + 32 * tb;
+                if (co >= g.c_out) continue;
+#pragma unroll
+                for (int q = 0; q < 16; ++q) {
+                    const int ci = ci0 - r + 32 * ta + tile_chan(q, h);
+                    if (ci < g.c_in) out[(int64_t)ci * g.c_out + co] = acc[ta][tb][q];
+                }
+            }
+    }
+}
+
+// one workgroup per slice: thread t sums channel t % c_out over the rows t / c_out, t / c_out + R, ... of the slice in
+// ascending order, then the R row classes are added in ascending order
+__global__ __launch_bounds__(SP_BLOCK) void sp_wgrad_bias_kernel(const SpWgradGeom g, int64_t slices) {
+    __shared__ float s_sum[SP_BLOCK];
+    const int64_t n_out = sp_live(g.n_out, g.out_cap);
+    const int R = SP_BLOCK / g.c_out, c = threadIdx.x % g.c_out, k = threadIdx.x / g.c_out;
+    for (int64_t slice = blockIdx.x; slice < slices; slice += gridDim.x) {
+        const int64_t s0 = slice * WG_SLICE;
+        if (s0 >= n_out) break;
+        const int64_t s1 = s0 + WG_SLICE < n_out ? s0 + WG_SLICE : n_out;
+        float v = 0.f;
+        if (k < R)
+            for (int64_t i = s0 + k; i < s1; i += R) v += g.dy[i * g.c_out + c];
+        s_sum[threadIdx.x] = v;
+        __syncthreads();
+        if (threadIdx.x < g.c_out) {
+            float t = 0.f;
+            for (int j = 0; j < R; ++j) t += s_sum[j * g.c_out + threadIdx.x];
+            g.part_b[slice * g.c_out + threadIdx.x] = t;
+        }
+        __syncthreads();
+    }
+}
+
+// dw = the live slices' partials in ascending slice order; db the same (the elements behind dw's)
+__global__ __launch_bounds__(SP_BLOCK) void sp_wgrad_reduce_kernel(const SpWgradGeom g) {
+    const int64_t n_out = sp_live(g.n_out, g.out_cap);
+    const int64_t live = (n_out + WG_SLICE - 1) / WG_SLICE;
+    const int64_t nw = (int64_t)g.taps * g.c_in * g.c_out, total = nw + (g.db ? g.c_out : 0);
+    for (int64_t e = (int64_t)blockIdx.x * SP_BLOCK + threadIdx.x; e < total; e += (int64_t)gridDim.x * SP_BLOCK) {
+        float v = 0.f;
+        if (e < nw) {
+            for (int64_t s = 0; s < live; ++s) v += g.part[s * nw + e];
+            g.dw[e] = v;
+        } else {
+            for (int64_t s = 0; s < live; ++s) v += g.part_b[s * g.c_out + (e - nw)];
+            g.db[e - nw] = v;
+        }
+    }
+}
+
+struct SpWgradWs {
+    float *part, *part_b;
+};
+inline SpWgradWs carve_wgrad(Carver& c, int taps, int c_in, int c_out, int64_t out_cap) {
+    SpWgradWs w;
+    const int64_t slices = wg_slices(out_cap);
+    w.part = c.take<float>((size_t)(slices * taps * c_in * c_out));
+    w.part_b = c.take<float>((size_t)(slices * c_out));
+    return w;
+}
+
+}  // namespace
+
+hipError_t launch_sp_table_transposed(const dal3_sp_table_transposed_args* args, hipStream_t s) {
+    const dal3_sp_table_transposed_args& a = *args;
+    const int64_t total = (int64_t)a.kernel[0] * a.kernel[1] * a.kernel[2] * a.in_capacity;
+    if (total <= 0) return hipSuccess;
+    hipLaunchKernelGGL(sp_table_transposed_kernel, dim3(sp_grid(sp_tiles(total), a.max_workgroups)), dim3(SP_BLOCK), 0, s,
+                       a.in_indices, a.in_capacity, a.n_in, sp_shape(a.B, a.in_shape), sp_shape(a.B, a.out_shape),
+                       sp_window(a.kernel, a.stride, a.padding), a.out_key, a.out_capacity, a.n_out, a.table);
+    return hipGetLastError();
+}
+
+size_t sp_wgrad_workspace_bytes(int taps, int c_in, int c_out, int64_t out_capacity) {
+    Carver c(nullptr, 0);
+    carve_wgrad(c, taps, c_in, c_out, out_capacity);
+    return c.off;
+}
+
+hipError_t launch_sp_wgrad(const dal3_sp_wgrad_args* args, hipStream_t s) {
+    const dal3_sp_wgrad_args& a = *args;
+    Carver c(a.workspace, a.workspace_bytes);
+    const SpWgradWs w = carve_wgrad(c, a.taps, a.c_in, a.c_out, a.out_capacity);
+    SpWgradGeom g = {};
+    g.taps = a.taps, g.c_in = a.c_in, g.c_out = a.c_out;
+    g.ci_tiles = (a.c_in + 31) / 32, g.co_tiles = (a.c_out + 31) / 32;
+    const int ct = g.ci_tiles >= 2 ? 2 : 1, ot = g.co_tiles >= 4 ? 4 : g.co_tiles >= 2 ? 2 : 1;
+    g.ci_groups = g.ci_tiles / ct, g.co_groups = g.co_tiles / ot;
+    g.in_cap = a.in_capacity, g.out_cap = a.out_capacity;
+    const int64_t slices = wg_slices(a.out_capacity);
+    g.n_work = slices * a.taps * g.ci_groups * g.co_groups;
+    g.n_out = a.n_out, g.table = a.table, g.x = a.x, g.dy = a.dy, g.part = w.part, g.part_b = w.part_b, g.dw = a.dw, g.db = a.db;
+    if (slices > 0) {
+        const dim3 grid(sp_grid((g.n_work + SP_WAVES - 1) / SP_WAVES, a.max_workgroups)), blk(SP_BLOCK);
+        if (ct == 2 && ot == 4) hipLaunchKernelGGL((sp_wgrad_kernel<2, 4>), grid, blk, 0, s, g);
+        else if (ct == 2 && ot == 2) hipLaunchKernelGGL((sp_wgrad_kernel<2, 2>), grid, blk, 0, s, g);
+        else if (ct == 2) hipLaunchKernelGGL((sp_wgrad_kernel<2, 1>), grid, blk, 0, s, g);
+        else if (ot == 4) hipLaunchKernelGGL((sp_wgrad_kernel<1, 4>), grid, blk, 0, s, g);
+        else if (ot == 2) hipLaunchKernelGGL((sp_wgrad_kernel<1, 2>), grid, blk, 0, s, g);
+        else hipLaunchKernelGGL((sp_wgrad_kernel<1, 1>), grid, blk, 0, s, g);
+        if (a.db) hipLaunchKernelGGL(sp_wgrad_bias_kernel, dim3(sp_grid(slices, a.max_workgroups)), blk, 0, s, g, slices);
+    }
+    const int64_t total = (int64_t)a.taps * a.c_in * a.c_out + (a.db ? a.c_out : 0);
+    hipLaunchKernelGGL(sp_wgrad_reduce_kernel, dim3(sp_grid(sp_tiles(total), a.max_workgroups)), dim3(SP_BLOCK), 0, s, g);
+    return hipGetLastError();
+}

@@ -11,7 +11,9 @@ the current stream; the read-back of the kept boxes inside `predict` is the only
 `double_flip` (test-time augmentation) is served by both: `forward` takes the reference's batch of four views per sample,
 `detect` makes the views itself. The loss is not built: `return_loss=True` is refused. `VoxelNet` has the same two doors
 with the 3-D grid, VoxelFeatureExtractorV3 and the sparse middle (sparse.SpMiddleResNetFHD) in front of the neck.
-`forward_two_stage` stays refused: the two-stage model is two_stage.TwoStageDetector, which wraps either detector, runs
+`VoxelNet.first_stage_loss(example)` is the training step up to the loss: the reader, the backbone's differentiable
+`train_forward`, the neck's and the head's stock-torch routes and `CenterHead.loss` (`forward(return_loss=True)` stays
+refused). `forward_two_stage` stays refused: the two-stage model is two_stage.TwoStageDetector, which wraps either detector, runs
 its stages up to the head itself and keeps the kept boxes on the device for the RoI head.
 """
 import torch
@@ -149,6 +151,20 @@ class VoxelNet(SingleStageDetector):
                     batch_size=len(example["num_voxels"]), input_shape=example["shape"][0])
         x, _ = self.extract_feat(data)
         return self.bbox_head.predict(example, self.bbox_head(x), self.test_cfg)
+
+    def first_stage_loss(self, example):
+        """the first stage's training step up to its loss: reader -> backbone.train_forward -> the neck's and the head's
+        stock-torch composite routes (BatchNorm by its mode) -> CenterHead.loss. example: the voxeliser's entries (voxels,
+        coordinates, num_points, num_voxels, shape; optionally n_voxels, the device count of a capacity-sized batch) and
+        the lists of center_loss.center_targets -> CenterHead.loss's dictionary; `loss` carries the graph to every
+        parameter of the backbone, the neck and the head."""
+        n_voxels = example.get("n_voxels")
+        feats = self.reader(example["voxels"], example["num_points"], n_pillars=n_voxels)
+        x, _ = self.backbone.train_forward(feats, example["coordinates"], len(example["num_voxels"]), example["shape"][0],
+                                           n_voxels=n_voxels, capacities=self.sparse_capacities)
+        if self.with_neck:
+            x = self.neck.composite(x)
+        return self.bbox_head.loss(example, self.bbox_head.composite(x))
 
     def forward_two_stage(self, example, return_loss=False, **kwargs):
         raise NotImplementedError("VoxelNet.forward_two_stage: the second stage is not built into this method: two_stage."

@@ -6,9 +6,14 @@ Weights are spconv 1.x's (kD, kH, kW, c_in, c_out) and the operation is a cross-
 in[p * stride - padding + k] @ W[k] over the taps whose input site is active. A submanifold layer (kernel 3) keeps its input's
 sites and row order; a SparseConv3d's sites are emitted in ascending (b, z, y, x) order. Site counts stay on the device
 (`SparseConvTensor.n`, an int64 (1) tensor the later kernels read): the forward never synchronises, every buffer is
-capacity-sized, and a level that would exceed its capacity sets _hip.SP_OVERFLOW in `status` and stays in bounds. Eval mode,
-float32; a train-mode forward is refused. There is no CPU route.
+capacity-sized, and a level that would exceed its capacity sets _hip.SP_OVERFLOW in `status` and stays in bounds. float32.
+`forward` is the eval-mode route (BatchNorm folded into the packs; a train-mode forward is refused). `train_forward` is
+the differentiable one: every convolution is a torch.autograd.Function around dal3_sp_conv whose backward runs the data
+gradient on the same kernel (the transposed pack on the inverse table) and the weight gradient through dal3_sp_wgrad;
+BatchNorm over the live rows (`batch_norm_rows`), ReLU and the residual are stock torch ops. There is no CPU route.
 """
+from types import SimpleNamespace
+
 import numpy as np
 import torch
 from torch import nn
@@ -225,6 +230,131 @@ def conv(features, table, n_out, packed, c_in, c_out, status, relu=False, residu
     return canvas if canvas is not None else out
 
 
+# ------------------------------------------------------------------------------------- the backward pass
+DGRAD_WIDTHS = (16, 32, 64, 128)                # the kernel's output widths: a data gradient has the layer's c_in channels
+
+
+def transposed_table(x, out_keys, out_n, out_capacity, shape_out, kernel, stride, padding, max_workgroups=0, table=None):
+    """(taps, x.capacity) int32, tap-major: the output row that reads input row j under each tap, -1 for none
+    (dal3_sp_table_transposed). out_keys: `downsample`'s ascending keys of the output sites"""
+    taps = int(np.prod(kernel))
+    if table is None:
+        table = torch.empty((taps, x.capacity), dtype=torch.int32, device=x.features.device)
+    a = _hip.SpTableTransposedArgs(B=x.batch_size, in_shape=_i3(x.spatial_shape), out_shape=_i3(shape_out), kernel=_i3(kernel),
+                                   stride=_i3(stride), padding=_i3(padding), in_capacity=x.capacity, n_in=_hip.ptr(x.n),
+                                   in_indices=_hip.ptr(x.indices), out_capacity=out_capacity, n_out=_hip.ptr(out_n),
+                                   out_key=_hip.ptr(out_keys), table=_hip.ptr(table), max_workgroups=int(max_workgroups))
+    _hip.check(_hip.lib().dal3_sp_table_transposed(a, _hip.stream()))
+    return table
+
+
+def wgrad(features, table, n_out, dy, kernel_size, bias=True, max_workgroups=0):
+    """one dal3_sp_wgrad launch: the layer's input rows (in_capacity, c_in), its forward table (taps, out_capacity) and the
+    incoming gradient (out_capacity, c_out) -> (dW (kD, kH, kW, c_in, c_out), db (c_out) or None)"""
+    taps, out_cap = table.shape
+    dev, c_in, c_out = features.device, features.shape[1], dy.shape[1]
+    for t, what, rows in ((features, "features", features.shape[0]), (dy, "dy", out_cap)):
+        _hip.require_gpu(t, what)
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape[0] != rows:
+            raise ValueError(f"{what} must be contiguous float32 ({rows}, C), got {t.dtype} {tuple(t.shape)}")
+    lib = _hip.lib()
+    nbytes = lib.dal3_sp_wgrad_workspace_bytes(taps, c_in, c_out, out_cap)
+    if not nbytes and out_cap:
+        raise ValueError(f"the kernel serves c_in 1 .. 8, 16, 32, 64, 128 and c_out 16, 32, 64, 128, not {c_in} -> {c_out}")
+    ws = _hip.workspace(nbytes, dev)
+    dw = torch.empty((*kernel_size, c_in, c_out), dtype=torch.float32, device=dev)
+    db = torch.empty(c_out, dtype=torch.float32, device=dev) if bias else None
+    a = _hip.SpWgradArgs(taps=taps, c_in=c_in, c_out=c_out, in_capacity=features.shape[0], x=_hip.ptr(features), out_capacity=out_cap,
+                         n_out=_hip.ptr(n_out), table=_hip.ptr(table), dy=_hip.ptr(dy), dw=_hip.ptr(dw), db=_hip.ptr(db),
+                         max_workgroups=int(max_workgroups), workspace=_hip.ptr(ws), workspace_bytes=nbytes)
+    _hip.check(lib.dal3_sp_wgrad(a, _hip.stream()))
+    return dw, db
+
+
+def _pack_raw(weight, bias, kernel_size):
+    """the unfolded pack of a (kD, kH, kW, c_in, c_out) weight"""
+    return pack_layer(SimpleNamespace(weight=weight, bias=bias, in_channels=weight.shape[3], out_channels=weight.shape[4],
+                                      kernel_size=kernel_size), None)
+
+
+class _SparseConvFunction(torch.autograd.Function):
+    """y = dal3_sp_conv(features; weight, bias) on a layer's tables. Rows of y, and of the gradients, at or beyond the device
+    counts are +0. The backward: dx through dal3_sp_conv on the inverse table with the transposed pack, (dW, db) through
+    dal3_sp_wgrad; either is skipped when nothing asks for it."""
+
+    @staticmethod
+    def forward(ctx, features, weight, bias, geom):
+        features = features.contiguous()
+        c_in, c_out = weight.shape[3], weight.shape[4]
+        packed = _pack_raw(weight.detach(), None if bias is None else bias.detach(), geom.kernel_size)
+        out = torch.zeros((geom.table.shape[1], c_out), dtype=torch.float32, device=features.device)
+        conv(features, geom.table, geom.n_out, packed, c_in, c_out, geom.status, center_tap=geom.center, out=out,
+             max_workgroups=geom.max_workgroups)
+        ctx.save_for_backward(features, weight)
+        ctx.geom, ctx.has_bias = geom, bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        features, weight = ctx.saved_tensors
+        g = ctx.geom
+        dy = dy.contiguous()
+        c_in, c_out = weight.shape[3], weight.shape[4]
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            w = weight.detach()
+            wt = (w.flip(0, 1, 2) if g.subm else w).transpose(3, 4).contiguous()
+            dx = torch.zeros_like(features)
+            conv(dy, g.inverse, g.n_in, _pack_raw(wt, None, g.kernel_size), c_out, c_in, g.status, center_tap=g.center, out=dx,
+                 max_workgroups=g.max_workgroups)
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            dw, db = wgrad(features, g.table, g.n_out, dy, g.kernel_size, ctx.has_bias, g.max_workgroups)
+        return dx, dw, db, None
+
+
+def _mask_rows(n, rows, device):
+    """(rows, 1) bool: the rows in use; None without a count"""
+    return None if n is None else (torch.arange(rows, device=device) < n)[:, None]
+
+
+def batch_norm_rows(bn, features, n=None):
+    """nn.BatchNorm1d `bn` over the first n rows of features (capacity, C); n: a device int64 (1) tensor or None (every row).
+    Stock torch ops, differentiable, nothing synchronises. Rows at or beyond n are replaced by +0 before any arithmetic and
+    are +0 in the output, so a NaN there reaches neither a statistic nor a gradient. In train mode the statistics are the
+    biased batch ones over the n live rows and the running ones take the layer's momentum (the cumulative average with
+    momentum None) with the unbiased variance; num_batches_tracked is incremented. In eval mode (a frozen BatchNorm) the
+    running statistics are used. nn.BatchNorm1d raises for one row in train mode; that would need the count on the host.
+    Here n <= 1 normalises with the batch statistics as they are (one row becomes the bias, no row gives no output) and
+    leaves running_mean and running_var untouched; num_batches_tracked still counts the step."""
+    if not (isinstance(bn, nn.BatchNorm1d) and bn.affine and bn.track_running_stats):
+        raise RuntimeError("the norm layer must be an affine nn.BatchNorm1d with running statistics")
+    rows = features.shape[0]
+    mask = _mask_rows(n, rows, features.device)
+    x = features if mask is None else torch.where(mask, features, torch.zeros((), dtype=features.dtype, device=features.device))
+    if bn.training:
+        if n is None:
+            cnt = torch.full((), float(rows), dtype=features.dtype, device=features.device)
+        else:
+            cnt = n.clamp(0, rows).to(features.dtype).reshape(())
+        den = cnt.clamp(min=1.0)
+        mean = x.sum(0) / den
+        d = x - mean
+        if mask is not None:
+            d = torch.where(mask, d, torch.zeros((), dtype=features.dtype, device=features.device))
+        var = (d * d).sum(0) / den
+        with torch.no_grad():
+            bn.num_batches_tracked += 1
+            m = 1.0 / bn.num_batches_tracked.to(features.dtype) if bn.momentum is None else bn.momentum
+            m = torch.where(cnt > 1, m * torch.ones_like(cnt), torch.zeros_like(cnt))
+            bn.running_mean += m * (mean - bn.running_mean)
+            bn.running_var += m * (var * (cnt / (cnt - 1).clamp(min=1.0)) - bn.running_var)
+    else:
+        mean, var = bn.running_mean, bn.running_var
+        d = x - mean
+    y = d / torch.sqrt(var + bn.eps) * bn.weight + bn.bias
+    return y if mask is None else torch.where(mask, y, torch.zeros((), dtype=y.dtype, device=y.device))
+
+
 class _SparseConv(_PackedLayers):
     """a parameter container with spconv 1.x's shapes: weight (kD, kH, kW, c_in, c_out), bias (c_out) or None"""
     subm = False
@@ -284,6 +414,33 @@ class _SparseConv(_PackedLayers):
         with torch.no_grad():
             return self.run(x, self.packed()[0], capacity=capacity, max_workgroups=max_workgroups)
 
+    def train_forward(self, x, capacity=None, max_workgroups=0):
+        """the differentiable layer: y = conv(x) + bias with gradients to x.features, weight and bias; no BatchNorm, no
+        ReLU. A SparseConv3d's inverse table is built with the forward one when the input asks for a gradient."""
+        need_dx = torch.is_grad_enabled() and x.features.requires_grad
+        if need_dx and self.in_channels not in DGRAD_WIDTHS:
+            raise RuntimeError(f"{type(self).__name__} with {self.in_channels} input channels has no data gradient (the kernel "
+                               f"produces {DGRAD_WIDTHS} channels): its input features must not require grad")
+        _hip.require_gpu(x.features, "features")
+        g = SimpleNamespace(subm=self.subm, kernel_size=self.kernel_size, n_in=x.n, status=x.status, max_workgroups=max_workgroups,
+                            inverse=None)
+        if self.subm:
+            if self.kernel_size != (3, 3, 3) or self.stride != (1, 1, 1):
+                raise NotImplementedError("SubMConv3d is served with kernel 3 and stride 1")
+            g.table = g.inverse = subm_table(x, self.indice_key, max_workgroups)      # the inverse: the same table, taps mirrored
+            g.n_out, g.center = x.n, 13
+            return x.like(_SparseConvFunction.apply(x.features, self.weight, self.bias, g))
+        indices, keys, n_out, cap, shape = downsample(x, self.kernel_size, self.stride, self.padding, capacity, max_workgroups)
+        g.table = neighbour_table(x, indices, n_out, cap, shape, self.kernel_size, self.stride, self.padding, max_workgroups)
+        if need_dx:
+            g.inverse = transposed_table(x, keys, n_out, cap, shape, self.kernel_size, self.stride, self.padding, max_workgroups)
+        g.n_out, g.center = n_out, -1
+        out = SparseConvTensor(_SparseConvFunction.apply(x.features, self.weight, self.bias, g), indices, shape, x.batch_size, n_out,
+                               x.status)
+        out.sorted = (keys, None)
+        out.rulebook = (g.table, g.inverse)                 # the level's tables, the inverse beside the forward one
+        return out
+
 
 class SubMConv3d(_SparseConv):
     """spconv.SubMConv3d, kernel 3: the output sites are the input sites in the same row order; `padding` plays no part"""
@@ -336,6 +493,15 @@ class SparseBasicBlock(_PackedLayers):
             p1, p2 = self.packed()
             out = self.conv1.run(x, p1, relu=True, max_workgroups=max_workgroups)
             return self.conv2.run(out, p2, relu=True, residual=x.features, max_workgroups=max_workgroups)
+
+    def train_forward(self, x, max_workgroups=0):
+        """the same block, differentiable: BatchNorm by its mode over the live rows (batch_norm_rows)"""
+        out = self.conv1.train_forward(x, max_workgroups=max_workgroups)
+        out = x.like(torch.relu(batch_norm_rows(self.bn1, out.features, x.n)))
+        out = self.conv2.train_forward(out, max_workgroups=max_workgroups)
+        f = torch.relu(batch_norm_rows(self.bn2, out.features, x.n) + x.features)
+        mask = _mask_rows(x.n, x.capacity, f.device)
+        return x.like(f if mask is None else torch.where(mask, f, torch.zeros((), dtype=f.dtype, device=f.device)))
 
 
 class SpMiddleResNetFHD(_PackedLayers):
@@ -397,3 +563,34 @@ class SpMiddleResNetFHD(_PackedLayers):
                 out[name] = x
             bev = self.extra_conv[0].run(x, packs["extra_conv"], relu=True, capacity=caps.get("extra_conv"), canvas=True, **kw)
             return bev, out
+
+    def train_forward(self, voxel_features, coors, batch_size, input_shape, n_voxels=None, capacities=None, max_workgroups=0):
+        """forward's arguments and outputs, differentiable in every parameter (and in voxel_features when the first layer
+        has 16 or more input channels): BatchNorm by its mode over the live rows, the BEV map through .dense(). Nothing
+        synchronises, in either direction."""
+        sparse_shape = tuple(int(v) for v in (np.array(input_shape[::-1]) + [1, 0, 0]))
+        if not torch.is_tensor(coors) or not torch.is_tensor(voxel_features):
+            raise TypeError("voxel_features and coors must be tensors")
+        x = SparseConvTensor(voxel_features, coors.int(), sparse_shape, batch_size, n=n_voxels)
+        self.last_status = x.status
+        caps = dict(self.capacities or {}, **(capacities or {}))
+        kw = dict(max_workgroups=max_workgroups)
+
+        def stem(name, x):
+            seq = getattr(self, name)
+            y = seq[0].train_forward(x, **(kw if name == "conv_input" else dict(kw, capacity=caps.get(name))))
+            return y.like(torch.relu(batch_norm_rows(seq[1], y.features, y.n)))
+
+        x = stem("conv_input", x)
+        out = {}
+        for name in ("conv1", "conv2", "conv3", "conv4"):
+            blocks = list(getattr(self, name))
+            if name != "conv1":
+                x = stem(name, x)
+                blocks = blocks[3:]
+            for b in blocks:
+                x = b.train_forward(x, **kw)
+            out[name] = x
+        d = stem("extra_conv", x).dense()
+        B, C, D, H, W = d.shape
+        return d.reshape(B, C * D, H, W), out

@@ -1081,6 +1081,68 @@ size_t dal3_sp_conv_pack_floats(int taps, int c_in, int c_out);
 int dal3_sp_conv_pack(const dal3_layer* layer, int taps, double eps, float* out, int32_t* status, dal3_stream stream);
 int dal3_sp_conv(const dal3_sp_conv_args* args, dal3_stream stream);
 
+/* ---- the backward pass of the sparse convolutions (training the backbone).
+ *
+ * The data gradient needs no entry of its own: dx[j] = sum over taps k of dy[inv[k][j]] . W[k]^T is dal3_sp_conv with
+ * x = dy, the count of the layer's INPUT, the inverse table inv (taps, in_capacity) and the pack of the transposed weight
+ * (kD, kH, kW, c_out, c_in) through dal3_sp_conv_pack without bias or BatchNorm. A submanifold layer's inverse table is its
+ * own table with the taps mirrored (inv[k] = table[26 - k]): pack the flipped, transposed weight and pass the forward table
+ * with center_tap = 13. A SparseConv3d's comes from dal3_sp_table_transposed: table (taps, in_capacity) int32, tap-major:
+ * for input site j and tap k = (kz, ky, kx) the row of the output site o = (j + padding - k) / stride, when the division is
+ * exact on every axis, o lies in the output grid and is an active output site: found by lower_bound in out_key, the
+ * ascending keys of dal3_sp_downsample, whose rows are in key order; -1 otherwise (a site that an overflowed level dropped
+ * is simply absent). Columns [0, *n_in) are written; only the first min(*n_out, out_capacity) keys are read. No atomics;
+ * the bytes are the same for every max_workgroups.
+ *
+ * dal3_sp_wgrad: dw[k][ci][co] = sum over i < *n_out with table[k][i] >= 0 of x[table[k][i]][ci] * dy[i][co] and
+ * db[co] = sum over i < *n_out of dy[i][co], written in the parameter's own layout (kD, kH, kW, c_in, c_out) and (c_out);
+ * db may be NULL. Per tap a GEMM with the sites as the contraction on the fp32 MFMA: input channels on its rows, output
+ * channels on its columns, lane half h supplies site 2 s + h of k-step s, an absent neighbour supplies zeros and a k-step
+ * or a tap that no site of the wave has is skipped wave-uniformly. The sites are cut into slices of
+ * DAL3_SP_WGRAD_SLICE rows whatever the grid; every (tap, slice) writes its partial sums to the workspace and a second
+ * kernel adds the partials of the live slices in ascending slice order: no floating-point atomics, the bits are the same
+ * for every max_workgroups and from run to run. Rows of dy and table at or beyond min(*n_out, out_capacity) are never
+ * read, and x is read only through the table (entries outside [0, in_capacity) count as absent). c_in 1 .. 8, 16, 32,
+ * 64 or 128; c_out 16, 32, 64 or 128; 1 <= taps <= 27. x and dy are row-major with exactly c_in / c_out floats a row.
+ * workspace: dal3_sp_wgrad_workspace_bytes(taps, c_in, c_out, out_capacity) bytes (0 for bad arguments), 8-byte aligned.
+ * Invalid arguments return DAL3_EINVAL and nothing is launched. */
+enum { DAL3_SP_WGRAD_SLICE = 1024 };
+
+typedef struct dal3_sp_table_transposed_args {
+    int64_t B;
+    int32_t in_shape[3], out_shape[3];
+    int32_t kernel[3], stride[3], padding[3];
+    int32_t reserved;                    /* 0 */
+    int64_t in_capacity;
+    const int64_t* n_in;                 /* optional device (1) */
+    const int32_t* in_indices;           /* (in_capacity, 4) */
+    int64_t out_capacity;
+    const int64_t* n_out;                /* optional device (1) */
+    const int32_t* out_key;              /* (out_capacity) ascending: row r is output site r */
+    int32_t* table;                      /* (taps, in_capacity) */
+    int64_t max_workgroups;
+} dal3_sp_table_transposed_args;
+
+typedef struct dal3_sp_wgrad_args {
+    int32_t taps, c_in, c_out;
+    int32_t reserved;                    /* 0 */
+    int64_t in_capacity;
+    const float* x;                      /* (in_capacity, c_in): the layer's input */
+    int64_t out_capacity;
+    const int64_t* n_out;                /* optional device (1) */
+    const int32_t* table;                /* (taps, out_capacity): the forward table */
+    const float* dy;                     /* (out_capacity, c_out) */
+    float* dw;                           /* (taps, c_in, c_out) */
+    float* db;                           /* optional (c_out) */
+    int64_t max_workgroups;
+    void* workspace;
+    size_t workspace_bytes;
+} dal3_sp_wgrad_args;
+
+int dal3_sp_table_transposed(const dal3_sp_table_transposed_args* args, dal3_stream stream);
+size_t dal3_sp_wgrad_workspace_bytes(int taps, int c_in, int c_out, int64_t out_capacity);
+int dal3_sp_wgrad(const dal3_sp_wgrad_args* args, dal3_stream stream);
+
 /* ---- crop extraction from full sweeps: the per-detection loop of _create_pd_detection
  * (det3d/datasets/waymo/waymo_common.py:166-171, 193) for F frames at once. points (P_total,3) f32 vehicle-frame
  * sweeps concatenated, point_offsets (F+1); planes (K_total,6,4) f64 face equations of every frame's detections
