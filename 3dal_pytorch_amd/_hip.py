@@ -359,6 +359,34 @@ class CenterLossArgs(C.Structure):
                 ("grad", vp), ("workspace", vp), ("workspace_bytes", C.c_size_t)]
 
 
+AUG_TOO_MANY, AUG_OVERFLOW, AUG_BAD_ROW = 32768, 65536, 131072
+AUG_MAX_BOXES, AUG_MAX_CAND = 1024, 64
+
+
+class GtPasteArgs(C.Structure):
+    """dal3_gt_paste_args"""
+    _fields_ = [("B", C.c_int64), ("max_gt", C.c_int32), ("max_cand", C.c_int32), ("gt_boxes", vp), ("gt_classes", vp),
+                ("gt_counts", vp), ("cand_boxes", vp), ("cand_group", vp), ("cand_counts", vp), ("accept", vp), ("coll", vp),
+                ("status", vp)]
+
+
+class AugmentPointsArgs(C.Structure):
+    """dal3_augment_points_args"""
+    _fields_ = [("B", C.c_int64), ("n", C.c_int64), ("n_scene", C.c_int64), ("db_rows", C.c_int64), ("F", C.c_int32),
+                ("transform", C.c_int32), ("max_cand", C.c_int64), ("scene", vp), ("scene_offsets", vp), ("db_points", vp),
+                ("out_offsets", vp), ("cand_counts", vp), ("cand_seg_start", vp), ("cand_rows", vp), ("cand_db_row", vp),
+                ("cand_boxes", vp), ("accept", vp), ("keys", vp), ("xform", vp), ("out", vp), ("status", vp),
+                ("max_workgroups", C.c_int64), ("workspace", vp), ("workspace_bytes", C.c_size_t)]
+
+
+class AugmentBoxesArgs(C.Structure):
+    """dal3_augment_boxes_args"""
+    _fields_ = [("B", C.c_int64), ("max_gt", C.c_int32), ("max_cand", C.c_int32), ("max_objs", C.c_int32), ("n_classes", C.c_int32),
+                ("transform", C.c_int32), ("reserved", C.c_int32), ("gt_boxes", vp), ("gt_classes", vp), ("gt_counts", vp),
+                ("cand_boxes", vp), ("cand_classes", vp), ("cand_counts", vp), ("accept", vp), ("xform", vp),
+                ("range", C.c_float * 4), ("out", vp), ("out_count", vp), ("status", vp)]
+
+
 # every symbol include/dal3.h declares: (restype, argtypes)
 _i, _i64, _u64, _sz = C.c_int, C.c_int64, C.c_uint64, C.c_size_t
 SIGNATURES = {
@@ -445,6 +473,10 @@ SIGNATURES = {
     "dal3_center_targets": (_i, [C.POINTER(CenterTargetsArgs), vp]),
     "dal3_center_loss_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "dal3_center_loss": (_i, [C.POINTER(CenterLossArgs), vp]),
+    "dal3_gt_paste_select": (_i, [C.POINTER(GtPasteArgs), vp]),
+    "dal3_augment_points_workspace_bytes": (_sz, [_i64, _i64]),
+    "dal3_augment_points": (_i, [C.POINTER(AugmentPointsArgs), vp]),
+    "dal3_augment_boxes": (_i, [C.POINTER(AugmentBoxesArgs), vp]),
     "dal3_crop_workspace_bytes": (_sz, [_i64, _i64]),
     "dal3_crop_count": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, _sz, vp]),
     "dal3_crop_fill": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, vp, vp, vp, _i64, vp, _sz, vp]),

@@ -2600,3 +2600,61 @@ extern "C" int dal3_center_loss(const dal3_center_loss_args* args, dal3_stream s
     HIP_TRY(e);
     return 0;
 }
+
+// ---------------------------------------------------------------------------------- the training input
+static bool aug_dims_ok(int64_t B, int32_t max_gt, int64_t max_cand) {
+    return B >= 0 && B <= 65535 && max_gt >= 1 && max_gt <= DAL3_AUG_MAX_BOXES && max_cand >= 1 && max_cand <= DAL3_AUG_MAX_CAND;
+}
+
+extern "C" int dal3_gt_paste_select(const dal3_gt_paste_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "gt_paste_select: null args");
+    const dal3_gt_paste_args& a = *args;
+    if (!aug_dims_ok(a.B, a.max_gt, a.max_cand))
+        return fail(DAL3_EINVAL, "gt_paste_select: bad B (<= 65535) / max_gt (1 .. %d) / max_cand (1 .. %d)", DAL3_AUG_MAX_BOXES, DAL3_AUG_MAX_CAND);
+    if (!a.gt_boxes || !a.gt_classes || !a.gt_counts || !a.cand_boxes || !a.cand_group || !a.cand_counts || !a.accept || !a.status)
+        return fail(DAL3_EINVAL, "gt_paste_select: null argument");
+    HIP_TRY(launch_gt_paste_select(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+extern "C" size_t dal3_augment_points_workspace_bytes(int64_t B, int64_t n) {
+    if (B < 0 || B > 65535 || n < 0 || n >= ((int64_t)1 << 31)) return 0;
+    return augment_points_workspace_bytes(B, n);
+}
+
+extern "C" int dal3_augment_points(const dal3_augment_points_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "augment_points: null args");
+    const dal3_augment_points_args& a = *args;
+    if (a.B < 0 || a.B > 65535 || a.n < 0 || a.n >= ((int64_t)1 << 31) || a.n_scene < 0 || a.db_rows < 0)
+        return fail(DAL3_EINVAL, "augment_points: bad B (<= 65535) / n (< 2^31) / n_scene / db_rows");
+    if (a.F < 3 || a.F > 8) return fail(DAL3_EINVAL, "augment_points: F %d (3 .. 8)", (int)a.F);
+    if (a.max_cand < 1 || a.max_cand > DAL3_AUG_MAX_CAND || a.max_workgroups < 0)
+        return fail(DAL3_EINVAL, "augment_points: bad max_cand (1 .. %d) / max_workgroups", DAL3_AUG_MAX_CAND);
+    if (!a.status || !a.workspace || (reinterpret_cast<uintptr_t>(a.workspace) & 7)) return fail(DAL3_EINVAL, "augment_points: null status, or workspace null or misaligned");
+    if (a.n > 0 && a.B > 0) {
+        if (!a.out || !a.out_offsets || !a.scene_offsets || !a.cand_counts || !a.cand_seg_start || !a.cand_rows || !a.cand_db_row ||
+            (a.n_scene > 0 && !a.scene) || (a.db_rows > 0 && (!a.db_points || !a.cand_boxes || !a.accept)) || (a.transform && !a.xform))
+            return fail(DAL3_EINVAL, "augment_points: null argument");
+        if (a.F == 4 && ((reinterpret_cast<uintptr_t>(a.out) | reinterpret_cast<uintptr_t>(a.scene) | reinterpret_cast<uintptr_t>(a.db_points)) & 15))
+            return fail(DAL3_EINVAL, "augment_points: four-column rows must be 16-byte aligned");
+    }
+    hipError_t e = hipSuccess;
+    if (!launch_augment_points(args, static_cast<hipStream_t>(stream), &e))
+        return fail(DAL3_EWORKSPACE, "augment_points: workspace of %zu bytes, %zu needed", a.workspace_bytes, augment_points_workspace_bytes(a.B, a.n));
+    HIP_TRY(e);
+    return 0;
+}
+
+extern "C" int dal3_augment_boxes(const dal3_augment_boxes_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "augment_boxes: null args");
+    const dal3_augment_boxes_args& a = *args;
+    if (!aug_dims_ok(a.B, a.max_gt, a.max_cand))
+        return fail(DAL3_EINVAL, "augment_boxes: bad B (<= 65535) / max_gt (1 .. %d) / max_cand (1 .. %d)", DAL3_AUG_MAX_BOXES, DAL3_AUG_MAX_CAND);
+    if (a.max_objs < 1 || a.max_objs > DAL3_CENTER_MAX_OBJS || a.n_classes < 1 || a.n_classes > DAL3_CENTER_MAX_CLASSES)
+        return fail(DAL3_EINVAL, "augment_boxes: bad max_objs (1 .. %d) / n_classes (1 .. %d)", DAL3_CENTER_MAX_OBJS, DAL3_CENTER_MAX_CLASSES);
+    if (!a.gt_boxes || !a.gt_classes || !a.gt_counts || !a.out || !a.out_count || !a.status || (a.transform && !a.xform) ||
+        (a.accept && (!a.cand_boxes || !a.cand_classes || !a.cand_counts)))
+        return fail(DAL3_EINVAL, "augment_boxes: null argument");
+    HIP_TRY(launch_augment_boxes(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}

@@ -570,3 +570,8 @@ hipError_t launch_roi_loss(const float* rcnn_cls, const float* rcnn_reg, int64_t
 hipError_t launch_center_targets(const dal3_center_targets_args* a, hipStream_t s);
 size_t center_loss_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W);
 bool launch_center_loss(const dal3_center_loss_args* a, hipStream_t s, hipError_t* err);
+// the training input (dal3_augment.hip): GT paste selection, the points' augmentation and shuffle, the boxes' side
+hipError_t launch_gt_paste_select(const dal3_gt_paste_args* a, hipStream_t s);
+size_t augment_points_workspace_bytes(int64_t B, int64_t n);
+bool launch_augment_points(const dal3_augment_points_args* a, hipStream_t s, hipError_t* err);
+hipError_t launch_augment_boxes(const dal3_augment_boxes_args* a, hipStream_t s);

@@ -166,6 +166,29 @@ class VoxelNet(SingleStageDetector):
             x = self.neck.composite(x)
         return self.bbox_head.loss(example, self.bbox_head.composite(x))
 
+    def set_train_input(self, preprocess, assigner):
+        """the stages `train_step_from_sweeps` feeds the loss with: an augment.Preprocess and a center_loss.AssignLabel"""
+        self.train_input = (preprocess, assigner)
+
+    def train_step_from_sweeps(self, points, point_offsets, annotations, draws=None):
+        """resident sweeps and annotations -> CenterHead.loss's dictionary, on the current stream with no host
+        synchronisation: augment.train_example (GT paste, augmentation, shuffle; voxelisation; AssignLabel) and then
+        first_stage_loss. points (N, F) float32 CUDA, point_offsets (B + 1) on the host, annotations: {gt_boxes (B, max_gt, 9)
+        CUDA, gt_classes, gt_counts} as augment.Preprocess takes them; draws: the step's augment.Draws (None: drawn on the
+        device). `last_example` keeps the example."""
+        if getattr(self, "train_input", None) is None:
+            raise RuntimeError("train_step_from_sweeps needs set_train_input(preprocess, assigner) first")
+        if self.voxel_size is None:
+            raise RuntimeError("train_step_from_sweeps needs the reader's voxel_size and pc_range: build the model with them")
+        from . import augment
+        preprocess, assigner = self.train_input
+        example = augment.train_example(preprocess, assigner, points, point_offsets, annotations["gt_boxes"], annotations["gt_classes"],
+                                        annotations["gt_counts"], voxel_size=self.voxel_size, pc_range=self.pc_range,
+                                        max_points=self.max_points, max_voxels=self.max_voxels, draws=draws,
+                                        candidates=annotations.get("candidates"))
+        self.last_example = example
+        return self.first_stage_loss(example)
+
     def forward_two_stage(self, example, return_loss=False, **kwargs):
         raise NotImplementedError("VoxelNet.forward_two_stage: the second stage is not built into this method: two_stage."
                                   "TwoStageDetector runs the first stage through extract_feat and bbox_head itself")

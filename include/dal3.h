@@ -1900,6 +1900,118 @@ int dal3_center_targets(const dal3_center_targets_args* args, dal3_stream stream
 size_t dal3_center_loss_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W);
 int dal3_center_loss(const dal3_center_loss_args* args, dal3_stream stream);
 
+/* ---- The training input (det3d/datasets/pipelines/preprocess.py Preprocess in train mode, Voxelization's
+ * filter_gt_box_outside_range, AssignLabel's regrouping; det3d/core/sampler/sample_ops.py DataBaseSamplerV2.sample_all):
+ * ground-truth paste, the global augmentation of points and boxes, the point shuffle. float32, B samples in one enqueue,
+ * nothing read back. (Additions only; DAL3_VERSION stays.)
+ *
+ * Boxes have 9 columns x, y, z, w, l, h, vx, vy, rot. A sample has gt_counts[b] <= max_gt annotated boxes and
+ * cand_counts[b] <= max_cand candidates from the object database, which the host has drawn (the integer bookkeeping of
+ * sample_all) in the order of the sampler's groups: cand_group is non-decreasing within a sample. A GT class is the 1-based
+ * index into class_names, 0 for a name outside it (the box still blocks a paste, and is dropped from the output), negative
+ * for a name the reference removes first (DontCare, ignore, UNKNOWN: the box takes part in nothing).
+ *
+ * dal3_gt_paste_select: sample_class_v2 for every group of every sample, one workgroup per sample.
+ *   BEV corners as center_to_corner_box2d forms them in float32 (clockwise from the minimum corner; sin and cos of the
+ *   angle rounded once). Entry [i, j] of the pair matrix, candidate i against box j (the GT boxes, then the candidates), is
+ *   box_collision_test's: stand-up boxes overlapping by more than 0 on both axes, then any of the sixteen edge pairs crossing
+ *   by its four strict orientation tests, else every corner of one box strictly inside the other (cross >= 0 is outside).
+ *   Every product and difference is one float32 rounding. The diagonal is false. coll (optional, zeroed by the caller)
+ *   receives the matrix as (B, max_cand, max_gt + max_cand) bytes, the candidates' columns from max_gt on.
+ *   Acceptance is the reference's serial loop: in candidate order, candidate i is rejected when it collides with a GT box,
+ *   with an accepted candidate of an earlier group, or with a candidate of its own group that has not been rejected (later
+ *   ones included); a rejected candidate's row and column are dead from then on. accept (B, max_cand) gets 1 / 0.
+ *   The matrix is held in LDS, 40 bytes a box of the 64 KiB a workgroup declares: gt_counts[b] + cand_counts[b] <=
+ *   DAL3_AUG_MAX_BOXES and cand_counts[b] <= DAL3_AUG_MAX_CAND (a column is one 64-bit word); a sample beyond that accepts
+ *   nothing and sets DAL3_AUG_TOO_MANY.
+ *
+ * dal3_augment_points: out (n, F), n = out_offsets[B]. Sample b's source rows, indexed like its output segment
+ *   [out_offsets[b], out_offsets[b + 1]), are its candidates' rows in candidate order (candidate k: rows cand_db_row[k] ..
+ *   + cand_rows[k] of db_points, the first of them at source index cand_seg_start[k]; accepted or not, so the sizes are the
+ *   host's) followed by its scene rows [scene_offsets[b], scene_offsets[b + 1]): the reference's order before its shuffle.
+ *   Output row p is the source row of rank p - out_offsets[b] under a stable ascending sort of the sample's order keys
+ *   (keys (n) int32, the low 31 bits; NULL: the identity). The ranks come from one chunked radix sort of (sample, key).
+ *   A candidate's row is first moved by its box centre; the row of a rejected candidate is written as NaN in every column
+ *   (dal3_voxelize drops such rows). With transform != 0 every other row then gets, each step one float32 rounding:
+ *   y = -y if xform[b][0], x = -x if xform[b][1]; (x, y) = (x c + y s, -x s + y c) with s, c the float32 of sin, cos of the
+ *   float64 xform[b][2]; xyz *= (float)xform[b][3]; xyz = (float)((double)xyz + xform[b][4..6]) (the reference adds a float64
+ *   array to its float32 points, which NumPy evaluates in float64). Columns 3 .. F - 1 are copied. 3 <= F <= 8.
+ *   A source row outside its arrays is written as NaN and sets DAL3_AUG_BAD_ROW (the device offsets disagree with the
+ *   host's). workspace: dal3_augment_points_workspace_bytes(B, n); n < 2^31, B <= 65535.
+ *
+ * dal3_augment_boxes: gt_boxes_and_cls (B, max_objs, 10) and out_count (B), one workgroup per sample. The GT boxes, then the
+ *   accepted candidates (accept NULL: none); rows whose class is outside 1 .. n_classes are dropped. With transform != 0,
+ *   in the reference's order: flips (y = -y, rot = -rot + pi, vy = -vy; x = -x, rot = -rot + 2 pi, vx = -vx), rotation (xyz
+ *   as the points; (vx, vy) by the float64 sine and cosine, rounded once; rot += (float)angle), columns 0 .. 7 times the
+ *   scale, xyz plus the translation as for the points. Then filter_gt_box_outside_range: a box stays when one of its four
+ *   BEV corners lies strictly inside minmax_to_corner_2d(range)'s polygon (range: x0, y0, x1, y1); limit_period(rot, 0.5, 2 pi);
+ *   and AssignLabel's order, stable by class (its tasks partition class_names in order, so task order then class order within
+ *   the task is class order, and the merged class id is the class itself). Row: x, y, z, w, l, h, rot, vx, vy, class; zero
+ *   rows behind the count. More than max_objs rows keep the first max_objs and set DAL3_AUG_OVERFLOW (the reference asserts).
+ *   The same limits as dal3_gt_paste_select. */
+enum { DAL3_AUG_TOO_MANY = 32768, DAL3_AUG_OVERFLOW = 65536, DAL3_AUG_BAD_ROW = 131072 };   /* status bits */
+#define DAL3_AUG_MAX_BOXES 1024
+#define DAL3_AUG_MAX_CAND 64
+
+typedef struct dal3_gt_paste_args {
+    int64_t B;
+    int32_t max_gt, max_cand;
+    const float* gt_boxes;               /* (B, max_gt, 9) */
+    const int32_t* gt_classes;           /* (B, max_gt) */
+    const int32_t* gt_counts;            /* (B) */
+    const float* cand_boxes;             /* (B, max_cand, 9) */
+    const int64_t* cand_group;           /* (B, max_cand) */
+    const int64_t* cand_counts;          /* (B) */
+    uint8_t* accept;                     /* (B, max_cand) */
+    uint8_t* coll;                       /* optional (B, max_cand, max_gt + max_cand), zeroed by the caller */
+    int32_t* status;                     /* (1) OR-ed */
+} dal3_gt_paste_args;
+
+typedef struct dal3_augment_points_args {
+    int64_t B, n, n_scene, db_rows;
+    int32_t F, transform;
+    int64_t max_cand;
+    const float* scene;                  /* (n_scene, F) */
+    const int64_t* scene_offsets;        /* (B + 1) */
+    const float* db_points;              /* (db_rows, F) */
+    const int64_t* out_offsets;          /* (B + 1) */
+    const int64_t* cand_counts;          /* (B) */
+    const int64_t* cand_seg_start;       /* (B, max_cand) */
+    const int64_t* cand_rows;            /* (B, max_cand) */
+    const int64_t* cand_db_row;          /* (B, max_cand) */
+    const float* cand_boxes;             /* (B, max_cand, 9) */
+    const uint8_t* accept;               /* (B, max_cand) */
+    const int32_t* keys;                 /* (n) or NULL */
+    const double* xform;                 /* (B, 7): flip y, flip x, rotation, scale, translation; NULL without transform */
+    float* out;                          /* (n, F) */
+    int32_t* status;
+    int64_t max_workgroups;
+    void* workspace;
+    size_t workspace_bytes;
+} dal3_augment_points_args;
+
+typedef struct dal3_augment_boxes_args {
+    int64_t B;
+    int32_t max_gt, max_cand, max_objs, n_classes, transform, reserved;
+    const float* gt_boxes;
+    const int32_t* gt_classes;
+    const int32_t* gt_counts;
+    const float* cand_boxes;
+    const int64_t* cand_classes;         /* (B, max_cand) */
+    const int64_t* cand_counts;
+    const uint8_t* accept;               /* NULL: no candidates */
+    const double* xform;
+    float range[4];
+    float* out;                          /* (B, max_objs, 10) */
+    int32_t* out_count;                  /* (B) */
+    int32_t* status;
+} dal3_augment_boxes_args;
+
+int dal3_gt_paste_select(const dal3_gt_paste_args* args, dal3_stream stream);
+size_t dal3_augment_points_workspace_bytes(int64_t B, int64_t n);
+int dal3_augment_points(const dal3_augment_points_args* args, dal3_stream stream);
+int dal3_augment_boxes(const dal3_augment_boxes_args* args, dal3_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
