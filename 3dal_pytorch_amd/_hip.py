@@ -640,9 +640,11 @@ def bcn(t):
 
 
 def layer_struct(conv, bn):
-    """nn.Conv1d(k=1)/nn.Linear (+ optional nn.BatchNorm1d) -> dal3_layer of raw device pointers."""
+    """a convolution or nn.Linear (+ optional BatchNorm) -> dal3_layer of raw device pointers. The widths are the
+    module's in_channels / out_channels where it has them (a transposed or sparse convolution's weight is not
+    (c_out, c_in, ...)), the weight's first two extents otherwise."""
     w = conv.weight
-    c_out, c_in = w.shape[0], w.shape[1]
+    c_in, c_out = getattr(conv, "in_channels", w.shape[1]), getattr(conv, "out_channels", w.shape[0])
     if not w.is_contiguous() or w.dtype != torch.float32:
         raise RuntimeError("weights must be contiguous fp32")
     L = Layer(ptr(w), ptr(conv.bias), None, None, None, None, c_in, c_out)
@@ -650,6 +652,19 @@ def layer_struct(conv, bn):
         L.bn_weight, L.bn_bias = ptr(bn.weight), ptr(bn.bias)
         L.bn_mean, L.bn_var = ptr(bn.running_mean), ptr(bn.running_var)
     return L
+
+
+def fold_layer_struct(conv, bn, what="the layer's parameters"):
+    """layer_struct for the packers that fold a BatchNorm on the device: every tensor of the (conv, bn) pair, the
+    running statistics too, must be on the GPU and contiguous fp32."""
+    ts = [conv.weight] + ([conv.bias] if conv.bias is not None else [])
+    if bn is not None:
+        ts += [bn.weight, bn.bias, bn.running_mean, bn.running_var]
+    for t in ts:
+        require_gpu(t, what)
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError("weights must be contiguous fp32")
+    return layer_struct(conv, bn)
 
 
 F16_MAX = 65504.0

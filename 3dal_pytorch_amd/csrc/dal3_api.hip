@@ -1332,6 +1332,20 @@ extern "C" int dal3_voxel_mean(const float* voxels, const int32_t* num_points, i
 // ---------------------------------------------------------------------------------- the detector's dense stage
 static bool conv2d_kind_ok(int kind) { return kind >= DAL3_CONV2D_3X3 && kind <= DAL3_CONV2D_DECONV4; }
 
+// What the three pack entries of the folded MFMA layers ask of a layer (the fold: dal3_fold.h). index >= 0: the layer's
+// place in a list (roi_pack's wording). The point heads' check_layer has other rules (a bias is mandatory) and is not this.
+static int check_fold_layer(const char* who, const dal3_layer* L, int index, double eps, const float* out) {
+    if (!L->weight) return index < 0 ? fail(DAL3_EINVAL, "%s: null weight", who) : fail(DAL3_EINVAL, "%s: layer %d has no weight", who, index);
+    const bool bn = L->bn_weight || L->bn_bias || L->bn_mean || L->bn_var;
+    if (bn && !(L->bn_weight && L->bn_bias && L->bn_mean && L->bn_var))
+        return fail(DAL3_EINVAL, "%s: a BatchNorm needs all four of weight, bias, mean and var", who);
+    if (bn && !(eps > 0.0))
+        return index < 0 ? fail(DAL3_EINVAL, "%s: bad eps (> 0)", who)
+                         : fail(DAL3_EINVAL, "%s: layer %d needs its BatchNorm's eps (> 0)", who, index);
+    if (reinterpret_cast<uintptr_t>(out) & 15) return fail(DAL3_EINVAL, "%s: out must be 16-byte aligned", who);
+    return 0;
+}
+
 extern "C" size_t dal3_conv2d_pack_floats(int kind, int c_in, int c_out) {
     if (!conv2d_kind_ok(kind) || c_in < 1 || c_in > 4096 || c_out < 1 || c_out > 4096) return 0;
     return conv2d_pack_floats(kind, c_in, c_out);
@@ -1342,13 +1356,8 @@ extern "C" int dal3_conv2d_pack(const dal3_layer* layer, int kind, double eps, f
     if (!conv2d_kind_ok(kind)) return fail(DAL3_EINVAL, "conv2d_pack: kind %d is no DAL3_CONV2D_* form", kind);
     if (layer->c_in < 1 || layer->c_in > 4096 || layer->c_out < 1 || layer->c_out > 4096)
         return fail(DAL3_EINVAL, "conv2d_pack: bad c_in / c_out (1 .. 4096)");
-    if (!layer->weight) return fail(DAL3_EINVAL, "conv2d_pack: null weight");
-    const bool bn = layer->bn_weight || layer->bn_bias || layer->bn_mean || layer->bn_var;
-    if (bn && !(layer->bn_weight && layer->bn_bias && layer->bn_mean && layer->bn_var))
-        return fail(DAL3_EINVAL, "conv2d_pack: a BatchNorm needs all four of weight, bias, mean and var");
-    if (bn && !(eps > 0.0)) return fail(DAL3_EINVAL, "conv2d_pack: bad eps (> 0)");
-    if (reinterpret_cast<uintptr_t>(out) & 15) return fail(DAL3_EINVAL, "conv2d_pack: out must be 16-byte aligned");
-    HIP_TRY(launch_conv2d_pack(layer, kind, eps, out, static_cast<hipStream_t>(stream)));
+    TRY(check_fold_layer("conv2d_pack", layer, -1, eps, out));
+    HIP_TRY(launch_conv2d_pack(FoldLayer(*layer, eps), kind, out, static_cast<hipStream_t>(stream)));
     return 0;
 }
 
@@ -1469,13 +1478,8 @@ extern "C" int dal3_sp_conv_pack(const dal3_layer* layer, int taps, double eps, 
     if (!sp_channels_ok(layer->c_in, layer->c_out))
         return fail(DAL3_EINVAL, "sp_conv_pack: %d -> %d channels (c_in 1 .. 8, 16, 32, 64, 128; c_out 16, 32, 64, 128)", (int)layer->c_in,
                     (int)layer->c_out);
-    if (!layer->weight) return fail(DAL3_EINVAL, "sp_conv_pack: null weight");
-    const bool bn = layer->bn_weight || layer->bn_bias || layer->bn_mean || layer->bn_var;
-    if (bn && !(layer->bn_weight && layer->bn_bias && layer->bn_mean && layer->bn_var))
-        return fail(DAL3_EINVAL, "sp_conv_pack: a BatchNorm needs all four of weight, bias, mean and var");
-    if (bn && !(eps > 0.0)) return fail(DAL3_EINVAL, "sp_conv_pack: bad eps (> 0)");
-    if (reinterpret_cast<uintptr_t>(out) & 15) return fail(DAL3_EINVAL, "sp_conv_pack: out must be 16-byte aligned");
-    HIP_TRY(launch_sp_conv_pack(layer, taps, eps, out, status, static_cast<hipStream_t>(stream)));
+    TRY(check_fold_layer("sp_conv_pack", layer, -1, eps, out));
+    HIP_TRY(launch_sp_conv_pack(FoldLayer(*layer, eps), taps, out, status, static_cast<hipStream_t>(stream)));
     return 0;
 }
 
@@ -2447,18 +2451,13 @@ extern "C" int dal3_roi_pack(const dal3_roi_shape* shape, const dal3_layer* laye
         return fail(DAL3_EINVAL, "roi_pack: the shape is not served (1 .. 3 layers a list, widths multiples of 16 up to %d, "
                     "num_class 1, code_size 7 or 9)", DAL3_ROI_MAX_WIDTH);
     if (n_layers != want) return fail(DAL3_EINVAL, "roi_pack: %d layers given, the shape has %d", n_layers, want);
-    if (reinterpret_cast<uintptr_t>(out) & 15) return fail(DAL3_EINVAL, "roi_pack: out must be 16-byte aligned");
     for (int i = 0; i < n_layers; ++i) {
         const dal3_layer& L = layers[i];
         int c_in, c_out;
         roi_layer_dims(shape, i, &c_in, &c_out);
         if (L.c_in != c_in || L.c_out != c_out)
             return fail(DAL3_EINVAL, "roi_pack: layer %d is %d -> %d, the shape says %d -> %d", i, (int)L.c_in, (int)L.c_out, c_in, c_out);
-        if (!L.weight) return fail(DAL3_EINVAL, "roi_pack: layer %d has no weight", i);
-        const bool bn = L.bn_weight || L.bn_bias || L.bn_mean || L.bn_var;
-        if (bn && !(L.bn_weight && L.bn_bias && L.bn_mean && L.bn_var))
-            return fail(DAL3_EINVAL, "roi_pack: a BatchNorm needs all four of weight, bias, mean and var");
-        if (bn && !(eps && eps[i] > 0.0)) return fail(DAL3_EINVAL, "roi_pack: layer %d needs its BatchNorm's eps (> 0)", i);
+        TRY(check_fold_layer("roi_pack", &L, i, eps ? eps[i] : 0.0, out));
     }
     HIP_TRY(launch_roi_pack(shape, layers, eps, out, static_cast<hipStream_t>(stream)));
     return 0;

@@ -1,6 +1,6 @@
 // dal3_block.h — what the run kernels (dal3_motion.hip, dal3_track.hip, dal3_nms.hip, dal3_pillars.hip) share: the
 // workspace carver, the grid clamp, the integer workgroup primitives of their ordered compactions, radix sorts and
-// scans, the two binary searches, and the chunked radix sort of (key, position) pairs that the grouping run and the
+// scans, the float64 fixed-tree workgroup sum of the loss and training kernels, the two binary searches, and the chunked radix sort of (key, position) pairs that the grouping run and the
 // voxeliser both stand on. Everything here is used at two or more call sites; a building block with one user stays in
 // its file. A run kernel's workspace size is its carve on a null base (Carver::off), never a formula of its own.
 //
@@ -132,6 +132,22 @@ __device__ __forceinline__ void block_scan_inclusive(T* s) {
         s[t] += add;
         __syncthreads();
     }
+}
+
+// The float64 sum of one value per thread of a workgroup of `width` threads (a power of two) in a fixed tree: halves
+// from width / 2 down to 1, so the bits depend on nothing but the values. Every thread gets the sum; s[width] is free
+// again on return. `width` is a constant at most call sites and folds.
+__device__ __forceinline__ double block_sum_f64(double v, double* s, int width) {
+    const int t = threadIdx.x;
+    s[t] = v;
+    __syncthreads();
+    for (int off = width >> 1; off > 0; off >>= 1) {
+        if (t < off) s[t] += s[t + off];
+        __syncthreads();
+    }
+    const double r = s[0];
+    __syncthreads();
+    return r;
 }
 
 // In-place exclusive scan of n int32 by ONE workgroup of BLOCK threads: thread t owns the contiguous span

@@ -213,20 +213,6 @@ __device__ __forceinline__ int32_t mask_count(const uint8_t* mask, int64_t n, in
 // -1 / num_pos, or -1 in the num_pos == 0 branch: d hm_loss / d (the negative sum)
 __device__ __forceinline__ float hm_scale(int32_t num_pos) { return num_pos == 0 ? -1.f : __fdiv_rn(-1.f, (float)num_pos); }
 
-template <int BLOCK>
-__device__ __forceinline__ double block_sum(double v, double* s) {
-    const int t = threadIdx.x;
-    s[t] = v;
-    __syncthreads();
-    for (int off = BLOCK / 2; off > 0; off >>= 1) {
-        if (t < off) s[t] += s[t + off];
-        __syncthreads();
-    }
-    const double r = s[0];
-    __syncthreads();
-    return r;
-}
-
 struct LossWs {
     double* neg;        // one per workgroup of center_map_kernel
     double* sample;     // (B, CL_SUMS)
@@ -250,7 +236,7 @@ __global__ __launch_bounds__(CL_BLOCK) void center_map_kernel(const dal3_center_
         sum += (double)neg_term(cs.p, a.target_hm[i], dp);
         a.grad[b * GHW + rem] = __fmul_rn(__fmul_rn(k, dp), cs.ds);
     }
-    sum = block_sum<CL_BLOCK>(sum, s);
+    sum = block_sum_f64(sum, s, CL_BLOCK);
     if (t == 0) ws.neg[blockIdx.x] = sum;
     // this workgroup's share of the regression gradients' zero fill
     const uint32_t per = (n_reg + gridDim.x - 1) / gridDim.x, RHW = a.n_cols * HW;
@@ -307,7 +293,7 @@ __global__ __launch_bounds__(CS_BLOCK) void center_slot_kernel(const dal3_center
         }
     }
     for (int c = 0; c < 1 + cols; ++c) {
-        const double v = block_sum<CS_BLOCK>(sums[c], s);
+        const double v = block_sum_f64(sums[c], s, CS_BLOCK);
         if (t == 0) ws.sample[b * CL_SUMS + c] = v;
     }
 
@@ -359,7 +345,7 @@ __global__ __launch_bounds__(CL_BLOCK) void center_final_kernel(const dal3_cente
     const int32_t num_pos = mask_count(a.mask, a.B * a.max_objs, &s_count);
     double neg = 0.0;
     for (int64_t i = t; i < n_blocks; i += CL_BLOCK) neg += ws.neg[i];
-    neg = block_sum<CL_BLOCK>(neg, s);
+    neg = block_sum_f64(neg, s, CL_BLOCK);
     if (t < 1 + a.n_cols) {
         double v = 0.0;
         for (int64_t b = 0; b < a.B; ++b) v += ws.sample[b * CL_SUMS + t];

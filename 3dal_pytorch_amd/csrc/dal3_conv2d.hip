@@ -24,29 +24,16 @@ constexpr int CV_BLOCK = 256, CV_WAVES = 4, CV_T = 2, CV_ROWS = CV_WAVES * CV_T,
 __host__ __device__ constexpr int cv_taps(int kind) { return kind == DAL3_CONV2D_3X3 ? 9 : 1; }
 __host__ __device__ constexpr int cv_sub(int kind) { return kind == DAL3_CONV2D_DECONV2 ? 4 : kind == DAL3_CONV2D_DECONV4 ? 16 : 1; }
 
-struct ConvPackLayer {
-    const float *w, *bias, *g, *beta, *mean, *var;
-    int c_in, c_out;
-};
-
-// The fold, each operation a separately rounded float64 one (no contraction: tests/rpn_ref.py restates it bit for bit)
-__device__ __forceinline__ double cv_scale(const ConvPackLayer& L, int co, double eps) {
-    return L.g ? (double)L.g[co] / __dsqrt_rn(__dadd_rn((double)L.var[co], eps)) : 1.0;
-}
-
-__global__ __launch_bounds__(CV_BLOCK) void conv2d_pack_kernel(const ConvPackLayer L, int kind, double eps, int n_tiles, int nc8,
-                                                               int64_t total, float* out) {
+// (the fold itself: dal3_fold.h. Every index that grows with c_in is 64-bit or a channel number: the RoI head's first
+// layer comes here with up to 5 * 65535 inputs)
+__global__ __launch_bounds__(CV_BLOCK) void conv2d_pack_kernel(const FoldLayer L, int kind, int n_tiles, int nc8, int64_t total,
+                                                               float* out) {
     const int taps = cv_taps(kind), sub = cv_sub(kind), rows = L.c_out * sub;
     for (int64_t i = (int64_t)blockIdx.x * CV_BLOCK + threadIdx.x; i < total; i += (int64_t)gridDim.x * CV_BLOCK) {
         float v = 0.f;
         if (i < (int64_t)n_tiles * 32) {
             const int row = (int)i;
-            if (row < rows) {
-                const int co = row / sub;
-                const double b = L.bias ? (double)L.bias[co] : 0.0;
-                v = L.g ? (float)__dadd_rn(__dmul_rn(__dadd_rn(b, -(double)L.mean[co]), cv_scale(L, co, eps)), (double)L.beta[co])
-                        : (float)b;
-            }
+            if (row < rows) v = fold_bias(L, row / sub);
         } else {
             const int64_t j = i - (int64_t)n_tiles * 32;
             const int e = (int)(j & 3), lane = (int)((j >> 2) & 63);
@@ -56,7 +43,7 @@ __global__ __launch_bounds__(CV_BLOCK) void conv2d_pack_kernel(const ConvPackLay
             if (row < rows && ci < L.c_in) {
                 const int co = row / sub;
                 const int64_t at = sub == 1 ? ((int64_t)co * L.c_in + ci) * taps + tap : ((int64_t)ci * L.c_out + co) * sub + row % sub;
-                v = (float)__dmul_rn((double)L.w[at], cv_scale(L, co, eps));
+                v = fold_weight(L, at, co);
             }
         }
         out[i] = v;
@@ -206,13 +193,11 @@ size_t conv2d_pack_floats(int kind, int c_in, int c_out) {
     return (size_t)(n_tiles * 32 + n_tiles * nc8 * cv_taps(kind) * 256);
 }
 
-hipError_t launch_conv2d_pack(const dal3_layer* layer, int kind, double eps, float* out, hipStream_t s) {
-    const ConvPackLayer L = {layer->weight, layer->bias, layer->bn_weight, layer->bn_bias, layer->bn_mean, layer->bn_var,
-                             layer->c_in, layer->c_out};
+hipError_t launch_conv2d_pack(const FoldLayer& L, int kind, float* out, hipStream_t s) {
     const int64_t rows = (int64_t)L.c_out * cv_sub(kind), total = (int64_t)conv2d_pack_floats(kind, L.c_in, L.c_out);
     int64_t blocks = (total + CV_BLOCK - 1) / CV_BLOCK;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(conv2d_pack_kernel, dim3((unsigned)blocks), dim3(CV_BLOCK), 0, s, L, kind, eps, (int)((rows + 31) / 32),
+    hipLaunchKernelGGL(conv2d_pack_kernel, dim3((unsigned)blocks), dim3(CV_BLOCK), 0, s, L, kind, (int)((rows + 31) / 32),
                        (L.c_in + 7) / 8, total, out);
     return hipGetLastError();
 }

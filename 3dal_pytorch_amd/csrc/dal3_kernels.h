@@ -6,6 +6,7 @@
 
 #include "../../include/dal3.h"
 #include "dal3_device.h"
+#include "dal3_fold.h"
 
 // point tiles (of 32 points) per wave; see profiles/LEDGER_r01_r03.md §4 "register budget"
 #ifndef DAL3_ENC_T
@@ -333,7 +334,8 @@ hipError_t launch_voxel_mean(const float* voxels, const int32_t* num_points, int
                              int C, float* out, hipStream_t s);
 // the detector's dense stage (dal3_conv2d.hip): 3x3 / 1x1 / transposed convolutions as one implicit GEMM on the fp32 MFMA
 size_t conv2d_pack_floats(int kind, int c_in, int c_out);
-hipError_t launch_conv2d_pack(const dal3_layer* layer, int kind, double eps, float* out, hipStream_t s);
+// (internal: any c_in / c_out the format can hold, not only the public entry's 4096; the RoI head packs its sections here)
+hipError_t launch_conv2d_pack(const FoldLayer& layer, int kind, float* out, hipStream_t s);
 hipError_t launch_conv2d(const dal3_conv2d_args* a, hipStream_t s);
 // the VoxelNet detector's sparse 3-D middle (dal3_spconv.hip): site bookkeeping on the chunked radix sort, gather-GEMM convolutions
 size_t sp_sort_workspace_bytes(int64_t capacity);
@@ -343,7 +345,7 @@ size_t sp_downsample_workspace_bytes(int64_t in_capacity, int candidates);
 hipError_t launch_sp_downsample(const dal3_sp_downsample_args* a, hipStream_t s);
 hipError_t launch_sp_table(const dal3_sp_table_args* a, hipStream_t s);
 size_t sp_conv_pack_floats(int taps, int c_in, int c_out);
-hipError_t launch_sp_conv_pack(const dal3_layer* layer, int taps, double eps, float* out, int32_t* status, hipStream_t s);
+hipError_t launch_sp_conv_pack(const FoldLayer& layer, int taps, float* out, int32_t* status, hipStream_t s);
 hipError_t launch_sp_conv(const dal3_sp_conv_args* a, hipStream_t s);
 hipError_t launch_sp_table_transposed(const dal3_sp_table_transposed_args* a, hipStream_t s);
 size_t sp_wgrad_workspace_bytes(int taps, int c_in, int c_out, int64_t out_capacity);

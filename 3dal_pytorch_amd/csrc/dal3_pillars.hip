@@ -201,6 +201,8 @@ struct PackLayer {
     int c_in, c_out;
 };
 
+// Not dal3_fold.h's fold: the bias here is beta - mean * scale without pinned roundings (the compiler may contract it
+// into an fma), so moving this pack onto the shared fold could change its bits. It keeps its own two functions.
 __device__ __forceinline__ float folded_weight(const PackLayer& L, int row, int col, double eps) {
     if (row >= L.c_out || col >= L.c_in) return 0.f;
     const double scale = (double)L.g[row] / sqrt((double)L.var[row] + eps);

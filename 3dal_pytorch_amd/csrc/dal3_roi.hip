@@ -170,41 +170,6 @@ __global__ __launch_bounds__(256) void roi_prepare_kernel(const PrepareGeom g) {
     }
 }
 
-// ---------------------------------------------------------------------------------- the pack
-struct RoiPackLayer {
-    const float *w, *bias, *g, *beta, *mean, *var;
-    double eps;
-};
-
-// The fold, each operation a separately rounded float64 one (tests/roi_ref.py restates it bit for bit)
-__device__ __forceinline__ double roi_scale(const RoiPackLayer& L, int co) {
-    return L.g ? (double)L.g[co] / __dsqrt_rn(__dadd_rn((double)L.var[co], L.eps)) : 1.0;
-}
-
-__global__ __launch_bounds__(256) void roi_pack_kernel(const RoiPackLayer P, const RoiLayer L, float* out) {
-    const int64_t n_bias = (int64_t)L.n_tiles * 32, total = n_bias + (int64_t)L.n_tiles * L.nc8 * 256;
-    float* dst = out + L.bias_off;       // the fragments follow the bias
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        float v = 0.f;
-        if (i < n_bias) {
-            const int co = (int)i;
-            if (co < L.c_out) {
-                const double b = P.bias ? (double)P.bias[co] : 0.0;
-                v = P.g ? (float)__dadd_rn(__dmul_rn(__dadd_rn(b, -(double)P.mean[co]), roi_scale(P, co)), (double)P.beta[co])
-                        : (float)b;
-            }
-        } else {
-            const int64_t j = i - n_bias;
-            const int e = (int)(j & 3), lane = (int)((j >> 2) & 63);
-            const int64_t t = j >> 8;
-            const int c8 = (int)(t % L.nc8), ot = (int)(t / L.nc8);
-            const int co = 32 * ot + (lane & 31), ci = 8 * c8 + 2 * e + (lane >> 5);
-            if (co < L.c_out && ci < L.c_in) v = (float)__dmul_rn((double)P.w[(int64_t)co * L.c_in + ci], roi_scale(P, co));
-        }
-        dst[i] = v;
-    }
-}
-
 // ---------------------------------------------------------------------------------- the MLP
 struct MlpGeom {
     RoiNet net;
@@ -354,7 +319,9 @@ __global__ __launch_bounds__(RH_BLOCK) void roi_mlp_kernel(const MlpGeom g) {
 
 bool width_ok(int w) { return w >= 16 && w <= RH_MAXW && w % 16 == 0; }
 
-// the network of a shape -> false when it is not served
+// the network of a shape -> false when it is not served. A layer's section of the pack, [bias_off, next bias_off), IS
+// dal3_conv2d_pack's blob of a DAL3_CONV2D_1X1 layer of the same (c_in, c_out): conv2d_pack_floats(1X1, c_in, c_out)
+// floats, the n_tiles * 32 folded biases and then the [out tile][8 inputs][lane] float4 fragments at frag_off
 bool roi_net(const dal3_roi_shape& s, RoiNet& net) {
     net = RoiNet{};
     if (s.c_in < 1 || s.c_in > 5 * 65535 || s.num_class != 1 || (s.code_size != 7 && s.code_size != 9)) return false;
@@ -457,16 +424,12 @@ void roi_layer_dims(const dal3_roi_shape* shape, int i, int* c_in, int* c_out) {
     *c_out = net.L[i].c_out;
 }
 
+// every section is the dense stage's 1x1 pack of its layer (roi_net), written by that packer with the layer's own eps
 hipError_t launch_roi_pack(const dal3_roi_shape* shape, const dal3_layer* layers, const double* eps, float* out, hipStream_t s) {
     RoiNet net;
     roi_net(*shape, net);
     for (int i = 0; i < net.n_layers; ++i) {
-        const dal3_layer& l = layers[i];
-        const RoiPackLayer P = {l.weight, l.bias, l.bn_weight, l.bn_bias, l.bn_mean, l.bn_var, eps ? eps[i] : 1e-5};
-        const RoiLayer& L = net.L[i];
-        const int64_t total = (int64_t)L.n_tiles * 32 + (int64_t)L.n_tiles * L.nc8 * 256;
-        hipLaunchKernelGGL(roi_pack_kernel, dim3(blocks_for(total, 256)), dim3(256), 0, s, P, L, out);
-        const hipError_t e = hipGetLastError();
+        const hipError_t e = launch_conv2d_pack(FoldLayer(layers[i], eps ? eps[i] : 1e-5), DAL3_CONV2D_1X1, out + net.L[i].bias_off, s);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

@@ -252,20 +252,6 @@ struct LossGeom {
     float *loss, *d_cls, *d_reg;
 };
 
-// the sums of a workgroup in a fixed tree; s[RL_BLOCK] is free again on return
-__device__ __forceinline__ double block_sum(double v, double* s) {
-    const int t = threadIdx.x;
-    s[t] = v;
-    __syncthreads();
-    for (int off = RL_BLOCK / 2; off > 0; off >>= 1) {
-        if (t < off) s[t] += s[t + off];
-        __syncthreads();
-    }
-    const double r = s[0];
-    __syncthreads();
-    return r;
-}
-
 __global__ __launch_bounds__(RL_BLOCK) void roi_loss_kernel(const LossGeom g) {
     __shared__ double s[RL_BLOCK];
     const int t = threadIdx.x;
@@ -284,10 +270,10 @@ __global__ __launch_bounds__(RL_BLOCK) void roi_loss_kernel(const LossGeom g) {
                 reg_sum += (double)__fmul_rn(fabsf(__fsub_rn(g.reg[i * g.code + c], g.target[i * (g.code + 1) + c])), g.cw[c]);
         }
     }
-    cls_sum = block_sum(cls_sum, s);
-    reg_sum = block_sum(reg_sum, s);
-    n_cls = block_sum(n_cls, s);
-    n_fg = block_sum(n_fg, s);
+    cls_sum = block_sum_f64(cls_sum, s, RL_BLOCK);
+    reg_sum = block_sum_f64(reg_sum, s, RL_BLOCK);
+    n_cls = block_sum_f64(n_cls, s, RL_BLOCK);
+    n_fg = block_sum_f64(n_fg, s, RL_BLOCK);
     const double dc = n_cls > 1.0 ? n_cls : 1.0, df = n_fg > 1.0 ? n_fg : 1.0;
     if (t == 0) {
         const float lc = (float)(cls_sum / dc) * g.cls_w, lr = (float)(reg_sum / df) * g.reg_w;

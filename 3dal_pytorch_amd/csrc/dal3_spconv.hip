@@ -190,39 +190,25 @@ __global__ __launch_bounds__(SP_BLOCK) void sp_table_kernel(const int32_t* out_i
 }
 
 // ---------------------------------------------------------------------------------- the convolution
-struct SpPackLayer {
-    const float *w, *bias, *g, *beta, *mean, *var;
-    int c_in, c_out;
-};
-
 __host__ __device__ constexpr int sp_cp(int c_in) { return c_in <= 8 ? 8 : c_in; }    // zero-padded input channels
 
-// The fold, each operation a separately rounded float64 one (tests/sparse_ref.py restates it bit for bit)
-__device__ __forceinline__ double sp_scale(const SpPackLayer& L, int co, double eps) {
-    return L.g ? (double)L.g[co] / __dsqrt_rn(__dadd_rn((double)L.var[co], eps)) : 1.0;
-}
-
-__global__ __launch_bounds__(SP_BLOCK) void sp_conv_pack_kernel(const SpPackLayer L, int taps, double eps, int mt_total, int ns4,
-                                                                int64_t total, float* out, int32_t* status) {
+// (the fold itself: dal3_fold.h; the layout, the non-finite flag and the 64-float head are this packer's own)
+__global__ __launch_bounds__(SP_BLOCK) void sp_conv_pack_kernel(const FoldLayer L, int taps, int mt_total, int ns4, int64_t total,
+                                                                float* out, int32_t* status) {
     const int half = sp_cp(L.c_in) / 2;
     for (int64_t i = SP_HEAD_FLOATS + (int64_t)blockIdx.x * SP_BLOCK + threadIdx.x; i < total; i += (int64_t)gridDim.x * SP_BLOCK) {
         float v = 0.f;
         const int64_t at = i - SP_HEAD_FLOATS;
         if (at < (int64_t)mt_total * 32) {
             const int co = (int)at;
-            if (co < L.c_out) {
-                const double b = L.bias ? (double)L.bias[co] : 0.0;
-                v = L.g ? (float)__dadd_rn(__dmul_rn(__dadd_rn(b, -(double)L.mean[co]), sp_scale(L, co, eps)), (double)L.beta[co])
-                        : (float)b;
-            }
+            if (co < L.c_out) v = fold_bias(L, co);
         } else {
             const int64_t j = at - (int64_t)mt_total * 32;
             const int e = (int)(j & 3), lane = (int)((j >> 2) & 63);
             const int64_t t = j >> 8;
             const int mt = (int)(t % mt_total), s4 = (int)((t / mt_total) % ns4), tap = (int)(t / ((int64_t)mt_total * ns4));
             const int co = 32 * mt + (lane & 31), ci = (lane >> 5) * half + 4 * s4 + e;
-            if (co < L.c_out && ci < L.c_in)
-                v = (float)__dmul_rn((double)L.w[((int64_t)tap * L.c_in + ci) * L.c_out + co], sp_scale(L, co, eps));
+            if (co < L.c_out && ci < L.c_in) v = fold_weight(L, ((int64_t)tap * L.c_in + ci) * L.c_out + co, co);
         }
         if (bits_nonfinite(v)) {
             atomicOr(reinterpret_cast<int32_t*>(out), 1);
@@ -451,13 +437,11 @@ size_t sp_conv_pack_floats(int taps, int c_in, int c_out) {
     return (size_t)(SP_HEAD_FLOATS + mt * 32 + (int64_t)taps * ns4 * mt * 256);
 }
 
-hipError_t launch_sp_conv_pack(const dal3_layer* layer, int taps, double eps, float* out, int32_t* status, hipStream_t s) {
-    const SpPackLayer L = {layer->weight, layer->bias, layer->bn_weight, layer->bn_bias, layer->bn_mean, layer->bn_var,
-                           layer->c_in, layer->c_out};
+hipError_t launch_sp_conv_pack(const FoldLayer& L, int taps, float* out, int32_t* status, hipStream_t s) {
     const int64_t total = (int64_t)sp_conv_pack_floats(taps, L.c_in, L.c_out);
     hipError_t e = launch_fill_words(out, SP_HEAD_FLOATS, 0, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(sp_conv_pack_kernel, dim3(sp_grid(sp_tiles(total), 4096)), dim3(SP_BLOCK), 0, s, L, taps, eps,
+    hipLaunchKernelGGL(sp_conv_pack_kernel, dim3(sp_grid(sp_tiles(total), 4096)), dim3(SP_BLOCK), 0, s, L, taps,
                        (L.c_out + 31) / 32, sp_cp(L.c_in) / 8, total, out, status);
     return hipGetLastError();
 }

@@ -17,6 +17,7 @@
 // < 1 % of the work) and M is a multiple of 32.
 #include <type_traits>
 
+#include "dal3_block.h"
 #include "dal3_device.h"
 #include "dal3_kernels.h"
 
@@ -3337,18 +3338,6 @@ hipError_t launch_tr_pool_coef(const float* dg, const float* g, const float* zar
 // kernels instead of ~35 stock launches (W.double(), three rocBLAS dgemms of 16 MFLOP at 40 us each, products, sums,
 // casts): K = the layer's input channels (64, 128 or 256: one thread per input channel), C its output channels (one
 // workgroup each). All sums in float64 in a fixed order (loops in index order, LDS trees of a fixed shape).
-__device__ __forceinline__ double tr_block_sum(double v, double* red, int K) {   // K a power of two <= 256; all threads get the sum
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = K >> 1; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
 // forward: [sum z, sum z^2] over the M points of z = W a + b from the moments of a: m1 = sum a (K), Sc = sum of the
 // CENTRED a a^T (K x K, fp32 from the wgrad kernel):  mu_c = w_c . m1 / M + b_c,  var_c = max(w_c^T (Sc / M) w_c, 0),
 // sums = [mu M | (var + mu^2) M]
@@ -3362,8 +3351,8 @@ __global__ __launch_bounds__(256) void tr_pool_moments_kernel(const float* __res
     double t = 0.0;
 #pragma unroll 8
     for (int j = 0; j < K; ++j) t += wrow[j] * (double)Sc[(int64_t)j * K + k];
-    const double var = tr_block_sum(t * wrow[k] / (double)M, red, K);
-    const double mean = tr_block_sum(wrow[k] * (m1[k] / (double)M), red, K);
+    const double var = block_sum_f64(t * wrow[k] / (double)M, red, K);
+    const double mean = block_sum_f64(wrow[k] * (m1[k] / (double)M), red, K);
     if (k == 0) {
         const double mu = mean + (double)b[c], v = var > 0.0 ? var : 0.0;
         sums[c] = mu * (double)M;
@@ -3418,7 +3407,7 @@ __global__ __launch_bounds__(256) void tr_pool_dw_kernel(const double* __restric
 #pragma unroll 8
     for (int j = 0; j < K; ++j) t += wrow[j] * (double)S[(int64_t)j * K + k];
     const double m1k = m1[k];
-    if (centred) t += tr_block_sum(wrow[k] * m1k, red, K) * m1k / (double)M;   // (W m1) m1^T / M
+    if (centred) t += block_sum_f64(wrow[k] * m1k, red, K) * m1k / (double)M;   // (W m1) m1^T / M
     const double A = coef[2 * (int64_t)C + c], Bc = coef[3 * (int64_t)C + c];
     dW[(int64_t)c * K + k] = (float)(A * m1k + Bc * (t + (double)b[c] * m1k) + (double)dWs[(int64_t)c * K + k]);
 }

@@ -300,11 +300,9 @@ class PillarFeatureNet(nn.Module):
         ts = self._tensors()
         stamp = tuple((t.data_ptr(), t._version, t.device) for t in ts)
         if self._packed is None or stamp != self._stamp:
-            for t in ts:
-                _hip.require_gpu(t, "PillarFeatureNet's parameters")
-                if t.dtype != torch.float32 or not t.is_contiguous():
-                    raise RuntimeError("weights must be contiguous fp32")
-            layers = (_hip.Layer * len(self.pfn_layers))(*[_hip.layer_struct(l.linear, l.norm) for l in self.pfn_layers])
+            # (only the check is shared with the MFMA layers' packers: dal3_pillar_pack folds with its own kernel)
+            layers = (_hip.Layer * len(self.pfn_layers))(*[_hip.fold_layer_struct(l.linear, l.norm, "PillarFeatureNet's parameters")
+                                                           for l in self.pfn_layers])
             buf = torch.empty(_hip.PILLAR_PACK_FLOATS, dtype=torch.float32, device=ts[0].device)
             _hip.check(_hip.lib().dal3_pillar_pack(layers, len(self.pfn_layers), self.num_input,
                                                    float(self.pfn_layers[0].norm.eps), _hip.ptr(buf), _hip.stream()))

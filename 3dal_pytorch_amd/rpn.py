@@ -58,18 +58,9 @@ def _norm_ok(bn):
 
 def pack_layer(conv, bn, kind):
     """fold and pack one layer -> a float32 device tensor (dal3_conv2d_pack)"""
-    ts = [conv.weight] + ([conv.bias] if conv.bias is not None else []) + \
-        ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
-    for t in ts:
-        _hip.require_gpu(t, "the layer's parameters")
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise RuntimeError("weights must be contiguous fp32")
-    c_in, c_out = conv.in_channels, conv.out_channels
-    L = _hip.Layer(_hip.ptr(conv.weight), _hip.ptr(conv.bias), None, None, None, None, c_in, c_out)
-    if bn is not None:
-        L.bn_weight, L.bn_bias, L.bn_mean, L.bn_var = (_hip.ptr(t) for t in ts[-4:])
+    L = _hip.fold_layer_struct(conv, bn)
     lib = _hip.lib()
-    buf = torch.empty(lib.dal3_conv2d_pack_floats(kind, c_in, c_out), dtype=torch.float32, device=conv.weight.device)
+    buf = torch.empty(lib.dal3_conv2d_pack_floats(kind, L.c_in, L.c_out), dtype=torch.float32, device=conv.weight.device)
     _hip.check(lib.dal3_conv2d_pack(L, kind, float(bn.eps) if bn is not None else 1e-5, _hip.ptr(buf), _hip.stream()))
     return buf
 

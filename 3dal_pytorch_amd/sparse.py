@@ -182,17 +182,9 @@ def downsample(x, kernel, stride, padding, capacity=None, max_workgroups=0, indi
 def pack_layer(conv, bn, status=None):
     """fold and pack one layer -> a float32 device tensor (dal3_sp_conv_pack). conv: SubMConv3d / SparseConv3d; bn:
     nn.BatchNorm1d or None"""
-    ts = [conv.weight] + ([conv.bias] if conv.bias is not None else []) + \
-        ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
-    for t in ts:
-        _hip.require_gpu(t, "the layer's parameters")
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise RuntimeError("weights must be contiguous fp32")
+    L = _hip.fold_layer_struct(conv, bn)
     if bn is not None and not (isinstance(bn, nn.BatchNorm1d) and bn.affine and bn.track_running_stats):
         raise RuntimeError("the norm layer must be an affine nn.BatchNorm1d with running statistics")
-    L = _hip.Layer(_hip.ptr(conv.weight), _hip.ptr(conv.bias), None, None, None, None, conv.in_channels, conv.out_channels)
-    if bn is not None:
-        L.bn_weight, L.bn_bias, L.bn_mean, L.bn_var = (_hip.ptr(t) for t in ts[-4:])
     lib = _hip.lib()
     taps = int(np.prod(conv.kernel_size))
     floats = lib.dal3_sp_conv_pack_floats(taps, conv.in_channels, conv.out_channels)

@@ -312,11 +312,7 @@ class RoIHead(rpn._PackedLayers):
         n = len(plan)
         layers, eps = (_hip.Layer * n)(), (C.c_double * n)()
         for i, (conv, bn) in enumerate(plan):
-            for t in list(conv.parameters()) + (list(bn.parameters()) + [bn.running_mean, bn.running_var] if bn is not None else []):
-                _hip.require_gpu(t, "the RoI head's parameters")
-                if t.dtype != torch.float32 or not t.is_contiguous():
-                    raise RuntimeError("weights must be contiguous fp32")
-            layers[i] = _hip.layer_struct(conv, bn)
+            layers[i] = _hip.fold_layer_struct(conv, bn, "the RoI head's parameters")
             eps[i] = float(bn.eps) if bn is not None else 1e-5
         floats = lib.dal3_roi_pack_floats(shape)
         if floats == 0:

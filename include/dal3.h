@@ -915,10 +915,17 @@ int dal3_voxel_mean(const float* voxels, const int32_t* num_points, int64_t P, c
 /* ---- the detector's dense stage: the 2-D convolutions of RPN (det3d/models/necks/rpn.py) and of CenterHead.forward /
  * SepHead (det3d/models/bbox_heads/center_head.py:65-110, 167-244), float32, eval mode.
  *
- * A layer is Conv + optional BatchNorm2d + optional ReLU with the BatchNorm folded by dal3_conv2d_pack, in float64 and
- * rounded once to float32, with the layer's own eps (the neck's norm_cfg says 1e-3, the head's nn.BatchNorm2d 1e-5):
- *   scale = g / sqrt(var + eps),  W' = W * scale,  b' = (bias - mean) * scale + beta     (the product and the sum each
- * rounded by itself); without BatchNorm scale = 1 and b' = bias; a NULL bias is 0. Three forms, x and y float32 NCHW
+ * The fold. dal3_conv2d_pack, dal3_sp_conv_pack and dal3_roi_pack fold a layer's optional eval-mode BatchNorm into its
+ * weight and bias by ONE rule (csrc/dal3_fold.h), with the layer's own eps, in float64, every operation rounded by
+ * itself (no fused multiply-add), in this order, and one rounding of W' and b' to float32:
+ *   scale = g / sqrt(var + eps)      the sum, the square root, the quotient
+ *   W'    = W * scale
+ *   b'    = ((bias - mean) * scale) + beta
+ * Without BatchNorm scale = 1 and b' = bias; a NULL bias is 0. A BatchNorm needs all four of weight, bias, mean and var
+ * and an eps > 0; out is 16-byte aligned.
+ *
+ * A layer is Conv + optional BatchNorm2d + optional ReLU with the BatchNorm folded by dal3_conv2d_pack (the fold above;
+ * the neck's norm_cfg says eps 1e-3, the head's nn.BatchNorm2d 1e-5). Three forms, x and y float32 NCHW
  * tensors read and written through the element strides of a dal3_map, a (B, H, W, C) view:
  *   DAL3_CONV2D_3X3      y[b,co,oy,ox] = act(b'[co] + sum W'[co,ci,ky,kx] * x[b,ci,oy*s+ky-1,ox*s+kx-1]), zeros outside the
  *                        image, s = stride 1 or 2, output (floor((H-1)/s)+1, floor((W-1)/s)+1): both ZeroPad2d(1) +
@@ -982,9 +989,8 @@ int dal3_conv2d(const dal3_conv2d_args* args, dal3_stream stream);
  * dal3_sp_downsample emits them: its out_key). The status words are OR-ed. No atomic decides a position or a count; the
  * bytes are the same for every max_workgroups.
  *
- * dal3_sp_conv_pack folds Conv (+ optional bias) + optional eval-mode BatchNorm1d in float64, every operation rounded
- * by itself, one rounding to float32: scale = g / sqrt(var + eps), W' = W * scale, b' = (bias - mean) * scale + beta
- * (without BatchNorm scale = 1, b' = bias; a NULL bias is 0). c_in 1 .. 8, 16, 32, 64 or 128; c_out 16, 32, 64 or 128;
+ * dal3_sp_conv_pack folds Conv (+ optional bias) + optional eval-mode BatchNorm1d by the fold stated at the dense stage
+ * ("The fold", above dal3_conv2d_pack). c_in 1 .. 8, 16, 32, 64 or 128; c_out 16, 32, 64 or 128;
  * 1 <= taps <= 27. out: dal3_sp_conv_pack_floats(taps, c_in, c_out) floats (0 for bad arguments), 16-byte aligned. A
  * folded weight that is not finite marks the pack and sets DAL3_SP_BAD_WEIGHT in *status (optional): dal3_sp_conv on
  * such a pack writes nothing and sets the same bit.
@@ -1617,10 +1623,9 @@ int dal3_dynamic_forward(const dal3_dynamic_args* args, int phases, dal3_stream 
  * layers Conv1d(k = 1, no bias) + BatchNorm1d + ReLU of the widths shared[] / cls[] / reg[] (multiples of 16, <= 256), and
  * the two final biased Conv1d to num_class (1) and code_size (7 or 9) outputs; Dropout is the identity. dal3_roi_pack
  * takes the layers in the order shared, cls (its final layer last), reg (likewise), n_layers = n_shared + n_cls + n_reg
- * + 2, with eps[i] the BatchNorm's own (ignored for a layer without one), and folds in float64, every operation
- * rounded by itself, one rounding to float32, by the formula of dal3_conv2d_pack above: scale = g / sqrt(var + eps),
- * W' = W * scale, b' = (bias - mean) * scale + beta. out: dal3_roi_pack_floats(shape) floats (0 for a shape that is not
- * served), 16-byte aligned.
+ * + 2, with eps[i] the BatchNorm's own (ignored for a layer without one), by the fold stated at the dense stage ("The
+ * fold", above dal3_conv2d_pack); a layer's section of the blob is dal3_conv2d_pack's DAL3_CONV2D_1X1 blob of that layer.
+ * out: dal3_roi_pack_floats(shape) floats (0 for a shape that is not served), 16-byte aligned.
  *
  * dal3_roi_head, the fused form (keep != NULL): from CenterHeadPost's device results (dal3_center_decode + dal3_nms: boxes
  * (K, box_cols), scores, labels, keep (F, keep_stride), keep_count (F), seg_offsets (F + 1), segment f = task * B +

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+import fold_ref
 import pillars_ref as P
 
 synth = P.synth
@@ -126,15 +127,8 @@ def head_weights(input_channels, cfg, code_size, tag="roi"):
 
 
 def fold(w, bias, bn, eps):
-    """-> (W' float32 (c_out, c_in), b' float32 (c_out)): float64 operations in include/dal3.h's order, each rounded by
-    itself, one rounding to float32"""
-    w64 = np.asarray(w, np.float64).reshape(np.shape(w)[0], -1)
-    b64 = np.zeros(w64.shape[0]) if bias is None else np.asarray(bias, np.float64)
-    if bn is None:
-        return w64.astype(np.float32), b64.astype(np.float32)
-    g, beta, mean, var = (np.asarray(v, np.float64) for v in bn)
-    scale = g / np.sqrt(var + eps)
-    return (w64 * scale[:, None]).astype(np.float32), ((b64 - mean) * scale + beta).astype(np.float32)
+    """fold_ref.fold with a Conv1d's weight as (c_out, c_in)"""
+    return fold_ref.fold(np.asarray(w).reshape(np.shape(w)[0], -1), bias, bn, eps, 0)
 
 
 def bn_of(sd, p):

@@ -9,6 +9,7 @@ tests/test_gpu_rpn.py derive their expected bits from it. `fault=` plants one wr
 The measures are pillars_ref.judge's, on (rows, channels) arrays: `rows_of` turns an NCHW map into one."""
 import numpy as np
 
+import fold_ref
 import pillars_ref as P
 
 synth = P.synth
@@ -121,17 +122,8 @@ def bn_of(sd, p):
 
 # ------------------------------------------------------------------------------------- the fold, bit for bit
 def fold(w, bias, bn, eps, deconv=False):
-    """-> (W' float32 shaped like w, b' float32 (c_out)): float64 operations in include/dal3.h's order, each rounded by
-    itself, one rounding to float32"""
-    w64 = np.asarray(w, np.float64)
-    c_out = w64.shape[1] if deconv else w64.shape[0]
-    b64 = np.zeros(c_out) if bias is None else np.asarray(bias, np.float64)
-    if bn is None:
-        return w64.astype(np.float32), b64.astype(np.float32)
-    g, beta, mean, var = (np.asarray(v, np.float64) for v in bn)
-    scale = g / np.sqrt(var + eps)
-    shape = (1, -1, 1, 1) if deconv else (-1,) + (1,) * (w64.ndim - 1)
-    return (w64 * scale.reshape(shape)).astype(np.float32), ((b64 - mean) * scale + beta).astype(np.float32)
+    """fold_ref.fold with a Conv2d's (c_out, c_in, k, k) or a ConvTranspose2d's (c_in, c_out, s, s) weight"""
+    return fold_ref.fold(w, bias, bn, eps, 1 if deconv else 0)
 
 
 # ------------------------------------------------------------------------------------- the three forms, float64

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 from torch.nn import functional as F
 
+import fold_ref
 import pillars_ref as P
 import rpn_ref as R
 
@@ -117,15 +118,8 @@ def backbone_weights(c_in=5, tag="scn"):
 
 
 def fold(w, bias, bn, eps=EPS):
-    """-> (W' float32 shaped like w, b' float32 (c_out)): float64 operations in include/dal3.h's order, each rounded by
-    itself, one rounding to float32"""
-    w64 = np.asarray(w, np.float64)
-    b64 = np.zeros(w64.shape[-1]) if bias is None else np.asarray(bias, np.float64)
-    if bn is None:
-        return w64.astype(np.float32), b64.astype(np.float32)
-    g, beta, mean, var = (np.asarray(v, np.float64) for v in bn)
-    scale = g / np.sqrt(var + eps)
-    return (w64 * scale).astype(np.float32), ((b64 - mean) * scale + beta).astype(np.float32)
+    """fold_ref.fold with spconv's (kD, kH, kW, c_in, c_out) weight"""
+    return fold_ref.fold(w, bias, bn, eps, -1)
 
 
 # ------------------------------------------------------------------------------------- the rulebook (integers)
