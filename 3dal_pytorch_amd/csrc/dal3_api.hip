@@ -67,6 +67,8 @@ static InsSegW ins_seg_walk(Cursor& c) {
     w.scr_pq = c.take(2 * 1024);
     w.scr_flag = reinterpret_cast<const int32_t*>(c.take(64));
     w.dw2c = c.take((size_t)512 * 256);
+    w.dw3c = c.take((size_t)256 * 128);
+    w.dw4c = c.take((size_t)128 * 128);
     w.dec_flag = reinterpret_cast<const int32_t*>(c.take(64));
     return w;
 }
@@ -433,8 +435,10 @@ extern "C" int dal3_pack_weights(int head_kind, const dal3_layer* L, int n_layer
         HIP_TRY(launch_pack_weight(L[4], PACK_ROWMAJOR, 0, 128, 0, 0, mut(w.w5row), s));
         HIP_TRY(launch_pack_weight_lp(L[4], DAL3_F16, 0, 0, 128, 32, 4, reinterpret_cast<uint16_t*>(mut(w.w5h)), s));
         HIP_TRY(launch_pack_enc_screen(L[4], mut(w.scr_pq), reinterpret_cast<int32_t*>(mut(w.scr_flag)), s));
-        // the compacted dconv2's chain-ordered copy and its guard flag
+        // the compacted dconv2 - dconv4's chain-ordered copies and their guard flag
         HIP_TRY(launch_pack_dec_sparse(L[6], w.db2, mut(w.dw2c), reinterpret_cast<int32_t*>(const_cast<int32_t*>(w.dec_flag)), s));
+        HIP_TRY(launch_pack_dec_queue(L[7], 256, w.db3, mut(w.dw3c), reinterpret_cast<int32_t*>(const_cast<int32_t*>(w.dec_flag)), s));
+        HIP_TRY(launch_pack_dec_queue(L[8], 128, w.db4, mut(w.dw4c), reinterpret_cast<int32_t*>(const_cast<int32_t*>(w.dec_flag)), s));
         return 0;
     }
     if (head_kind == DAL3_HEAD_DYNAMIC_BOX_EST) {

@@ -79,7 +79,12 @@ struct InsSegW {
     // the compacted dconv2 of the throughput decoder (dal3_pointmlp.hip, DESIGN.md "Compacted dconv2")
     const float* dw2c;        // dconv2 folded, [k 0..511][row 0..31][out-tile 0..7]: W'[32 mt + row][32 c + tile_chan(r, h)] at
                               // chain index k = 32 c + 2 r + h (chunk, accumulator register, lane half: the dense k order)
-    const int32_t* dec_flag;  // nonzero: a folded dconv2 weight is not finite or a folded dconv2 bias is -0 -> dense path only
+    // the same for dconv3 / dconv4, whose live input rows go through a per-wave queue: [k][row 0..31][out-tile 0..3],
+    // W'[32 mt + row][32 kt + tile_chan(r, h)] at chain index k = 32 kt + 2 r + h (mlp_layer_ring's k order)
+    const float* dw3c;        // k 0..255
+    const float* dw4c;        // k 0..127
+    const int32_t* dec_flag;  // nonzero: a folded dconv2 / dconv3 / dconv4 weight is not finite or one of their folded biases is -0
+                              // -> dense path only
 };
 enum {                        // stream geometry in fragments of 256 floats
     ENC_W2 = 0, ENC_W3 = 16, ENC_W4 = 32, ENC_W5 = 64, ENC_FRAGS = 64 + 512,
@@ -212,6 +217,7 @@ hipError_t launch_ins_seg_encode_screen(const InsSegW& w, BCN pts, int c_in, int
 hipError_t launch_pack_enc_screen(const dal3_layer& L, float* pq, int32_t* flag, hipStream_t s);
 // db2: the layer's packed bias (written earlier on s)
 hipError_t launch_pack_dec_sparse(const dal3_layer& L, const float* db2, float* dw2c, int32_t* flag, hipStream_t s);
+hipError_t launch_pack_dec_queue(const dal3_layer& L, int c_in, const float* bias, float* wcopy, int32_t* flag, hipStream_t s);
 hipError_t launch_ins_seg_decode(const InsSegW& w, BCN pts, int c_in, int B, int N, const float* gbias,
                                  float* logits, uint8_t* mask, hipStream_t s);
 // distinct (B) i32 or NULL: only the first distinct[b] points of item b are distinct (the rest duplicate them)

@@ -204,6 +204,24 @@ hipError_t launch_pack_dec_sparse(const dal3_layer& L, const float* db2, float* 
     return hipGetLastError();
 }
 
+// The same for the queue layers dconv3 (c_in 256) and dconv4 (c_in 128), 128 outputs each: [k][row][out-tile 0..3]
+__global__ void pack_dec_queue_kernel(dal3_layer L, int c_in, const float* __restrict__ bias, float* __restrict__ out,
+                                      int32_t* __restrict__ flag) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= c_in * 128) return;
+    const int mt = i & 3, row = (i >> 2) & 31, k = i >> 7;
+    const int kt = k >> 5, r = (k & 31) >> 1, h = k & 1;
+    const float v = folded_w(L, 32 * mt + row, 32 * kt + tile_chan(r, h), 0, c_in);
+    out[i] = v;
+    bool bad = (__float_as_uint(v) & 0x7F800000u) == 0x7F800000u;
+    if (i < 128) bad |= __float_as_uint(bias[i]) == 0x80000000u;
+    if (bad) atomicOr(flag, 1);
+}
+hipError_t launch_pack_dec_queue(const dal3_layer& L, int c_in, const float* bias, float* wcopy, int32_t* flag, hipStream_t s) {
+    hipLaunchKernelGGL(pack_dec_queue_kernel, dim3(c_in * 128 / 256), dim3(256), 0, s, L, c_in, bias, wcopy, flag);
+    return hipGetLastError();
+}
+
 hipError_t launch_pack_bias(const dal3_layer& L, float* out, hipStream_t s) {
     const int padded = (L.c_out + 31) / 32 * 32;
     hipLaunchKernelGGL(pack_bias_kernel, dim3((padded + 255) / 256), dim3(256), 0, s, L, out, padded);

@@ -17,8 +17,8 @@
 #include "dal3_device.h"
 #include "dal3_kernels.h"
 
-// Diagnostic build only (-DDAL3_STAMP): s_memtime stamps of the decode kernel's phases, written to a
-// buffer of their own (dal3_debug_set_stamps). No stamp executes in the shipped library.
+// Diagnostic build only (-DDAL3_STAMP): s_memtime stamps of the decode kernel's phases (0..4; the compacted body adds 5: dconv3's
+// rows queued, 6: dconv3 done, 7: dconv4's rows queued), written to a buffer of their own (dal3_debug_set_stamps). No stamp executes in the shipped library.
 #ifdef DAL3_STAMP
 __device__ long long* g_stamps = nullptr;
 extern "C" int dal3_debug_set_stamps(void* p) {
@@ -98,6 +98,13 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_encode_kernel(InsS
 // live channel waits in slab row 32 for the next chunk's first live one; the very last one is paired with row 33 (zeros).
 // The weight ring has by then fetched the first DAL3_PF dense fragments of the chunk: they are dropped, the stream
 // offset jumps over the chunk's other fragments and the ring is refilled while the compact steps run.
+// lanes whose post-ReLU bits are not +0: NaN and Inf are live. As asm: this file is built -fno-honor-nans, and hipcc turns
+// the integer compare on the ReLU's result into v_cmp_lt_f32 0, v, which is false for a NaN.
+__device__ __forceinline__ uint64_t live_ballot(float v) {
+    uint64_t bal;
+    asm("v_cmp_ne_u32_e64 %0, 0, %1" : "=s"(bal) : "v"(v));
+    return bal;
+}
 #ifndef DAL3_DEC_SPARSE
 #define DAL3_DEC_SPARSE 1               // 0: every chunk on the dense path (A/B builds)
 #endif
@@ -106,13 +113,14 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_encode_kernel(InsS
 #endif
 #define DEC_SLAB_FLOATS (34 * 32)       // rows 0..31: the chunk in chain order | 32: the pending channel | 33: zeros
 // Diagnostic build only (-DDAL3_DEC_COUNT): [0] tiles, [1] dense chunks, [2] compacted chunks, [3] compact k-steps (the
-// final zero-padded one included), [4] live channels, [5] tiles in the compacted body. No counter executes in the shipped library.
+// final zero-padded one included), [4] live channels, [5] tiles in the compacted body, [6] / [7] dconv3's compact k-steps and
+// live rows, [8] / [9] dconv4's (compacted body only; `out` holds 12 words). No counter executes in the shipped library.
 #ifdef DAL3_DEC_COUNT
-__device__ unsigned long long g_dec_count[8];
+__device__ unsigned long long g_dec_count[12];
 extern "C" int dal3_debug_dec_counts(unsigned long long* out, int reset) {
     hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_dec_count), sizeof(g_dec_count));
     if (e == hipSuccess && reset) {
-        unsigned long long z[8] = {};
+        unsigned long long z[12] = {};
         e = hipMemcpyToSymbol(HIP_SYMBOL(g_dec_count), z, sizeof(z));
     }
     return (int)e;
@@ -123,7 +131,122 @@ struct DecStep {                        // operands of one compact k-step: weigh
     float b;
 };
 
-// One wave's tile(s): SP = with the compacted dconv2 (slab: the wave's DEC_SLAB_FLOATS of LDS)
+// Compacted dconv3 / dconv4 (DESIGN.md "Compacted dconv2 - dconv4"). The layer's whole input (KT accumulator tiles, post-ReLU)
+// is complete when the layer starts, so it goes through ONE per-wave row queue in LDS and ONE compact k-loop with a single
+// start. A row is one input channel's 32 points; row k of the queue is chain index k = 32 kt + 2 r + h (k-tile, accumulator
+// register r, lane half h: the order of mlp_layer_ring's terms), so the 16 KT row writes need no address arithmetic. One
+// wave ballot per register gives the two live bits; they are kept as scalar words (bit k of the layer's mask) and touched
+// with scalar instructions only. The mask then becomes the LIST of live chain indices in chain order, 64 indices per
+// pass: lane L owns index 64 j + L, its place in the list is the number of live indices below it (v_mbcnt on the mask word
+// plus the scalar count of the words before), and only live lanes write. Compact k-step s: half-wave h takes list entry
+// 2 s + h, reads that row as its B operand and 16 bytes per lane of the chain-ordered weight copy [k][row 0..31][out-tile 0..3]
+// as the A operands of the step's four MFMAs. An odd count ends on row 256, the row of zeros, whose weights lie past the
+// copy's end and read as zeros. Every output keeps its chain of the live terms in the dense order.
+// The loop runs two stages ahead of the MFMAs: a step's list entry is read 2 DAL3_DEC_QNB steps early, its row and weights
+// DAL3_DEC_QNB steps early, so neither the LDS nor the L2 round trip is waited for. Entries past the list's end are the row
+// of zeros (DEC_Q_OVER of them are written): every address stays inside the queue, and those operands are never multiplied.
+#ifndef DAL3_DEC_QNB
+#define DAL3_DEC_QNB 4                  // queue k-steps whose operands are in flight (1 KiB of weights + one LDS row each)
+#endif
+#define DEC_Q_ZERO 256                  // the row of zeros, behind the 256 rows of dconv3's input
+#define DEC_Q_OVER 32                   // list entries past the end that the loop may read: 2 (2 DAL3_DEC_QNB) + 2 at the most
+#define DEC_Q_LIST (256 + DEC_Q_OVER)
+#define DEC_Q_FLOATS ((DEC_Q_ZERO + 1) * 32 + DEC_Q_LIST)   // rows | list. The dconv2 slab aliases rows 0..33
+static_assert(DEC_Q_FLOATS >= DEC_SLAB_FLOATS, "the dconv2 slab lives in the queue's first rows");
+static_assert(4 * DAL3_DEC_QNB + 2 <= DEC_Q_OVER, "the loop reads list entries up to 2 (steps - 1 + 2 DAL3_DEC_QNB) + 1");
+struct QStep {
+    f32x4 a;
+    float b;
+};
+template <int KT, int STAMP0>
+__device__ __forceinline__ void dec_queue_layer(const f32x16 (&X)[KT], f32x16 (&Y)[4], const float* __restrict__ bvec,
+                                                const float* __restrict__ wcopy, float* q, int lane, uint32_t& n_steps,
+                                                uint32_t& n_live) {
+    static_assert(KT % 2 == 0, "two k-tiles per 64-bit mask word");
+    const uint32_t h = (uint32_t)lane >> 5, pt = (uint32_t)lane & 31u;
+    uint32_t* kl = reinterpret_cast<uint32_t*>(q + (DEC_Q_ZERO + 1) * 32);
+    const __amdgpu_buffer_rsrc_t wq = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wcopy), 0, KT * 32 * 512, 0x00020000);
+    f32x16 acc[4];
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) acc[mt] = tile_from_channels(bvec + 32 * mt, (int)h);
+    // (LDS operations of a wave execute in order: these rows never overtake the reads of whatever used the queue before)
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    uint32_t m[KT];                                    // live mask, word kt: bit 2 r + h
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt) {
+        m[kt] = 0;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float v = X[kt][r];
+            q[(32 * kt + 2 * r) * 32 + lane] = v;      // rows 32 kt + 2 r (low half) and + 1 (high half)
+            const uint64_t bal = live_ballot(v);
+            // bits 2 r and 2 r + 1 of the word: "half != 0" as s_min_u32 half, 1 (see note_live in ins_seg_decode_tile). The
+            // whole update is one asm block: written in C++, hipcc takes the tile's ballots first, reassociates the ORs to
+            // the end and spills the scalars in between to vector lanes
+            uint32_t lo, hi;
+            asm("s_min_u32 %1, %3, 1\n\ts_min_u32 %2, %4, 1\n\ts_lshl1_add_u32 %1, %2, %1\n\ts_lshl_b32 %1, %1, %5\n\ts_or_b32 %0, %0, %1"
+                : "+s"(m[kt]), "=&s"(lo), "=&s"(hi)
+                : "s"((uint32_t)bal), "s"((uint32_t)(bal >> 32)), "n"(2 * r)
+                : "scc");
+        }
+    }
+    q[DEC_Q_ZERO * 32 + pt] = 0.0f;
+    uint32_t cnt = 0;                                  // live rows (wave-uniform)
+#pragma unroll
+    for (int j = 0; j < KT / 2; ++j) {
+        const uint32_t below = __builtin_amdgcn_mbcnt_hi(m[2 * j + 1], __builtin_amdgcn_mbcnt_lo(m[2 * j], 0u));
+        const uint32_t word = h ? m[2 * j + 1] : m[2 * j];
+        if ((word >> pt) & 1u) kl[cnt + below] = 64u * j + (uint32_t)lane;
+        cnt += __builtin_popcount(m[2 * j]) + __builtin_popcount(m[2 * j + 1]);
+    }
+    if (lane < DEC_Q_OVER) kl[cnt + (uint32_t)lane] = DEC_Q_ZERO;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t steps = (cnt + 1u) >> 1;
+    n_steps += steps, n_live += cnt;
+#ifdef DAL3_STAMP
+    const int wave = threadIdx.x >> 6;
+    STAMP(STAMP0);
+#endif
+    auto mma = [&](const QStep& S) {
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) acc[mt] = mfma32(S.a[mt], S.b, acc[mt]);
+    };
+    auto issue = [&](QStep& S, uint32_t k) {           // row k and its weights
+        S.b = q[k * 32u + pt];
+        S.a = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wq, k * 512u + pt * 16u, 0, 0));
+    };
+    const uint32_t* kp = kl + h;                       // kp[2 t]: this half's chain index of step t
+    QStep S[DAL3_DEC_QNB];
+    uint32_t K[DAL3_DEC_QNB];
+#pragma unroll
+    for (int u = 0; u < DAL3_DEC_QNB; ++u) K[u] = kp[2 * u];
+#pragma unroll
+    for (int u = 0; u < DAL3_DEC_QNB; ++u) {
+        issue(S[u], K[u]);
+        K[u] = kp[2 * (DAL3_DEC_QNB + u)];
+    }
+    uint32_t s = 0;
+    for (; s + DAL3_DEC_QNB <= steps; s += DAL3_DEC_QNB) {
+        kp += 2 * DAL3_DEC_QNB;
+#pragma unroll
+        for (int u = 0; u < DAL3_DEC_QNB; ++u) {
+            mma(S[u]);
+            issue(S[u], K[u]);
+            K[u] = kp[2 * (DAL3_DEC_QNB + u)];
+            DAL3_SCHED_FENCE();
+        }
+    }
+#pragma unroll
+    for (int u = 0; u + 1 < DAL3_DEC_QNB; ++u) {
+        if (s + u < steps) mma(S[u]);
+    }
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) Y[mt] = relu16(acc[mt]);
+}
+
+// One wave's tile(s): SP = with the compacted dconv2 - dconv4 (slab: the wave's DEC_Q_FLOATS of LDS)
 template <int T, bool SP>
 __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN& pts, int c_in, int n_pts, int64_t b, int n0,
                                                     const float* __restrict__ gb, float* __restrict__ logits,
@@ -190,7 +313,7 @@ __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN&
     };
     // post-ReLU bits: negatives and -0 are +0 already, NaN / Inf are live. Two scalar bits per accumulator register.
     auto note_live = [&](float v, int r) {
-        const uint64_t bal = __builtin_amdgcn_ballot_w64(__float_as_uint(v) != 0u);
+        const uint64_t bal = live_ballot(v);
         // "word != 0" as s_min_u32 word, 1 on the scalar unit: written as a compare, hipcc turns the boolean into a lane
         // mask and a v_cndmask, and the mask and everything computed from it moves to the vector ALU
         uint32_t lo, hi;
@@ -339,8 +462,23 @@ __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN&
     }
 
     f32x16 y3[T][4], y4[T][4];
-    mlp_layer_ring<8, 4, T>(ring, w.db3, w.db4, bias, a2, y3, lane);
-    mlp_layer_ring<4, 4, T>(ring, w.db4, w.db4, bias, y3, y4, lane);
+    if constexpr (SP) {                                // one route here too: both layers through the queue, even with nothing dead
+        uint32_t q_steps3 = 0, q_live3 = 0, q_steps4 = 0, q_live4 = 0;
+        dec_queue_layer<8, 5>(a2[0], y3[0], w.db3, w.dw3c, slab, lane, q_steps3, q_live3);
+        STAMP(6);
+        dec_queue_layer<4, 7>(y3[0], y4[0], w.db4, w.dw4c, slab, lane, q_steps4, q_live4);
+#ifdef DAL3_DEC_COUNT
+        if (lane == 0) {
+            atomicAdd(&g_dec_count[6], (unsigned long long)q_steps3);
+            atomicAdd(&g_dec_count[7], (unsigned long long)q_live3);
+            atomicAdd(&g_dec_count[8], (unsigned long long)q_steps4);
+            atomicAdd(&g_dec_count[9], (unsigned long long)q_live4);
+        }
+#endif
+    } else {
+        mlp_layer_ring<8, 4, T>(ring, w.db3, w.db4, bias, a2, y3, lane);
+        mlp_layer_ring<4, 4, T>(ring, w.db4, w.db4, bias, y3, y4, lane);
+    }
 
     STAMP(3);
     // dconv5 (128 -> 2, no BN/ReLU) on the VALU: each lane holds 64 of its point's 128 channels
@@ -387,11 +525,12 @@ __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN&
 // loop. (The choice is about speed only: both bodies give the same bits. The compacted body sends every chunk, a fully
 // live one included, through the slab: a crop with few dead channels would lose more to the ballots, the slab and the
 // mask walk than compaction returns.)
-// 160 = 0.3125 of the channels is the smallest dead share with a measured gain: with exactly that share dead in every
-// tile (the other channels live) the compacted body runs the 4096 x 1024 launch in 14.32 / 13.28 / 12.75 / 12.16 / 11.66 ms
-// at 0.125 / 0.25 / 0.3125 / 0.375 / 0.4375 against 12.98 - 13.06 ms dense — break-even near 0.28 (LEDGER_r09.md, section 3).
+// 128 = 0.25 of the channels is the smallest dead share with a measured gain: with exactly that share of dconv1 dead in every
+// tile (the other channels live) the compacted body runs the 4096 x 1024 launch in 13.64 / 13.10 / 12.57 / 12.11 / 10.99 ms
+// at 0.125 / 0.1875 / 0.25 / 0.3125 / 0.4375 against 12.85 - 13.04 ms dense — break-even near 0.2; it was 0.28 before dconv3
+// and dconv4 went through the row queue (LEDGER_r11.md, section 3).
 #ifndef DAL3_DEC_MIN_DEAD
-#define DAL3_DEC_MIN_DEAD 160
+#define DAL3_DEC_MIN_DEAD 128
 #endif
 template <int T>
 __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_decode_kernel(InsSegW w, BCN pts, int c_in, int n_pts,
@@ -418,7 +557,7 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_decode_kernel(InsS
     if (n0 >= n_pts) return;
     const float* gb = gbias + b * 512;                 // W1g . g + b1' of this crop
     constexpr bool SP = DAL3_DEC_SPARSE != 0 && T == 1;    // one tile per wave only: the live mask is the tile's
-    __shared__ float s_slab[SP ? DAL3_WG_WAVES * DEC_SLAB_FLOATS : 1];
+    extern __shared__ __attribute__((aligned(16))) float s_slab[];   // SP: DAL3_WG_WAVES queues of DEC_Q_FLOATS (dynamic: above 64 KiB)
     if constexpr (SP) {
         const f32x4 g0 = reinterpret_cast<const f32x4*>(gb)[2 * lane], g1 = reinterpret_cast<const f32x4*>(gb)[2 * lane + 1];
         uint32_t neg = 0;                              // sign bits among the crop's 512 entries (a NaN term counts or not: dense either way is right)
@@ -427,10 +566,14 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_decode_kernel(InsS
             neg += __builtin_popcountll(__builtin_amdgcn_ballot_w64(__float_as_int(g0[e]) < 0)) +
                    __builtin_popcountll(__builtin_amdgcn_ballot_w64(__float_as_int(g1[e]) < 0));
         if (neg >= DAL3_DEC_MIN_DEAD && *w.dec_flag == 0) {
-            ins_seg_decode_tile<T, true>(w, pts, c_in, n_pts, b, n0, gb, logits, mask, s_slab + wave * DEC_SLAB_FLOATS, lane, wave);
+            ins_seg_decode_tile<T, true>(w, pts, c_in, n_pts, b, n0, gb, logits, mask, s_slab + wave * DEC_Q_FLOATS, lane, wave);
             return;
         }
     }
+    // The dense body starts on a 256-byte boundary of its own (the padding is s_nop, executed once per wave): its loops keep
+    // their place relative to the instruction fetch windows whatever the length of the code in front of them. Without it
+    // the same dense instructions ran 0.9 % slower once the prologue had become one scalar load shorter (LEDGER_r11.md, section 4).
+    asm volatile(".p2align 8");
     ins_seg_decode_tile<T, false>(w, pts, c_in, n_pts, b, n0, gb, logits, mask, s_slab, lane, wave);
 }
 
@@ -686,7 +829,14 @@ hipError_t launch_ins_seg_decode(const InsSegW& w, BCN pts, int c_in, int B, int
     if (lat_use((int64_t)B * ((N + 31) / 32), pts.flags, DAL3_LAT_MAX_TILES_DEC)) return launch_ins_seg_decode_lat(w, pts, c_in, B, N, gbias, logits, mask, s);
     constexpr int T = DAL3_DEC_T;
     const int tpi = tiles_per_item(N, T);
-    hipLaunchKernelGGL(ins_seg_decode_kernel<T>, dim3((unsigned)((int64_t)B * tpi)), dim3(64 * DAL3_WG_WAVES), 0, s, w, pts, c_in, N, tpi,
+    // the compacted body's row queues: one per wave, above the 64 KiB a kernel may take without asking
+    constexpr size_t lds = DAL3_DEC_SPARSE != 0 && T == 1 ? (size_t)DAL3_WG_WAVES * DEC_Q_FLOATS * sizeof(float) : 0;
+    if (lds) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ins_seg_decode_kernel<T>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(ins_seg_decode_kernel<T>, dim3((unsigned)((int64_t)B * tpi)), dim3(64 * DAL3_WG_WAVES), lds, s, w, pts, c_in, N, tpi,
                        gbias, logits, mask);
     return hipGetLastError();
 }

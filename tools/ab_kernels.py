@@ -93,7 +93,7 @@ for name, lib in libs:
     assert d["enc"]() == 0, lib.dal3_last_error()
     assert lib.dal3_ins_seg_global_bias(hip.ptr(w_seg), DT, hip.ptr(g), B, hip.ptr(gb), st) == 0
     if hasattr(lib, "dal3_debug_dec_counts"):         # a -DDAL3_DEC_COUNT build: what the compacted dconv2 saw in ONE launch
-        cnt = (C.c_ulonglong * 8)()
+        cnt = (C.c_ulonglong * 12)()
         lib.dal3_debug_dec_counts(cnt, 1)
     assert d["dec"]() == 0 and d["head"]() == 0, lib.dal3_last_error()
     if hasattr(lib, "dal3_debug_dec_counts"):
@@ -102,6 +102,10 @@ for name, lib in libs:
         tiles, dense, comp, steps, live, sp_tiles = (int(v) for v in cnt[:6])
         print(f"{name}: decode tiles {tiles} ({sp_tiles} in the compacted body), dense chunks {dense}, compacted chunks {comp}, compact k-steps {steps} "
               f"({(steps + 16 * dense) / (256.0 * tiles):.4f} of the dense k-steps), live channels {live / (512.0 * tiles):.4f}")
+        s3, l3, s4, l4 = (int(v) for v in cnt[6:10])      # the queue layers, tiles of the compacted body only
+        if sp_tiles:
+            print(f"{name}: dconv3 compact k-steps {s3} ({s3 / (128.0 * sp_tiles):.4f} of dense), live rows {l3 / (256.0 * sp_tiles):.4f}; "
+                  f"dconv4 compact k-steps {s4} ({s4 / (64.0 * sp_tiles):.4f} of dense), live rows {l4 / (128.0 * sp_tiles):.4f}")
     state.append(d)
 torch.cuda.synchronize()
 ref = state[0]
@@ -126,8 +130,9 @@ for r in range(args.rounds):
     for k in ("enc", "dec", "head"):
         for (name, _), d in zip(libs, state):
             res[(name, k)].append(timed(d[k]))
-print(f"B={B} N={N}: ms per launch, median (min) over {args.rounds} interleaved rounds")
+print(f"B={B} N={N}: ms per launch, median (min, max - min) over {args.rounds} interleaved rounds")
 for name, _ in libs:
-    row = "  ".join(f"{k} {statistics.median(res[(name, k)]):7.3f} ({min(res[(name, k)]):7.3f})" for k in ("enc", "dec", "head"))
+    row = "  ".join(f"{k} {statistics.median(res[(name, k)]):7.3f} ({min(res[(name, k)]):7.3f}, {max(res[(name, k)]) - min(res[(name, k)]):5.3f})"
+                    for k in ("enc", "dec", "head"))
     tot = sum(statistics.median(res[(name, k)]) for k in ("enc", "dec", "head"))
     print(f"{name:40s} {row}   sum {tot:7.3f}")
