@@ -90,14 +90,23 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_encode_kernel(InsS
 // 32-channel chunk is +0 in all 32 points of a wave's tile (the per-crop term gb drives whole channels negative). A term
 // fmaf(w, +0, acc) with finite w leaves acc as it is (up to the sign of a zero accumulator, which the ReLU after dconv2
 // removes), so the dead channels are dropped from the k loop and every output keeps its chain of the live terms in the
-// dense order — the same bits. Per chunk: 16 wave ballots give the live mask in chain order (bit 2r + h = accumulator
-// register r, lane half h); every chunk of the compacted body, a fully live one included (16 k-steps in the dense order),
-// puts its activations through the wave's LDS slab (row 2r + h, 32 points) and runs popcount / 2 compact k-steps:
-// half-wave h reads the slab row of live channel L[2s + h] as the B operand and 32 bytes
-// per lane of the chain-ordered weight copy dw2c[k][row][out-tile] as the A operands of the step's eight MFMAs. An odd
-// live channel waits in slab row 32 for the next chunk's first live one; the very last one is paired with row 33 (zeros).
-// The weight ring has by then fetched the first DAL3_PF dense fragments of the chunk: they are dropped, the stream
-// offset jumps over the chunk's other fragments and the ring is refilled while the compact steps run.
+// dense order — the same bits. dconv1 produces that input in chunks of 32 channels; the compact k-loop runs once per
+// GROUP of DAL3_DEC_GROUP chunks (one start — list, first LDS and L2 round trips — per group instead of one per chunk).
+// Per chunk, in the shadow of the next chunk's dconv1 MFMAs: 16 wave ballots give the live mask in chain order (bit
+// 2r + h = accumulator register r, lane half h), kept as one scalar word, and the 16 registers go to rows 32 u + 2r + h
+// of the wave's row queue in LDS (u: the chunk's place in its group; immediate offsets, no address arithmetic). Per
+// group: the mask words become the LIST of live chain indices in chain order with v_mbcnt, 64 indices per pass; an entry
+// is two words, the byte offset k * 1024 of the channel's weights and the float offset of its row. The leftover of the
+// groups before, if any, is entry 0. Compact k-step s: half-wave h takes entry 2 s + h, reads that row as the B operand
+// and 32 bytes per lane of the chain-ordered weight copy dw2c[k][row][out-tile] as the A operands of the step's eight
+// MFMAs; a step's entry is read 2 DAL3_DEC_NB steps ahead, its row and weights DAL3_DEC_NB steps ahead (the two-stage
+// loop of dec_queue_layer). An odd total leaves its last entry over: the row is copied to row DEC_G_PEND — the next
+// groups overwrite the rows of this one, however many of them are entirely dead — and the entry goes first in the next
+// list; the very last one is paired with the row of zeros. A fully live group is 16 DAL3_DEC_GROUP k-steps in the dense
+// order; there is one route only.
+// The weight ring of this body never holds a dense dconv2 fragment: before every dconv1 block the stream offset steps
+// over the 32 fragments of the dconv2 chunk that lie between two dconv1 chunks in dec_stream, so the block's eight
+// fetches are the next dconv1 chunk.
 // lanes whose post-ReLU bits are not +0: NaN and Inf are live. As asm: this file is built -fno-honor-nans, and hipcc turns
 // the integer compare on the ReLU's result into v_cmp_lt_f32 0, v, which is false for a NaN.
 __device__ __forceinline__ uint64_t live_ballot(float v) {
@@ -111,7 +120,12 @@ __device__ __forceinline__ uint64_t live_ballot(float v) {
 #ifndef DAL3_DEC_NB
 #define DAL3_DEC_NB 3                   // compact k-steps whose operands are in flight (2 KiB of weights + one LDS row each)
 #endif
-#define DEC_SLAB_FLOATS (34 * 32)       // rows 0..31: the chunk in chain order | 32: the pending channel | 33: zeros
+#ifndef DAL3_DEC_GROUP
+#define DAL3_DEC_GROUP 4                // dconv1 chunks per compact loop of dconv2: 1, 2, 4 or 8
+#endif
+static_assert(DAL3_DEC_GROUP == 1 || DAL3_DEC_GROUP == 2 || DAL3_DEC_GROUP == 4 || DAL3_DEC_GROUP == 8,
+              "a group's rows fit the queue's 256, and the groups tile the 16 chunks");
+static_assert(DAL3_PF == 8, "the compacted body's ring holds exactly one dconv1 chunk between two blocks");
 // Diagnostic build only (-DDAL3_DEC_COUNT): [0] tiles, [1] dense chunks, [2] compacted chunks, [3] compact k-steps (the
 // final zero-padded one included), [4] live channels, [5] tiles in the compacted body, [6] / [7] dconv3's compact k-steps and
 // live rows, [8] / [9] dconv4's (compacted body only; `out` holds 12 words). No counter executes in the shipped library.
@@ -151,9 +165,15 @@ struct DecStep {                        // operands of one compact k-step: weigh
 #define DEC_Q_ZERO 256                  // the row of zeros, behind the 256 rows of dconv3's input
 #define DEC_Q_OVER 32                   // list entries past the end that the loop may read: 2 (2 DAL3_DEC_QNB) + 2 at the most
 #define DEC_Q_LIST (256 + DEC_Q_OVER)
-#define DEC_Q_FLOATS ((DEC_Q_ZERO + 1) * 32 + DEC_Q_LIST)   // rows | list. The dconv2 slab aliases rows 0..33
-static_assert(DEC_Q_FLOATS >= DEC_SLAB_FLOATS, "the dconv2 slab lives in the queue's first rows");
+// dconv2's groups use rows 0 .. 32 DAL3_DEC_GROUP - 1 and the row of zeros, and behind dconv3's / dconv4's list a row and a
+// list of their own: row DEC_G_PEND holds the leftover, the list has two words per entry (the leftover, a group's rows,
+// DEC_Q_OVER entries behind the end)
+#define DEC_G_PEND ((DEC_Q_ZERO + 1) + DEC_Q_LIST / 32)
+#define DEC_G_LIST ((DEC_G_PEND + 1) * 32)                  // float offset of dconv2's list
+#define DEC_Q_FLOATS (DEC_G_LIST + 2 * (1 + 256 + DEC_Q_OVER))   // rows | zeros | list | leftover row | dconv2's list
+static_assert(DEC_Q_LIST % 32 == 0, "the leftover row starts where dconv3's list ends");
 static_assert(4 * DAL3_DEC_QNB + 2 <= DEC_Q_OVER, "the loop reads list entries up to 2 (steps - 1 + 2 DAL3_DEC_QNB) + 1");
+static_assert(4 * DAL3_DEC_NB + 2 <= DEC_Q_OVER, "dconv2's loop reads list entries up to 2 (steps - 1 + 2 DAL3_DEC_NB) + 1");
 struct QStep {
     f32x4 a;
     float b;
@@ -264,10 +284,16 @@ __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN&
 
     const int pt = lane & 31;
     __amdgpu_buffer_rsrc_t wc = ring.rsrc;
-    uint32_t live = 0, pend = 0, pend_k = 0;           // this chunk's live mask; a channel waiting for a partner, its k
+    constexpr int G = DAL3_DEC_GROUP;
+    constexpr int TRIP = SP && G > 2 ? G : 2;          // chunks per trip of the chunk loop (the dense body's stays at two)
+    uint32_t m[TRIP] = {};                             // SP: live mask of the trip's chunks, bit 2r + h
+    uint32_t pend = 0;                                 // SP: an entry waits for a partner
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    u32x2 pend_e = {0u, DEC_Q_ZERO * 32u};             // that entry: weight byte offset, float offset of row DEC_G_PEND
+    u32x2* kl = reinterpret_cast<u32x2*>(slab + DEC_G_LIST);
     if constexpr (SP) {
         wc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(w.dw2c), 0, 512 * 1024, 0x00020000);
-        slab[33 * 32 + pt] = 0.0f;
+        slab[DEC_Q_ZERO * 32 + pt] = 0.0f;
     }
 #ifdef DAL3_DEC_COUNT
     uint32_t n_dense = 0, n_comp = 0, n_steps = 0, n_live = 0;
@@ -311,61 +337,76 @@ __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN&
             DAL3_SCHED_FENCE();
         }
     };
-    // post-ReLU bits: negatives and -0 are +0 already, NaN / Inf are live. Two scalar bits per accumulator register.
-    auto note_live = [&](float v, int r) {
-        const uint64_t bal = live_ballot(v);
-        // "word != 0" as s_min_u32 word, 1 on the scalar unit: written as a compare, hipcc turns the boolean into a lane
-        // mask and a v_cndmask, and the mask and everything computed from it moves to the vector ALU
-        uint32_t lo, hi;
-        asm("s_min_u32 %0, %2, 1\n\ts_min_u32 %1, %3, 1" : "=&s"(lo), "=s"(hi) : "s"((uint32_t)bal), "s"((uint32_t)(bal >> 32)) : "scc");
-        live |= (lo | (hi << 1)) << (2 * r);
-    };
     auto compact_mma = [&](const DecStep& S) {
 #pragma unroll
         for (int mt = 0; mt < 8; ++mt) a2[0][mt] = mfma32(mt < 4 ? S.a0[mt & 3] : S.a1[mt & 3], S.b, a2[0][mt]);
     };
-    // half-wave h: weights of chain index k_h (32 bytes per lane), activation row r_h of the slab
-    auto compact_load = [&](DecStep& S, uint32_t k0, uint32_t r0, uint32_t k1, uint32_t r1) {
-        const uint32_t k = h ? k1 : k0, r = h ? r1 : r0;
-        const uint32_t voff = k * 1024u + (uint32_t)pt * 32u;
-        S.b = slab[r * 32u + (uint32_t)pt];
+    // this lane's operands of list entry e: its row (B), 32 bytes of the channel's weights (A of the eight out-tiles)
+    auto compact_issue = [&](DecStep& S, u32x2 e) {
+        const uint32_t voff = e[0] + (uint32_t)pt * 32u;
+        S.b = slab[e[1] + (uint32_t)pt];
         S.a0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wc, voff, 0, 0));
         S.a1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wc, voff + 16u, 0, 0));
     };
-    auto dconv2_compact = [&](const f32x16 (&t)[T], int c) {
-        // the stream: drop the DAL3_PF dense fragments of this chunk the ring holds, skip the others, refill
-        ring.soff += (32 - DAL3_PF) * 1024;
-#pragma unroll
-        for (int i = 0; i < DAL3_PF; ++i) ring.slot[i] = ring.fetch();
-        // (LDS operations of a wave execute in order: the next chunk's rows never overtake this chunk's reads, one slab is enough)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-#pragma unroll
-        for (int r = 0; r < 16; ++r) slab[r * 64 + lane] = t[0][r];       // row 2r + h
+    // The group of chunks c0 .. c0 + NG - 1, whose rows are in the queue and whose masks are mg[0 .. NG - 1]
+    auto dconv2_group = [&](int c0, const uint32_t* mg) {
+        constexpr int NG = G;
+        // (LDS operations of a wave execute in order: the next group's rows never overtake this group's reads)
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        const uint32_t n = __builtin_popcount(live), total = n + pend, steps = total >> 1;
-        // (scalar bit arithmetic only: a select or a borrow on these wave-uniform words sends them to the vector ALU)
-        uint32_t mm = live;
-        auto pop = [&](uint32_t keep) {                // next live channel in chain order (31 once the mask is empty);
-            const uint32_t p = (uint32_t)__builtin_ctz(mm | 0x80000000u);   // keep = ~0: look, do not take
-            mm &= (mm - 1u) | keep;
-            return p;
-        };
-        auto next = [&](DecStep& S, uint32_t wait) {   // operands of the next step in order (harmless past the last);
-            const uint32_t p0 = pop(wait);             // wait = ~0: the waiting channel is this step's low half
-            const uint32_t k0 = (pend_k & wait) | ((32u * c + p0) & ~wait), r0 = (32u & wait) | (p0 & ~wait);
-            const uint32_t r1 = pop(0u);
-            compact_load(S, k0, r0, 32u * c + r1, r1);
-        };
-        DecStep S[DAL3_DEC_NB];                        // operands in flight, rotating by name
+        kl[0] = pend_e;                                // the leftover goes first (without one, entry 0 is written again below)
+        uint32_t total = pend;
 #pragma unroll
-        for (int u = 0; u < DAL3_DEC_NB; ++u) next(S[u], u == 0 ? 0u - pend : 0u);
+        for (int j = 0; j < (NG + 1) / 2; ++j) {       // 64 chain indices per pass: lane L owns 32 (c0 + 2j) + L
+            const uint32_t w0 = mg[2 * j], w1 = 2 * j + 1 < NG ? mg[2 * j + 1] : 0u;
+            const uint32_t below = __builtin_amdgcn_mbcnt_hi(w1, __builtin_amdgcn_mbcnt_lo(w0, 0u));
+            const uint32_t word = h ? w1 : w0;
+            if ((word >> pt) & 1u) {
+                u32x2 e;
+                e[0] = (32u * (uint32_t)(c0 + 2 * j) + (uint32_t)lane) * 1024u;
+                e[1] = (64u * j + (uint32_t)lane) * 32u;
+                kl[total + below] = e;
+            }
+            total += __builtin_popcount(w0) + __builtin_popcount(w1);
+        }
+        if (lane < DEC_Q_OVER) {                       // behind the end: the row of zeros (read ahead, never multiplied)
+            u32x2 e;
+            e[0] = 0u, e[1] = DEC_Q_ZERO * 32u;
+            kl[total + (uint32_t)lane] = e;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const uint32_t steps = total >> 1;
+        const u32x2* kp = kl + h;                      // kp[2 t]: this half's entry of step t
+        DecStep S[DAL3_DEC_NB];                        // operands in flight, rotating by name
+        u32x2 K[DAL3_DEC_NB];
+#pragma unroll
+        for (int u = 0; u < DAL3_DEC_NB; ++u) K[u] = kp[2 * u];
+#pragma unroll
+        for (int u = 0; u < DAL3_DEC_NB; ++u) {
+            compact_issue(S[u], K[u]);
+            K[u] = kp[2 * (DAL3_DEC_NB + u)];
+        }
+        if (total & 1u) {
+            // the last entry is left over: its row moves to row DEC_G_PEND behind the reads above (the only ones of that
+            // row: a leftover is entry 0), before the next groups write over this group's rows
+            pend_e = kl[total - 1u];
+            const float v = slab[pend_e[1] + (uint32_t)pt];
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            slab[DEC_G_PEND * 32 + pt] = v;
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            pend_e[1] = DEC_G_PEND * 32u;
+        }
+        pend = total & 1u;
         uint32_t s = 0;
         for (; s + DAL3_DEC_NB <= steps; s += DAL3_DEC_NB) {
+            kp += 2 * DAL3_DEC_NB;
 #pragma unroll
             for (int u = 0; u < DAL3_DEC_NB; ++u) {
                 compact_mma(S[u]);
-                next(S[u], 0u);
+                compact_issue(S[u], K[u]);
+                K[u] = kp[2 * (DAL3_DEC_NB + u)];
                 DAL3_SCHED_FENCE();
             }
         }
@@ -373,26 +414,18 @@ __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN&
         for (int u = 0; u + 1 < DAL3_DEC_NB; ++u) {
             if (s + u < steps) compact_mma(S[u]);
         }
-        if ((total & 1u) && n) {                       // the last live channel waits (an older one still waiting stays)
-            const uint32_t hi = 31u - (uint32_t)__builtin_clz(live);
-            const float v = slab[hi * 32u + (uint32_t)pt];
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            slab[32 * 32 + pt] = v;
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            pend_k = 32u * c + hi;
-        }
-        pend = total & 1u;
 #ifdef DAL3_DEC_COUNT
-        ++n_comp, n_steps += steps, n_live += n;
+        n_comp += NG, n_steps += steps;
+#pragma unroll
+        for (int j = 0; j < NG; ++j) n_live += __builtin_popcount(mg[j]);
 #endif
     };
-    // ONE route per body: the compacted body sends every chunk through the slab (a fully live chunk is 16 k-steps in the
-    // dense order), the dense body every chunk through the registers. A second route inside the compacted body made the
+    // ONE route per body: the compacted body sends every chunk through the queue (a fully live group runs its k-steps in
+    // the dense order), the dense body every chunk through the registers. A second route inside the compacted body made the
     // compiler move the dconv2 accumulators between two register sets at every chunk (profiles/LEDGER_r09.md).
-    auto dconv2_chunk = [&](const f32x16 (&t)[T], int c) {
+    auto dconv2_chunk = [&](const f32x16 (&t)[T], int c, int u) {
         if constexpr (SP) {
-            dconv2_compact(t, c);
+            if ((u + 1) % G == 0) dconv2_group(c + 1 - G, m + (u + 1 - G));
         } else {
 #ifdef DAL3_DEC_COUNT
             ++n_dense, n_live += 32;
@@ -400,44 +433,68 @@ __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN&
             dconv2_part(t);
         }
     };
-    auto relu_note = [&](f32x16& t, int i) {           // ReLU and liveness of two registers per fragment group
+    // ReLU of two registers per fragment group; SP: their rows of the queue and their live bits (post-ReLU bits:
+    // negatives and -0 are +0 already, NaN / Inf are live)
+    auto relu_note = [&](f32x16& t, int i, int u) {
         t[2 * i] = relu1(t[2 * i]);
         t[2 * i + 1] = relu1(t[2 * i + 1]);
         if constexpr (SP) {
-            if (i == 0) live = 0;
-            note_live(t[2 * i], 2 * i);
-            note_live(t[2 * i + 1], 2 * i + 1);
+            if (i == 0) m[u] = 0;
+#pragma unroll
+            for (int r = 2 * i; r < 2 * i + 2; ++r) {
+                const float v = t[r];
+                slab[(32 * (u % G) + 2 * r) * 32 + lane] = v;          // rows 32 u + 2 r (low half) and + 1 (high half)
+                const uint64_t bal = live_ballot(v);
+                // bits 2 r and 2 r + 1 of the chunk's word, in one asm block on the scalar unit (see dec_queue_layer)
+                uint32_t lo, hi;
+                asm("s_min_u32 %1, %3, 1\n\ts_min_u32 %2, %4, 1\n\ts_lshl1_add_u32 %1, %2, %1\n\ts_lshl_b32 %1, %1, %5\n\ts_or_b32 %0, %0, %1"
+                    : "+s"(m[u]), "=&s"(lo), "=&s"(hi)
+                    : "s"((uint32_t)bal), "s"((uint32_t)(bal >> 32)), "n"(2 * r)
+                    : "scc");
+            }
         }
+    };
+    // SP: the ring steps over the dconv2 chunk that lies in front of the dconv1 chunk the next block fetches
+    auto skip_dconv2 = [&]() {
+        if constexpr (SP) ring.soff += 32 * 1024;
     };
 #pragma unroll
     for (int j = 0; j < T; ++j) tA[j] = bias;
     mma_block_ring<2, T>(ring, x2, tA, [&](int i) {
         if (i == 0) bias = tile_from_channels(gb + 32, h);
     });
-    for (int c = 0; c < 16; c += 2) {
+    for (int c0 = 0; c0 < 16; c0 += TRIP) {
 #pragma unroll
-        for (int j = 0; j < T; ++j) tB[j] = bias;
-        mma_block_ring<2, T>(ring, x2, tB, [&](int i) {                // chunk c+1; ReLU(chunk c) in its shadow
-            if (i == 0) bias = tile_from_channels(gb + 32 * ((c + 2) & 15), h);
+        for (int u = 0; u < TRIP; u += 2) {            // u: the chunk's place in the trip (a constant once unrolled)
+            const int c = c0 + u;
 #pragma unroll
-            for (int j = 0; j < T; ++j) relu_note(tA[j], i);
-        });
-        dconv2_chunk(tA, c);
+            for (int j = 0; j < T; ++j) tB[j] = bias;
+            skip_dconv2();
+            mma_block_ring<2, T>(ring, x2, tB, [&](int i) {            // chunk c+1; ReLU(chunk c) in its shadow
+                if (i == 0) bias = tile_from_channels(gb + 32 * ((c + 2) & 15), h);
 #pragma unroll
-        for (int j = 0; j < T; ++j) tA[j] = bias;
-        // chunk c+2 (on the last round its 8 fragments are the stream's zero filler; the result is unused)
-        mma_block_ring<2, T>(ring, x2, tA, [&](int i) {
-            if (i == 0)
-                bias = c + 2 < 16 ? tile_from_channels(gb + 32 * ((c + 3) & 15), h) : tile_from_channels(w.db3, h);
+                for (int j = 0; j < T; ++j) relu_note(tA[j], i, u);
+            });
+            dconv2_chunk(tA, c, u);
 #pragma unroll
-            for (int j = 0; j < T; ++j) relu_note(tB[j], i);
-        });
-        dconv2_chunk(tB, c + 1);
+            for (int j = 0; j < T; ++j) tA[j] = bias;
+            skip_dconv2();
+            // chunk c+2 (on the last round its 8 fragments are the stream's zero filler; the result is unused)
+            mma_block_ring<2, T>(ring, x2, tA, [&](int i) {
+                if (i == 0)
+                    bias = c + 2 < 16 ? tile_from_channels(gb + 32 * ((c + 3) & 15), h) : tile_from_channels(w.db3, h);
+#pragma unroll
+                for (int j = 0; j < T; ++j) relu_note(tB[j], i, u + 1);
+            });
+            dconv2_chunk(tB, c + 1, u + 1);
+        }
     }
     if constexpr (SP) {
         if (pend) {                                    // the very last live channel: its partner is the row of zeros
             DecStep S;
-            compact_load(S, pend_k, 32, pend_k, 33);
+            u32x2 e = pend_e;
+            if (h) e[1] = DEC_Q_ZERO * 32u;
+            compact_issue(S, e);
             compact_mma(S);
 #ifdef DAL3_DEC_COUNT
             ++n_steps;
@@ -523,14 +580,14 @@ __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN&
 // dconv1 channels — the channels that are dead for (nearly) every point of the crop — and never when the blob's guard
 // flag is set. Every other tile runs the dense body, which is the kernel as it was: no ballot, no branch in its chunk
 // loop. (The choice is about speed only: both bodies give the same bits. The compacted body sends every chunk, a fully
-// live one included, through the slab: a crop with few dead channels would lose more to the ballots, the slab and the
-// mask walk than compaction returns.)
-// 128 = 0.25 of the channels is the smallest dead share with a measured gain: with exactly that share of dconv1 dead in every
-// tile (the other channels live) the compacted body runs the 4096 x 1024 launch in 13.64 / 13.10 / 12.57 / 12.11 / 10.99 ms
-// at 0.125 / 0.1875 / 0.25 / 0.3125 / 0.4375 against 12.85 - 13.04 ms dense — break-even near 0.2; it was 0.28 before dconv3
-// and dconv4 went through the row queue (LEDGER_r11.md, section 3).
+// live one included, through the queue: a crop with few dead channels would lose more to the ballots, the rows and the
+// lists than compaction returns.)
+// 64 = 0.125 of the channels is the smallest dead share with a measured gain: with exactly that share of dconv1 dead in every
+// tile (the other channels live) the compacted body runs the 4096 x 1024 launch in 13.58 / 12.65 / 12.17 / 11.68 / 11.18 ms
+// at 0 / 0.125 / 0.1875 / 0.25 / 0.3125 against 12.89 - 12.92 ms dense — break-even below 0.125; it was near 0.2 while dconv2's
+// compact loop ran once per chunk (LEDGER_r12.md, section 3). With nothing dead it still loses 5 %: the dense body stays.
 #ifndef DAL3_DEC_MIN_DEAD
-#define DAL3_DEC_MIN_DEAD 128
+#define DAL3_DEC_MIN_DEAD 64
 #endif
 template <int T>
 __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_decode_kernel(InsSegW w, BCN pts, int c_in, int n_pts,
