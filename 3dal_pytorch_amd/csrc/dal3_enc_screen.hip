@@ -20,18 +20,24 @@
 #include "dal3_device.h"
 #include "dal3_kernels.h"
 #include "dal3_lp.h"
+#include "dal3_screen.h"
 
 #ifndef SCR_CAP
 #define SCR_CAP 1024                    // candidate entries per wave and 32-point tile (bench input: 130 on average, 426 at most in the CPU model)
 #endif
 #define SCR_XLD 132                     // floats per point row of the LDS copy of x4: 128 + 4, rows start 4 banks apart
+#define SCR_STAGE_LD 36                 // words per candidate row of the recompute's weight stage: a 32-channel slice + 4
+#ifndef SCR_DEPTH
+#define SCR_DEPTH 2                     // slices of the recompute in flight (measured 1 / 2 / 4: 4.13 / 4.12 / 4.19 ms, profiles/LEDGER_r13.md)
+#endif
 #define SCR_XMAX_BITS 0x476A6000        // 60000.0f: activations up to here round to a FINITE fp16
 // Pass A visits the wave-slots (32 * DAL3_ENC_T consecutive points) of a crop whose index is a multiple of this stride.
-// 1: every slot, the launches of the unstrided kernel (A/B builds). Measured (profiles/LEDGER_r09.md): the encoder at
-// 4096 x 1024 takes 5.97 / 5.37 / 5.67 / 7.02 ms at 1 / 2 / 4 / 8 — beyond 2 pass B's extra candidates (100 / 150 / 281
-// per 32-point tile against 82) cost more than pass A still saves — and at 1024 x 5120 6.70 / 5.71 / 5.36 / 5.55 ms.
+// 1: every slot, the launches of the unstrided kernel (A/B builds). Measured (profiles/LEDGER_r13.md, lists built once
+// per wave and staged recompute): the encoder at 4096 x 1024 takes 5.00 / 4.18 / 4.12 / 5.04 ms at 1 / 2 / 4 / 8 — 103 / 161
+// candidates per 32-point tile at 2 / 4; at 8 pass B's candidates cost more than pass A still saves — and at 1024 x 5120
+// 4.69 / 4.21 ms at 2 / 4, at 64 x 4096 0.252 / 0.234 ms.
 #ifndef DAL3_SCR_A_STRIDE
-#define DAL3_SCR_A_STRIDE 2
+#define DAL3_SCR_A_STRIDE 4
 #endif
 static_assert(DAL3_SCR_A_STRIDE >= 1, "pass A's stride over the wave-slots");
 
@@ -70,11 +76,14 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_encode_screen_kern
     __shared__ float s_g[PASS == 1 ? 1024 : 1];        // pass B: the crop's row of g = the thresholds
     __shared__ __attribute__((aligned(16))) float s_x[PASS == 1 ? DAL3_WG_WAVES * 32 * SCR_XLD : 4];
     __shared__ uint32_t s_list[PASS == 1 ? DAL3_WG_WAVES * T * SCR_CAP : 1];
+    // per wave: the sweep's parked hit words (32 blocks x 64 lanes), then the recompute's staged weight rows
+    __shared__ __attribute__((aligned(16))) uint32_t s_stage[PASS == 1 ? DAL3_WG_WAVES * 64 * SCR_STAGE_LD : 4];
     int* gi = reinterpret_cast<int*>(g + b * 1024);
-    // static LDS: the four tables, the waves' x4 copies and candidate lists. One workgroup per CU by LDS alone (the
-    // kernel holds one wave per SIMD by registers anyway). Too large: lower SCR_CAP, DAL3_WG_WAVES or DAL3_ENC_T.
-    static_assert(20 * 1024 + DAL3_WG_WAVES * (32 * SCR_XLD * 4 + T * SCR_CAP * 4) <= 160 * 1024,
+    // static LDS: the four tables, the waves' x4 copies, candidate lists and stages. One workgroup per CU by LDS alone
+    // (the kernel holds one wave per SIMD by registers anyway). Too large: lower SCR_CAP, DAL3_WG_WAVES or DAL3_ENC_T.
+    static_assert(20 * 1024 + DAL3_WG_WAVES * (32 * SCR_XLD * 4 + T * SCR_CAP * 4 + 64 * SCR_STAGE_LD * 4) <= 160 * 1024,
                   "pass B's LDS exceeds a CU's 160 KiB: lower SCR_CAP, DAL3_WG_WAVES or DAL3_ENC_T");
+    static_assert(32 * 64 <= 64 * SCR_STAGE_LD, "a wave's stage holds the hit words of conv5's 32 blocks");
     // conv5 not finite in fp16 (the blob's flag): no wave can be screened, pass A has no bound to give and pass B is the
     // dense encoder. (Uniform: one word.)
     if (PASS == 0 && *w.scr_flag != 0) return;
@@ -149,9 +158,9 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_encode_screen_kern
             }
 
             uint32_t* const list = s_list + (PASS == 1 ? wave * T * SCR_CAP : 0);
-            uint32_t cnt[T];
-#pragma unroll
-            for (int j = 0; j < T; ++j) cnt[j] = 0;
+            uint32_t* const stage = s_stage + (PASS == 1 ? wave * 64 * SCR_STAGE_LD : 0);
+            ScreenHits<T> hits;
+            hits.init();
 
             // Per 32-channel block the wave holds ONE constant per lane (= channel): pass A the error bound E_c, pass B the
             // threshold on the fp16 score. chain32 <= s16 + E; s16 <= thr <= G - b - E  ==>  chain32 + b <= G  ==>
@@ -168,7 +177,8 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_encode_screen_kern
             };
             // The epilogue of a block is cut into 8 slices (registers 2i, 2i+1 of every tile) that ride behind the MFMAs
             // of the NEXT block's fragment i, like MaxEpilogueT's steps: pass A a running max, pass B one bit per
-            // (tile, register) whose score is above the threshold. No branch, no ballot inside the MFMA stream.
+            // (tile, register) whose score is above the threshold (scr_push_hit: 32 pushes replace the whole word). The
+            // block's word is parked and counted; the lists are built once, after the sweep (dal3_screen.h).
             static_assert(16 * T <= 32, "one hit bit per (tile, register) in a 32-bit word");
             float m = 0.0f;
             uint32_t hb = 0;
@@ -181,7 +191,7 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_encode_screen_kern
                         if (PASS == 0)
                             m = (r == 0 && j == 0) ? acc[0][0] : __builtin_fmaxf(m, acc[j][r]);
                         else
-                            hb |= acc[j][r] > k ? (1u << (16 * j + r)) : 0u;
+                            hb = scr_push_hit(hb, acc[j][r], k);
                     }
                 }
             };
@@ -195,25 +205,7 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_encode_screen_kern
                     bits = bits > 0 ? bits : 0;
                     if (lane < 32 && bits > 0) atomicMax(&s_max[c], bits);
                 } else {
-                    uint32_t bits = hb;                // the block's hits of this lane: one (channel, point) pair per bit
-                    hb = 0;
-                    while (__builtin_amdgcn_ballot_w64(bits != 0)) {
-                        const bool act = bits != 0;
-                        const int idx = act ? __builtin_ctz(bits) : 0;
-                        const int r = idx & 15;
-                        const uint32_t e = ((uint32_t)c << 8) | (uint32_t)((r & 3) + 8 * (r >> 2) + 4 * h);   // tile_chan(r, h)
-#pragma unroll
-                        for (int j = 0; j < T; ++j) {
-                            const bool mine = act && (idx >> 4) == j;
-                            const unsigned long long mask = __builtin_amdgcn_ballot_w64(mine);
-                            if (mask) {
-                                const uint32_t pos = cnt[j] + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-                                if (mine && pos < SCR_CAP) list[j * SCR_CAP + pos] = e;
-                                cnt[j] += (uint32_t)__builtin_popcountll(mask);
-                            }
-                        }
-                        bits &= bits - 1;
-                    }
+                    hits.park_block(stage, mt, hb, lane);
                 }
             };
 
@@ -254,12 +246,10 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_encode_screen_kern
             ep_finish(mt, kB);
 
             if (PASS == 1) {
-                bool overflow = false;
+                uint32_t cnt[T];
+                const bool overflow = scr_build_lists<T, 32, SCR_CAP>(stage, list, hits, cnt, lane);
 #pragma unroll
-                for (int j = 0; j < T; ++j) {
-                    overflow |= cnt[j] > SCR_CAP;
-                    SCR_COUNT(3, cnt[j]);
-                }
+                for (int j = 0; j < T; ++j) SCR_COUNT(3, cnt[j]);
                 if (overflow) {                        // the lists do not hold the tile's candidates: the dense layer, exact
                     SCR_COUNT(2, 1);
                     WRing<DAL3_PF> r32;
@@ -285,32 +275,15 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_encode_screen_kern
                             }
                         }
                         __builtin_amdgcn_wave_barrier();
-                        // one candidate per lane: the dense kernel's chain. v_mfma_f32_32x32x2_f32 from a zero
-                        // accumulator is, per output, fma(a1, b1, fma(a0, b0, acc)) over its k-steps in issue order,
-                        // k = 0 from lane half 0: channels 8i, 8i+4, 8i+1, 8i+5, ... for i = 4 kt + q.
-                        for (uint32_t base = 0; base < cnt[j]; base += 64) {
-                            SCR_COUNT(4, 1);
-                            const uint32_t idx = base + lane;
-                            const bool live = idx < cnt[j];
-                            const uint32_t e = list[j * SCR_CAP + (live ? idx : 0u)];
-                            const int c = (int)(e >> 8), p = (int)(e & 31u);
-                            const f32x4* wr = reinterpret_cast<const f32x4*>(w.w5row + c * 128);
-                            const f32x4* xr = reinterpret_cast<const f32x4*>(xw + p * SCR_XLD);
-                            float a = 0.0f;
-#pragma unroll
-                            for (int i = 0; i < 16; ++i) {
-                                const f32x4 w0 = wr[2 * i], w1 = wr[2 * i + 1];
-                                const f32x4 x0 = xr[2 * i], x1 = xr[2 * i + 1];
-#pragma unroll
-                                for (int q = 0; q < 4; ++q) {
-                                    a = fmaf(x0[q], w0[q], a);
-                                    a = fmaf(x1[q], w1[q], a);
-                                }
-                            }
-                            int bits = __float_as_int(a + s_b5[c]);
-                            bits = bits > 0 ? bits : 0;
-                            if (live && bits > 0) atomicMax(&s_max[c], bits);
-                        }
+                        // one candidate per lane: the dense kernel's chain from +0 (scr_recompute)
+                        SCR_COUNT(4, (cnt[j] + 63) / 64);
+                        scr_recompute<32, 4, SCR_DEPTH, true>(
+                            w.w5row, 128, list + j * SCR_CAP, cnt[j], xw, SCR_XLD, stage, lane, [](uint32_t, bool) { return 0.0f; },
+                            [&](float a, int c, uint32_t, bool live) {
+                                int bits = __float_as_int(a + s_b5[c]);
+                                bits = bits > 0 ? bits : 0;
+                                if (live && bits > 0) atomicMax(&s_max[c], bits);
+                            });
                     }
                 }
             }

@@ -20,11 +20,16 @@
 #include "dal3_device.h"
 #include "dal3_kernels.h"
 #include "dal3_lp.h"
+#include "dal3_screen.h"
 
 #ifndef HEAD_SCR_CAP
 #define HEAD_SCR_CAP 1024               // candidate entries per 32-point tile (CPU model, bench crops: at most 856 at stride 4)
 #endif
 #define HEAD_SCR_XLD 132                // floats per point row of the LDS copy of HALF of x3: 128 + 4, rows start 4 banks apart
+#define HEAD_SCR_SW 16                  // channels per slice of the recompute's weight stage (rows of 16 + 4 words: what the CU's LDS leaves)
+#ifndef HEAD_SCR_DEPTH
+#define HEAD_SCR_DEPTH 1                // slices in flight, of the 8 of a half of k: a second one already spills (x3 alone is 128 registers)
+#endif
 #define HEAD_SCR_XMAX_BITS 0x476A6000   // 60000.0f: activations up to here round to a FINITE fp16
 #ifndef HEAD_RUN
 #define HEAD_RUN 6                      // as point_head_pers_kernel
@@ -65,10 +70,14 @@ __global__ __launch_bounds__(64) void point_head_screen_kernel(PointHeadW w, BCN
     __shared__ uint32_t s_list[HEAD_SCR_CAP];          // the tile's candidates: channel << 8 | point
     __shared__ float s_part[HEAD_SCR_CAP];             // their chains after the first half of k
     __shared__ __attribute__((aligned(16))) float s_x[32 * HEAD_SCR_XLD];   // half of x3, point-major
+    // the sweep's parked hit words (16 blocks x 64 lanes), then the recompute's staged weight rows
+    __shared__ __attribute__((aligned(16))) uint32_t s_stage[64 * (HEAD_SCR_SW + 4)];
     // Four one-wave workgroups per CU (one wave per SIMD at this register count) must fit the CU's 160 KiB: the four
-    // tables, the list, the partial chains and HALF of x3 (a whole point-major x3 is 33 KiB per wave and does not fit).
-    static_assert(4 * (3 * 512 * 4 + 512 * 8 + HEAD_SCR_CAP * 8 + 32 * HEAD_SCR_XLD * 4) <= 160 * 1024,
-                  "the screened head's LDS exceeds a quarter of a CU's 160 KiB: lower HEAD_SCR_CAP or HEAD_SCR_XLD");
+    // tables, the list, the partial chains, HALF of x3 (a whole point-major x3 is 33 KiB per wave and does not fit) and
+    // the stage.
+    static_assert(4 * (3 * 512 * 4 + 512 * 8 + HEAD_SCR_CAP * 8 + 32 * HEAD_SCR_XLD * 4 + 64 * (HEAD_SCR_SW + 4) * 4) <= 160 * 1024,
+                  "the screened head's LDS exceeds a quarter of a CU's 160 KiB: lower HEAD_SCR_CAP, HEAD_SCR_XLD or HEAD_SCR_SW");
+    static_assert(16 * 64 <= 64 * (HEAD_SCR_SW + 4), "the stage holds the hit words of conv4's 16 blocks");
     for (int i = threadIdx.x; i < 512; i += 64) {
         s_b4[i] = w.b4[i];
         s_run[i] = 0;
@@ -175,14 +184,16 @@ __global__ __launch_bounds__(64) void point_head_screen_kernel(PointHeadW w, BCN
 #pragma unroll
             for (int kt = 0; kt < KT; ++kt) xh[kt] = pack_relu<FP16>(x3[0][kt]);
 
-            uint32_t cnt = 0;
+            ScreenHits<T> hits;
+            hits.init();
             // the ragged last tile of an item repeats the item's last point (load_points): a copy is never listed, the
-            // point itself is in this tile. Bit r of vmask: accumulator register r of this lane half is a point of its own.
+            // point itself is in this tile. vmask: accumulator register r of this lane half is a point of its own, at
+            // the bit scr_push_hit leaves it (15 - r).
             uint32_t vmask = 0;
             {
                 const int left = e_n - e_t * 32;                         // >= 1
 #pragma unroll
-                for (int r = 0; r < 16; ++r) vmask |= ((r & 3) + 8 * (r >> 2) + 4 * h) < left ? (1u << r) : 0u;
+                for (int r = 0; r < 16; ++r) vmask |= tile_chan(r, h) < left ? (1u << (15 - r)) : 0u;
             }
             // Per 32-channel block one constant per lane (= channel): the threshold on the fp16 score.
             // chain32 <= s16 + E; s16 <= thr <= G - b - E  ==>  chain32 + b <= G  ==>  fl(chain32 + b) <= G.
@@ -196,26 +207,15 @@ __global__ __launch_bounds__(64) void point_head_screen_kernel(PointHeadW w, BCN
                 if (bits_nonfinite(G)) return 3.0e38f;                 // above every finite score: no candidate (decided on the bit pattern)
                 return (G - bb) - fmaf(__builtin_fabsf(G) + __builtin_fabsf(bb), 0x1p-22f, E);
             };
-            // one hit bit per accumulator register (= point), collected in 8 slices behind the NEXT block's first MFMAs
+            // one hit bit per accumulator register (= point), collected in 8 slices behind the NEXT block's first MFMAs;
+            // the block's word is parked and counted, the list is built once after the sweep (dal3_screen.h)
             uint32_t hb = 0;
             auto ep_slice = [&](const f32x16& acc, int i, float k) {
-                hb |= acc[2 * i] > k ? (1u << (2 * i)) : 0u;
-                hb |= acc[2 * i + 1] > k ? (2u << (2 * i)) : 0u;
+                hb = scr_push_hit(hb, acc[2 * i], k);
+                hb = scr_push_hit(hb, acc[2 * i + 1], k);
             };
             auto ep_finish = [&](int mt) {
-                const int c = 32 * mt + (lane & 31);
-                uint32_t bits = hb & vmask;            // the block's hits of this lane: one (channel, point) pair per bit
-                hb = 0;
-                while (__builtin_amdgcn_ballot_w64(bits != 0)) {
-                    const bool act = bits != 0;
-                    const int r = act ? __builtin_ctz(bits) : 0;
-                    const uint32_t ent = ((uint32_t)c << 8) | (uint32_t)((r & 3) + 8 * (r >> 2) + 4 * h);   // tile_chan(r, h)
-                    const unsigned long long mask = __builtin_amdgcn_ballot_w64(act);
-                    const uint32_t pos = cnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-                    if (act && pos < HEAD_SCR_CAP) s_list[pos] = ent;
-                    cnt += (uint32_t)__builtin_popcountll(mask);
-                    bits &= bits - 1;
-                }
+                hits.park_block(s_stage, mt, hb & vmask, lane);
             };
             // transposed tile, as conv_max_layer: points on the registers, channels on the lanes
             auto mm = [&](f32x16& acc, auto side) {
@@ -248,9 +248,12 @@ __global__ __launch_bounds__(64) void point_head_screen_kernel(PointHeadW w, BCN
 #pragma unroll
             for (int i = 0; i < 8; ++i) ep_slice(accB, i, kB);                     // last block: nothing left to hide under
             ep_finish(mt);
+            uint32_t cnt1[T];
+            const bool overflow = scr_build_lists<T, 16, HEAD_SCR_CAP>(s_stage, s_list, hits, cnt1, lane);
+            const uint32_t cnt = cnt1[0];
             HSCR_COUNT(3, cnt);
 
-            if (cnt > HEAD_SCR_CAP) {                  // the list does not hold the tile's candidates: the dense layer, exact
+            if (overflow) {                            // the list does not hold the tile's candidates: the dense layer, exact
                 HSCR_COUNT(2, 1);
                 dense_tile(x3);
             } else {
@@ -276,34 +279,19 @@ __global__ __launch_bounds__(64) void point_head_screen_kernel(PointHeadW w, BCN
                         }
                     }
                     __builtin_amdgcn_wave_barrier();
-                    for (uint32_t base = 0; base < cnt; base += 64) {
-                        if (half == 1) HSCR_COUNT(4, 1);
-                        const uint32_t idx = base + lane;
-                        const bool live = idx < cnt;
-                        const uint32_t li = live ? idx : 0u;
-                        const uint32_t ent = s_list[li];
-                        const int c = (int)(ent >> 8), p = (int)(ent & 31u);
-                        const f32x4* wr = reinterpret_cast<const f32x4*>(w.w4row + c * 256 + 128 * half);
-                        const f32x4* xr = reinterpret_cast<const f32x4*>(s_x + p * HEAD_SCR_XLD);
-                        float a = half == 0 ? 0.0f : s_part[li];
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) {
-                            const f32x4 w0 = wr[2 * i], w1 = wr[2 * i + 1];
-                            const f32x4 x0 = xr[2 * i], x1 = xr[2 * i + 1];
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) {
-                                a = fmaf(x0[q], w0[q], a);
-                                a = fmaf(x1[q], w1[q], a);
+                    if (half == 1) HSCR_COUNT(4, (cnt + 63) / 64);
+                    scr_recompute<HEAD_SCR_SW, 128 / HEAD_SCR_SW, HEAD_SCR_DEPTH, false>(
+                        w.w4row + 128 * half, 256, s_list, cnt, s_x, HEAD_SCR_XLD, s_stage, lane,
+                        [&](uint32_t idx, bool live) { return half == 0 ? 0.0f : s_part[live ? idx : 0u]; },
+                        [&](float a, int c, uint32_t idx, bool live) {
+                            if (half == 0) {
+                                if (live) s_part[idx] = a;
+                            } else {
+                                int bits = __float_as_int(a + s_b4[c]);
+                                bits = bits > 0 ? bits : 0;
+                                if (live && bits > 0) atomicMax(&s_run[c], bits);
                             }
-                        }
-                        if (half == 0) {
-                            if (live) s_part[li] = a;
-                        } else {
-                            int bits = __float_as_int(a + s_b4[c]);
-                            bits = bits > 0 ? bits : 0;
-                            if (live && bits > 0) atomicMax(&s_run[c], bits);
-                        }
-                    }
+                        });
                 }
             }
         }
