@@ -1795,17 +1795,15 @@ extern "C" int dal3_tr_pool_coef(const float* dg, const float* g, const float* z
     return 0;
 }
 
-static bool pool_k_ok(int K) { return K == 64 || K == 128 || K == 256; }
 
 extern "C" int dal3_tr_pool_moments(const float* W, int64_t ldw, const float* b, const double* m1, const float* Sc, int64_t M, int C,
                                     int K, double* sums, dal3_stream stream) {
-    if (!W || !b || !m1 || !Sc || !sums || M <= 0 || C <= 0 || !pool_k_ok(K) || ldw < K)
+    if (!W || !b || !m1 || !Sc || !sums || M <= 0 || C <= 0 || !tr_pool_k_ok(K) || ldw < K)
         return fail(DAL3_EINVAL, "tr_pool_moments: bad argument (K = 64, 128 or 256; ldw >= K)");
     HIP_TRY(launch_tr_pool_moments(W, ldw, b, m1, Sc, M, C, K, sums, static_cast<hipStream_t>(stream)));
     return 0;
 }
 
-static bool conv1_shape_ok(int c_in, int c_out) { return c_in >= 1 && c_in <= 8 && (c_out == 64 || c_out == 128); }
 
 extern "C" size_t dal3_tr_conv1_workspace_bytes(int64_t Mp, int c_out) { return Mp > 0 && c_out > 0 ? tr_conv1_workspace_bytes(Mp, c_out) : 0; }
 
@@ -1813,7 +1811,7 @@ extern "C" int dal3_tr_conv1_bn_stats(const float* x, int64_t M, int64_t Mp, int
                                       const float* bias, int c_out, float* z, int64_t ldz, const float* gamma, const float* beta,
                                       float* running_mean, float* running_var, float momentum, float eps, float* mu, float* rstd,
                                       float* scale, float* shift, void* workspace, size_t workspace_bytes, dal3_stream stream) {
-    if (!x || !W || !bias || !z || !gamma || !beta || !mu || !rstd || !scale || !shift || M < 2 || Mp < M || !conv1_shape_ok(c_in, c_out) ||
+    if (!x || !W || !bias || !z || !gamma || !beta || !mu || !rstd || !scale || !shift || M < 2 || Mp < M || !tr_conv1_ok(c_in, c_out) ||
         ldx < c_in || ldw < c_in || ldz < c_out || (ldz & 3) || (!running_mean != !running_var) ||
         (reinterpret_cast<uintptr_t>(z) & 15) || (reinterpret_cast<uintptr_t>(bias) & 15))
         return fail(DAL3_EINVAL, "tr_conv1_bn_stats: bad argument (c_in <= 8, c_out 64 or 128, 16-byte aligned z / bias, M >= 2)");
@@ -1826,7 +1824,7 @@ extern "C" int dal3_tr_conv1_bn_stats(const float* x, int64_t M, int64_t Mp, int
 
 extern "C" int dal3_tr_conv1_wgrad(const float* dz, int64_t lddz, const float* x, int64_t M, int c_in, int64_t ldx, int c_out,
                                    void* workspace, size_t workspace_bytes, float* dW, dal3_stream stream) {
-    if (!dz || !x || !dW || M <= 0 || !conv1_shape_ok(c_in, c_out) || ldx < c_in || lddz < c_out || (lddz & 3) ||
+    if (!dz || !x || !dW || M <= 0 || !tr_conv1_ok(c_in, c_out) || ldx < c_in || lddz < c_out || (lddz & 3) ||
         (reinterpret_cast<uintptr_t>(dz) & 15))
         return fail(DAL3_EINVAL, "tr_conv1_wgrad: bad argument (c_in <= 8, c_out 64 or 128, 16-byte aligned dz)");
     if (!workspace || workspace_bytes < tr_conv1_workspace_bytes(M, c_out))
@@ -1908,11 +1906,11 @@ extern "C" int dal3_tr_pool_zarg(const int32_t* arg, const float* a, int64_t lda
     return 0;
 }
 
-extern "C" size_t dal3_tr_pool_gv_workspace_bytes(int K) { return pool_k_ok(K) ? tr_pool_gv_workspace_bytes(K) : 0; }
+extern "C" size_t dal3_tr_pool_gv_workspace_bytes(int K) { return tr_pool_k_ok(K) ? tr_pool_gv_workspace_bytes(K) : 0; }
 
 extern "C" int dal3_tr_pool_gv(const double* coef, const float* W, int64_t ldw, const float* b, int C, int K, float* G, float* v,
                                void* workspace, size_t workspace_bytes, dal3_stream stream) {
-    if (!coef || !W || !b || !G || !v || C <= 0 || !pool_k_ok(K) || ldw < K)
+    if (!coef || !W || !b || !G || !v || C <= 0 || !tr_pool_k_ok(K) || ldw < K)
         return fail(DAL3_EINVAL, "tr_pool_gv: bad argument (K = 64, 128 or 256; ldw >= K)");
     if (!workspace || workspace_bytes < tr_pool_gv_workspace_bytes(K))
         return fail(DAL3_EWORKSPACE, "tr_pool_gv: workspace too small (dal3_tr_pool_gv_workspace_bytes)");
@@ -1922,7 +1920,7 @@ extern "C" int dal3_tr_pool_gv(const double* coef, const float* W, int64_t ldw, 
 
 extern "C" int dal3_tr_pool_dw(const double* coef, const float* W, int64_t ldw, const float* b, const float* S, const double* m1,
                                int64_t M, int centred, const float* dWs, int C, int K, float* dW, dal3_stream stream) {
-    if (!coef || !W || !b || !S || !m1 || !dWs || !dW || M <= 0 || C <= 0 || !pool_k_ok(K) || ldw < K)
+    if (!coef || !W || !b || !S || !m1 || !dWs || !dW || M <= 0 || C <= 0 || !tr_pool_k_ok(K) || ldw < K)
         return fail(DAL3_EINVAL, "tr_pool_dw: bad argument (K = 64, 128 or 256; ldw >= K)");
     HIP_TRY(launch_tr_pool_dw(coef, W, ldw, b, S, m1, M, centred, dWs, C, K, dW, static_cast<hipStream_t>(stream)));
     return 0;
@@ -2554,12 +2552,11 @@ extern "C" int dal3_roi_loss(const float* rcnn_cls, const float* rcnn_reg, int64
     return 0;
 }
 
-static bool center_dims_ok(int64_t B, int64_t H, int64_t W) { return B >= 0 && B <= 65535 && H >= 1 && H <= 65535 && W >= 1 && W <= 65535; }
 
 extern "C" int dal3_center_targets(const dal3_center_targets_args* args, dal3_stream stream) {
     if (!args) return fail(DAL3_EINVAL, "center_targets: null args");
     const dal3_center_targets_args& a = *args;
-    if (!center_dims_ok(a.B, a.H, a.W) || a.G < 1 || a.G > (1 << 20)) return fail(DAL3_EINVAL, "center_targets: bad B / G (1 .. 2^20) / H / W (1 .. 65535)");
+    if (!map_dims_ok(a.B, a.H, a.W) || a.G < 1 || a.G > (1 << 20)) return fail(DAL3_EINVAL, "center_targets: bad B / G (1 .. 2^20) / H / W (1 .. 65535)");
     if (a.T < 1 || a.T > DAL3_ROI_MAX_TASKS) return fail(DAL3_EINVAL, "center_targets: T %d (1 .. %d)", (int)a.T, DAL3_ROI_MAX_TASKS);
     if (a.max_objs < 1 || a.max_objs > DAL3_CENTER_MAX_OBJS) return fail(DAL3_EINVAL, "center_targets: max_objs %d (1 .. %d)", (int)a.max_objs, DAL3_CENTER_MAX_OBJS);
     if (!(a.voxel_size[0] > 0.f) || !(a.voxel_size[1] > 0.f) || !(a.out_size_factor > 0.f))
@@ -2578,14 +2575,14 @@ extern "C" int dal3_center_targets(const dal3_center_targets_args* args, dal3_st
 }
 
 extern "C" size_t dal3_center_loss_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W) {
-    if (!center_dims_ok(B, H, W) || C < 1 || C > DAL3_CENTER_MAX_CLASSES) return 0;
+    if (!map_dims_ok(B, H, W) || C < 1 || C > DAL3_CENTER_MAX_CLASSES) return 0;
     return center_loss_workspace_bytes(B, C, H, W);
 }
 
 extern "C" int dal3_center_loss(const dal3_center_loss_args* args, dal3_stream stream) {
     if (!args) return fail(DAL3_EINVAL, "center_loss: null args");
     const dal3_center_loss_args& a = *args;
-    if (!center_dims_ok(a.B, a.H, a.W) || a.C < 1 || a.C > DAL3_CENTER_MAX_CLASSES) return fail(DAL3_EINVAL, "center_loss: bad B / H / W (1 .. 65535) / C (1 .. %d)", DAL3_CENTER_MAX_CLASSES);
+    if (!map_dims_ok(a.B, a.H, a.W) || a.C < 1 || a.C > DAL3_CENTER_MAX_CLASSES) return fail(DAL3_EINVAL, "center_loss: bad B / H / W (1 .. 65535) / C (1 .. %d)", DAL3_CENTER_MAX_CLASSES);
     if (a.n_cols != 8 && a.n_cols != 10) return fail(DAL3_EINVAL, "center_loss: n_cols %d (8 or 10)", (int)a.n_cols);
     if (a.max_objs < 1 || a.max_objs > DAL3_CENTER_MAX_OBJS) return fail(DAL3_EINVAL, "center_loss: max_objs %d (1 .. %d)", (int)a.max_objs, DAL3_CENTER_MAX_OBJS);
     if (a.B * (a.C + a.n_cols) * a.H * a.W >= ((int64_t)1 << 31)) return fail(DAL3_EINVAL, "center_loss: B * (C + n_cols) * H * W must stay below 2^31");

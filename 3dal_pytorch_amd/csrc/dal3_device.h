@@ -372,3 +372,42 @@ __device__ __forceinline__ void conv_max_layer(WRing<D, CYC>& ring, const float*
     tile_b(mt);                                                            // n_tiles is even: mt == n_tiles - 1
     ep.all(accB, bias + 32 * mt, dst + 32 * mt, lane);                    // last tile: nothing left to hide under
 }
+
+// ---- the training step's max over points (the pooled linear kernels, tr_segmax_kernel): a segment's maximum per channel
+// is found by a 64-bit atomicMax over KEYS on a zero-filled table. High word: the bits of y = relu(bn(z)) (y >= +0, so the
+// bits order like the floats); low word: ~index of the point within its segment. The larger key is the larger value and,
+// among equal values, the EARLIER point: the first maximum wins, like torch.max.
+__device__ __forceinline__ unsigned long long pool_key(float y, uint32_t index) {
+    return ((unsigned long long)__float_as_uint(y) << 32) | (0xffffffffu - index);
+}
+__device__ __forceinline__ void pool_unkey(unsigned long long key, float& y, int32_t& index) {
+    y = __uint_as_float((uint32_t)(key >> 32)), index = (int32_t)(0xffffffffu - (uint32_t)key);
+}
+// One TRANSPOSED accumulator tile (lane = channel `c` of the layer, register r of lane half h = point tile_chan(r, h) of the
+// 32 points that start at row p0) becomes the channel's candidate: BN affine (sc, sh: this lane's channel's), ReLU, first
+// maximum over the lane's 16 points (increasing point index: '>' keeps the first), then over the two lane halves; the
+// lower half adds it to packed[segment of p0][c]. seg % 32 == 0 (a tile lies in one segment), p0 < 2^31.
+__device__ __forceinline__ void pool_candidate(const f32x16& acc, float sc, float sh, int h, int64_t p0, int64_t seg, int c_out,
+                                               int c, unsigned long long* __restrict__ packed) {
+    float bv = -1.0f;
+    int bi = 0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const float y = fmaxf(__builtin_fmaf(acc[r], sc, sh), 0.0f);
+        if (y > bv) {
+            bv = y;
+            bi = tile_chan(r, h);
+        }
+    }
+    const float ov = __shfl_xor(bv, 32);
+    const int oi = __shfl_xor(bi, 32);
+    if (ov > bv || (ov == bv && oi < bi)) {
+        bv = ov;
+        bi = oi;
+    }
+    if (h == 0) {
+        const int64_t s_idx = (int64_t)((uint32_t)p0 / (uint32_t)seg);
+        const uint32_t in_seg = (uint32_t)(p0 - s_idx * seg) + (uint32_t)bi;
+        atomicMax(packed + s_idx * c_out + c, pool_key(bv, in_seg));
+    }
+}

@@ -424,6 +424,10 @@ hipError_t launch_tr_pool_coef(const float* dg, const float* g, const float* zar
                                const float* gamma, int B, int C, int64_t M, double* coef, float* kd, hipStream_t s);
 hipError_t launch_tr_pool_moments(const float* W, int64_t ldw, const float* b, const double* m1, const float* Sc, int64_t M, int C,
                                   int K, double* sums, hipStream_t s);
+// the shapes the moment-route kernels / the conv1 kernels are built for (dal3_train.hip), for the C ABI's argument checks
+// (hidden: the library's exported names stay the C ABI's and the launchers')
+__attribute__((visibility("hidden"))) bool tr_pool_k_ok(int K);
+__attribute__((visibility("hidden"))) bool tr_conv1_ok(int c_in, int c_out);
 size_t tr_pool_gv_workspace_bytes(int K);
 hipError_t launch_tr_pool_gv(const double* coef, const float* W, int64_t ldw, const float* b, int C, int K, float* G, float* v,
                              double* ws, hipStream_t s);

@@ -225,6 +225,10 @@ __global__ void tr_pack_kernel(const float* __restrict__ W, int64_t ldw, int tra
                                float* __restrict__ out) {
     tr_pack_element(W, ldw, transpose_w, c_out, c_in, mtb, out, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
+static void tr_pack(const float* W, int64_t ldw, int transpose_w, int c_out, int c_in, int mtb, float* ws, hipStream_t s) {
+    hipLaunchKernelGGL(tr_pack_kernel, dim3((unsigned)(((int64_t)c_out * c_in + 255) / 256)), dim3(256), 0, s, W, ldw, transpose_w, c_out,
+                       c_in, mtb, ws);
+}
 // Every layer of a step packed by ONE launch (round 3: a training step issued 32 tr_pack launches of ~4 us, one in front
 // of each linear / dgrad call; the weights do not change between a step's forward and its backward, so both orientations
 // of every layer can be packed when the forward starts). The item table travels by value in the kernel arguments.
@@ -275,6 +279,19 @@ __device__ __forceinline__ void tr_act_lds(f32x16 (&X)[T], const float* __restri
     }
 }
 
+// The input activation's scale and shift copied to LDS, once per workgroup of 256 threads (barrier included); false: the
+// input carries no activation and nothing is staged.
+__device__ __forceinline__ bool tr_stage_act(const float* __restrict__ scale, const float* __restrict__ shift, int c_in,
+                                             float* __restrict__ s_sc, float* __restrict__ s_sh) {
+    if (!scale) return false;
+    for (int i = threadIdx.x; i < c_in; i += 256) {
+        s_sc[i] = scale[i];
+        s_sh[i] = shift[i];
+    }
+    __syncthreads();
+    return true;
+}
+
 template <int T>
 __device__ __forceinline__ void tr_load_x(TrX<T>& st, int kt, const float* __restrict__ a, int64_t lda,
                                           const int64_t (&prow)[T], int h) {
@@ -283,11 +300,7 @@ __device__ __forceinline__ void tr_load_x(TrX<T>& st, int kt, const float* __res
         const float* ap = a + prow[j] * lda + 32 * kt + 4 * h;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-#ifdef TR_ABL_NOLOADX
-            const f32x4 v = {(float)kt, (float)h, (float)q, (float)lda};
-#else
             const f32x4 v = *reinterpret_cast<const f32x4*>(ap + 8 * q);
-#endif
 #pragma unroll
             for (int e = 0; e < 4; ++e) st.X[j][4 * q + e] = v[e];
         }
@@ -336,14 +349,7 @@ __global__ __launch_bounds__(256, OCC) void tr_linear_ring_kernel(const float* _
                                                                 int accumulate, int n_mblk) {
     static_assert(DAL3_PF == 8 && (MTB == 1 || MTB == 2 || MTB == 4), "fragment order of tr_pack_kernel, ring slots");
     __shared__ float s_sc[TR_MAX_ACT_CIN], s_sh[TR_MAX_ACT_CIN];
-    const bool act = scale != nullptr;
-    if (act) {
-        for (int i = threadIdx.x; i < c_in; i += 256) {
-            s_sc[i] = scale[i];
-            s_sh[i] = shift[i];
-        }
-        __syncthreads();
-    }
+    const bool act = tr_stage_act(scale, shift, c_in, s_sc, s_sh);
     const int lane = threadIdx.x & 63, h = lane >> 5, m = lane & 31;
     // scalar (the ring's buffer descriptor stays in SGPRs: from a per-lane value hipcc builds a waterfall loop around every
     // fragment fetch) and 32-bit (a 64-bit division is ~200 instructions; the host keeps the unit count below 2^32)
@@ -401,9 +407,6 @@ __global__ __launch_bounds__(256, OCC) void tr_linear_ring_kernel(const float* _
 #pragma unroll
         for (int j = 0; j < T; ++j) {
             if (pt0 + 32 * j >= M) break;
-#ifdef TR_ABL_NOSTORE
-            if (acc[j][0][0] != 12345.678f) continue;
-#endif
             float* zp = z + (pt0 + 32 * j + m) * ldz + 4 * h;
 #pragma unroll
             for (int t = 0; t < MTB; ++t) {
@@ -439,28 +442,7 @@ __global__ __launch_bounds__(256, OCC) void tr_linear_ring_kernel(const float* _
 // (their data registers are read at issue), and the weight ring runs on cyclically (no refill bubble per unit).
 // Host-side conditions (launch_tr_linear): no accumulate, M % (32 T) == 0, seg == 0 or seg % (32 T) == 0 (one bias row per
 // unit), c_in % 64 == 0 (k-tiles in pairs; the ring's slot rotation is a compile-time pattern), n_waves % n_mblk == 0.
-#ifndef TR_PERS
-#define TR_PERS 1                       // 0: every layer through the one-unit-per-wave kernels (A/B builds)
-#endif
-struct WRingCyc {
-    __amdgpu_buffer_rsrc_t rsrc;
-    uint32_t voff, soff, len;
-    f32x4 slot[DAL3_PF];
-    __device__ __forceinline__ f32x4 fetch() {
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0);
-        soff += 1024;
-        if (soff == len) soff = 0;
-        return __builtin_bit_cast(f32x4, v);
-    }
-    __device__ __forceinline__ void init(const f32x4* stream, uint32_t bytes, int lane) {
-        rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<f32x4*>(stream), 0, 0x7fffffff, 0x00020000);
-        voff = (uint32_t)lane * 16u;
-        soff = 0;
-        len = bytes;
-#pragma unroll
-        for (int i = 0; i < DAL3_PF; ++i) slot[i] = fetch();
-    }
-};
+// The weight ring is the eval kernels' cyclic one (WRing<DAL3_PF, true> of dal3_device.h).
 
 // RED != 0: a column reduction over the points of the kernel's OWN OUTPUT, taken in the epilogue instead of by a second
 // pass over the tensor (round 4: the statistics / BatchNorm-backward passes were 1.0 of a training step's 7.9 ms, each a
@@ -492,19 +474,10 @@ __global__ __launch_bounds__(256, OCC) void tr_linear_pers_kernel(const float* _
                                                                 int64_t seg, int c_out, float* __restrict__ z, int64_t ldz,
                                                                 int n_mblk, uint32_t n_units, TrRed red) {
     static_assert(DAL3_PF == 8 && (MTB == 1 || MTB == 2 || MTB == 4), "fragment order of tr_pack_kernel, ring slots");
-#ifndef TR_PERS_SW
-#define TR_PERS_SW 1                   // 1: every persistent linear kernel computes its tile transposed (whole-row stores), reduction or not
-#endif
-    constexpr bool SW = RED != 0 || TR_PERS_SW;
+    // Every instantiation computes its tile TRANSPOSED (tr_ring_block SWAP), reduction or not: the stores are whole 128-byte
+    // rows (measured against the untransposed tile: profiles/LEDGER_r04.md 2.1 item 2).
     __shared__ float s_sc[TR_MAX_ACT_CIN], s_sh[TR_MAX_ACT_CIN];
-    const bool act = scale != nullptr;
-    if (act) {
-        for (int i = threadIdx.x; i < c_in; i += 256) {
-            s_sc[i] = scale[i];
-            s_sh[i] = shift[i];
-        }
-        __syncthreads();
-    }
+    const bool act = tr_stage_act(scale, shift, c_in, s_sc, s_sh);
     const int lane = threadIdx.x & 63, h = lane >> 5, m = lane & 31;
     uint32_t unit = blockIdx.x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t wave0 = unit;                              // this wave's index on the chip
@@ -513,22 +486,18 @@ __global__ __launch_bounds__(256, OCC) void tr_linear_pers_kernel(const float* _
     const int mblk = (int)(unit % (uint32_t)n_mblk);          // the same for every unit of this wave
     const int mt0 = mblk * MTB;
     const int KT = KTC ? KTC : c_in / 32;
-    WRingCyc ring;
-    ring.init(wpk + (int64_t)mblk * KT * (4 * MTB) * 64, (uint32_t)(KT * 4 * MTB) * 1024u, lane);
+    WRing<DAL3_PF, true> ring;
+    ring.init(wpk + (int64_t)mblk * KT * (4 * MTB) * 64, lane, (uint32_t)(KT * 4 * MTB) * 1024u);
     auto bias_row = [&](int64_t pt0) {                        // scalar: one 32-bit division per unit
         return seg > 0 ? bias + (int64_t)((uint32_t)pt0 / (uint32_t)seg) * c_out + 32 * mt0 : bias + 32 * mt0;
     };
     auto bias_tile = [&](int64_t pt0, int t) {
         if (!bias) return f32x16{};
-        if constexpr (SW) {                                   // transposed tile: this lane's one channel in every register
-            const float v = bias_row(pt0)[32 * t + m];
-            f32x16 o;
+        const float v = bias_row(pt0)[32 * t + m];            // transposed tile: this lane's one channel in every register
+        f32x16 o;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) o[r] = v;
-            return o;
-        } else {
-            return tile_from_channels(bias_row(pt0) + 32 * t, h);
-        }
+        for (int r = 0; r < 16; ++r) o[r] = v;
+        return o;
     };
     int64_t pt0 = (int64_t)(unit / (uint32_t)n_mblk) * (32 * T);
     f32x16 bnext[MTB];
@@ -580,8 +549,9 @@ __global__ __launch_bounds__(256, OCC) void tr_linear_pers_kernel(const float* _
 #pragma unroll
             for (int t = 0; t < MTB; ++t) bnext[t] = bias_tile(pt0_n, t);
         }
-        __amdgpu_buffer_rsrc_t zrs, bzrs;                       // (scalar: the unit's first row of z / bz)
-        if constexpr (SW) zrs = __builtin_amdgcn_make_buffer_rsrc(z + pt0 * ldz, 0, 0x7fffffff, 0x00020000);
+        // (scalar: the unit's first row of z / bz)
+        const __amdgpu_buffer_rsrc_t zrs = __builtin_amdgcn_make_buffer_rsrc(z + pt0 * ldz, 0, 0x7fffffff, 0x00020000);
+        __amdgpu_buffer_rsrc_t bzrs;
         if constexpr (RED == 2) bzrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(red.bz) + pt0 * red.ldbz, 0, 0x7fffffff, 0x00020000);
         // RED == 2: the tile of bz under output tile t (the same rows and channels, the transposed tile's own pattern: two
         // whole 128-byte rows per instruction), requested one output tile ahead of its use
@@ -604,25 +574,13 @@ __global__ __launch_bounds__(256, OCC) void tr_linear_pers_kernel(const float* _
         auto store_tile = [&](int t) {
 #pragma unroll
             for (int j = 0; j < T; ++j) {
-#ifdef TR_ABL_NOSTORE
-                if (acc[j][0][0] != 12345.678f) continue;
-#endif
-                if constexpr (SW) {
-                    // through a buffer descriptor based at the unit's first row: the address of every store is that base +
-                    // ONE per-lane offset register + a scalar offset (with flat pointers hipcc keeps a 64-bit VGPR pair
-                    // per store in flight: 64 registers for a tile pair, and the kernel spilled)
+                // through a buffer descriptor based at the unit's first row: the address of every store is that base +
+                // ONE per-lane offset register + a scalar offset (with flat pointers hipcc keeps a 64-bit VGPR pair
+                // per store in flight: 64 registers for a tile pair, and the kernel spilled)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r)
-                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc[j][t][r]), zrs, loff_z,   // (not __builtin_bit_cast: on a vector ELEMENT it read element 0)
-                                                              (uint32_t)(((32 * j + (r & 3) + 8 * (r >> 2)) * (uint32_t)ldz + 32 * (mt0 + t)) * 4u), 0);
-                } else {
-                    float* zp = z + (pt0 + 32 * j + m) * ldz + 4 * h + 32 * (mt0 + t);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const f32x4 o = {acc[j][t][4 * q], acc[j][t][4 * q + 1], acc[j][t][4 * q + 2], acc[j][t][4 * q + 3]};
-                        *reinterpret_cast<f32x4*>(zp + 8 * q) = o;
-                    }
-                }
+                for (int r = 0; r < 16; ++r)
+                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc[j][t][r]), zrs, loff_z,   // (not __builtin_bit_cast: on a vector ELEMENT it read element 0)
+                                                          (uint32_t)(((32 * j + (r & 3) + 8 * (r >> 2)) * (uint32_t)ldz + 32 * (mt0 + t)) * 4u), 0);
             }
         };
         auto reduce_tile = [&](int t) {                         // (float64 per element, as the separate pass adds them)
@@ -662,17 +620,17 @@ __global__ __launch_bounds__(256, OCC) void tr_linear_pers_kernel(const float* _
             if (act) tr_act_lds<T>(xa.X, s_sc, s_sh, kt, h, relu_in);
             if (LAST) load_bz(0);
             if (LAST)
-                tr_ring_block<T, MTB, 0, SW>(ring, xa.X, acc, [&](int i) {
+                tr_ring_block<T, MTB, 0, true>(ring, xa.X, acc, [&](int i) {
                     if (i == 2 * MTB && MTB > 1) load_bz(1);       // (half a round later: the two requests do not queue up together)
                 });
             else
-                tr_ring_block<T, MTB, 0, SW>(ring, xa.X, acc);
+                tr_ring_block<T, MTB, 0, true>(ring, xa.X, acc);
             // k-tile kt + 2 of this unit, or — in the last round — the NEXT unit's first k-tile, ahead of the stores
             tr_load_x<T>(xa, LAST ? 0 : kt + 2, a, lda, LAST ? prow_n : prow, h);
             DAL3_SCHED_FENCE();
             if (act) tr_act_lds<T>(xb.X, s_sc, s_sh, kt + 1, h, relu_in);
             if (LAST)
-                tr_ring_block<T, MTB, BASE2, SW>(ring, xb.X, acc, [&](int i) {
+                tr_ring_block<T, MTB, BASE2, true>(ring, xb.X, acc, [&](int i) {
                     if (i % 4 == 3) {
                         store_tile(i / 4);
                         reduce_tile(i / 4);
@@ -680,7 +638,7 @@ __global__ __launch_bounds__(256, OCC) void tr_linear_pers_kernel(const float* _
                     }
                 });
             else
-                tr_ring_block<T, MTB, BASE2, SW>(ring, xb.X, acc);
+                tr_ring_block<T, MTB, BASE2, true>(ring, xb.X, acc);
         };
         // first and last round peeled (the same one when K = 64): hipcc's wait counts are per code location, and the
         // waits of a unit's first fragments — fetched before the previous unit's stores — must count those stores as
@@ -717,18 +675,16 @@ __global__ __launch_bounds__(256, OCC) void tr_linear_pers_kernel(const float* _
     }
 }
 
-__global__ void tr_segmax_unpack_kernel(const unsigned long long* __restrict__ packed, int64_t n, float* __restrict__ g,
-                                        int32_t* __restrict__ arg);
 // ---- the pooled layer's forward without its output tensor: conv (W, b) -> BN -> ReLU -> max over the points of each
 // segment, for layers whose batch statistics are known BEFORE the layer runs (train.py obtains them from the second
 // moments of the layer's input). Same ring / ping-pong structure as tr_linear_ring_kernel, but the MFMA operands are
 // SWAPPED (D^T = act(a) . W^T: points on the accumulator's registers, channels on its lanes — the idiom of the eval
 // kernels' max-pooled layers), so the max over a tile's 32 points is a compare chain over 16 registers plus one
-// exchange between the lane halves, each carrying the point index (first maximum wins, like torch.max). The MFMA
-// computes the same k-ordered FMA chain per output element whichever operand is which, so z — and with it g and
-// arg — are bit-identical to tr_linear + tr_segmax. Candidates of different tiles / waves meet in the packed 64-bit
-// atomicMax of tr_segmax_kernel (high word: bits of y >= +0, low word: ~index). z itself (1 GB for ins_seg's conv5 at
-// 64 x 4096 points) is never written. seg must be a multiple of 32 (a tile lies in one segment).
+// exchange between the lane halves, each carrying the point index (pool_candidate of dal3_device.h, which also defines
+// the key and the tie rule). The MFMA computes the same k-ordered FMA chain per output element whichever operand is
+// which, so z — and with it g and arg — are bit-identical to tr_linear + tr_segmax. Candidates of different tiles /
+// waves meet in the packed 64-bit atomicMax of tr_segmax_kernel. z itself (1 GB for ins_seg's conv5 at 64 x 4096
+// points) is never written. seg must be a multiple of 32 (a tile lies in one segment).
 __global__ __launch_bounds__(256, 2) void tr_linear_pool_kernel(const float* __restrict__ a, int64_t M, int c_in, int64_t lda,
                                                                 const float* __restrict__ scale,
                                                                 const float* __restrict__ shift, int relu_in,
@@ -737,14 +693,7 @@ __global__ __launch_bounds__(256, 2) void tr_linear_pool_kernel(const float* __r
                                                                 const float* __restrict__ out_shift, int64_t seg, int c_out,
                                                                 unsigned long long* __restrict__ packed, int n_mblk) {
     __shared__ float s_sc[TR_MAX_ACT_CIN], s_sh[TR_MAX_ACT_CIN];
-    const bool act = scale != nullptr;
-    if (act) {
-        for (int i = threadIdx.x; i < c_in; i += 256) {
-            s_sc[i] = scale[i];
-            s_sh[i] = shift[i];
-        }
-        __syncthreads();
-    }
+    const bool act = tr_stage_act(scale, shift, c_in, s_sc, s_sh);
     const int lane = threadIdx.x & 63, h = lane >> 5, m = lane & 31;
     const uint32_t unit = blockIdx.x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (scalar, 32-bit: see tr_linear_ring_kernel)
     const int mblk = (int)(unit % (uint32_t)n_mblk);
@@ -768,30 +717,16 @@ __global__ __launch_bounds__(256, 2) void tr_linear_pool_kernel(const float* __r
     }
     TrX<TR_T> xa, xb;
     tr_load_x(xa, 0, a, lda, prow, h);
-    auto block = [&](const f32x16 (&X)[TR_T]) {                     // tr_ring_block with the operands swapped
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            ring_batch_wait<DAL3_PF>(ring, i);
-            const f32x4 w = ring.slot[i % DAL3_PF];
-            ring.slot[i % DAL3_PF] = ring.fetch();
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-#pragma unroll
-                for (int j = 0; j < TR_T; ++j) acc[j][i / 4] = mfma32(X[j][4 * (i % 4) + e], w[e], acc[j][i / 4]);
-            }
-            DAL3_SCHED_FENCE();
-        }
-    };
     for (int kt = 0; kt < KT; kt += 2) {
         tr_load_x(xb, min(kt + 1, KT - 1), a, lda, prow, h);
         DAL3_SCHED_FENCE();
         if (act) tr_act_lds(xa.X, s_sc, s_sh, kt, h, relu_in);
-        block(xa.X);
+        tr_ring_block<TR_T, TR_MTB, 0, true>(ring, xa.X, acc);
         tr_load_x(xa, min(kt + 2, KT - 1), a, lda, prow, h);
         DAL3_SCHED_FENCE();
         if (kt + 1 < KT) {
             if (act) tr_act_lds(xb.X, s_sc, s_sh, kt + 1, h, relu_in);
-            block(xb.X);
+            tr_ring_block<TR_T, TR_MTB, 0, true>(ring, xb.X, acc);
         }
     }
 #pragma unroll
@@ -801,29 +736,7 @@ __global__ __launch_bounds__(256, 2) void tr_linear_pool_kernel(const float* __r
 #pragma unroll
         for (int j = 0; j < TR_T; ++j) {
             if (pt0 + 32 * j >= M) break;
-            const int64_t p0 = pt0 + 32 * j;                           // the tile's first point; rows (r&3) + 8 (r>>2) + 4 h
-            float bv = -1.0f;
-            int bi = 0;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {                             // increasing point index: '>' keeps the first maximum
-                const float y = fmaxf(__builtin_fmaf(acc[j][t][r], sc, sh), 0.0f);
-                if (y > bv) {
-                    bv = y;
-                    bi = (r & 3) + 8 * (r >> 2) + 4 * h;
-                }
-            }
-            const float ov = __shfl_xor(bv, 32);
-            const int oi = __shfl_xor(bi, 32);
-            if (ov > bv || (ov == bv && oi < bi)) {
-                bv = ov;
-                bi = oi;
-            }
-            if (h == 0) {
-                const int64_t s_idx = (int64_t)((uint32_t)p0 / (uint32_t)seg);   // (32-bit: M < 2^31 rows)
-                const uint32_t in_seg = (uint32_t)(p0 - s_idx * seg) + (uint32_t)bi;
-                const unsigned long long key = ((unsigned long long)__float_as_uint(bv) << 32) | (0xffffffffu - in_seg);
-                atomicMax(packed + s_idx * c_out + c, key);
-            }
+            pool_candidate(acc[j][t], sc, sh, h, pt0 + 32 * j, seg, c_out, c, packed);
         }
     }
 }
@@ -844,14 +757,7 @@ __global__ __launch_bounds__(256, OCC) void tr_linear_pool_pers_kernel(const flo
                                                                      unsigned long long* __restrict__ packed, int n_mblk,
                                                                      uint32_t n_units) {
     __shared__ float s_sc[TR_MAX_ACT_CIN], s_sh[TR_MAX_ACT_CIN];
-    const bool act = scale != nullptr;
-    if (act) {
-        for (int i = threadIdx.x; i < c_in; i += 256) {
-            s_sc[i] = scale[i];
-            s_sh[i] = shift[i];
-        }
-        __syncthreads();
-    }
+    const bool act = tr_stage_act(scale, shift, c_in, s_sc, s_sh);
     const int lane = threadIdx.x & 63, h = lane >> 5, m = lane & 31;
     uint32_t unit = blockIdx.x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t n_waves = gridDim.x * 4u;
@@ -859,8 +765,8 @@ __global__ __launch_bounds__(256, OCC) void tr_linear_pool_pers_kernel(const flo
     const int mblk = (int)(unit % (uint32_t)n_mblk);
     const int mt0 = mblk * TR_MTB;
     const int KT = KTC ? KTC : c_in / 32;
-    WRingCyc ring;
-    ring.init(wpk + (int64_t)mblk * KT * 16 * 64, (uint32_t)(KT * 16) * 1024u, lane);
+    WRing<DAL3_PF, true> ring;
+    ring.init(wpk + (int64_t)mblk * KT * 16 * 64, lane, (uint32_t)(KT * 16) * 1024u);
     float bch[TR_MTB], osc[TR_MTB], osh[TR_MTB];               // this lane's channel of each output tile
 #pragma unroll
     for (int t = 0; t < TR_MTB; ++t) {
@@ -891,59 +797,25 @@ __global__ __launch_bounds__(256, OCC) void tr_linear_pool_pers_kernel(const flo
 #pragma unroll
         for (int j = 0; j < TR_T; ++j) prow_n[j] = pt0_n + 32 * j + m;
         auto finish_tile = [&](int t) {                         // the epilogue of tr_linear_pool_kernel for output tile t
-            const int c = 32 * (mt0 + t) + m;
 #pragma unroll
-            for (int j = 0; j < TR_T; ++j) {
-                const int64_t p0 = pt0 + 32 * j;
-                float bv = -1.0f;
-                int bi = 0;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float y = fmaxf(__builtin_fmaf(acc[j][t][r], osc[t], osh[t]), 0.0f);
-                    if (y > bv) {
-                        bv = y;
-                        bi = (r & 3) + 8 * (r >> 2) + 4 * h;
-                    }
-                }
-                const float ov = __shfl_xor(bv, 32);
-                const int oi = __shfl_xor(bi, 32);
-                if (ov > bv || (ov == bv && oi < bi)) {
-                    bv = ov;
-                    bi = oi;
-                }
-                if (h == 0) {
-                    const int64_t s_idx = (int64_t)((uint32_t)p0 / (uint32_t)seg);
-                    const uint32_t in_seg = (uint32_t)(p0 - s_idx * seg) + (uint32_t)bi;
-                    const unsigned long long key = ((unsigned long long)__float_as_uint(bv) << 32) | (0xffffffffu - in_seg);
-                    atomicMax(packed + s_idx * c_out + c, key);
-                }
-            }
-        };
-        auto block = [&](const f32x16 (&X)[TR_T], auto base_c, auto last_c) {
-            constexpr int BASE = decltype(base_c)::value;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const f32x4 w = ring.slot[(BASE + i) % DAL3_PF];
-                ring.slot[(BASE + i) % DAL3_PF] = ring.fetch();
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-#pragma unroll
-                    for (int j = 0; j < TR_T; ++j) acc[j][i / 4] = mfma32(X[j][4 * (i % 4) + e], w[e], acc[j][i / 4]);
-                }
-                DAL3_SCHED_FENCE();
-                if (decltype(last_c)::value && i % 4 == 3) finish_tile(i / 4);
-            }
+            for (int j = 0; j < TR_T; ++j)
+                pool_candidate(acc[j][t], osc[t], osh[t], h, pt0 + 32 * j, seg, c_out, 32 * (mt0 + t) + m, packed);
         };
         auto kstep = [&](int kt, auto last_c) {
             constexpr bool LAST = decltype(last_c)::value;
             tr_load_x(xb, kt + 1, a, lda, prow, h);
             DAL3_SCHED_FENCE();
             if (act) tr_act_lds(xa.X, s_sc, s_sh, kt, h, relu_in);
-            block(xa.X, std::integral_constant<int, 0>{}, std::false_type{});
+            tr_ring_block<TR_T, TR_MTB, 0, true>(ring, xa.X, acc);
             tr_load_x(xa, LAST ? 0 : kt + 2, a, lda, LAST ? prow_n : prow, h);
             DAL3_SCHED_FENCE();
             if (act) tr_act_lds(xb.X, s_sc, s_sh, kt + 1, h, relu_in);
-            block(xb.X, std::integral_constant<int, 0>{}, last_c);
+            if (LAST)                                           // an output tile's epilogue behind its last MFMA
+                tr_ring_block<TR_T, TR_MTB, 0, true>(ring, xb.X, acc, [&](int i) {
+                    if (i % 4 == 3) finish_tile(i / 4);
+                });
+            else
+                tr_ring_block<TR_T, TR_MTB, 0, true>(ring, xb.X, acc);
         };
         if constexpr (KTC == 2) {
             kstep(0, std::true_type{});
@@ -1005,8 +877,8 @@ __global__ __launch_bounds__(256, 1) void tr_linear_pool_res_kernel(const float*
     uint32_t group = (blockIdx.x * 4u + wv) * gpw;
     if (group >= n_groups) return;
     const uint32_t group_end = min(group + gpw, n_groups);
-    WRingCyc ring;
-    ring.init(wpk, (uint32_t)c_out * 128u * 4u, lane);
+    WRing<DAL3_PF, true> ring;
+    ring.init(wpk, lane, (uint32_t)c_out * 128u * 4u);
     const int n_tiles = c_out / 32;
     auto flush = [&](int64_t s_idx) {                           // this wave's candidates of segment s_idx -> packed, row cleared
         for (int c = lane; c < c_out; c += 64) {
@@ -1061,14 +933,15 @@ __global__ __launch_bounds__(256, 1) void tr_linear_pool_res_kernel(const float*
             }
             asm volatile("" : "+v"(bv[0]), "+v"(bv[1]), "+v"(bi[0]), "+v"(bi[1]));
         };
-        // the pending tile's candidates leave: as packed keys (value bits, ~index: the larger key is the larger value, at
-        // equal values the earlier point) the two point tiles and the two lane halves meet by plain 64-bit maxima; the
+        // the pending tile's candidates leave: as keys (pool_key: the larger key is the larger value, at equal values
+        // the earlier point) the two point tiles and the two lane halves meet by plain 64-bit maxima; the
         // halves are exchanged by v_permlane32_swap (no LDS round trip), the lower half's lanes write
         auto epi_finish = [&](int ptile) {
             uint32_t kh = 0, kl = 0;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                const uint32_t vh = __float_as_uint(bv[j]), vl = 0xffffffffu - (in_seg0 + 32u * j + (uint32_t)bi[j]);
+                const unsigned long long k = pool_key(bv[j], in_seg0 + 32u * j + (uint32_t)bi[j]);
+                const uint32_t vh = (uint32_t)(k >> 32), vl = (uint32_t)k;      // (the key's words travel separately: 32-bit compares and swaps)
                 const bool up = j == 0 || vh > kh || (vh == kh && vl > kl);
                 kh = up ? vh : kh;
                 kl = up ? vl : kl;
@@ -1134,55 +1007,43 @@ __global__ __launch_bounds__(256, 1) void tr_linear_pool_res_kernel(const float*
     flush(cur_seg);
 }
 
+#ifndef TR_POOL_OCC
+#define TR_POOL_OCC 1                   // (at 2 the persistent kernel spills 120-170 registers)
+#endif
 hipError_t launch_tr_linear_pool(const float* a, int64_t M, int c_in, int64_t lda, const float* scale, const float* shift,
                                  int relu_in, const float* W, int64_t ldw, const float* bias, const float* out_scale,
                                  const float* out_shift, int64_t seg, int c_out, float* g, int32_t* arg, float* ws,
                                  unsigned long long* packed, hipStream_t s) {
     const int n_mblk = c_out / 128;
     const int64_t units = ((M + 32 * TR_T - 1) / (32 * TR_T)) * n_mblk;
-    const int64_t n = (int64_t)c_out * c_in, n_seg = M / seg;
+    const int64_t n_seg = M / seg;
     hipError_t e = launch_fill_words(packed, (size_t)n_seg * c_out * 2, 0u, s);
     if (e != hipSuccess) return e;
-#ifndef TR_POOL_RES
-#define TR_POOL_RES 1                   // 0: the 128-channel case through the per-block kernels too (A/B builds)
-#endif
-    if (TR_POOL_RES && c_in == 128 && M % 64 == 0 && seg % 64 == 0 && c_out % 64 == 0 && c_out <= TR_POOL_RES_MAX_COUT &&
-        M / 64 >= 1024 && M < (int64_t)1 << 31) {            // (point indices are taken as 32-bit values inside)
-        const uint32_t n_groups = (uint32_t)(M / 64), gpw = (n_groups + 1023u) / 1024u;
-        hipLaunchKernelGGL(tr_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, W, ldw, 0, c_out, c_in, 1, ws);
-        hipLaunchKernelGGL(tr_linear_pool_res_kernel, dim3((n_groups + 4u * gpw - 1u) / (4u * gpw)), dim3(256), 0, s, a, M, lda, scale, shift,
-                           relu_in, reinterpret_cast<const f32x4*>(ws), bias, out_scale, out_shift, seg, c_out, packed, n_groups, gpw);
-        const int64_t total = n_seg * c_out;
-        hipLaunchKernelGGL(tr_segmax_unpack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, packed, total, g, arg);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(tr_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, W, ldw, 0, c_out, c_in, TR_MTB, ws);
-#ifndef TR_POOL_OCC
-#define TR_POOL_OCC 1                   // (at 2 the persistent kernel spills 120-170 registers)
-#endif
+    const auto wpk = reinterpret_cast<const f32x4*>(ws);
     const unsigned pers_grid = 256u * TR_POOL_OCC;
-    if (TR_PERS && M % (32 * TR_T) == 0 && c_in % 64 == 0 && (4 * pers_grid) % (unsigned)n_mblk == 0 &&
-        units >= 2 * 4 * (int64_t)pers_grid && units < (int64_t)1 << 31) {
-        if (c_in == 64)
-            hipLaunchKernelGGL((tr_linear_pool_pers_kernel<TR_POOL_OCC, 2>), dim3(pers_grid), dim3(256), 0, s, a, M, c_in, lda, scale,
-                               shift, relu_in, reinterpret_cast<const f32x4*>(ws), bias, out_scale, out_shift, seg, c_out, packed,
-                               n_mblk, (uint32_t)units);
-        else
-            hipLaunchKernelGGL((tr_linear_pool_pers_kernel<TR_POOL_OCC, 0>), dim3(pers_grid), dim3(256), 0, s, a, M, c_in, lda, scale,
-                               shift, relu_in, reinterpret_cast<const f32x4*>(ws), bias, out_scale, out_shift, seg, c_out, packed,
-                               n_mblk, (uint32_t)units);
+    // (the 128-channel case through the per-block kernels instead: profiles/LEDGER_r04.md 2.1 item 9)
+    if (c_in == 128 && M % 64 == 0 && seg % 64 == 0 && c_out % 64 == 0 && c_out <= TR_POOL_RES_MAX_COUT && M / 64 >= 1024 &&
+        M < (int64_t)1 << 31) {                             // (point indices are taken as 32-bit values inside)
+        const uint32_t n_groups = (uint32_t)(M / 64), gpw = (n_groups + 1023u) / 1024u;
+        tr_pack(W, ldw, 0, c_out, c_in, 1, ws, s);
+        hipLaunchKernelGGL(tr_linear_pool_res_kernel, dim3((n_groups + 4u * gpw - 1u) / (4u * gpw)), dim3(256), 0, s, a, M, lda, scale, shift,
+                           relu_in, wpk, bias, out_scale, out_shift, seg, c_out, packed, n_groups, gpw);
     } else {
-        hipLaunchKernelGGL(tr_linear_pool_kernel, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, s, a, M, c_in, lda, scale, shift,
-                           relu_in, reinterpret_cast<const f32x4*>(ws), bias, out_scale, out_shift, seg, c_out, packed, n_mblk);
+        tr_pack(W, ldw, 0, c_out, c_in, TR_MTB, ws, s);
+        const auto pers = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(pers_grid), dim3(256), 0, s, a, M, c_in, lda, scale, shift, relu_in, wpk, bias, out_scale,
+                               out_shift, seg, c_out, packed, n_mblk, (uint32_t)units);
+        };
+        if (M % (32 * TR_T) != 0 || c_in % 64 != 0 || (4 * pers_grid) % (unsigned)n_mblk != 0 || units < 2 * 4 * (int64_t)pers_grid ||
+            units >= (int64_t)1 << 31)
+            hipLaunchKernelGGL(tr_linear_pool_kernel, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, s, a, M, c_in, lda, scale, shift,
+                               relu_in, wpk, bias, out_scale, out_shift, seg, c_out, packed, n_mblk);
+        else if (c_in == 64)
+            pers(tr_linear_pool_pers_kernel<TR_POOL_OCC, 2>);
+        else
+            pers(tr_linear_pool_pers_kernel<TR_POOL_OCC, 0>);
     }
-    const int64_t total = n_seg * c_out;
-    hipLaunchKernelGGL(tr_segmax_unpack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, packed, total, g, arg);
-    return hipGetLastError();
-}
-
-hipError_t launch_tr_segmax_unpack(const unsigned long long* packed, int64_t total, float* g, int32_t* arg, hipStream_t s) {
-    hipLaunchKernelGGL(tr_segmax_unpack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, packed, total, g, arg);
-    return hipGetLastError();
+    return launch_tr_segmax_unpack(packed, n_seg * c_out, g, arg, s);
 }
 
 // every layer with whole 32-channel tiles can take a ring path (which one depends on M: see launch_tr_linear)
@@ -1197,22 +1058,21 @@ static bool tr_linear_pers_ok(int64_t M, int c_in, int64_t seg, int c_out, int a
     const int n_mblk = c_out / (32 * MTB);
     const int64_t units = ((M + 32 * T - 1) / (32 * T)) * n_mblk;
     const unsigned pers_grid = 256u * OCC;                  // one workgroup per wave slot: 4 * pers_grid waves
-    return TR_PERS && MTB >= 2 && c_out % (32 * MTB) == 0 && !accumulate && M % (32 * T) == 0 &&
+    return MTB >= 2 && c_out % (32 * MTB) == 0 && !accumulate && M % (32 * T) == 0 &&
            (seg == 0 || seg % (32 * T) == 0) && c_in % 64 == 0 && (4 * pers_grid) % (unsigned)n_mblk == 0 &&
            units >= 2 * 4 * (int64_t)pers_grid && units < (int64_t)1 << 31;
 }
 
 template <int T, int MTB, int OCC>
-static void tr_linear_ring_launch(const float* a, int64_t M, int c_in, int64_t lda, const float* scale, const float* shift,
-                                  int relu_in, const float* W, int64_t ldw, int transpose_w, const float* bias, int64_t seg,
-                                  int c_out, float* z, int64_t ldz, int accumulate, float* ws, hipStream_t s, bool prepacked,
-                                  int red_mode = 0, const TrRed* red = nullptr) {
+struct TrTile {};                                           // names an instantiation of the ring kernels (deduced by the launcher below)
+template <int T, int MTB, int OCC>
+static void tr_linear_ring_launch(TrTile<T, MTB, OCC>, const float* a, int64_t M, int c_in, int64_t lda, const float* scale,
+                                  const float* shift, int relu_in, const float* W, int64_t ldw, int transpose_w, const float* bias,
+                                  int64_t seg, int c_out, float* z, int64_t ldz, int accumulate, float* ws, hipStream_t s,
+                                  bool prepacked, int red_mode = 0, const TrRed* red = nullptr) {
     const int n_mblk = c_out / (32 * MTB);
     const int64_t units = ((M + 32 * T - 1) / (32 * T)) * n_mblk;
-    const int64_t n = (int64_t)c_out * c_in;
-    if (!prepacked)                                          // (prepacked: ws already holds this layer in fragment order, MTB = this path's)
-        hipLaunchKernelGGL(tr_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, W, ldw, transpose_w, c_out, c_in,
-                           MTB, ws);
+    if (!prepacked) tr_pack(W, ldw, transpose_w, c_out, c_in, MTB, ws, s);   // (prepacked: ws already holds this layer in fragment order, MTB = this path's)
     const int KT = c_in / 32;
     const unsigned pers_grid = 256u * OCC;
     if constexpr (MTB >= 2) {
@@ -1302,18 +1162,18 @@ hipError_t launch_tr_linear(const float* a, int64_t M, int c_in, int64_t lda, co
                             int c_out, float* z, int64_t ldz, int accumulate, float* ws, hipStream_t s, bool prepacked) {
     bool small;
     const int mtb = tr_linear_path(M, c_in, seg, c_out, accumulate, ws != nullptr, scale != nullptr, &small);
+    const auto ring = [&](auto tile) {
+        tr_linear_ring_launch(tile, a, M, c_in, lda, scale, shift, relu_in, W, ldw, transpose_w, bias, seg, c_out, z, ldz, accumulate,
+                              ws, s, prepacked);
+    };
     if (small) {
-        tr_linear_ring_launch<1, 1, 2>(a, M, c_in, lda, scale, shift, relu_in, W, ldw, transpose_w, bias, seg, c_out, z, ldz,
-                                       accumulate, ws, s, prepacked);
+        ring(TrTile<1, 1, 2>{});
     } else if (mtb == TR_MTB) {
-        tr_linear_ring_launch<TR_T, TR_MTB, TR_RING_OCC>(a, M, c_in, lda, scale, shift, relu_in, W, ldw, transpose_w, bias, seg,
-                                                         c_out, z, ldz, accumulate, ws, s, prepacked);
+        ring(TrTile<TR_T, TR_MTB, TR_RING_OCC>{});
     } else if (mtb == 2) {
-        tr_linear_ring_launch<TR_T, 2, 2>(a, M, c_in, lda, scale, shift, relu_in, W, ldw, transpose_w, bias, seg, c_out, z, ldz,
-                                          accumulate, ws, s, prepacked);
+        ring(TrTile<TR_T, 2, 2>{});
     } else if (mtb == 1) {                                  // c_out = 32, 96, ...: one output tile per wave
-        tr_linear_ring_launch<TR_T, 1, 2>(a, M, c_in, lda, scale, shift, relu_in, W, ldw, transpose_w, bias, seg, c_out, z, ldz,
-                                          accumulate, ws, s, prepacked);
+        ring(TrTile<TR_T, 1, 2>{});
     } else {
         const int n_mblk = (c_out / 32 + TR_MTB - 1) / TR_MTB;
         const int64_t units = ((M + 32 * TR_T - 1) / (32 * TR_T)) * n_mblk;
@@ -1352,12 +1212,14 @@ static hipError_t launch_tr_linear_red(const float* a, int64_t M, int c_in, int6
                                        int c_out, float* z, int64_t ldz, float* ws, hipStream_t s, int red_mode, const TrRed& red) {
     bool small;
     const int mtb = tr_linear_path(M, c_in, seg, c_out, 0, true, scale != nullptr, &small);
+    const auto ring = [&](auto tile) {
+        tr_linear_ring_launch(tile, a, M, c_in, lda, scale, shift, relu_in, W, ldw, transpose_w, bias, seg, c_out, z, ldz, 0, ws, s,
+                              true, red_mode, &red);
+    };
     if (mtb == TR_MTB)
-        tr_linear_ring_launch<TR_T, TR_MTB, TR_RING_OCC>(a, M, c_in, lda, scale, shift, relu_in, W, ldw, transpose_w, bias, seg,
-                                                         c_out, z, ldz, 0, ws, s, true, red_mode, &red);
+        ring(TrTile<TR_T, TR_MTB, TR_RING_OCC>{});
     else
-        tr_linear_ring_launch<TR_T, 2, 2>(a, M, c_in, lda, scale, shift, relu_in, W, ldw, transpose_w, bias, seg, c_out, z, ldz,
-                                          0, ws, s, true, red_mode, &red);
+        ring(TrTile<TR_T, 2, 2>{});
     return hipGetLastError();
 }
 
@@ -1983,9 +1845,6 @@ __device__ __forceinline__ void wg_compute(WgBlock<MT, KT>& bk, f32x16 (&acc)[MT
 // one is consumed. The big layers run <4, 2, 2> (128 accumulator registers, 96 of operands); layers with at most 64
 // output channels would leave most of that idle and are bound by the latency of their loads instead (one 16-point block
 // in flight per wave: 93 us for 134 MB), so they run <2, 2, 4>: three blocks in flight in the same registers (55 us).
-#ifndef WG_COMBINE
-#define WG_COMBINE 1                    // 0: one partial sum per wave for every layer (A/B builds)
-#endif
 // COMB: the four waves of a workgroup take four consecutive slices of ONE tile block and add their tiles through LDS before
 // anything is written (see below). Not for the 4 x 4-tile variant: its waves then stop sharing operand rows in L1 and its
 // 256 accumulator registers spill around the exchange (A/B, both orders: 512 x 256 +2–3 %, the small layers −5…−10 %).
@@ -2179,7 +2038,7 @@ static int64_t wgrad_slice_pts(int64_t M, int c_out, int c_in) {
 }
 
 // partial sums in memory: one per workgroup (its four waves' slices added through LDS: tr_wgrad_kernel COMB) or one per wave
-static bool wgrad_comb(int c_out, int c_in) { return WG_COMBINE && (wgrad_small(c_out) || wgrad_kt(c_out, c_in) != 4); }
+static bool wgrad_comb(int c_out, int c_in) { return wgrad_small(c_out) || wgrad_kt(c_out, c_in) != 4; }
 static int64_t wgrad_out_slices(int64_t M, int64_t pts, bool comb) {
     const int64_t n = (M + pts - 1) / pts;
     return comb ? (n + 3) / 4 : n;
@@ -2238,11 +2097,10 @@ hipError_t launch_tr_wgrad(const float* dz, int64_t lddz, const float* a, int64_
     const bool comb = wgrad_comb(c_out, c_in);
     const int64_t n_slices = wgrad_out_slices(M, pts, comb);    // as they reach memory
     const dim3 grid(comb ? (unsigned)(n_slices * n_mb * n_kb) : (unsigned)((n_slices * n_mb * n_kb + 3) / 4));
-#ifndef WG_FULL
-#define WG_FULL 1                       // 0: the clamped-offset loads for every layer (A/B builds)
-#endif
+    // whole blocks take the compile-time tile offsets (FULL; against the clamped-offset loads: profiles/LEDGER_r04.md 2.1 item 10);
+    // wgrad_comb is the one place that decides COMB (both kinds of every shape stay instantiated)
     const auto go = [&](auto plain, auto full, int mt, int kt) {
-        if (WG_FULL && c_out % (32 * mt) == 0 && c_in % (32 * kt) == 0)
+        if (c_out % (32 * mt) == 0 && c_in % (32 * kt) == 0)
             hipLaunchKernelGGL(full, grid, dim3(256), 0, s, dz, lddz, a, lda, scale, shift, relu_in, M, c_out, c_in, part, n_mb, n_kb, pts);
         else
             hipLaunchKernelGGL(plain, grid, dim3(256), 0, s, dz, lddz, a, lda, scale, shift, relu_in, M, c_out, c_in, part, n_mb, n_kb, pts);
@@ -2706,7 +2564,7 @@ __global__ __launch_bounds__(256) void tr_conv1_wgrad_kernel(const float* __rest
         part[(int64_t)blockIdx.x * (C * KIN) + i] = t;       // = part[(blk * C' + i / 2) * 2 + i % 2], C' = C * KIN / 2
     }
 }
-static bool tr_conv1_ok(int c_in, int c_out) { return c_in >= 1 && c_in <= 8 && (c_out == 64 || c_out == 128); }
+bool tr_conv1_ok(int c_in, int c_out) { return c_in >= 1 && c_in <= 8 && (c_out == 64 || c_out == 128); }
 size_t tr_conv1_workspace_bytes(int64_t Mp, int c_out) {     // forward: pairs per channel; wgrad: c_out * 8 entries per block
     return (size_t)((Mp + TR_RED_ROWS - 1) / TR_RED_ROWS) * c_out * 8 * sizeof(double);
 }
@@ -2759,8 +2617,8 @@ hipError_t launch_tr_conv1_wgrad(const float* dz, int64_t lddz, const float* x, 
 // ---------------------------------------------------------------------------------------------- max over points
 // g[s][c] = max_p act(z[p][c]) over the `seg` points of segment s, with the index of the FIRST maximum for the
 // backward pass. Block = 64 channels x 4 row-lanes over one of SEG_CHUNKS chunks of the segment; candidates meet
-// through a packed 64-bit atomicMax: high word = the value's bit pattern (values are >= +0 after the ReLU, so the
-// bits order like the floats), low word = ~index, so that among equal values the smallest index wins.
+// through a 64-bit atomicMax over the keys of pool_key (dal3_device.h), under which the smallest index wins among
+// equal values.
 #define SEG_CHUNKS 16
 __global__ __launch_bounds__(256) void tr_segmax_kernel(const float* __restrict__ z, int64_t ldz, int64_t seg, int C,
                                                         const float* __restrict__ scale, const float* __restrict__ shift,
@@ -2785,7 +2643,7 @@ __global__ __launch_bounds__(256) void tr_segmax_kernel(const float* __restrict_
                 bi = p;
             }
         }
-        if (bv >= 0.0f) best = ((unsigned long long)__float_as_uint(bv) << 32) | (0xffffffffu - (uint32_t)bi);
+        if (bv >= 0.0f) best = pool_key(bv, (uint32_t)bi);
     }
     sm[rl][cl] = best;
     __syncthreads();
@@ -2800,9 +2658,11 @@ __global__ void tr_segmax_unpack_kernel(const unsigned long long* __restrict__ p
                                         int32_t* __restrict__ arg) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const unsigned long long b = packed[i];
-    g[i] = __uint_as_float((uint32_t)(b >> 32));
-    arg[i] = (int32_t)(0xffffffffu - (uint32_t)b);
+    pool_unkey(packed[i], g[i], arg[i]);
+}
+hipError_t launch_tr_segmax_unpack(const unsigned long long* packed, int64_t total, float* g, int32_t* arg, hipStream_t s) {
+    hipLaunchKernelGGL(tr_segmax_unpack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, packed, total, g, arg);
+    return hipGetLastError();
 }
 
 hipError_t launch_tr_segmax(const float* z, int64_t ldz, int64_t seg, int C, const float* scale, const float* shift,
@@ -2811,9 +2671,7 @@ hipError_t launch_tr_segmax(const float* z, int64_t ldz, int64_t seg, int C, con
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(tr_segmax_kernel, dim3((C + 63) / 64, (unsigned)(n_seg * SEG_CHUNKS)), dim3(256), 0, s, z, ldz, seg, C,
                        scale, shift, packed);
-    const int64_t total = n_seg * C;
-    hipLaunchKernelGGL(tr_segmax_unpack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, packed, total, g, arg);
-    return hipGetLastError();
+    return launch_tr_segmax_unpack(packed, n_seg * C, g, arg, s);
 }
 
 // per-segment column sums: out[s][c] = sum_{p in segment s} x[p][c]  (gradient of the decoder's per-crop term).
@@ -3412,7 +3270,7 @@ __global__ __launch_bounds__(256) void tr_pool_dw_kernel(const double* __restric
     dW[(int64_t)c * K + k] = (float)(A * m1k + Bc * (t + (double)b[c] * m1k) + (double)dWs[(int64_t)c * K + k]);
 }
 
-static bool tr_pool_k_ok(int K) { return K == 64 || K == 128 || K == 256; }
+bool tr_pool_k_ok(int K) { return K == 64 || K == 128 || K == 256; }
 hipError_t launch_tr_pool_moments(const float* W, int64_t ldw, const float* b, const double* m1, const float* Sc, int64_t M, int C,
                                   int K, double* sums, hipStream_t s) {
     if (!tr_pool_k_ok(K)) return hipErrorInvalidValue;

@@ -60,19 +60,14 @@ __device__ __forceinline__ void trx_split_quad(const f32x4& xq, const f32x4& scq
 //   input(n + 3) requested under k-step 8 of k-tile n  |  input(n + 1) read from its stage and split under the first 8 k-steps of
 //   k-tile n  |  MFMAs on split(n)  |  in a group's last k-tile: an out-tile's bias add + stores under the next tile's MFMAs.
 // LDS: ring 2 x 32 KiB | input stages 4 waves x 2 x 8 KiB | scale | shift (c_in floats each) | bias rows 2 x 256 floats.
-#ifdef TRX_ABL_NOSTORE_X3                                    // timing experiment only: the output is not written
-#define TRX_STORE(p, o) do { if ((o)[0] == 12345.678f) *reinterpret_cast<f32x4*>(p) = (o); } while (0)
-#else
-#define TRX_STORE(p, o) (*reinterpret_cast<f32x4*>(p) = (o))
-#endif
 #define TRX_STAGE_BYTES 8192
 #ifndef TRX_EARLY_REQUEST
 #define TRX_EARLY_REQUEST 1             // 0: request a stage's next k-tile at the open (A/B)
 #endif
 // POOL: the pooled layer's forward without its output tensor (tr_linear_pool_kernel of dal3_train.hip): the blocks run
 // with the MFMA operands swapped (points on the accumulator's registers, channels on its lanes), an out-tile's epilogue is
-// conv bias -> BN affine -> ReLU -> max over the tile's 32 points with the point index (first maximum wins) -> the packed
-// 64-bit atomicMax of tr_segmax_kernel; bias / out_scale / out_shift are per channel (LDS: 3 x 256 floats), z is unused.
+// conv bias, then pool_candidate of dal3_device.h (BN affine -> ReLU -> first maximum over the tile's 32 points -> the keyed
+// 64-bit atomicMax of tr_segmax_kernel); bias / out_scale / out_shift are per channel (LDS: 3 x 256 floats), z is unused.
 template <bool ACT, bool POOL>
 __global__ __launch_bounds__(256) void tr_linear_x3_kernel(const float* __restrict__ a, int64_t lda, int c_in,
                                                            const float* __restrict__ scale, const float* __restrict__ shift,
@@ -141,11 +136,7 @@ __global__ __launch_bounds__(256) void tr_linear_x3_kernel(const float* __restri
     // k-tile tau of group g's sequence (tau >= KT: a following group's; past the last group: a harmless re-read of g's own)
     const auto request = [&](int buf, int g, int tau) {
         const int gq = tau >= 2 * KT ? 2 : tau >= KT ? 1 : 0;
-#ifdef TRX_ABL_SAMEROWS                                       // timing experiment only: every group reads the first group's rows (L2 hits)
-        const int gt = (int)(blockIdx.x / (unsigned)n_mblk) + 0 * (g + gq);
-#else
         const int gt = g + gq * gstride < n_groups ? g + gq * gstride : g;
-#endif
         const char* src = reinterpret_cast<const char*>(a + ((int64_t)gt * 256 + wave * 64) * lda + 32 * (tau - gq * KT));
 #pragma unroll
         for (int j = 0; j < T; ++j)
@@ -186,30 +177,10 @@ __global__ __launch_bounds__(256) void tr_linear_x3_kernel(const float* __restri
     // POOL: the epilogue of out-tile t, point tile j of the group whose first row (this wave's) is `row`
     const auto pool_tile = [&](const f32x16& acc_tj, int t, int j, int64_t row) {
         const int c = 32 * t + m;                               // this lane's channel within the output block
-        const float bch = s_bias[c], osc = s_bias[256 + c], osh = s_bias[512 + c];
-        float bv = -1.0f;
-        int bi = 0;
+        f32x16 zt;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {                          // increasing point index: '>' keeps the first maximum
-            const float y = fmaxf(__builtin_fmaf(acc_tj[r] + bch, osc, osh), 0.0f);
-            if (y > bv) {
-                bv = y;
-                bi = (r & 3) + 8 * (r >> 2) + 4 * h;
-            }
-        }
-        const float ov = __shfl_xor(bv, 32);
-        const int oi = __shfl_xor(bi, 32);
-        if (ov > bv || (ov == bv && oi < bi)) {
-            bv = ov;
-            bi = oi;
-        }
-        if (h == 0) {
-            const int64_t p0 = row + 32 * j;
-            const int64_t s_idx = (int64_t)((uint32_t)p0 / (uint32_t)seg);
-            const uint32_t in_seg = (uint32_t)(p0 - s_idx * seg) + (uint32_t)bi;
-            const unsigned long long key = ((unsigned long long)__float_as_uint(bv) << 32) | (0xffffffffu - in_seg);
-            atomicMax(packed + s_idx * c_out + 32 * mt0 + c, key);
-        }
+        for (int r = 0; r < 16; ++r) zt[r] = acc_tj[r] + s_bias[c];
+        pool_candidate(zt, s_bias[256 + c], s_bias[512 + c], h, row + 32 * j, seg, c_out, 32 * mt0 + c, packed);
     };
     int par = 0;                                            // which bias buffer this group reads
     for (int g = g0; g < n_groups; g += gstride, par ^= 1) {
@@ -269,7 +240,7 @@ __global__ __launch_bounds__(256) void tr_linear_x3_kernel(const float* __restri
                                     o[1] = __builtin_fmaf(o[1], s_out, bprev[4 * q + 1]);
                                     o[2] = __builtin_fmaf(o[2], s_out, bprev[4 * q + 2]);
                                     o[3] = __builtin_fmaf(o[3], s_out, bprev[4 * q + 3]);
-                                    TRX_STORE(zp + 8 * q, o);
+                                    *reinterpret_cast<f32x4*>(zp + 8 * q) = o;
                                 }
                             }
                             if (s == 1) bprev = tile_from_channels(sb + 32 * t, h);      // (behind its last use: tile t's, for the next block)
@@ -325,7 +296,7 @@ __global__ __launch_bounds__(256) void tr_linear_x3_kernel(const float* __restri
                     o[1] = __builtin_fmaf(o[1], s_out, bprev[4 * q + 1]);
                     o[2] = __builtin_fmaf(o[2], s_out, bprev[4 * q + 2]);
                     o[3] = __builtin_fmaf(o[3], s_out, bprev[4 * q + 3]);
-                    TRX_STORE(zp + 8 * q, o);
+                    *reinterpret_cast<f32x4*>(zp + 8 * q) = o;
                 }
             }
         }

@@ -431,7 +431,10 @@ def test_persistent_linear_kernels_match_float64_and_the_one_unit_kernels_bitwis
                                             # the kernel with resident activations (c_in 128, >= 1024 groups of 64 points):
                                             # two and four groups per wave, waves that cross a segment, few channels
                                             (20, 3840, 128, 1024), (400, 192, 128, 256), (64, 4096, 128, 1024),
-                                            (18, 4096, 128, 128)])
+                                            (18, 4096, 128, 128),
+                                            # the generic-K persistent kernel (too few groups for the resident one, 2,048
+                                            # units): K = 128, and K = 256 with the K loop's middle rounds
+                                            (8, 2048, 128, 1024), (64, 512, 256, 512)])
 def test_fused_linear_pool_equals_linear_then_segmax_bitwise(B, N, c_in, c_out):
     """dal3_tr_linear_pool (conv -> BN -> ReLU -> max over each crop's points without writing the layer's output) must
     give the bits of dal3_tr_linear + dal3_tr_segmax: same g, same arg-max (first maximum), ties included"""

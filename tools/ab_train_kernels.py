@@ -50,8 +50,8 @@ def timed(fn, iters=5):
     return a.elapsed_time(b) / iters * 1e3
 
 
-def pool_case():
-    """dal3_tr_linear_pool at conv5's shape (128 -> 1024, 64 x 4096 points)"""
+def pool_case(entry, use):
+    """dal3_tr_linear_pool, or its f16x3 twin (the same argument list), at conv5's shape (128 -> 1024, 64 x 4096 points)"""
     ci, co, seg = 128, 1024, 4096
     a = torch.randn((M, ci), device=dev)
     W = torch.randn((co, ci), device=dev) * 0.1
@@ -60,24 +60,27 @@ def pool_case():
     osc, osh = torch.rand(co, device=dev) + 0.5, torch.randn(co, device=dev) * 0.1
     n_seg = M // seg
     out = []
-    res = {n: [] for n, _ in libs}
+    res = {n: [] for n, _ in use}
     for r in range(args.rounds):
-        for n, lib in libs:
+        for n, lib in use:
             g = torch.empty((n_seg, co), device=dev)
             arg = torch.empty((n_seg, co), dtype=torch.int32, device=dev)
             need = lib.dal3_tr_linear_pool_workspace_bytes(ci, co, n_seg)
             w2 = torch.empty(need, dtype=torch.uint8, device=dev)
-            f = lambda: lib.dal3_tr_linear_pool(hip.ptr(a), M, ci, ci, hip.ptr(sc), hip.ptr(sh), 1, hip.ptr(W), ci, hip.ptr(b),
-                                                hip.ptr(osc), hip.ptr(osh), seg, co, hip.ptr(g), hip.ptr(arg), hip.ptr(w2), need, st)
+            f = lambda: getattr(lib, entry)(hip.ptr(a), M, ci, ci, hip.ptr(sc), hip.ptr(sh), 1, hip.ptr(W), ci, hip.ptr(b),
+                                            hip.ptr(osc), hip.ptr(osh), seg, co, hip.ptr(g), hip.ptr(arg), hip.ptr(w2), need, st)
             res[n].append(timed(f))
             if r == 0:
                 out.append((g.clone(), arg.clone()))
     same = all(torch.equal(out[0][0], o[0]) and torch.equal(out[0][1], o[1]) for o in out)
-    print("linear_pool 128 -> 1024 + max: " + "  ".join(f"[{n}] {statistics.median(v):7.1f} us" for n, v in res.items()) + f"  (same bits: {same})")
+    print(f"{entry[8:]} 128 -> 1024 + max: " + "  ".join(f"[{n}] {statistics.median(v):7.1f} us" for n, v in res.items()) + f"  (same bits: {same})")
 
 
 if M % 4096 == 0 and M >= 8192:
-    pool_case()
+    pool_case("dal3_tr_linear_pool", libs)
+    x3 = [(n, lib) for n, lib in libs if hasattr(lib, "dal3_tr_linear_pool_x3_ok") and lib.dal3_tr_linear_pool_x3_ok(M, 128, 4096, 1024) == 1]
+    if x3:
+        pool_case("dal3_tr_linear_pool_x3", x3)
 for ci, co in shapes:
     a = torch.randn((M, ci), device=dev)
     W = torch.randn((co, ci), device=dev) * 0.1
