@@ -55,8 +55,7 @@ __device__ __forceinline__ bool inside_box_lds(const float* pl, float x, float y
     bool in = true;
 #pragma unroll
     for (int f = 0; f < 6; ++f) {
-        const float sgn = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(x, pl[f * 4 + 0]), __fmul_rn(y, pl[f * 4 + 1])),
-                                              __fmul_rn(z, pl[f * 4 + 2])), pl[f * 4 + 3]);
+        const float sgn = face_sign(x, y, z, pl[f * 4 + 0], pl[f * 4 + 1], pl[f * 4 + 2], pl[f * 4 + 3]);
         in = in && !ge_zero(sgn);
     }
     return in;
