@@ -69,7 +69,12 @@ static InsSegW ins_seg_walk(Cursor& c) {
     w.dw2c = c.take((size_t)512 * 256);
     w.dw3c = c.take((size_t)256 * 128);
     w.dw4c = c.take((size_t)128 * 128);
-    w.dec_flag = reinterpret_cast<const int32_t*>(c.take(64));
+    w.dw1c = c.take((size_t)(DEC_NULL_K + 1) * 64);
+    w.w1h = c.take4((size_t)16 * 2 * 2 * 256);
+    w.prn_pq = c.take(2 * 512);
+    w.dec_ident = reinterpret_cast<const uint32_t*>(c.take(DEC_PLAN_LD));
+    w.prn_flag = reinterpret_cast<const int32_t*>(c.take(64));
+    w.dec_flag = reinterpret_cast<const int32_t*>(c.take(64));      // (stays the blob's last section)
     return w;
 }
 
@@ -439,6 +444,10 @@ extern "C" int dal3_pack_weights(int head_kind, const dal3_layer* L, int n_layer
         HIP_TRY(launch_pack_dec_sparse(L[6], w.db2, mut(w.dw2c), reinterpret_cast<int32_t*>(const_cast<int32_t*>(w.dec_flag)), s));
         HIP_TRY(launch_pack_dec_queue(L[7], 256, w.db3, mut(w.dw3c), reinterpret_cast<int32_t*>(const_cast<int32_t*>(w.dec_flag)), s));
         HIP_TRY(launch_pack_dec_queue(L[8], 128, w.db4, mut(w.dw4c), reinterpret_cast<int32_t*>(const_cast<int32_t*>(w.dec_flag)), s));
+        // dconv1's crop-dead channels: the chain-ordered fp32 copy, the fp16 fragments and the bound's coefficients
+        HIP_TRY(launch_pack_weight_lp(L[5], DAL3_F16, 0, 0, 64, 16, 2, reinterpret_cast<uint16_t*>(mut(w.w1h)), s));
+        HIP_TRY(launch_pack_dec_prune(L[5], mut(w.dw1c), mut(w.prn_pq), const_cast<uint32_t*>(w.dec_ident),
+                                      const_cast<int32_t*>(w.prn_flag), s));
         return 0;
     }
     if (head_kind == DAL3_HEAD_DYNAMIC_BOX_EST) {
@@ -507,7 +516,7 @@ static int check_bcn(const dal3_bcn& t, const char* what) {
     if (t.dtype != DAL3_F32 && t.dtype != DAL3_BF16 && t.dtype != DAL3_F16)
         return fail(DAL3_EINVAL, "%s: storage dtype %d is none of DAL3_F32 / DAL3_BF16 / DAL3_F16", what, t.dtype);
     if (t.dtype != DAL3_F32 && (reinterpret_cast<uintptr_t>(t.data) & 1)) return fail(DAL3_EINVAL, "%s: 16-bit data must be 2-byte aligned", what);
-    if (t.flags & ~(DAL3_BCN_NO_SMALL_JOB_KERNELS | DAL3_BCN_NO_WORKLIST | DAL3_BCN_NO_LDS_SAMPLER)) return fail(DAL3_EINVAL, "%s: unknown bits in flags (%d)", what, t.flags);
+    if (t.flags & ~(DAL3_BCN_NO_SMALL_JOB_KERNELS | DAL3_BCN_NO_WORKLIST | DAL3_BCN_NO_LDS_SAMPLER | DAL3_BCN_NO_DEC_PLAN)) return fail(DAL3_EINVAL, "%s: unknown bits in flags (%d)", what, t.flags);
     return 0;
 }
 
@@ -527,17 +536,33 @@ static int check_extent(int64_t B, int64_t N, const char* what) {
 }
 
 // ---------------------------------------------------------------------------------- ins_seg
-struct InsSegWs { float* g; float* gb; };
+// prune: the encoder's maxima of dconv1a's fp16 scores; plan_*: the decoder's plan (dal3_kernels.h: DecPlan)
+struct InsSegWs { float* g; float* gb; uint32_t* prune; uint32_t* plan_k; float* plan_gbc; int32_t* plan_nch; };
 static InsSegWs carve_ins_seg(Carver& c, int B) {
     InsSegWs w;
     w.g = c.take<float>((size_t)B * 1024);
     w.gb = c.take<float>((size_t)B * 512);
+    w.prune = c.take<uint32_t>((size_t)B * 513);
+    w.plan_k = c.take<uint32_t>((size_t)B * DEC_PLAN_LD);
+    w.plan_gbc = c.take<float>((size_t)B * 512);
+    w.plan_nch = c.take<int32_t>((size_t)B);
     return w;
 }
 extern "C" size_t dal3_ins_seg_workspace_bytes(int B) {
     Carver c(nullptr, 0);
     carve_ins_seg(c, B);
     return c.off;
+}
+
+extern "C" int dal3_ins_seg_plan_layout(int B, size_t off[4], int* min_dead) {
+    if (B <= 0 || !off) return fail(DAL3_EINVAL, "ins_seg_plan_layout: bad argument");
+    char* const origin = reinterpret_cast<char*>(uintptr_t(4096));      // (a base that is not NULL: the carver then hands out addresses)
+    Carver c(origin, ~size_t(0));
+    const InsSegWs w = carve_ins_seg(c, B);
+    off[0] = reinterpret_cast<char*>(w.prune) - origin, off[1] = reinterpret_cast<char*>(w.plan_k) - origin;
+    off[2] = reinterpret_cast<char*>(w.plan_gbc) - origin, off[3] = reinterpret_cast<char*>(w.plan_nch) - origin;
+    if (min_dead) *min_dead = DAL3_DEC_MIN_DEAD;
+    return 0;
 }
 
 static int check_dtype(int dtype) {
@@ -557,10 +582,16 @@ static int ins_seg_run(const void* packed, int dtype, int c_in, const dal3_bcn& 
     HIP_TRY(launch_nonfinite_rows(x, B, N, c_in, ws.g, 1024, s));      // g = 0 (NaN for a crop with a non-finite coordinate)
     if (dtype == DAL3_F32) {
         const InsSegW w = ins_seg_view(static_cast<const float*>(packed), c_in);
-        HIP_TRY(launch_ins_seg_encode(w, x, c_in, B, N, ws.g, s));
+        // the screened encoder and the compacted decoder both run: dconv1's channels that are dead for a whole crop are
+        // proved so from the encoder's fp16 maxima and the decoder leaves them out (DESIGN.md "Crop-dead channels of dconv1")
+        const bool plan = dec_plan_route(x.flags, B, N);
+        if (plan) HIP_TRY(hipMemsetAsync(ws.prune, 0, (size_t)B * 513 * sizeof(uint32_t), s));
+        HIP_TRY(launch_ins_seg_encode(w, x, c_in, B, N, ws.g, s, plan ? ws.prune : nullptr));
         // per-crop part of dconv1: gb = W1g' . g + b1'   (static_model.py:286-289 without the repeat+cat)
         HIP_TRY(launch_fc(w.dw1g, w.db1, ws.g, 1024, ws.gb, 512, B, 1024, 512, 0, s));
-        HIP_TRY(launch_ins_seg_decode(w, x, c_in, B, N, ws.gb, logits, mask, s));
+        if (plan) HIP_TRY(launch_dec_plan(w, ws.gb, ws.prune, B, ws.plan_k, ws.plan_gbc, ws.plan_nch, s));
+        HIP_TRY(launch_ins_seg_decode(w, x, c_in, B, N, ws.gb, logits, mask, s,
+                                      plan ? DecPlan{ws.plan_k, ws.plan_gbc, ws.plan_nch} : DecPlan{nullptr, nullptr, nullptr}));
     } else if (dtype == DAL3_F16X3) {
         const InsSegX3W w = ins_seg_x3_view(packed);
         HIP_TRY(launch_ins_seg_encode_x3(w, x, c_in, B, N, ws.g, s));

@@ -61,9 +61,77 @@ extern "C" int dal3_debug_screen_counts(unsigned long long* out, int reset) {
 #define SCR_COUNT(k, v)
 #endif
 
+// The bound of the decoder's plan (DESIGN.md "Crop-dead channels of dconv1"), taken while conv2's output x2 is in
+// registers: the wave's maximum over its points of dconv1a's fp16 score, per channel, into the workgroup's key table s_u
+// (prune_key: the scores are signed), and X >= ||x2(p)||_2 of every point into s_x. The transposed orientation of the
+// conv5 sweep: a lane is a channel, its registers are the points. A wave with an activation beyond fp16's range (or a
+// blob whose dconv1a weights are beyond it) gives X = +Inf and no scores: its crop gets no plan.
+// (Measured and not kept, profiles/LEDGER_r14.md: the epilogue cut into slices behind the next block's fragments with the
+// ring started in front of conv2, and both lane halves sending their maxima without the exchange: each 0.08 ms slower.)
+template <int T>
+__device__ __forceinline__ void dec_prune_sweep(const InsSegW& w, const f32x16 (&x2)[T][2], uint32_t* s_u, int* s_x, int lane) {
+    int xm = 0;
+    float x2max = 0.0f;
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+        float ss = 0.0f;
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int v = __float_as_int(x2[j][kt][r]);         // >= +0 after the ReLU; a NaN pattern lies above the limit
+                xm = v > xm ? v : xm;
+                ss = fmaf(x2[j][kt][r], x2[j][kt][r], ss);
+            }
+        }
+        ss += __shfl_xor(ss, 32);
+        x2max = __builtin_fmaxf(x2max, ss);
+    }
+#pragma unroll
+    for (int d = 16; d >= 1; d >>= 1) x2max = __builtin_fmaxf(x2max, __shfl_xor(x2max, d));
+    const bool over = *w.prn_flag != 0 || __builtin_amdgcn_ballot_w64(xm > SCR_XMAX_BITS) != 0;
+    const float X = sqrtf(x2max) * (1.0f + 0x1p-16f);              // (margin: 64 roundings of the sum, the root)
+    if (lane == 0) atomicMax(s_x, over ? 0x7F800000 : __float_as_int(X));
+    if (over) return;
+    ActTile<FP16> xh[T][2];
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt) xh[j][kt] = pack_relu<FP16>(x2[j][kt]);
+    }
+    WRing<4> r16;
+    r16.init(w.w1h, lane);                             // [out-tile][kt][s]: a block's 4 fragments are fetched a block ahead
+    f32x16 acc[2][T];
+    auto fold = [&](const f32x16 (&a)[T], int mt) {    // the block's maxima -> the table
+        float m = a[0][0];
+#pragma unroll
+        for (int j = 0; j < T; ++j) {
+#pragma unroll
+            for (int r = (j == 0 ? 1 : 0); r < 16; ++r) m = __builtin_fmaxf(m, a[j][r]);
+        }
+        m = __builtin_fmaxf(m, __shfl_xor(m, 32));
+        if (lane < 32) atomicMax(&s_u[32 * mt + lane], prune_key(__float_as_uint(m)));
+    };
+#pragma unroll
+    for (int mt = 0; mt < 16; ++mt) {
+#pragma unroll
+        for (int j = 0; j < T; ++j) acc[mt & 1][j] = f32x16{};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const f16x8_t a = __builtin_bit_cast(f16x8_t, r16.slot[i]);
+            r16.slot[i] = r16.fetch();
+#pragma unroll
+            for (int j = 0; j < T; ++j) acc[mt & 1][j] = FP16::mfma(xh[j][i >> 1].k[i & 1], a, acc[mt & 1][j]);
+        }
+        if (mt > 0) fold(acc[(mt - 1) & 1], mt - 1);   // (behind this block's MFMAs)
+    }
+    fold(acc[1], 15);
+}
+
 template <int PASS, int T>
 __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_encode_screen_kernel(InsSegW w, BCN pts, int c_in, int n_pts,
-                                                                                  int tiles_per_item, float* __restrict__ g) {
+                                                                                  int tiles_per_item, float* __restrict__ g,
+                                                                                  uint32_t* __restrict__ prune) {
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int h = lane >> 5;
@@ -78,10 +146,12 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_encode_screen_kern
     __shared__ uint32_t s_list[PASS == 1 ? DAL3_WG_WAVES * T * SCR_CAP : 1];
     // per wave: the sweep's parked hit words (32 blocks x 64 lanes), then the recompute's staged weight rows
     __shared__ __attribute__((aligned(16))) uint32_t s_stage[PASS == 1 ? DAL3_WG_WAVES * 64 * SCR_STAGE_LD : 4];
+    __shared__ uint32_t s_u[PASS == 1 ? 512 : 1];      // pass B with `prune`: the workgroup's keys of dconv1a's score maxima
+    __shared__ int s_xn[1];                            // ... and the bits of its X
     int* gi = reinterpret_cast<int*>(g + b * 1024);
     // static LDS: the four tables, the waves' x4 copies, candidate lists and stages. One workgroup per CU by LDS alone
     // (the kernel holds one wave per SIMD by registers anyway). Too large: lower SCR_CAP, DAL3_WG_WAVES or DAL3_ENC_T.
-    static_assert(20 * 1024 + DAL3_WG_WAVES * (32 * SCR_XLD * 4 + T * SCR_CAP * 4 + 64 * SCR_STAGE_LD * 4) <= 160 * 1024,
+    static_assert(22 * 1024 + 64 + DAL3_WG_WAVES * (32 * SCR_XLD * 4 + T * SCR_CAP * 4 + 64 * SCR_STAGE_LD * 4) <= 160 * 1024,
                   "pass B's LDS exceeds a CU's 160 KiB: lower SCR_CAP, DAL3_WG_WAVES or DAL3_ENC_T");
     static_assert(32 * 64 <= 64 * SCR_STAGE_LD, "a wave's stage holds the hit words of conv5's 32 blocks");
     // conv5 not finite in fp16 (the blob's flag): no wave can be screened, pass A has no bound to give and pass B is the
@@ -97,7 +167,9 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_encode_screen_kern
         // (other workgroups of the crop may be raising g already: any value read here is <= the final one, which is all
         // the threshold needs)
         if (PASS == 1) s_g[i] = __int_as_float(__hip_atomic_load(gi + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        if (PASS == 1 && i < 512) s_u[i] = 0;
     }
+    if (threadIdx.x == 0) s_xn[0] = 0;
     __syncthreads();
     if (n0 < n_pts) {                                  // (no early return: every wave meets the barrier below)
         WRing<DAL3_PF> ring;
@@ -108,6 +180,7 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_encode_screen_kern
         f32x16 x1[T][2], x2[T][2], x3[T][2], x4[T][4];
         first_layer<2, 2, T>(w.w1, w.b1, in, x1, lane);
         mlp_layer_ring<2, 2, T>(ring, w.b2, w.b3, bias, x1, x2, lane);
+        if (PASS == 1 && prune) dec_prune_sweep<T>(w, x2, s_u, s_xn, lane);
         mlp_layer_ring<2, 2, T>(ring, w.b3, w.b4, bias, x2, x3, lane);
         mlp_layer_ring<2, 4, T>(ring, w.b4, w.b4, bias, x3, x4, lane);
         SCR_COUNT(0, 1);
@@ -294,18 +367,26 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_encode_screen_kern
         const int v = s_max[c];
         if (v > 0) atomicMax(gi + c, v);
     }
+    if (PASS == 1 && prune) {                          // one global atomic per channel and workgroup, as for g
+        uint32_t* pu = prune + b * 513;
+        for (int c = threadIdx.x; c < 512; c += 64 * DAL3_WG_WAVES) {
+            const uint32_t v = s_u[c];
+            if (v > 0) atomicMax(pu + c, v);
+        }
+        if (threadIdx.x == 0 && s_xn[0] > 0) atomicMax(reinterpret_cast<int*>(pu + 512), s_xn[0]);
+    }
 }
 
-hipError_t launch_ins_seg_encode_screen(const InsSegW& w, BCN pts, int c_in, int B, int N, float* g, hipStream_t s) {
+hipError_t launch_ins_seg_encode_screen(const InsSegW& w, BCN pts, int c_in, int B, int N, float* g, hipStream_t s, uint32_t* prune) {
     constexpr int T = DAL3_ENC_T;
     const int tpi = (N + 32 * DAL3_WG_WAVES * T - 1) / (32 * DAL3_WG_WAVES * T);
     // pass A: ceil(slots / stride) visited wave-slots per crop, DAL3_WG_WAVES of them per workgroup
     const int slots = (N + 32 * T - 1) / (32 * T);
     const int tpi_a = ((slots + DAL3_SCR_A_STRIDE - 1) / DAL3_SCR_A_STRIDE + DAL3_WG_WAVES - 1) / DAL3_WG_WAVES;
     const dim3 grid_a((unsigned)((int64_t)B * tpi_a)), grid((unsigned)((int64_t)B * tpi)), block(64 * DAL3_WG_WAVES);
-    hipLaunchKernelGGL((ins_seg_encode_screen_kernel<0, T>), grid_a, block, 0, s, w, pts, c_in, N, tpi_a, g);
+    hipLaunchKernelGGL((ins_seg_encode_screen_kernel<0, T>), grid_a, block, 0, s, w, pts, c_in, N, tpi_a, g, nullptr);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((ins_seg_encode_screen_kernel<1, T>), grid, block, 0, s, w, pts, c_in, N, tpi, g);
+    hipLaunchKernelGGL((ins_seg_encode_screen_kernel<1, T>), grid, block, 0, s, w, pts, c_in, N, tpi, g, prune);
     return hipGetLastError();
 }

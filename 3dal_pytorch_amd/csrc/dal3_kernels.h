@@ -85,6 +85,33 @@ struct InsSegW {
     const float* dw4c;        // k 0..127
     const int32_t* dec_flag;  // nonzero: a folded dconv2 / dconv3 / dconv4 weight is not finite or one of their folded biases is -0
                               // -> dense path only
+    // dconv1's channels proved dead for a whole crop (DESIGN.md "Crop-dead channels of dconv1")
+    const float* dw1c;        // dconv1a folded, [chain index k 0..512][k-half h][32]: the 32 floats a lane of half h holds of row
+                              // 32 c + tile_chan(r, h) (k = 32 c + 2 r + h) in the dense fragments, float 4 i + e = column
+                              // 32 (i / 4) + tile_chan(4 (i % 4) + e, h); row 512, the null channel, is zeros
+    const f32x4* w1h;         // dconv1a as fp16 MFMA fragments [16 out-tiles][2 kt][2 s] of 1 KiB (the layout of w5h)
+    const float* prn_pq;      // (512,2): |fp16 score - (fp32 chain from gb - gb)| <= X * P_c + Q_c + 2 K 2^-24 |gb| for ||x2||_2 <= X
+    const uint32_t* dec_ident;   // DEC_PLAN_LD words: the plan of a crop with nothing flagged (k, then the null channel)
+    const int32_t* prn_flag;  // nonzero: a folded dconv1a weight is not finite in fp16 -> no crop has a plan
+};
+// dead dconv1 channels from which a crop's tiles take the decoder's compacted body (dal3_pointmlp.hip, where it is measured)
+#ifndef DAL3_DEC_MIN_DEAD
+#define DAL3_DEC_MIN_DEAD 64
+#endif
+// a plan's chunk count is rounded up to a multiple of this: 2 (the decoder's chunk loop goes in pairs), or 4 = DAL3_DEC_GROUP
+// for A/B builds (no shorter last group; measured slower, profiles/LEDGER_r14.md)
+#ifndef DAL3_DEC_PLAN_ROUND
+#define DAL3_DEC_PLAN_ROUND 2
+#endif
+// A crop's dconv1 plan (dec_plan_kernel, dal3_misc.hip): its unflagged chain indices in ascending order, padded with the
+// null channel DEC_NULL_K; its term gb gathered to match, in the row order tile_from_channels reads (-1 for the null
+// channel); its chunk count (even, >= 2; 0: the crop has no plan and the decoder decides on gb as without one).
+#define DEC_PLAN_LD 640       // 16 chunks + the four the decoder's loop reads ahead
+#define DEC_NULL_K 512
+struct DecPlan {
+    const uint32_t* k;        // (B, DEC_PLAN_LD)
+    const float* gbc;         // (B, 512)
+    const int32_t* nch;       // (B)
 };
 enum {                        // stream geometry in fragments of 256 floats
     ENC_W2 = 0, ENC_W3 = 16, ENC_W4 = 32, ENC_W5 = 64, ENC_FRAGS = 64 + 512,
@@ -212,14 +239,22 @@ FcW fc_head_view(const float* base);
 void point_head_dims(int head_kind, int* c_in, int* ks, int c[4], int* n_fc, int fc_in[3], int fc_out[3]);
 
 // ---- launchers (all asynchronous on s)
-hipError_t launch_ins_seg_encode(const InsSegW& w, BCN pts, int c_in, int B, int N, float* g, hipStream_t s);
-hipError_t launch_ins_seg_encode_screen(const InsSegW& w, BCN pts, int c_in, int B, int N, float* g, hipStream_t s);
+// prune (optional, (B, 513) words, ZERO-FILLED by the caller): the screened encoder leaves there, per crop, the keys of
+// U_c = max_p s16(c,p) of dconv1a's fp16 scores (prune_key) and, in word 512, the bits of X = max_p ||x2(p)||_2 (+Inf:
+// the crop has no bound). Written only where dec_plan_route() says the screened encoder runs.
+hipError_t launch_ins_seg_encode(const InsSegW& w, BCN pts, int c_in, int B, int N, float* g, hipStream_t s, uint32_t* prune = nullptr);
+hipError_t launch_ins_seg_encode_screen(const InsSegW& w, BCN pts, int c_in, int B, int N, float* g, hipStream_t s, uint32_t* prune);
+bool dec_plan_route(int flags, int B, int N);
+hipError_t launch_pack_dec_prune(const dal3_layer& L, float* dw1c, float* pq, uint32_t* ident, int32_t* flag, hipStream_t s);
+// plan_k (B, DEC_PLAN_LD), plan_gbc (B, 512), plan_nch (B): see DecPlan
+hipError_t launch_dec_plan(const InsSegW& w, const float* gb, const uint32_t* prune, int B, uint32_t* plan_k, float* plan_gbc,
+                           int32_t* plan_nch, hipStream_t s);
 hipError_t launch_pack_enc_screen(const dal3_layer& L, float* pq, int32_t* flag, hipStream_t s);
 // db2: the layer's packed bias (written earlier on s)
 hipError_t launch_pack_dec_sparse(const dal3_layer& L, const float* db2, float* dw2c, int32_t* flag, hipStream_t s);
 hipError_t launch_pack_dec_queue(const dal3_layer& L, int c_in, const float* bias, float* wcopy, int32_t* flag, hipStream_t s);
 hipError_t launch_ins_seg_decode(const InsSegW& w, BCN pts, int c_in, int B, int N, const float* gbias,
-                                 float* logits, uint8_t* mask, hipStream_t s);
+                                 float* logits, uint8_t* mask, hipStream_t s, DecPlan plan = DecPlan{nullptr, nullptr, nullptr});
 // distinct (B) i32 or NULL: only the first distinct[b] points of item b are distinct (the rest duplicate them)
 // feat (B,512) need NOT be initialised: the launchers zero it (NaN rows for items with non-finite inputs) themselves.
 // worklist (optional, point_head_worklist_bytes(B, M) bytes of device scratch): lets the throughput family run as

@@ -2,6 +2,7 @@
 // device-side mask compaction + object-point sampling, the two-stage re-centring, box decode.
 #include "dal3_device.h"
 #include "dal3_kernels.h"
+#include "dal3_screen.h"
 
 #define BN_EPS 1e-5f
 
@@ -201,6 +202,92 @@ __global__ void pack_dec_sparse_kernel(dal3_layer L, const float* __restrict__ d
 }
 hipError_t launch_pack_dec_sparse(const dal3_layer& L, const float* db2, float* dw2c, int32_t* flag, hipStream_t s) {
     hipLaunchKernelGGL(pack_dec_sparse_kernel, dim3(512), dim3(256), 0, s, L, db2, dw2c, flag);
+    return hipGetLastError();
+}
+
+// dconv1's crop-dead channels (DESIGN.md "Crop-dead channels of dconv1"): the chain-ordered copy of dconv1a that the compacted
+// decoder reads its A operands from (InsSegW::dw1c), the plan of a crop with nothing flagged, and the coefficients of
+//   |s16(c,p) - (chain32(c,p) - gb_c)| <= X P_c + Q_c + 2 K 2^-24 |gb_c|,   K = 64,
+//   P_c = kappa ||w_c||_2 + 2^-24 sqrt(64),  Q_c = 2^-24 ||w_c||_1 + 2^-40,  kappa = 1.02 * 2^-10 + 64 * 2^-23,
+// in double with the 1e-6 margin, as pack_enc_screen_kernel. flag: a weight that fp16 cannot hold.
+__global__ void pack_dec_prune_kernel(dal3_layer L, float* __restrict__ dw1c, float* __restrict__ pq, uint32_t* __restrict__ ident,
+                                      int32_t* __restrict__ flag) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < (DEC_NULL_K + 1) * 64) {
+        const int k = i >> 6, hh = (i >> 5) & 1, f = i & 31;
+        const int ch = 32 * (k >> 5) + tile_chan((k & 31) >> 1, k & 1);
+        dw1c[i] = k < DEC_NULL_K ? folded_w(L, ch, 32 * (f >> 4) + tile_chan(f & 15, hh), 0, 64) : 0.0f;
+    }
+    if (i < DEC_PLAN_LD) ident[i] = i < DEC_NULL_K ? (uint32_t)i : (uint32_t)DEC_NULL_K;
+    if (i >= 512) return;
+    double s2 = 0.0, s1 = 0.0;
+    bool bad = false;
+    for (int k = 0; k < 64; ++k) {
+        const float v = folded_w(L, i, k, 0, 64);
+        bad |= !(fabsf(v) < 65504.0f);
+        s2 += (double)v * (double)v;
+        s1 += fabs((double)v);
+    }
+    const double kappa = 1.02 * 0x1p-10 + 64.0 * 0x1p-23;
+    pq[2 * i] = (float)((kappa * sqrt(s2) + 0x1p-24 * 8.0) * (1.0 + 1e-6));
+    pq[2 * i + 1] = (float)((0x1p-24 * s1 + 0x1p-40) * (1.0 + 1e-6));
+    if (bad) atomicOr(flag, 1);
+}
+hipError_t launch_pack_dec_prune(const dal3_layer& L, float* dw1c, float* pq, uint32_t* ident, int32_t* flag, hipStream_t s) {
+    hipLaunchKernelGGL(pack_dec_prune_kernel, dim3(((DEC_NULL_K + 1) * 64 + 255) / 256), dim3(256), 0, s, L, dw1c, pq, ident, flag);
+    return hipGetLastError();
+}
+
+// The plan of one crop, one workgroup, thread = chain index k (channel 32 c + tile_chan(r, h), k = 32 c + 2 r + h).
+// Channel c is FLAGGED iff gb_c + U_c + E_c < 0 with E_c >= X P_c + Q_c + 2^-17 |gb_c|: then the decoder's chain from gb_c is
+// negative at every point of the crop and its ReLU is +0. Every rounding goes against flagging: t = fl(gb + U) is off by at
+// most 2^-24 (|gb| + |U|), which the 2^-22 term covers; E's own evaluation (non-negative terms only) is inside the 2^-20
+// margin; fl(t + E) < 0 iff t + E < 0. A NaN anywhere (a crop with a non-finite coordinate has gb = NaN, a crop without a
+// bound X = +Inf) compares false: nothing flagged. A crop with fewer than DAL3_DEC_MIN_DEAD flagged channels gets nch = 0.
+__global__ __launch_bounds__(512) void dec_plan_kernel(const float* __restrict__ gb, const uint32_t* __restrict__ prune,
+                                                       const float* __restrict__ pq, const int32_t* __restrict__ prn_flag,
+                                                       const int32_t* __restrict__ dec_flag, uint32_t* __restrict__ plan_k,
+                                                       float* __restrict__ plan_gbc, int32_t* __restrict__ plan_nch) {
+    __shared__ uint32_t s_k[DEC_PLAN_LD];
+    __shared__ uint32_t s_cnt[8];
+    const int64_t b = blockIdx.x;
+    const int k = threadIdx.x, lane = k & 63, wv = k >> 6;
+    const int ch = 32 * (k >> 5) + tile_chan((k & 31) >> 1, k & 1);
+    const float* gbb = gb + b * 512;
+    const uint32_t* pu = prune + b * 513;
+    const float g = gbb[ch];
+    const uint32_t key = pu[ch];
+    const float U = __uint_as_float(prune_unkey(key)), X = __uint_as_float(pu[512]);
+    float E = fmaf(X, pq[2 * ch], pq[2 * ch + 1]);
+    E = fmaf(fabsf(g), 0x1p-17f, E);
+    const float t = g + U;
+    E = fmaf(fabsf(g) + fabsf(U), 0x1p-22f, E);
+    E = fmaf(E, 0x1p-20f, E);
+    const bool flagged = *prn_flag == 0 && *dec_flag == 0 && key != 0u && t + E < 0.0f;
+    const uint64_t bal = __ballot(!flagged);
+    if (lane == 0) s_cnt[wv] = (uint32_t)__popcll(bal);
+    for (int i = k; i < DEC_PLAN_LD; i += 512) s_k[i] = DEC_NULL_K;
+    __syncthreads();
+    uint32_t below = 0, n_live = 0;
+    for (int i = 0; i < 8; ++i) {
+        below += i < wv ? s_cnt[i] : 0u;
+        n_live += s_cnt[i];
+    }
+    if (!flagged) s_k[below + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = (uint32_t)k;
+    __syncthreads();
+    const int nch = 512 - (int)n_live < DAL3_DEC_MIN_DEAD
+                        ? 0 : max(2, (((int)n_live + 31) / 32 + DAL3_DEC_PLAN_ROUND - 1) & ~(DAL3_DEC_PLAN_ROUND - 1));
+    if (k == 0) plan_nch[b] = nch;
+    for (int i = k; i < DEC_PLAN_LD; i += 512) plan_k[b * DEC_PLAN_LD + i] = s_k[i];
+    // gb gathered in the row order of tile_from_channels: row m of chunk j holds list entry 32 j + 2 r + h, m = tile_chan(r, h)
+    const int m = k & 31, hh = (m >> 2) & 1, r = (m & 3) + 4 * (m >> 3);
+    const uint32_t kk = s_k[32 * (k >> 5) + 2 * r + hh];
+    plan_gbc[b * 512 + k] = kk < DEC_NULL_K ? gbb[32 * (kk >> 5) + tile_chan((kk & 31) >> 1, kk & 1)] : -1.0f;
+}
+hipError_t launch_dec_plan(const InsSegW& w, const float* gb, const uint32_t* prune, int B, uint32_t* plan_k, float* plan_gbc,
+                           int32_t* plan_nch, hipStream_t s) {
+    hipLaunchKernelGGL(dec_plan_kernel, dim3((unsigned)B), dim3(512), 0, s, gb, prune, w.prn_pq, w.prn_flag, w.dec_flag, plan_k,
+                       plan_gbc, plan_nch);
     return hipGetLastError();
 }
 

@@ -14,6 +14,8 @@
 // fragments shared by all waves of the chip.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "dal3_device.h"
 #include "dal3_kernels.h"
 
@@ -104,9 +106,8 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_encode_kernel(InsS
 // groups overwrite the rows of this one, however many of them are entirely dead — and the entry goes first in the next
 // list; the very last one is paired with the row of zeros. A fully live group is 16 DAL3_DEC_GROUP k-steps in the dense
 // order; there is one route only.
-// The weight ring of this body never holds a dense dconv2 fragment: before every dconv1 block the stream offset steps
-// over the 32 fragments of the dconv2 chunk that lie between two dconv1 chunks in dec_stream, so the block's eight
-// fetches are the next dconv1 chunk.
+// The weight ring of this body carries conv2 only: dconv1's A operands come from the chain-ordered copy dw1c, row by row
+// of the crop's plan (see ins_seg_decode_tile), into the ring's eight slots.
 // lanes whose post-ReLU bits are not +0: NaN and Inf are live. As asm: this file is built -fno-honor-nans, and hipcc turns
 // the integer compare on the ReLU's result into v_cmp_lt_f32 0, v, which is false for a NaN.
 __device__ __forceinline__ uint64_t live_ballot(float v) {
@@ -121,10 +122,10 @@ __device__ __forceinline__ uint64_t live_ballot(float v) {
 #define DAL3_DEC_NB 3                   // compact k-steps whose operands are in flight (2 KiB of weights + one LDS row each)
 #endif
 #ifndef DAL3_DEC_GROUP
-#define DAL3_DEC_GROUP 4                // dconv1 chunks per compact loop of dconv2: 1, 2, 4 or 8
+#define DAL3_DEC_GROUP 4                // dconv1 chunks per compact loop of dconv2: 2, 4 or 8
 #endif
-static_assert(DAL3_DEC_GROUP == 1 || DAL3_DEC_GROUP == 2 || DAL3_DEC_GROUP == 4 || DAL3_DEC_GROUP == 8,
-              "a group's rows fit the queue's 256, and the groups tile the 16 chunks");
+static_assert(DAL3_DEC_GROUP == 2 || DAL3_DEC_GROUP == 4 || DAL3_DEC_GROUP == 8,
+              "a group's rows fit the queue's 256; the chunk loop goes in pairs, and the last group may be shorter");
 static_assert(DAL3_PF == 8, "the compacted body's ring holds exactly one dconv1 chunk between two blocks");
 // Diagnostic build only (-DDAL3_DEC_COUNT): [0] tiles, [1] dense chunks, [2] compacted chunks, [3] compact k-steps (the
 // final zero-padded one included), [4] live channels, [5] tiles in the compacted body, [6] / [7] dconv3's compact k-steps and
@@ -266,11 +267,20 @@ __device__ __forceinline__ void dec_queue_layer(const f32x16 (&X)[KT], f32x16 (&
     for (int mt = 0; mt < 4; ++mt) Y[mt] = relu16(acc[mt]);
 }
 
-// One wave's tile(s): SP = with the compacted dconv2 - dconv4 (slab: the wave's DEC_Q_FLOATS of LDS)
+// One wave's tile(s): SP = with the compacted dconv2 - dconv4 (slab: the wave's DEC_Q_FLOATS of LDS).
+// SP runs dconv1 over the crop's PLAN (DESIGN.md "Crop-dead channels of dconv1"): pk[0 .. 32 nch) are the chain indices of the
+// channels it computes, ascending and padded with the null channel, gbc their per-crop terms in row order, nch the chunk
+// count (even). Row m = tile_chan(r, h) of chunk j is list entry 32 j + 2 r + h — the place the dense kernel gives that row —
+// so registers, ballots, rows and list positions are those of a dense chunk and only the entry's dconv2 weight offset comes
+// from the plan. A crop without a plan passes the identity (InsSegW::dec_ident, gb itself, 16 chunks). dconv1's A operands:
+// a lane reads the 128 bytes of its row and k-half from the chain-ordered copy dw1c as eight 16-byte loads into the ring's
+// slots, one chunk ahead; the row's chain index is read one chunk before that. The ring proper carries conv2 only.
 template <int T, bool SP>
 __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN& pts, int c_in, int n_pts, int64_t b, int n0,
                                                     const float* __restrict__ gb, float* __restrict__ logits,
-                                                    uint8_t* __restrict__ mask, float* __restrict__ slab, int lane, int wave) {
+                                                    uint8_t* __restrict__ mask, float* __restrict__ slab, int lane, int wave,
+                                                    const uint32_t* __restrict__ pk = nullptr, const float* __restrict__ gbc = nullptr,
+                                                    int nch = 16) {
     const int h = lane >> 5;
     STAMP(0);
     // stream: conv2 | dconv1a(0) | { dconv1a(c+1), dconv2(c) } c = 0..15 | dconv3 | dconv4
@@ -285,15 +295,23 @@ __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN&
     const int pt = lane & 31;
     __amdgpu_buffer_rsrc_t wc = ring.rsrc;
     constexpr int G = DAL3_DEC_GROUP;
-    constexpr int TRIP = SP && G > 2 ? G : 2;          // chunks per trip of the chunk loop (the dense body's stays at two)
+    constexpr int TRIP = SP ? G : 2;                   // chunks per trip of the chunk loop (the dense body's stays at two)
     uint32_t m[TRIP] = {};                             // SP: live mask of the trip's chunks, bit 2r + h
+    uint32_t kq[TRIP / 2] = {};                        // SP: the plan's chain index of list position 64 j + lane of the trip
     uint32_t pend = 0;                                 // SP: an entry waits for a partner
     typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
     u32x2 pend_e = {0u, DEC_Q_ZERO * 32u};             // that entry: weight byte offset, float offset of row DEC_G_PEND
     u32x2* kl = reinterpret_cast<u32x2*>(slab + DEC_G_LIST);
+    __amdgpu_buffer_rsrc_t wd1 = ring.rsrc;            // SP: dconv1a in chain order, 256 bytes per channel, the null channel last
+    // SP: this lane's row of a chunk sits at list position 2 r + h, lane & 31 = tile_chan(r, h)
+    const int row_pos = 2 * ((lane & 3) + 4 * ((lane & 31) >> 3)) + ((lane >> 2) & 1);
+    uint32_t kf = 0, kn = 0;                           // SP: chain index of this lane's row in the chunk fetched next / after that
     if constexpr (SP) {
         wc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(w.dw2c), 0, 512 * 1024, 0x00020000);
+        wd1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(w.dw1c), 0, (DEC_NULL_K + 1) * 256, 0x00020000);
         slab[DEC_Q_ZERO * 32 + pt] = 0.0f;
+        kf = pk[row_pos];
+        kn = pk[32 + row_pos];
     }
 #ifdef DAL3_DEC_COUNT
     uint32_t n_dense = 0, n_comp = 0, n_steps = 0, n_live = 0;
@@ -305,7 +323,31 @@ __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN&
         load_points<2, T>(pts, b, n0, n_pts, c_in, in, lane);
         f32x16 x1[T][2];
         first_layer<2, 2, T>(w.w1, w.b1, in, x1, lane);
-        mlp_layer_ring<2, 2, T>(ring, w.b2, gb, bias, x1, x2, lane);       // leaves bias = gb chunk 0
+        if constexpr (SP) {
+            // conv2 as mlp_layer_ring runs it, except that the second tile's block refills the slots with chunk 0 of dconv1
+            f32x16 c2a[T], c2b[T];
+            c2a[0] = bias;
+            mma_block_ring<2, T>(ring, x1, c2a, [&](int i) {
+                if (i == 0) bias = tile_from_channels(w.b2 + 32, h);
+            });
+            c2b[0] = bias;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const f32x4 a = ring.slot[i];
+                ring.slot[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wd1, kf * 256u + (uint32_t)h * 128u + 16u * i, 0, 0));
+#pragma unroll
+                for (int e = 0; e < 4; ++e) c2b[0] = mfma32(a[e], x1[0][i / 4][4 * (i % 4) + e], c2b[0]);
+                DAL3_SCHED_FENCE();
+                if (i == 0) bias = tile_from_channels(gbc, h);
+                x2[0][0][2 * i] = relu1(c2a[0][2 * i]);
+                x2[0][0][2 * i + 1] = relu1(c2a[0][2 * i + 1]);
+                DAL3_SCHED_FENCE();
+            }
+            x2[0][1] = relu16(c2b[0]);
+            kf = kn;
+        } else {
+            mlp_layer_ring<2, 2, T>(ring, w.b2, gb, bias, x1, x2, lane);   // leaves bias = gb chunk 0
+        }
     }
 
     // dconv1 (512 outputs, 16 chunks of 32) streamed into dconv2 (256 outputs = 8 accumulator tiles).
@@ -349,8 +391,8 @@ __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN&
         S.a1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wc, voff + 16u, 0, 0));
     };
     // The group of chunks c0 .. c0 + NG - 1, whose rows are in the queue and whose masks are mg[0 .. NG - 1]
-    auto dconv2_group = [&](int c0, const uint32_t* mg) {
-        constexpr int NG = G;
+    auto dconv2_group = [&](auto ng, int c0, const uint32_t* mg) {
+        constexpr int NG = decltype(ng)::value;        // G, or less for the crop's last group
         // (LDS operations of a wave execute in order: the next group's rows never overtake this group's reads)
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -363,7 +405,7 @@ __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN&
             const uint32_t word = h ? w1 : w0;
             if ((word >> pt) & 1u) {
                 u32x2 e;
-                e[0] = (32u * (uint32_t)(c0 + 2 * j) + (uint32_t)lane) * 1024u;
+                e[0] = kq[j] * 1024u;                  // (without a plan: 32 (c0 + 2 j) + lane)
                 e[1] = (64u * j + (uint32_t)lane) * 32u;
                 kl[total + below] = e;
             }
@@ -424,14 +466,10 @@ __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN&
     // the dense order), the dense body every chunk through the registers. A second route inside the compacted body made the
     // compiler move the dconv2 accumulators between two register sets at every chunk (profiles/LEDGER_r09.md).
     auto dconv2_chunk = [&](const f32x16 (&t)[T], int c, int u) {
-        if constexpr (SP) {
-            if ((u + 1) % G == 0) dconv2_group(c + 1 - G, m + (u + 1 - G));
-        } else {
 #ifdef DAL3_DEC_COUNT
-            ++n_dense, n_live += 32;
+        ++n_dense, n_live += 32;
 #endif
-            dconv2_part(t);
-        }
+        dconv2_part(t);
     };
     // ReLU of two registers per fragment group; SP: their rows of the queue and their live bits (post-ReLU bits:
     // negatives and -0 are +0 already, NaN / Inf are live)
@@ -454,10 +492,64 @@ __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN&
             }
         }
     };
-    // SP: the ring steps over the dconv2 chunk that lies in front of the dconv1 chunk the next block fetches
-    auto skip_dconv2 = [&]() {
-        if constexpr (SP) ring.soff += 32 * 1024;
+    // SP: one dconv1 block. The slots hold this chunk's rows; they are refilled with the next chunk's (this lane's row: chain
+    // index kf), and the chain index of the row after that is asked for (chunk cn2 of the plan; the loop reads up to four
+    // chunks past the crop's last one, which DEC_PLAN_LD holds: null channels, never used)
+    auto dconv1_block = [&](f32x16& acc, int cn2, auto side) {
+        const uint32_t voff = kf * 256u + (uint32_t)h * 128u;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const f32x4 a = ring.slot[i];
+            ring.slot[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wd1, voff + 16u * i, 0, 0));
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc = mfma32(a[e], x2[0][i / 4][4 * (i % 4) + e], acc);
+            DAL3_SCHED_FENCE();
+            if (i == 0) kn = pk[32 * cn2 + row_pos];
+            side(i);
+            DAL3_SCHED_FENCE();
+        }
+        kf = kn;
     };
+    if constexpr (SP) {
+        tA[0] = bias;
+        dconv1_block(tA[0], 2, [&](int i) {
+            if (i == 0) bias = tile_from_channels(gbc + 32, h);
+        });
+        // chunks c, c + 1 of the crop's plan, at places u, u + 1 of their group
+        auto pair = [&](int c, auto uc) {
+            constexpr int u = decltype(uc)::value;
+            tB[0] = bias;
+            dconv1_block(tB[0], c + 3, [&](int i) {                     // chunk c+1; ReLU(chunk c) in its shadow
+                if (i == 0) bias = tile_from_channels(gbc + 32 * (c + 2 < nch ? c + 2 : 0), h);
+                if (i == 1) kq[(u / 2) % (TRIP / 2)] = pk[32 * c + lane];
+                relu_note(tA[0], i, u);
+            });
+            tA[0] = bias;
+            // chunk c+2 (behind the crop's last chunk: null channels or chunks the plan left out; the result is unused)
+            dconv1_block(tA[0], c + 4, [&](int i) {
+                if (i == 0) bias = c + 2 < nch ? tile_from_channels(gbc + 32 * (c + 3 < nch ? c + 3 : 0), h) : tile_from_channels(w.db3, h);
+                relu_note(tB[0], i, u + 1);
+            });
+        };
+        for (int c0 = 0; c0 < nch; c0 += G) {
+            bool done = false;
+#pragma unroll
+            for (int u = 0; u < G; u += 2) {           // u: the pair's place in the group (a constant once unrolled)
+                if (done) continue;
+                if (u == 0) pair(c0, std::integral_constant<int, 0>());
+                if (u == 2) pair(c0 + 2, std::integral_constant<int, 2>());
+                if (u == 4) pair(c0 + 4, std::integral_constant<int, 4>());
+                if (u == 6) pair(c0 + 6, std::integral_constant<int, 6>());
+                if (u + 2 < G && c0 + u + 2 >= nch) {  // the crop's last group is shorter (wave-uniform)
+                    if (u == 0) dconv2_group(std::integral_constant<int, 2>(), c0, m);
+                    if (u == 2) dconv2_group(std::integral_constant<int, 4>(), c0, m);
+                    if (u == 4) dconv2_group(std::integral_constant<int, 6>(), c0, m);
+                    done = true;
+                }
+            }
+            if (!done) dconv2_group(std::integral_constant<int, G>(), c0, m);
+        }
+    } else {
 #pragma unroll
     for (int j = 0; j < T; ++j) tA[j] = bias;
     mma_block_ring<2, T>(ring, x2, tA, [&](int i) {
@@ -469,7 +561,6 @@ __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN&
             const int c = c0 + u;
 #pragma unroll
             for (int j = 0; j < T; ++j) tB[j] = bias;
-            skip_dconv2();
             mma_block_ring<2, T>(ring, x2, tB, [&](int i) {            // chunk c+1; ReLU(chunk c) in its shadow
                 if (i == 0) bias = tile_from_channels(gb + 32 * ((c + 2) & 15), h);
 #pragma unroll
@@ -478,7 +569,6 @@ __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN&
             dconv2_chunk(tA, c, u);
 #pragma unroll
             for (int j = 0; j < T; ++j) tA[j] = bias;
-            skip_dconv2();
             // chunk c+2 (on the last round its 8 fragments are the stream's zero filler; the result is unused)
             mma_block_ring<2, T>(ring, x2, tA, [&](int i) {
                 if (i == 0)
@@ -488,6 +578,7 @@ __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN&
             });
             dconv2_chunk(tB, c + 1, u + 1);
         }
+    }
     }
     if constexpr (SP) {
         if (pend) {                                    // the very last live channel: its partner is the row of zeros
@@ -586,13 +677,15 @@ __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN&
 // tile (the other channels live) the compacted body runs the 4096 x 1024 launch in 13.58 / 12.65 / 12.17 / 11.68 / 11.18 ms
 // at 0 / 0.125 / 0.1875 / 0.25 / 0.3125 against 12.89 - 12.92 ms dense — break-even below 0.125; it was near 0.2 while dconv2's
 // compact loop ran once per chunk (LEDGER_r12.md, section 3). With nothing dead it still loses 5 %: the dense body stays.
+// A crop with a plan (DESIGN.md "Crop-dead channels of dconv1") is counted on the plan's flags, by dec_plan_kernel, against the
+// same number: at exactly 64 flags the planned call is level with the unplanned one, at 128 it gains 0.35 ms (LEDGER_r14.md).
 #ifndef DAL3_DEC_MIN_DEAD
 #define DAL3_DEC_MIN_DEAD 64
 #endif
 template <int T>
 __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_decode_kernel(InsSegW w, BCN pts, int c_in, int n_pts,
                                                              int tiles_per_item, const float* __restrict__ gbias,
-                                                             float* __restrict__ logits, uint8_t* __restrict__ mask) {
+                                                             float* __restrict__ logits, uint8_t* __restrict__ mask, DecPlan plan) {
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     // Which (crop, tile) this workgroup takes. The hardware deals consecutive workgroup ids round-robin over the 8 XCDs,
@@ -616,14 +709,25 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_decode_kernel(InsS
     constexpr bool SP = DAL3_DEC_SPARSE != 0 && T == 1;    // one tile per wave only: the live mask is the tile's
     extern __shared__ __attribute__((aligned(16))) float s_slab[];   // SP: DAL3_WG_WAVES queues of DEC_Q_FLOATS (dynamic: above 64 KiB)
     if constexpr (SP) {
-        const f32x4 g0 = reinterpret_cast<const f32x4*>(gb)[2 * lane], g1 = reinterpret_cast<const f32x4*>(gb)[2 * lane + 1];
-        uint32_t neg = 0;                              // sign bits among the crop's 512 entries (a NaN term counts or not: dense either way is right)
+        // With a plan the dead channels are the plan's flags (dec_plan_kernel counts them: nch > 0 means at least
+        // DAL3_DEC_MIN_DEAD and a clear guard flag); a crop without one is counted on gb and runs the identity plan.
+        int nch = plan.nch ? plan.nch[b] : 0;
+        const uint32_t* pk = plan.k + b * DEC_PLAN_LD;
+        const float* gbc = plan.gbc + b * 512;
+        bool sparse = nch > 0;
+        if (!sparse) {
+            const f32x4 g0 = reinterpret_cast<const f32x4*>(gb)[2 * lane], g1 = reinterpret_cast<const f32x4*>(gb)[2 * lane + 1];
+            uint32_t neg = 0;                          // sign bits among the crop's 512 entries (a NaN term counts or not: dense either way is right)
 #pragma unroll
-        for (int e = 0; e < 4; ++e)
-            neg += __builtin_popcountll(__builtin_amdgcn_ballot_w64(__float_as_int(g0[e]) < 0)) +
-                   __builtin_popcountll(__builtin_amdgcn_ballot_w64(__float_as_int(g1[e]) < 0));
-        if (neg >= DAL3_DEC_MIN_DEAD && *w.dec_flag == 0) {
-            ins_seg_decode_tile<T, true>(w, pts, c_in, n_pts, b, n0, gb, logits, mask, s_slab + wave * DEC_Q_FLOATS, lane, wave);
+            for (int e = 0; e < 4; ++e)
+                neg += __builtin_popcountll(__builtin_amdgcn_ballot_w64(__float_as_int(g0[e]) < 0)) +
+                       __builtin_popcountll(__builtin_amdgcn_ballot_w64(__float_as_int(g1[e]) < 0));
+            sparse = neg >= DAL3_DEC_MIN_DEAD && *w.dec_flag == 0;
+            nch = 16, pk = w.dec_ident, gbc = gb;
+        }
+        if (sparse) {
+            ins_seg_decode_tile<T, true>(w, pts, c_in, n_pts, b, n0, gb, logits, mask, s_slab + wave * DEC_Q_FLOATS, lane, wave, pk,
+                                         gbc, nch);
             return;
         }
     }
@@ -863,7 +967,17 @@ static inline int tiles_per_item(int n_pts, int T) {
 #endif
 bool lat_use(int64_t tiles, int flags, int64_t max_tiles) { return !(flags & DAL3_BCN_NO_SMALL_JOB_KERNELS) && tiles <= max_tiles; }
 
-hipError_t launch_ins_seg_encode(const InsSegW& w, BCN pts, int c_in, int B, int N, float* g, hipStream_t s) {
+// Do the screened encoder and the throughput decoder's compacted body both run for this job? Then the encoder leaves the
+// bound of dconv1's crop-dead channels and the decoder takes a plan (dal3_api.hip: ins_seg_run). DAL3_BCN_NO_DEC_PLAN: never.
+bool dec_plan_route(int flags, int B, int N) {
+    const int64_t tiles = (int64_t)B * ((N + 31) / 32);
+    if (flags & DAL3_BCN_NO_DEC_PLAN) return false;
+    if (!DAL3_ENC_SCREEN || !DAL3_DEC_SPARSE || DAL3_DEC_T != 1) return false;
+    if (lat_use(tiles, flags, DAL3_LAT_MAX_TILES_ENC) || lat_use(tiles, flags, DAL3_LAT_MAX_TILES_DEC)) return false;
+    return !(DAL3_ENC_T > 1 && (int64_t)B * N <= 1024 * 64);
+}
+
+hipError_t launch_ins_seg_encode(const InsSegW& w, BCN pts, int c_in, int B, int N, float* g, hipStream_t s, uint32_t* prune) {
     if (lat_use((int64_t)B * ((N + 31) / 32), pts.flags, DAL3_LAT_MAX_TILES_ENC)) return launch_ins_seg_encode_lat(w, pts, c_in, B, N, g, s);
     constexpr int T = DAL3_ENC_T;
     // A wave runs its T tiles through the whole encoder one after the other (~150 us per tile at 2.4 GHz). When the
@@ -875,14 +989,14 @@ hipError_t launch_ins_seg_encode(const InsSegW& w, BCN pts, int c_in, int B, int
         return hipGetLastError();
     }
     // large jobs: conv5 screened in fp16, candidates recomputed exactly (dal3_enc_screen.hip); the same bits
-    if (DAL3_ENC_SCREEN) return launch_ins_seg_encode_screen(w, pts, c_in, B, N, g, s);
+    if (DAL3_ENC_SCREEN) return launch_ins_seg_encode_screen(w, pts, c_in, B, N, g, s, prune);
     const int tpi = tiles_per_item(N, T);
     hipLaunchKernelGGL(ins_seg_encode_kernel<T>, dim3((unsigned)((int64_t)B * tpi)), dim3(64 * DAL3_WG_WAVES), 0, s, w, pts, c_in, N, tpi, g);
     return hipGetLastError();
 }
 
 hipError_t launch_ins_seg_decode(const InsSegW& w, BCN pts, int c_in, int B, int N, const float* gbias,
-                                 float* logits, uint8_t* mask, hipStream_t s) {
+                                 float* logits, uint8_t* mask, hipStream_t s, DecPlan plan) {
     if (lat_use((int64_t)B * ((N + 31) / 32), pts.flags, DAL3_LAT_MAX_TILES_DEC)) return launch_ins_seg_decode_lat(w, pts, c_in, B, N, gbias, logits, mask, s);
     constexpr int T = DAL3_DEC_T;
     const int tpi = tiles_per_item(N, T);
@@ -894,7 +1008,7 @@ hipError_t launch_ins_seg_decode(const InsSegW& w, BCN pts, int c_in, int B, int
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(ins_seg_decode_kernel<T>, dim3((unsigned)((int64_t)B * tpi)), dim3(64 * DAL3_WG_WAVES), lds, s, w, pts, c_in, N, tpi,
-                       gbias, logits, mask);
+                       gbias, logits, mask, plan);
     return hipGetLastError();
 }
 

@@ -19,6 +19,12 @@ __device__ __forceinline__ uint32_t scr_push_hit(uint32_t hb, float acc, float k
     return __builtin_amdgcn_alignbit(hb, __float_as_uint(k - acc), 31);
 }
 
+// Order-preserving key of a SIGNED score for an unsigned atomic max (the maxima of dconv1a's fp16 scores, which the
+// decoder's plan reads: DESIGN.md "Crop-dead channels of dconv1"): a < b as floats <=> key(a) < key(b), -0 below +0; 0 lies
+// below the key of every finite value and of -Inf, so a zero-filled table is "nothing seen yet".
+__host__ __device__ __forceinline__ uint32_t prune_key(uint32_t bits) { return bits ^ ((bits >> 31) ? 0xFFFFFFFFu : 0x80000000u); }
+__host__ __device__ __forceinline__ uint32_t prune_unkey(uint32_t key) { return key ^ ((key >> 31) ? 0x80000000u : 0xFFFFFFFFu); }
+
 // bits of a hit word that belong to tile j: pushes s = j (mod T), bit 16 T - 1 - s
 template <int T>
 __host__ __device__ constexpr uint32_t scr_tile_mask(int j) {

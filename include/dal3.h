@@ -137,13 +137,25 @@ typedef struct {
  *   DAL3_BCN_NO_SMALL_JOB_KERNELS  never the small-job ("latency") family (jobs of <= 512 tiles of 32 points)
  *   DAL3_BCN_NO_WORKLIST           point heads: one workgroup per (item, tile) instead of the live-tile worklist
  *   DAL3_BCN_NO_LDS_SAMPLER        mask compaction + sampling: positions through global memory, keys recomputed per
- *                                  pass (what items of more than 7936 points always take) instead of both in LDS */
-enum { DAL3_BCN_NO_SMALL_JOB_KERNELS = 1, DAL3_BCN_NO_WORKLIST = 2, DAL3_BCN_NO_LDS_SAMPLER = 4 };
+ *                                  pass (what items of more than 7936 points always take) instead of both in LDS
+ *   DAL3_BCN_NO_DEC_PLAN           fp32 instance segmentation: the decoder computes every dconv1 channel of every tile
+ *                                  instead of leaving out the channels that the encoder's bound proves dead for the whole
+ *                                  crop (large jobs only; 8 is not a flag and stays refused) */
+enum { DAL3_BCN_NO_SMALL_JOB_KERNELS = 1, DAL3_BCN_NO_WORKLIST = 2, DAL3_BCN_NO_LDS_SAMPLER = 4, DAL3_BCN_NO_DEC_PLAN = 16 };
 
 /* ---- PointNetInstanceSeg.forward (static_model.py:271-296, dynamic_model.py:187-212) plus
  * the mask of point_cloud_masking (static_model.py:59). logits (B,N,2) fp32, mask (B,N) u8.
  * workspace: dal3_ins_seg_workspace_bytes(B). global_feat_out optional (B,1024). */
 size_t dal3_ins_seg_workspace_bytes(int B);
+/* Where a DAL3_F32 dal3_ins_seg_forward of a large job (the screened encoder and the throughput decoder both run, and
+ * DAL3_BCN_NO_DEC_PLAN is not set) leaves the decoder's plan in its workspace, as byte offsets: off[0] (B,513) u32, per
+ * crop the order-preserving keys of the maxima U_c of dconv1's fp16 scores (natural channel order; key = bits ^ 0x80000000
+ * for a non-negative value, ~bits for a negative one, 0 = nothing seen) and in word 512 the fp32 bits of X = max ||x2||_2
+ * (+Inf: no bound); off[1] (B,640) u32, the unflagged chain indices (k = 32 c + 2 r + h for channel 32 c + (r & 3) +
+ * 8 (r >> 2) + 4 h) in ascending order, padded with 512, the null channel; off[2] (B,512) f32, the crop's dconv1 term
+ * gathered to match (-1 for the null channel); off[3] (B) i32, the chunk count (even; 0 = fewer than *min_dead channels
+ * are flagged and the decoder runs as without a plan). For tests and measurements. */
+int dal3_ins_seg_plan_layout(int B, size_t off[4], int* min_dead);
 int dal3_ins_seg_forward(const void* packed, int dtype, int c_in, dal3_bcn pts, int B, int N,
                          float* logits, uint8_t* mask, float* global_feat_out,
                          void* workspace, size_t workspace_bytes, dal3_stream stream);

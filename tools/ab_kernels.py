@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """A/B timing of library builds in ONE process (cdna guide rule 24): interleaved rounds of the
 three shared-MLP kernels, median and min per build, outputs cross-checked against the first build.
+`seg` is dal3_ins_seg_forward — encoder, per-crop FC, the decoder's plan where the build has one, decoder — as a step runs
+them (`dec` alone is the stand-alone entry, which never has a plan); `seg0` the same call with DAL3_BCN_NO_DEC_PLAN.
 
   python tools/ab_kernels.py build_a.so build_b.so ... [--B 4096] [--N 1024] [--rounds 7]
 """
@@ -62,7 +64,10 @@ pts = torch.from_numpy(pts_np).to(dev).repeat(reps, 1, 1)[:B].contiguous().trans
 obj = pts.transpose(2, 1)[:, :512, :].contiguous().transpose(2, 1)
 x, xo = hip.bcn(pts), hip.bcn(obj)
 st = hip.stream()
-libs = [(os.path.basename(p), load(p)) for p in args.libs]
+names = [os.path.basename(p) for p in args.libs]
+if len(set(names)) < len(names):                          # the same file name in several trees: tell them apart by their paths
+    names = [os.path.relpath(p) for p in args.libs]
+libs = [(n, load(p)) for n, p in zip(names, args.libs)]
 state = []
 for name, lib in libs:
     need = C.c_size_t(0)
@@ -81,7 +86,18 @@ for name, lib in libs:
     mask = torch.empty((B, N), dtype=torch.uint8, device=dev)
     ws = torch.empty(lib.dal3_point_head_workspace_bytes(B), dtype=torch.uint8, device=dev)
     bp = torch.empty((B, 39), device=dev)
-    d = dict(w_seg=w_seg, w_box=w_box, g=g, gb=gb, logits=logits, mask=mask, ws=ws, bp=bp)
+    ws_seg = torch.zeros(lib.dal3_ins_seg_workspace_bytes(B), dtype=torch.uint8, device=dev)
+    lg_seg, mk_seg, g_seg = torch.empty_like(logits), torch.empty_like(mask), torch.empty_like(g)
+    d = dict(w_seg=w_seg, w_box=w_box, g=g, gb=gb, logits=logits, mask=mask, ws=ws, bp=bp, ws_seg=ws_seg, lg_seg=lg_seg,
+             mk_seg=mk_seg, g_seg=g_seg, has_plan=hasattr(lib, "dal3_ins_seg_plan_layout"))
+
+    def seg(lib=lib, d=d, flags=0):
+        v = hip.bcn(pts)
+        v.flags |= flags
+        return lib.dal3_ins_seg_forward(hip.ptr(d["w_seg"]), DT, 3, v, B, N, hip.ptr(d["lg_seg"]), hip.ptr(d["mk_seg"]),
+                                        hip.ptr(d["g_seg"]), hip.ptr(d["ws_seg"]), d["ws_seg"].numel(), st)
+    d["seg"] = seg
+    d["seg0"] = (lambda seg=seg: seg(flags=hip.BCN_NO_DEC_PLAN)) if d["has_plan"] else seg
     # g is zeroed before EVERY encode, as a step does (nonfinite_rows_kernel): the screened fp32 encoder's second launch
     # reads its thresholds from g, and on a g that already holds the final maxima it would find fewer candidates than it
     # ever does in a step. (The fill is a 16.8-MB memset, ~5 us, the same for every build.)
@@ -106,11 +122,38 @@ for name, lib in libs:
         if sp_tiles:
             print(f"{name}: dconv3 compact k-steps {s3} ({s3 / (128.0 * sp_tiles):.4f} of dense), live rows {l3 / (256.0 * sp_tiles):.4f}; "
                   f"dconv4 compact k-steps {s4} ({s4 / (64.0 * sp_tiles):.4f} of dense), live rows {l4 / (128.0 * sp_tiles):.4f}")
+    assert d["seg0"]() == 0, lib.dal3_last_error()
+    torch.cuda.synchronize()
+    d["lg_seg0"], d["mk_seg0"] = d["lg_seg"].clone(), d["mk_seg"].clone()
+    if hasattr(lib, "dal3_debug_dec_counts"):
+        lib.dal3_debug_dec_counts(cnt, 1)
+    assert d["seg"]() == 0, lib.dal3_last_error()
+    if hasattr(lib, "dal3_debug_dec_counts"):         # the same counts for the decoder inside the whole call (with its plan)
+        torch.cuda.synchronize()
+        lib.dal3_debug_dec_counts(cnt, 1)
+        tiles, dense, comp, steps, live, sp_tiles = (int(v) for v in cnt[:6])
+        print(f"{name}: ins_seg_forward: decode tiles {tiles} ({sp_tiles} in the compacted body), dense chunks {dense}, compacted chunks "
+              f"{comp} ({comp / max(sp_tiles, 1):.3f} per compacted tile), compact k-steps {steps} ({steps / max(sp_tiles, 1):.3f} per compacted tile), "
+              f"live channels among the computed ones {live / max(32.0 * (comp + dense), 1):.4f}")
+    if d["has_plan"] and DT == 0:
+        off, md = (C.c_size_t * 4)(), C.c_int(0)
+        assert lib.dal3_ins_seg_plan_layout(B, off, C.byref(md)) == 0
+        torch.cuda.synchronize()
+        nch = ws_seg[off[3]:off[3] + 4 * B].view(torch.int32).cpu().numpy()
+        lst = ws_seg[off[1]:off[1] + 4 * 640 * B].view(torch.int32).view(B, 640)[:, :512].cpu().numpy()
+        live = (lst < 512).sum(1)
+        print(f"{name}: plan: {int((nch > 0).sum())} of {B} crops, flagged share {1 - live.mean() / 512:.4f}, live channels "
+              f"{int(live.min())} - {int(live.max())}, chunks run per tile {np.where(nch > 0, nch, 16).mean():.2f} of 16")
     state.append(d)
 torch.cuda.synchronize()
 ref = state[0]
 for (name, _), d in zip(libs, state):
     same = (torch.equal(d["g"], ref["g"]), torch.equal(d["logits"], ref["logits"]), torch.equal(d["bp"], ref["bp"]))
+    bits = lambda t: t.view(torch.int32)
+    seg_same = (torch.equal(bits(d["g_seg"]), bits(ref["g_seg"])), torch.equal(bits(d["lg_seg"]), bits(ref["lg_seg0"])),
+                torch.equal(d["mk_seg"], ref["mk_seg0"]), torch.equal(bits(d["lg_seg0"]), bits(ref["lg_seg0"])))
+    print(f"{name}: ins_seg_forward bitwise-equal to the first build without a plan (g, logits, mask, logits of its own call "
+          f"without a plan) = {seg_same}")
     dl = (d["logits"] - ref["logits"]).abs().max().item() / ref["logits"].abs().max().item()
     print(f"{name}: bitwise-equal to first (g, logits, box_pred) = {same}, logits rel diff {dl:.2e}")
 
@@ -125,14 +168,15 @@ def timed(fn, iters=5):
     return a.elapsed_time(b) / iters
 
 
-res = {(n, k): [] for n, _ in libs for k in ("enc", "dec", "head")}
+KINDS = ("enc", "dec", "head", "seg", "seg0")
+res = {(n, k): [] for n, _ in libs for k in KINDS}
 for r in range(args.rounds):
-    for k in ("enc", "dec", "head"):
+    for k in KINDS:
         for (name, _), d in zip(libs, state):
             res[(name, k)].append(timed(d[k]))
 print(f"B={B} N={N}: ms per launch, median (min, max - min) over {args.rounds} interleaved rounds")
 for name, _ in libs:
     row = "  ".join(f"{k} {statistics.median(res[(name, k)]):7.3f} ({min(res[(name, k)]):7.3f}, {max(res[(name, k)]) - min(res[(name, k)]):5.3f})"
-                    for k in ("enc", "dec", "head"))
+                    for k in KINDS)
     tot = sum(statistics.median(res[(name, k)]) for k in ("enc", "dec", "head"))
     print(f"{name:40s} {row}   sum {tot:7.3f}")

@@ -162,6 +162,17 @@ def kernel_table(model, inputs, static, B, N, iters):
     row("ins_seg_decode" + sfx, events_ms(dec, iters), arch.ins_seg_decode_mac(c_in) * B * N, dec_exe * B * N,
         note=None if dec_exe == arch.ins_seg_decode_mac(c_in, True) else
         f"{dec_exe:.0f} of {arch.ins_seg_decode_mac(c_in, True)} MAC per point executed (dead input channels of dconv2-4 left out; counted on the first crops)")
+    if prec == "fp32":
+        # the segmentation network as a step runs it: one dal3_ins_seg_forward = zero-fill, encoder, per-crop FC, the
+        # decoder's plan (large jobs: dconv1 over the channels the encoder's bound does not prove dead for the crop, DESIGN.md
+        # "Crop-dead channels of dconv1") and decoder. The stand-alone decode entry of the row above never has a plan.
+        sws = torch.empty(int(lib.dal3_ins_seg_workspace_bytes(B)), dtype=torch.uint8, device=dev)
+
+        def seg():
+            hip.check(lib.dal3_ins_seg_forward(hip.ptr(w), dt, c_in, x, B, N, hip.ptr(logits), hip.ptr(mask), None, hip.ptr(sws),
+                                               sws.numel(), st()))
+        # (a field of the decoder's row, not a row: the table's rows are summed)
+        out["ins_seg_decode" + sfx]["ins_seg_forward_ms"] = round(events_ms(seg, iters), 4)
     t = events_ms(samp, iters)
     out["compact_sample_kernel"] = {"ms": round(t, 4), "algorithmic_gflop": 0.0, "executed_gflop": 0.0,
                                     "bytes": int(B * N + B * M * (4 + 4 * c_in)),
