@@ -20,7 +20,9 @@
 #include "dal3_kernels.h"
 
 // Diagnostic build only (-DDAL3_STAMP): s_memtime stamps of the decode kernel's phases (0..4; the compacted body adds 5: dconv3's
-// rows queued, 6: dconv3 done, 7: dconv4's rows queued), written to a buffer of their own (dal3_debug_set_stamps). No stamp executes in the shipped library.
+// rows queued, 6: dconv3 done, 7: dconv4's rows queued; 8 + i / 11 + i: entry and exit of dconv2's group i < 3, 14: those groups'
+// k-steps in bits 16 i ..), 16 words per wave, written to a buffer of their own (dal3_debug_set_stamps). No stamp executes in
+// the shipped library.
 #ifdef DAL3_STAMP
 __device__ long long* g_stamps = nullptr;
 extern "C" int dal3_debug_set_stamps(void* p) {
@@ -32,7 +34,7 @@ extern "C" int dal3_debug_set_stamps(void* p) {
         unsigned long long t_;                                                                    \
         asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");               \
         __builtin_amdgcn_sched_barrier(0);                                                        \
-        if (lane == 0 && blockIdx.x < 2048) g_stamps[(blockIdx.x * DAL3_WG_WAVES + wave) * 8 + (k)] = t_; \
+        if (lane == 0 && blockIdx.x < 2048) g_stamps[(blockIdx.x * DAL3_WG_WAVES + wave) * 16 + (k)] = t_; \
     } while (0)
 #else
 #define STAMP(k)
@@ -94,8 +96,9 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_encode_kernel(InsS
 // removes), so the dead channels are dropped from the k loop and every output keeps its chain of the live terms in the
 // dense order — the same bits. dconv1 produces that input in chunks of 32 channels; the compact k-loop runs once per
 // GROUP of DAL3_DEC_GROUP chunks (one start — list, first LDS and L2 round trips — per group instead of one per chunk).
-// Per chunk, in the shadow of the next chunk's dconv1 MFMAs: 16 wave ballots give the live mask in chain order (bit
-// 2r + h = accumulator register r, lane half h), kept as one scalar word, and the 16 registers go to rows 32 u + 2r + h
+// Per chunk, between the next chunk's dconv1 MFMAs: 16 wave ballots, collected in the lanes of one vector register and
+// compared once (note_halves / live_word), give the live mask in chain order (bit 2r + h = accumulator register r, lane
+// half h), kept as one scalar word, and the 16 registers go to rows 32 u + 2r + h
 // of the wave's row queue in LDS (u: the chunk's place in its group; immediate offsets, no address arithmetic). Per
 // group: the mask words become the LIST of live chain indices in chain order with v_mbcnt, 64 indices per pass; an entry
 // is two words, the byte offset k * 1024 of the channel's weights and the float offset of its row. The leftover of the
@@ -114,6 +117,20 @@ __device__ __forceinline__ uint64_t live_ballot(float v) {
     uint64_t bal;
     asm("v_cmp_ne_u32_e64 %0, 0, %1" : "=s"(bal) : "v"(v));
     return bal;
+}
+// The live mask of 16 registers (32 rows: bit 2 r + h = register r, lane half h) from their ballots. A row is live if its
+// half of the ballot is not 0. Taken on the scalar unit that is five instructions per register (two s_min_u32, a shift-add, a
+// shift, an OR), and on this chip every instruction a wave issues between its fp32 MFMAs costs its issue time, scalar ones
+// included (profiles/LEDGER_r15.md, section 2). Instead the two halves of ballot r go to lanes 2 r and 2 r + 1 of ONE vector
+// register, two v_writelane_b32 with constant lane numbers, and one compare of that register at the end gives the word.
+__device__ __forceinline__ void note_halves(uint32_t& halves, uint64_t bal, int r) {
+    // (the scalar operand is the DATA: a vector compare's result needs wait states only in front of a lane SELECT)
+    asm("v_writelane_b32 %0, %1, %3\n\tv_writelane_b32 %0, %2, %4"
+        : "+v"(halves)
+        : "s"((uint32_t)bal), "s"((uint32_t)(bal >> 32)), "n"(2 * r), "n"(2 * r + 1));
+}
+__device__ __forceinline__ uint32_t live_word(uint32_t halves) {   // (an integer compare: no NaN question; lanes 32 .. 63 hold 0)
+    return (uint32_t)__builtin_amdgcn_ballot_w64(halves != 0u);
 }
 #ifndef DAL3_DEC_SPARSE
 #define DAL3_DEC_SPARSE 1               // 0: every chunk on the dense path (A/B builds)
@@ -150,8 +167,13 @@ struct DecStep {                        // operands of one compact k-step: weigh
 // is complete when the layer starts, so it goes through ONE per-wave row queue in LDS and ONE compact k-loop with a single
 // start. A row is one input channel's 32 points; row k of the queue is chain index k = 32 kt + 2 r + h (k-tile, accumulator
 // register r, lane half h: the order of mlp_layer_ring's terms), so the 16 KT row writes need no address arithmetic. One
-// wave ballot per register gives the two live bits; they are kept as scalar words (bit k of the layer's mask) and touched
-// with scalar instructions only. The mask then becomes the LIST of live chain indices in chain order, 64 indices per
+// wave ballot per register holds the two live bits as its halves; the halves of a k-tile's 16 ballots go to the lanes of one
+// vector register and one compare of it gives the k-tile's mask word (note_halves / live_word: three vector instructions per
+// register where the scalar unit took five and a wait), kept as a scalar (bit k of the layer's mask). The rows are written and
+// the list is built BEFORE the loop starts: slicing the production by out-tile and running it between the k-steps of a loop
+// that consumes the list as far as it is final was built and measured, and did not pay — a wave's instructions between its
+// fp32 MFMAs cost their issue time there as they do here (profiles/LEDGER_r15.md, section 3).
+// The mask then becomes the LIST of live chain indices in chain order, 64 indices per
 // pass: lane L owns index 64 j + L, its place in the list is the number of live indices below it (v_mbcnt on the mask word
 // plus the scalar count of the words before), and only live lanes write. Compact k-step s: half-wave h takes list entry
 // 2 s + h, reads that row as its B operand and 16 bytes per lane of the chain-ordered weight copy [k][row 0..31][out-tile 0..3]
@@ -196,21 +218,14 @@ __device__ __forceinline__ void dec_queue_layer(const f32x16 (&X)[KT], f32x16 (&
     uint32_t m[KT];                                    // live mask, word kt: bit 2 r + h
 #pragma unroll
     for (int kt = 0; kt < KT; ++kt) {
-        m[kt] = 0;
+        uint32_t halves = 0;                           // lane 2 r + h: the ballot of register r in lane half h (see live_word)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const float v = X[kt][r];
             q[(32 * kt + 2 * r) * 32 + lane] = v;      // rows 32 kt + 2 r (low half) and + 1 (high half)
-            const uint64_t bal = live_ballot(v);
-            // bits 2 r and 2 r + 1 of the word: "half != 0" as s_min_u32 half, 1 (see note_live in ins_seg_decode_tile). The
-            // whole update is one asm block: written in C++, hipcc takes the tile's ballots first, reassociates the ORs to
-            // the end and spills the scalars in between to vector lanes
-            uint32_t lo, hi;
-            asm("s_min_u32 %1, %3, 1\n\ts_min_u32 %2, %4, 1\n\ts_lshl1_add_u32 %1, %2, %1\n\ts_lshl_b32 %1, %1, %5\n\ts_or_b32 %0, %0, %1"
-                : "+s"(m[kt]), "=&s"(lo), "=&s"(hi)
-                : "s"((uint32_t)bal), "s"((uint32_t)(bal >> 32)), "n"(2 * r)
-                : "scc");
+            note_halves(halves, live_ballot(v), r);
         }
+        m[kt] = live_word(halves);
     }
     q[DEC_Q_ZERO * 32 + pt] = 0.0f;
     uint32_t cnt = 0;                                  // live rows (wave-uniform)
@@ -316,6 +331,9 @@ __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN&
 #ifdef DAL3_DEC_COUNT
     uint32_t n_dense = 0, n_comp = 0, n_steps = 0, n_live = 0;
 #endif
+#ifdef DAL3_STAMP
+    unsigned long long stamp_steps = 0;
+#endif
 
     f32x16 x2[T][2];
     {
@@ -393,6 +411,9 @@ __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN&
     // The group of chunks c0 .. c0 + NG - 1, whose rows are in the queue and whose masks are mg[0 .. NG - 1]
     auto dconv2_group = [&](auto ng, int c0, const uint32_t* mg) {
         constexpr int NG = decltype(ng)::value;        // G, or less for the crop's last group
+#ifdef DAL3_STAMP
+        if (c0 / G < 3) STAMP(8 + c0 / G);
+#endif
         // (LDS operations of a wave execute in order: the next group's rows never overtake this group's reads)
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -456,6 +477,12 @@ __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN&
         for (int u = 0; u + 1 < DAL3_DEC_NB; ++u) {
             if (s + u < steps) compact_mma(S[u]);
         }
+#ifdef DAL3_STAMP
+        if (c0 / G < 3) {
+            STAMP(11 + c0 / G);
+            stamp_steps |= (unsigned long long)steps << (16 * (c0 / G));
+        }
+#endif
 #ifdef DAL3_DEC_COUNT
         n_comp += NG, n_steps += steps;
 #pragma unroll
@@ -473,23 +500,19 @@ __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN&
     };
     // ReLU of two registers per fragment group; SP: their rows of the queue and their live bits (post-ReLU bits:
     // negatives and -0 are +0 already, NaN / Inf are live)
+    uint32_t halves = 0;                               // SP: the ballots of the chunk whose ReLU is under way (see note_halves)
     auto relu_note = [&](f32x16& t, int i, int u) {
         t[2 * i] = relu1(t[2 * i]);
         t[2 * i + 1] = relu1(t[2 * i + 1]);
         if constexpr (SP) {
-            if (i == 0) m[u] = 0;
+            if (i == 0) halves = 0;
 #pragma unroll
             for (int r = 2 * i; r < 2 * i + 2; ++r) {
                 const float v = t[r];
                 slab[(32 * (u % G) + 2 * r) * 32 + lane] = v;          // rows 32 u + 2 r (low half) and + 1 (high half)
-                const uint64_t bal = live_ballot(v);
-                // bits 2 r and 2 r + 1 of the chunk's word, in one asm block on the scalar unit (see dec_queue_layer)
-                uint32_t lo, hi;
-                asm("s_min_u32 %1, %3, 1\n\ts_min_u32 %2, %4, 1\n\ts_lshl1_add_u32 %1, %2, %1\n\ts_lshl_b32 %1, %1, %5\n\ts_or_b32 %0, %0, %1"
-                    : "+s"(m[u]), "=&s"(lo), "=&s"(hi)
-                    : "s"((uint32_t)bal), "s"((uint32_t)(bal >> 32)), "n"(2 * r)
-                    : "scc");
+                note_halves(halves, live_ballot(v), r);                // bits 2 r and 2 r + 1 of the chunk's word
             }
+            if (i == 7) m[u] = live_word(halves);
         }
     };
     // SP: one dconv1 block. The slots hold this chunk's rows; they are refilled with the next chunk's (this lane's row: chain
@@ -665,6 +688,9 @@ __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN&
         }
     }
     STAMP(4);
+#ifdef DAL3_STAMP
+    if (lane == 0 && blockIdx.x < 2048) g_stamps[(blockIdx.x * DAL3_WG_WAVES + wave) * 16 + 14] = (long long)stamp_steps;
+#endif
 }
 
 // The compacted body is taken by the tiles of a crop whose term gb is negative in at least DAL3_DEC_MIN_DEAD of the 512
