@@ -396,6 +396,7 @@ SIGNATURES = {
     "dal3_pack_weights": (_i, [_i, C.POINTER(Layer), _i, _i, vp, C.POINTER(_sz), vp]),
     "dal3_ins_seg_workspace_bytes": (_sz, [_i]),
     "dal3_ins_seg_plan_layout": (_i, [_i, C.POINTER(_sz), C.POINTER(_i)]),
+    "dal3_ins_seg_encoder_route": (_i, [_i, _i, _i]),
     "dal3_ins_seg_forward": (_i, [vp, _i, _i, BCN, _i, _i, vp, vp, vp, vp, _sz, vp]),
     "dal3_ins_seg_encode": (_i, [vp, _i, _i, BCN, _i, _i, vp, vp]),
     "dal3_ins_seg_global_bias": (_i, [vp, _i, vp, _i, vp, vp]),
@@ -628,6 +629,8 @@ def host_offsets(offsets, n, name, sized_by, count):
 STORAGE = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 BCN_NO_SMALL_JOB_KERNELS, BCN_NO_WORKLIST, BCN_NO_LDS_SAMPLER = 1, 2, 4
 BCN_NO_DEC_PLAN = 16
+BCN_NO_ENC_RESIDENT = 32
+ENC_ROUTE_LATENCY, ENC_ROUTE_DENSE, ENC_ROUTE_TWO_LAUNCH, ENC_ROUTE_RESIDENT = 0, 1, 2, 3      # dal3_ins_seg_encoder_route
 # dal3_bcn.flags of every view bcn() builds (include/dal3.h, DAL3_BCN_*). 0 in normal use; A/B measurements and the
 # tests that pin "both kernel families give the same bits" set it around a call (binding-side, the library has no switch).
 DISPATCH_FLAGS = 0

@@ -516,7 +516,7 @@ static int check_bcn(const dal3_bcn& t, const char* what) {
     if (t.dtype != DAL3_F32 && t.dtype != DAL3_BF16 && t.dtype != DAL3_F16)
         return fail(DAL3_EINVAL, "%s: storage dtype %d is none of DAL3_F32 / DAL3_BF16 / DAL3_F16", what, t.dtype);
     if (t.dtype != DAL3_F32 && (reinterpret_cast<uintptr_t>(t.data) & 1)) return fail(DAL3_EINVAL, "%s: 16-bit data must be 2-byte aligned", what);
-    if (t.flags & ~(DAL3_BCN_NO_SMALL_JOB_KERNELS | DAL3_BCN_NO_WORKLIST | DAL3_BCN_NO_LDS_SAMPLER | DAL3_BCN_NO_DEC_PLAN)) return fail(DAL3_EINVAL, "%s: unknown bits in flags (%d)", what, t.flags);
+    if (t.flags & ~(DAL3_BCN_NO_SMALL_JOB_KERNELS | DAL3_BCN_NO_WORKLIST | DAL3_BCN_NO_LDS_SAMPLER | DAL3_BCN_NO_DEC_PLAN | DAL3_BCN_NO_ENC_RESIDENT)) return fail(DAL3_EINVAL, "%s: unknown bits in flags (%d)", what, t.flags);
     return 0;
 }
 
@@ -563,6 +563,13 @@ extern "C" int dal3_ins_seg_plan_layout(int B, size_t off[4], int* min_dead) {
     off[2] = reinterpret_cast<char*>(w.plan_gbc) - origin, off[3] = reinterpret_cast<char*>(w.plan_nch) - origin;
     if (min_dead) *min_dead = DAL3_DEC_MIN_DEAD;
     return 0;
+}
+
+extern "C" int dal3_ins_seg_encoder_route(int B, int N, int flags) {
+    TRY(check_extent(B, N, "ins_seg_encoder_route"));
+    if (flags & ~(DAL3_BCN_NO_SMALL_JOB_KERNELS | DAL3_BCN_NO_WORKLIST | DAL3_BCN_NO_LDS_SAMPLER | DAL3_BCN_NO_DEC_PLAN | DAL3_BCN_NO_ENC_RESIDENT))
+        return fail(DAL3_EINVAL, "ins_seg_encoder_route: unknown bits in flags (%d)", flags);
+    return enc_route(flags, B, N);
 }
 
 static int check_dtype(int dtype) {

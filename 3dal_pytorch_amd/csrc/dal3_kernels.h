@@ -245,6 +245,8 @@ void point_head_dims(int head_kind, int* c_in, int* ks, int c[4], int* n_fc, int
 hipError_t launch_ins_seg_encode(const InsSegW& w, BCN pts, int c_in, int B, int N, float* g, hipStream_t s, uint32_t* prune = nullptr);
 hipError_t launch_ins_seg_encode_screen(const InsSegW& w, BCN pts, int c_in, int B, int N, float* g, hipStream_t s, uint32_t* prune);
 bool dec_plan_route(int flags, int B, int N);
+int enc_route(int flags, int B, int N);                     // which fp32 encoder runs: DAL3_ENC_ROUTE_* (dal3.h)
+bool enc_resident_route(int flags, int B, int N);           // the screened encoder as ONE crop-resident launch (dal3_pointmlp.hip)
 hipError_t launch_pack_dec_prune(const dal3_layer& L, float* dw1c, float* pq, uint32_t* ident, int32_t* flag, hipStream_t s);
 // plan_k (B, DEC_PLAN_LD), plan_gbc (B, 512), plan_nch (B): see DecPlan
 hipError_t launch_dec_plan(const InsSegW& w, const float* gb, const uint32_t* prune, int B, uint32_t* plan_k, float* plan_gbc,

@@ -1003,6 +1003,40 @@ bool dec_plan_route(int flags, int B, int N) {
     return !(DAL3_ENC_T > 1 && (int64_t)B * N <= 1024 * 64);
 }
 
+// The screened encoder as one crop-resident launch (dal3_enc_screen.hip): when the job has at least
+// DAL3_ENC_RES_MIN_PER_CU whole-crop workgroups per CU; below that the two launches, whose workgroups are a quarter of a
+// short crop. A pure function of B, the CU count and the caller's flags (dal3.h: DAL3_BCN_NO_ENC_RESIDENT selects the two
+// launches for any job). Both give the same bits.
+// Measured (profiles/LEDGER_r16.md, 256 CUs, encoder ms resident / two launches): a round of 256 whole-crop workgroups
+// costs 0.76 of the two launches' time for 256 crops, so a batch a little above a whole number of rounds pays a nearly
+// empty extra round: 300 x 1024 0.388 / 0.345 and 513 x 5120 2.320 / 2.110 lose (the edge at 1 and at 2 per CU); from 3 per
+// CU nothing measured loses — 769 x 5120 3.180 / 3.168 is level within its spread of 0.044, 769 x 1024 0.757 / 0.816,
+// 1025 x 5120 3.896 / 4.173, 4096 x 1024 3.149 / 4.035.
+#ifndef DAL3_ENC_RES_MIN_PER_CU
+#define DAL3_ENC_RES_MIN_PER_CU 3
+#endif
+static int enc_cu_count() {
+    static int n = 0;
+    if (n == 0) {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
+            v = 256;
+        n = v;
+    }
+    return n;
+}
+bool enc_resident_route(int flags, int B, int N) {
+    (void)N;
+    return !(flags & DAL3_BCN_NO_ENC_RESIDENT) && (int64_t)B >= (int64_t)DAL3_ENC_RES_MIN_PER_CU * enc_cu_count();
+}
+// Which fp32 encoder launch_ins_seg_encode takes (dal3.h: dal3_ins_seg_encoder_route), in the order it decides.
+int enc_route(int flags, int B, int N) {
+    if (lat_use((int64_t)B * ((N + 31) / 32), flags, DAL3_LAT_MAX_TILES_ENC)) return DAL3_ENC_ROUTE_LATENCY;
+    if (DAL3_ENC_T > 1 && (int64_t)B * N <= 1024 * 64) return DAL3_ENC_ROUTE_DENSE;
+    if (!DAL3_ENC_SCREEN) return DAL3_ENC_ROUTE_DENSE;
+    return enc_resident_route(flags, B, N) ? DAL3_ENC_ROUTE_RESIDENT : DAL3_ENC_ROUTE_TWO_LAUNCH;
+}
+
 hipError_t launch_ins_seg_encode(const InsSegW& w, BCN pts, int c_in, int B, int N, float* g, hipStream_t s, uint32_t* prune) {
     if (lat_use((int64_t)B * ((N + 31) / 32), pts.flags, DAL3_LAT_MAX_TILES_ENC)) return launch_ins_seg_encode_lat(w, pts, c_in, B, N, g, s);
     constexpr int T = DAL3_ENC_T;

@@ -140,8 +140,12 @@ typedef struct {
  *                                  pass (what items of more than 7936 points always take) instead of both in LDS
  *   DAL3_BCN_NO_DEC_PLAN           fp32 instance segmentation: the decoder computes every dconv1 channel of every tile
  *                                  instead of leaving out the channels that the encoder's bound proves dead for the whole
- *                                  crop (large jobs only; 8 is not a flag and stays refused) */
-enum { DAL3_BCN_NO_SMALL_JOB_KERNELS = 1, DAL3_BCN_NO_WORKLIST = 2, DAL3_BCN_NO_LDS_SAMPLER = 4, DAL3_BCN_NO_DEC_PLAN = 16 };
+ *                                  crop (large jobs only; 8 is not a flag and stays refused)
+ *   DAL3_BCN_NO_ENC_RESIDENT       fp32 instance segmentation: the screened encoder as its two launches (bound, then
+ *                                  candidates; four workgroups per 1024 points) instead of one workgroup per crop, which
+ *                                  jobs of many crops take (dal3_ins_seg_encoder_route) */
+enum { DAL3_BCN_NO_SMALL_JOB_KERNELS = 1, DAL3_BCN_NO_WORKLIST = 2, DAL3_BCN_NO_LDS_SAMPLER = 4, DAL3_BCN_NO_DEC_PLAN = 16,
+       DAL3_BCN_NO_ENC_RESIDENT = 32 };
 
 /* ---- PointNetInstanceSeg.forward (static_model.py:271-296, dynamic_model.py:187-212) plus
  * the mask of point_cloud_masking (static_model.py:59). logits (B,N,2) fp32, mask (B,N) u8.
@@ -156,6 +160,12 @@ size_t dal3_ins_seg_workspace_bytes(int B);
  * gathered to match (-1 for the null channel); off[3] (B) i32, the chunk count (even; 0 = fewer than *min_dead channels
  * are flagged and the decoder runs as without a plan). For tests and measurements. */
 int dal3_ins_seg_plan_layout(int B, size_t off[4], int* min_dead);
+/* Which encoder a DAL3_F32 instance-segmentation job of B crops x N points takes with `flags` (DAL3_BCN_*) on the current
+ * device: the small-job family, the dense throughput kernel (short jobs), the screened encoder's two launches, or its
+ * crop-resident single launch. A pure function of its arguments and the device's CU count; negative (DAL3_EINVAL) for a
+ * bad argument. For tests and measurements: results are bit-identical on every route. */
+enum { DAL3_ENC_ROUTE_LATENCY = 0, DAL3_ENC_ROUTE_DENSE = 1, DAL3_ENC_ROUTE_TWO_LAUNCH = 2, DAL3_ENC_ROUTE_RESIDENT = 3 };
+int dal3_ins_seg_encoder_route(int B, int N, int flags);
 int dal3_ins_seg_forward(const void* packed, int dtype, int c_in, dal3_bcn pts, int B, int N,
                          float* logits, uint8_t* mask, float* global_feat_out,
                          void* workspace, size_t workspace_bytes, dal3_stream stream);

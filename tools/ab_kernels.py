@@ -3,6 +3,9 @@
 three shared-MLP kernels, median and min per build, outputs cross-checked against the first build.
 `seg` is dal3_ins_seg_forward — encoder, per-crop FC, the decoder's plan where the build has one, decoder — as a step runs
 them (`dec` alone is the stand-alone entry, which never has a plan); `seg0` the same call with DAL3_BCN_NO_DEC_PLAN.
+`enc2` / `seg2` are `enc` / `seg` with DAL3_BCN_NO_ENC_RESIDENT (the screened encoder's two launches) where the build knows
+that flag, the same call as `enc` / `seg` where it does not. A -DDAL3_SCREEN_COUNT build prints the screen's counters of one
+`seg` and one `seg2` call.
 
   python tools/ab_kernels.py build_a.so build_b.so ... [--B 4096] [--N 1024] [--rounds 7]
 """
@@ -98,10 +101,19 @@ for name, lib in libs:
                                         hip.ptr(d["g_seg"]), hip.ptr(d["ws_seg"]), d["ws_seg"].numel(), st)
     d["seg"] = seg
     d["seg0"] = (lambda seg=seg: seg(flags=hip.BCN_NO_DEC_PLAN)) if d["has_plan"] else seg
+    d["has_res"] = hasattr(lib, "dal3_ins_seg_encoder_route")
+    two = hip.BCN_NO_ENC_RESIDENT if d["has_res"] else 0
+    d["seg2"] = lambda seg=seg, two=two: seg(flags=two)
+    x2 = hip.bcn(pts)
+    x2.flags |= two
+    if d["has_res"]:
+        print(f"{name}: encoder route {lib.dal3_ins_seg_encoder_route(B, N, 0)} "
+              f"(with DAL3_BCN_NO_ENC_RESIDENT {lib.dal3_ins_seg_encoder_route(B, N, two)})")
     # g is zeroed before EVERY encode, as a step does (nonfinite_rows_kernel): the screened fp32 encoder's second launch
     # reads its thresholds from g, and on a g that already holds the final maxima it would find fewer candidates than it
     # ever does in a step. (The fill is a 16.8-MB memset, ~5 us, the same for every build.)
-    d["enc"] = lambda lib=lib, d=d: (d["g"].zero_(), lib.dal3_ins_seg_encode(hip.ptr(d["w_seg"]), DT, 3, x, B, N, hip.ptr(d["g"]), st))[1]
+    d["enc"] = lambda lib=lib, d=d, x=x: (d["g"].zero_(), lib.dal3_ins_seg_encode(hip.ptr(d["w_seg"]), DT, 3, x, B, N, hip.ptr(d["g"]), st))[1]
+    d["enc2"] = lambda enc=d["enc"], x2=x2: enc(x=x2)
     d["dec"] = lambda lib=lib, d=d: lib.dal3_ins_seg_decode(hip.ptr(d["w_seg"]), DT, 3, x, B, N, hip.ptr(d["gb"]),
                                                             hip.ptr(d["logits"]), hip.ptr(d["mask"]), st)
     d["head"] = lambda lib=lib, d=d: lib.dal3_point_head_forward(hip.HEAD_STATIC_BOX_EST, hip.ptr(d["w_box"]), DT, xo, B, 512,
@@ -135,6 +147,19 @@ for name, lib in libs:
         print(f"{name}: ins_seg_forward: decode tiles {tiles} ({sp_tiles} in the compacted body), dense chunks {dense}, compacted chunks "
               f"{comp} ({comp / max(sp_tiles, 1):.3f} per compacted tile), compact k-steps {steps} ({steps / max(sp_tiles, 1):.3f} per compacted tile), "
               f"live channels among the computed ones {live / max(32.0 * (comp + dense), 1):.4f}")
+    if hasattr(lib, "dal3_debug_screen_counts") and DT == 0:
+        sc = (C.c_ulonglong * 8)()
+        for kind in ("seg", "seg2") if d["has_res"] else ("seg",):
+            torch.cuda.synchronize()
+            lib.dal3_debug_screen_counts(sc, 1)
+            assert d[kind]() == 0, lib.dal3_last_error()
+            torch.cuda.synchronize()
+            lib.dal3_debug_screen_counts(sc, 1)
+            waves, rng, ovf, cand, rounds = (int(v) for v in sc[:5])
+            tiles = B * ((N + 63) // 64) * 2
+            print(f"{name} {kind} {B}x{N}: waves {waves}, dense for range {rng}, list overflow {ovf}, candidates {cand} = "
+                  f"{cand / tiles:.1f} per tile, recompute rounds {rounds} = {rounds / tiles:.2f} per tile")
+        assert d["seg"]() == 0, lib.dal3_last_error()
     if d["has_plan"] and DT == 0:
         off, md = (C.c_size_t * 4)(), C.c_int(0)
         assert lib.dal3_ins_seg_plan_layout(B, off, C.byref(md)) == 0
@@ -149,6 +174,10 @@ torch.cuda.synchronize()
 ref = state[0]
 for (name, _), d in zip(libs, state):
     same = (torch.equal(d["g"], ref["g"]), torch.equal(d["logits"], ref["logits"]), torch.equal(d["bp"], ref["bp"]))
+    assert d["enc2"]() == 0 and d["seg2"]() == 0, _.dal3_last_error()
+    torch.cuda.synchronize()
+    print(f"{name}: two-launch encoder bitwise-equal to the first build (g of enc2, g / logits / mask of seg2) = "
+          f"{(torch.equal(d['g'], ref['g']), torch.equal(d['g_seg'].view(torch.int32), ref['g_seg'].view(torch.int32)), torch.equal(d['lg_seg'].view(torch.int32), ref['lg_seg0'].view(torch.int32)), torch.equal(d['mk_seg'], ref['mk_seg0']))}")
     bits = lambda t: t.view(torch.int32)
     seg_same = (torch.equal(bits(d["g_seg"]), bits(ref["g_seg"])), torch.equal(bits(d["lg_seg"]), bits(ref["lg_seg0"])),
                 torch.equal(d["mk_seg"], ref["mk_seg0"]), torch.equal(bits(d["lg_seg0"]), bits(ref["lg_seg0"])))
@@ -168,7 +197,7 @@ def timed(fn, iters=5):
     return a.elapsed_time(b) / iters
 
 
-KINDS = ("enc", "dec", "head", "seg", "seg0")
+KINDS = ("enc", "enc2", "dec", "head", "seg", "seg2", "seg0")
 res = {(n, k): [] for n, _ in libs for k in KINDS}
 for r in range(args.rounds):
     for k in KINDS:
