@@ -387,6 +387,18 @@ class AugmentBoxesArgs(C.Structure):
                 ("range", C.c_float * 4), ("out", vp), ("out_count", vp), ("status", vp)]
 
 
+OPTIM_CHUNK, OPTIM_NORM_SPAN = 4096, 16384      # DAL3_OPTIM_CHUNK, DAL3_OPTIM_NORM_SPAN
+OPTIM_TRUE_WD, OPTIM_CLIP, OPTIM_FUSED_ZERO = 1, 2, 4
+# dal3_optim_hyper's 8-byte slots, as indices into the block seen as int64 or as float64
+(OPTIM_STEP, OPTIM_LR, OPTIM_BETA1, OPTIM_BETA2, OPTIM_EPS, OPTIM_WD, OPTIM_MAX_NORM, OPTIM_FLAGS, OPTIM_TOTAL_STEP,
+ OPTIM_TABLE, OPTIM_SLOTS) = range(11)
+
+
+class OptimChunk(C.Structure):
+    """dal3_optim_chunk (24 bytes)"""
+    _fields_ = [("param", vp), ("offset", C.c_int64), ("count", C.c_int32), ("decay", C.c_int32)]
+
+
 # every symbol include/dal3.h declares: (restype, argtypes)
 _i, _i64, _u64, _sz = C.c_int, C.c_int64, C.c_uint64, C.c_size_t
 SIGNATURES = {
@@ -479,6 +491,10 @@ SIGNATURES = {
     "dal3_augment_points_workspace_bytes": (_sz, [_i64, _i64]),
     "dal3_augment_points": (_i, [C.POINTER(AugmentPointsArgs), vp]),
     "dal3_augment_boxes": (_i, [C.POINTER(AugmentBoxesArgs), vp]),
+    "dal3_optim_partials": (_i64, [_i64]),
+    "dal3_optim_grad_norm": (_i, [vp, _i64, vp, vp, vp]),
+    "dal3_optim_step": (_i, [vp, _i64, vp, vp, vp, _i64, vp, vp, vp]),
+    "dal3_optim_total_norm": (_i, [vp, _i64, vp, vp]),
     "dal3_crop_workspace_bytes": (_sz, [_i64, _i64]),
     "dal3_crop_count": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, _sz, vp]),
     "dal3_crop_fill": (_i, [vp, vp, vp, vp, vp, _i, _i64, _i64, vp, vp, vp, vp, vp, _i64, vp, _sz, vp]),

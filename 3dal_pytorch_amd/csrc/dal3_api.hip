@@ -2696,3 +2696,33 @@ extern "C" int dal3_augment_boxes(const dal3_augment_boxes_args* args, dal3_stre
     HIP_TRY(launch_augment_boxes(args, static_cast<hipStream_t>(stream)));
     return 0;
 }
+
+// ---------------------------------------------------------------------------------- the optimiser step
+static bool optim_flat_ok(int64_t n_flat) { return n_flat > 0 && (n_flat & 3) == 0 && n_flat < ((int64_t)1 << 40); }
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+extern "C" int64_t dal3_optim_partials(int64_t n_flat) { return optim_flat_ok(n_flat) ? optim_partials(n_flat) : 0; }
+
+extern "C" int dal3_optim_grad_norm(const float* grad, int64_t n_flat, dal3_optim_hyper* hyper, double* partials, dal3_stream stream) {
+    if (!optim_flat_ok(n_flat)) return fail(DAL3_EINVAL, "optim_grad_norm: n_flat must be a positive multiple of 4 below 2^40");
+    if (!grad || !hyper || !partials || !aligned16(grad) || !aligned16(hyper)) return fail(DAL3_EINVAL, "optim_grad_norm: null or misaligned argument");
+    HIP_TRY(launch_optim_grad_norm(grad, n_flat, hyper, partials, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+extern "C" int dal3_optim_step(const dal3_optim_chunk* chunks, int64_t n_chunks, float* grad, float* exp_avg, float* exp_avg_sq,
+                               int64_t n_flat, const double* partials, dal3_optim_hyper* hyper, dal3_stream stream) {
+    if (!optim_flat_ok(n_flat)) return fail(DAL3_EINVAL, "optim_step: n_flat must be a positive multiple of 4 below 2^40");
+    if (n_chunks < 1 || n_chunks > 0x7fffffff) return fail(DAL3_EINVAL, "optim_step: bad n_chunks");
+    if (!chunks || !grad || !exp_avg || !exp_avg_sq || !partials || !hyper || !aligned16(grad) || !aligned16(exp_avg) ||
+        !aligned16(exp_avg_sq) || !aligned16(hyper))
+        return fail(DAL3_EINVAL, "optim_step: null or misaligned argument");
+    HIP_TRY(launch_optim_step(chunks, n_chunks, grad, exp_avg, exp_avg_sq, n_flat, partials, hyper, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+extern "C" int dal3_optim_total_norm(const double* partials, int64_t n_partials, float* out, dal3_stream stream) {
+    if (!partials || !out || n_partials < 1) return fail(DAL3_EINVAL, "optim_total_norm: null argument or no partials");
+    HIP_TRY(launch_optim_total_norm(partials, n_partials, out, static_cast<hipStream_t>(stream)));
+    return 0;
+}

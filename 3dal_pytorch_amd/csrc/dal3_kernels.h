@@ -624,3 +624,9 @@ hipError_t launch_gt_paste_select(const dal3_gt_paste_args* a, hipStream_t s);
 size_t augment_points_workspace_bytes(int64_t B, int64_t n);
 bool launch_augment_points(const dal3_augment_points_args* a, hipStream_t s, hipError_t* err);
 hipError_t launch_augment_boxes(const dal3_augment_boxes_args* a, hipStream_t s);
+// the optimiser step (dal3_optim.hip): the gradients' sum of squares per span, the fused clip + decay + Adam update
+int64_t optim_partials(int64_t n_flat);
+hipError_t launch_optim_grad_norm(const float* grad, int64_t n_flat, dal3_optim_hyper* hyper, double* partials, hipStream_t s);
+hipError_t launch_optim_step(const dal3_optim_chunk* chunks, int64_t n_chunks, float* grad, float* exp_avg, float* exp_avg_sq,
+                             int64_t n_flat, const double* partials, dal3_optim_hyper* hyper, hipStream_t s);
+hipError_t launch_optim_total_norm(const double* partials, int64_t n_partials, float* out, hipStream_t s);

@@ -2039,6 +2039,56 @@ size_t dal3_augment_points_workspace_bytes(int64_t B, int64_t n);
 int dal3_augment_points(const dal3_augment_points_args* args, dal3_stream stream);
 int dal3_augment_boxes(const dal3_augment_boxes_args* args, dal3_stream stream);
 
+/* ---- The optimiser step (det3d/solver/fastai_optim.py OptimWrapper over torch.optim.Adam, learning_schedules_fastai.py,
+ * OptimizerHook's clip_grad_norm_): Adam with decoupled or coupled weight decay, the gradient clip and a schedule table,
+ * for any number of float32 parameters in two launches, nothing read back. (Additions only; DAL3_VERSION stays.)
+ *
+ * Storage: three flat float32 device buffers of n_flat elements, gradients, exp_avg and exp_avg_sq, with the tensors'
+ * slices back to back, each slice padded to a multiple of 4 elements; the pad is zero and stays zero. The parameters stay
+ * where they are: row i of the chunk table covers elements [i0, i0 + count) of one tensor, count <= DAL3_OPTIM_CHUNK, by
+ * the pointer to the tensor's element i0 (i0 a multiple of DAL3_OPTIM_CHUNK) and the flat offset of the same element.
+ * The hyperparameter block lives on the device; the caller writes it with ordinary stream-ordered copies.
+ *
+ * dal3_optim_grad_norm: partials[w] = the float64 sum of squares of the gradient elements [w S, (w + 1) S), S =
+ *   DAL3_OPTIM_NORM_SPAN, in a fixed order, and hyper->step += 1 (by workgroup 0; one call per step, always before
+ *   dal3_optim_step on the same stream). partials holds dal3_optim_partials(n_flat) values.
+ * dal3_optim_step: with t = hyper->step, (lr, beta1) = table[min(t, total_step) - 1] when a table is attached, else the
+ *   block's scalars (with a table the row taken is left in hyper->lr, hyper->beta1); every product of hyperparameters in float64, rounded to float32 once, the element arithmetic float32:
+ *     DAL3_OPTIM_CLIP      c = min(1, max_norm / (sqrt(sum of partials) + 1e-6)), a NaN kept; g = g c, written back
+ *                          (c == 1 keeps the bits). The sum is taken in one fixed order by every workgroup.
+ *     decay rows, wd != 0  DAL3_OPTIM_TRUE_WD: p = p (1 - wd lr); otherwise g' = g + wd p (not written back)
+ *     exp_avg = lerp(exp_avg, g, 1 - beta1); exp_avg_sq = exp_avg_sq beta2 + (1 - beta2) g g
+ *     p = p - lr / (1 - beta1^t) * exp_avg / (sqrt(exp_avg_sq) / sqrt(1 - beta2^t) + eps)
+ *     DAL3_OPTIM_FUSED_ZERO the gradient slice is written as zeros instead
+ *   IEEE semantics throughout: a non-finite gradient poisons what it poisons in torch. The norm is accumulated in float64,
+ *   so gradients whose squares overflow float32 still have a finite norm here.
+ * dal3_optim_total_norm: out[0] = (float)sqrt(sum of partials), the same sum as the step's. Read-only.
+ * 1 <= n_chunks < 2^31, n_flat a positive multiple of 4 below 2^40, all buffers 16-byte aligned. */
+#define DAL3_OPTIM_CHUNK 4096
+#define DAL3_OPTIM_NORM_SPAN 16384
+enum { DAL3_OPTIM_TRUE_WD = 1, DAL3_OPTIM_CLIP = 2, DAL3_OPTIM_FUSED_ZERO = 4 };   /* dal3_optim_hyper.flags */
+
+typedef struct dal3_optim_chunk {
+    float* param;                        /* the tensor's element i0 */
+    int64_t offset;                      /* of the same element in the flat buffers; a multiple of 4 */
+    int32_t count;                       /* 1 .. DAL3_OPTIM_CHUNK */
+    int32_t decay;                       /* nonzero: weight decay applies to this tensor */
+} dal3_optim_chunk;
+
+typedef struct dal3_optim_hyper {        /* 80 bytes, every field 8 bytes wide */
+    int64_t step;                        /* steps taken so far */
+    double lr, beta1, beta2, eps, wd, max_norm;
+    int64_t flags;                       /* DAL3_OPTIM_* */
+    int64_t total_step;                  /* rows of table */
+    const double* table;                 /* (total_step, 2) device: lr, beta1 of step 1, 2, ...; NULL: the scalars */
+} dal3_optim_hyper;
+
+int64_t dal3_optim_partials(int64_t n_flat);
+int dal3_optim_grad_norm(const float* grad, int64_t n_flat, dal3_optim_hyper* hyper, double* partials, dal3_stream stream);
+int dal3_optim_step(const dal3_optim_chunk* chunks, int64_t n_chunks, float* grad, float* exp_avg, float* exp_avg_sq,
+                    int64_t n_flat, const double* partials, dal3_optim_hyper* hyper, dal3_stream stream);
+int dal3_optim_total_norm(const double* partials, int64_t n_partials, float* out, dal3_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
