@@ -4,6 +4,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "dal3_block.h"     // Carver: the workspace carving
 #include "dal3_kernels.h"
 #include "dal3_lp.h"
@@ -78,14 +80,18 @@ static InsSegW ins_seg_walk(Cursor& c) {
     return w;
 }
 
-size_t ins_seg_packed_floats(int) {
+// A layout is a WALK: a function that takes the blob's sections from a Cursor, in order, and returns the struct of their
+// addresses. measure() runs it on a null base (-> the sections' size in floats), view() on a packed blob.
+template <class Walk, class... A>
+static size_t measure(Walk walk, A... a) {
     Cursor c{nullptr, 0};
-    ins_seg_walk(c);
-    return c.off + DAL3_BLOB_TAIL_FLOATS;
+    walk(c, a...);
+    return c.off;
 }
-InsSegW ins_seg_view(const float* base, int) {
-    Cursor c{base, 0};
-    return ins_seg_walk(c);
+template <class Walk, class... A>
+static auto view(const void* base, Walk walk, A... a) {
+    Cursor c{static_cast<const float*>(base), 0};
+    return walk(c, a...);
 }
 
 void point_head_dims(int head_kind, int* c_in, int* ks, int c[4], int* n_fc, int fc_in[3], int fc_out[3]) {
@@ -105,6 +111,20 @@ void point_head_dims(int head_kind, int* c_in, int* ks, int c[4], int* n_fc, int
     }
 }
 
+// the FC sections of a head: per layer its row-major weight, then its bias padded to 32
+static FcW fc_walk(Cursor& cur, int n, const int fi[3], const int fo[3]) {
+    FcW f;
+    f.n = n;
+    for (int i = 0; i < 3; ++i) {
+        f.c_in[i] = fi[i];
+        f.c_out[i] = fo[i];
+        f.relu[i] = !(n == 3 && i == 2);                    // a third layer is a box estimator's output: no ReLU
+        f.w[i] = i < n ? cur.take((size_t)fi[i] * fo[i]) : nullptr;
+        f.b[i] = i < n ? cur.take((fo[i] + 31) / 32 * 32) : nullptr;
+    }
+    return f;
+}
+
 static PointHeadW point_head_walk(Cursor& cur, int head_kind) {
     int c_in, ks, c[4], n_fc, fi[3], fo[3];
     point_head_dims(head_kind, &c_in, &ks, c, &n_fc, fi, fo);
@@ -113,14 +133,7 @@ static PointHeadW point_head_walk(Cursor& cur, int head_kind) {
     w.b1 = cur.take(c[0]);    w.b2 = cur.take(c[1]);    w.b3 = cur.take(c[2]);    w.b4 = cur.take(c[3]);
     w.stream = cur.take4(((size_t)(c[1] / 32) * (c[0] / 32) + (size_t)(c[2] / 32) * (c[1] / 32) +
                           (size_t)(c[3] / 32) * (c[2] / 32)) * 1024);
-    w.fc.n = n_fc;
-    for (int i = 0; i < 3; ++i) {
-        w.fc.c_in[i] = fi[i];
-        w.fc.c_out[i] = fo[i];
-        w.fc.relu[i] = !(head_kind == DAL3_HEAD_STATIC_BOX_EST && i == 2);
-        w.fc.w[i] = i < n_fc ? cur.take((size_t)fi[i] * fo[i]) : nullptr;
-        w.fc.b[i] = i < n_fc ? cur.take((fo[i] + 31) / 32 * 32) : nullptr;
-    }
+    w.fc = fc_walk(cur, n_fc, fi, fo);
     // the screened conv4's copies (heads with conv4 256 -> 512): fp32 rows, fp16 fragments, bound coefficients, flag
     const bool scr = c[2] == 256 && c[3] == 512;
     w.w4row = scr ? cur.take((size_t)512 * 256) : nullptr;
@@ -129,147 +142,46 @@ static PointHeadW point_head_walk(Cursor& cur, int head_kind) {
     w.scr_flag = scr ? reinterpret_cast<const int32_t*>(cur.take(64)) : nullptr;
     return w;
 }
-size_t point_head_packed_floats(int head_kind) {
-    Cursor c{nullptr, 0};
-    point_head_walk(c, head_kind);
-    return c.off + DAL3_BLOB_TAIL_FLOATS;
-}
-PointHeadW point_head_view(const float* base, int head_kind) {
-    Cursor c{base, 0};
-    return point_head_walk(c, head_kind);
-}
 
 static const int kDynFcIn[3] = {384, 128, 128}, kDynFcOut[3] = {128, 128, 39};
-static FcW fc_head_walk(Cursor& cur) {
-    FcW f;
-    f.n = 3;
-    for (int i = 0; i < 3; ++i) {
-        f.c_in[i] = kDynFcIn[i];
-        f.c_out[i] = kDynFcOut[i];
-        f.relu[i] = i < 2;
-        f.w[i] = cur.take((size_t)kDynFcIn[i] * kDynFcOut[i]);
-        f.b[i] = cur.take((kDynFcOut[i] + 31) / 32 * 32);
-    }
-    return f;
-}
-size_t fc_head_packed_floats() {
-    Cursor c{nullptr, 0};
-    fc_head_walk(c);
-    return c.off;
-}
-FcW fc_head_view(const float* base) {
-    Cursor c{base, 0};
-    return fc_head_walk(c);
-}
+static FcW fc_head_walk(Cursor& cur) { return fc_walk(cur, 3, kDynFcIn, kDynFcOut); }
 
-// ---- 16-bit heads: fp32 sections first (float cursor), then the fragment streams (bytes)
-static InsSegLpW ins_seg_lp_walk(Cursor& c) {
-    InsSegLpW w;
+// ---- 16-bit and "f16x3" ins_seg (W: InsSegLpW / InsSegX3W, the same sections): fp32 sections first, then the two fragment
+// streams in ring segments (f16x3: 18 / 27 segments of 32 KiB, and no dw5 in bias_dec)
+template <class W>
+static W ins_seg_16_walk(Cursor& c) {
+    constexpr bool x3 = std::is_same<W, InsSegX3W>::value;
+    W w;
     w.w1 = c.take(2 * 2 * 64);
     w.b1 = c.take(64);
     w.bias_enc = c.take(1280);
-    w.bias_dec = c.take(864);
+    w.bias_dec = c.take(x3 ? 608 : 864);
     w.dw1g = c.take(512 * 1024);
     w.db1 = c.take(512);
-    w.enc_stream = reinterpret_cast<const uint16_t*>(c.take((size_t)LP_ENC_SEGS * LP_ENC_SEG * 256));
-    w.dec_stream = reinterpret_cast<const uint16_t*>(c.take((size_t)LP_DEC_SEGS * LP_DEC_SEG * 256));
+    w.enc_stream = reinterpret_cast<const uint16_t*>(c.take(x3 ? (size_t)18 * 32 * 256 : (size_t)LP_ENC_SEGS * LP_ENC_SEG * 256));
+    w.dec_stream = reinterpret_cast<const uint16_t*>(c.take(x3 ? (size_t)27 * 32 * 256 : (size_t)LP_DEC_SEGS * LP_DEC_SEG * 256));
     return w;
 }
-size_t ins_seg_lp_packed_bytes() {
-    Cursor c{nullptr, 0};
-    ins_seg_lp_walk(c);
-    return c.off * sizeof(float);
-}
-InsSegLpW ins_seg_lp_view(const void* base) {
-    Cursor c{static_cast<const float*>(base), 0};
-    return ins_seg_lp_walk(c);
-}
 static int lp_tps(int kt, int mt) { return lp_tiles_per_seg(kt, mt); }
-int point_head_lp_segments(int head_kind) {
+static int point_head_lp_segments(int head_kind) {
     int c_in, ks, c[4], n_fc, fi[3], fo[3];
     point_head_dims(head_kind, &c_in, &ks, c, &n_fc, fi, fo);
     int n = 0;
     for (int l = 1; l < 4; ++l) n += (c[l] / 32) / lp_tps(c[l - 1] / 32, c[l] / 32);
     return n;
 }
-static PointHeadLpW point_head_lp_walk(Cursor& cur, int head_kind) {
+// ---- 16-bit and "f16x3" heads: one blob shape; the f16x3 stream holds (hi, lo) fragment pairs, padded to whole ring segments
+static PointHeadLpW point_head_16_walk(Cursor& cur, int head_kind, bool x3) {
     int c_in, ks, c[4], n_fc, fi[3], fo[3];
     point_head_dims(head_kind, &c_in, &ks, c, &n_fc, fi, fo);
     PointHeadLpW w;
     w.w1 = cur.take((size_t)(c[0] / 32) * ks * 64);
     w.b1 = cur.take(c[0]);
     w.bias = cur.take(c[1] + c[2] + c[3]);
-    w.fc.n = n_fc;
-    for (int i = 0; i < 3; ++i) {
-        w.fc.c_in[i] = fi[i];
-        w.fc.c_out[i] = fo[i];
-        w.fc.relu[i] = !(head_kind == DAL3_HEAD_STATIC_BOX_EST && i == 2);
-        w.fc.w[i] = i < n_fc ? cur.take((size_t)fi[i] * fo[i]) : nullptr;
-        w.fc.b[i] = i < n_fc ? cur.take((fo[i] + 31) / 32 * 32) : nullptr;
-    }
-    w.stream = reinterpret_cast<const uint16_t*>(cur.take((size_t)point_head_lp_segments(head_kind) * LP_HEAD_SEG * 256));
+    w.fc = fc_walk(cur, n_fc, fi, fo);
+    const int segs = x3 ? point_head_x3_segments(head_kind) : point_head_lp_segments(head_kind);
+    w.stream = reinterpret_cast<const uint16_t*>(cur.take((size_t)segs * (x3 ? 32 : LP_HEAD_SEG) * 256));   // fragments of 256 floats
     return w;
-}
-size_t point_head_lp_packed_bytes(int head_kind) {
-    Cursor c{nullptr, 0};
-    point_head_lp_walk(c, head_kind);
-    return c.off * sizeof(float);
-}
-PointHeadLpW point_head_lp_view(const void* base, int head_kind) {
-    Cursor c{static_cast<const float*>(base), 0};
-    return point_head_lp_walk(c, head_kind);
-}
-
-// ---- "f16x3" ins_seg: fp32 sections, then the two fragment streams (18 / 27 segments of 32 KiB)
-static InsSegX3W ins_seg_x3_walk(Cursor& c) {
-    InsSegX3W w;
-    w.w1 = c.take(2 * 2 * 64);
-    w.b1 = c.take(64);
-    w.bias_enc = c.take(1280);
-    w.bias_dec = c.take(608);
-    w.dw1g = c.take(512 * 1024);
-    w.db1 = c.take(512);
-    w.enc_stream = reinterpret_cast<const uint16_t*>(c.take((size_t)18 * 32 * 256));
-    w.dec_stream = reinterpret_cast<const uint16_t*>(c.take((size_t)27 * 32 * 256));
-    return w;
-}
-size_t ins_seg_x3_packed_bytes() {
-    Cursor c{nullptr, 0};
-    ins_seg_x3_walk(c);
-    return c.off * sizeof(float) + DAL3_BLOB_TAIL_FLOATS * sizeof(float);
-}
-InsSegX3W ins_seg_x3_view(const void* base) {
-    Cursor c{static_cast<const float*>(base), 0};
-    return ins_seg_x3_walk(c);
-}
-
-// ---- "f16x3" heads: the 16-bit heads' blob with a stream of (hi, lo) fragment pairs, padded to whole ring segments
-static PointHeadX3W point_head_x3_walk(Cursor& cur, int head_kind) {
-    int c_in, ks, c[4], n_fc, fi[3], fo[3];
-    point_head_dims(head_kind, &c_in, &ks, c, &n_fc, fi, fo);
-    PointHeadX3W w;
-    w.w1 = cur.take((size_t)(c[0] / 32) * ks * 64);
-    w.b1 = cur.take(c[0]);
-    w.bias = cur.take(c[1] + c[2] + c[3]);
-    w.fc.n = n_fc;
-    for (int i = 0; i < 3; ++i) {
-        w.fc.c_in[i] = fi[i];
-        w.fc.c_out[i] = fo[i];
-        w.fc.relu[i] = !(head_kind == DAL3_HEAD_STATIC_BOX_EST && i == 2);
-        w.fc.w[i] = i < n_fc ? cur.take((size_t)fi[i] * fo[i]) : nullptr;
-        w.fc.b[i] = i < n_fc ? cur.take((fo[i] + 31) / 32 * 32) : nullptr;
-    }
-    w.stream = reinterpret_cast<const uint16_t*>(cur.take((size_t)point_head_x3_segments(head_kind) * 32 * 256));   // 32 fragments of 256 floats per segment
-    return w;
-}
-size_t point_head_x3_packed_bytes(int head_kind) {
-    Cursor c{nullptr, 0};
-    point_head_x3_walk(c, head_kind);
-    return c.off * sizeof(float) + DAL3_BLOB_TAIL_FLOATS * sizeof(float);
-}
-PointHeadX3W point_head_x3_view(const void* base, int head_kind) {
-    Cursor c{static_cast<const float*>(base), 0};
-    return point_head_x3_walk(c, head_kind);
 }
 
 // ---------------------------------------------------------------------------------- packing
@@ -287,10 +199,8 @@ static int check_layer(const dal3_layer& L, int c_in, int c_out, const char* wha
 
 // fragment blocks of one layer written at fragment offset `frag` of a stream (+ its folded bias)
 static int pack_frag(const dal3_layer& L, int mode, int col_off, int n_cols, const f32x4* stream, int frag,
-                     const float* b, hipStream_t s, int grp_blocks = 0, int64_t a0 = 0, int64_t a1 = 0,
-                     int64_t stride = 0) {
-    HIP_TRY(launch_pack_weight(L, mode, col_off, n_cols, L.c_out / 32, n_cols / 32, mut(stream) + (size_t)frag * 256, s,
-                               grp_blocks, a0, a1, stride));
+                     const float* b, hipStream_t s, PackGroups G = PackGroups{}) {
+    HIP_TRY(launch_pack_weight(L, mode, col_off, n_cols, L.c_out / 32, n_cols / 32, mut(stream) + (size_t)frag * 256, s, G));
     if (b) HIP_TRY(launch_pack_bias(L, mut(b), s));
     return 0;
 }
@@ -304,6 +214,41 @@ static int pack_fc(const dal3_layer* L, const FcW& f, hipStream_t s) {
     return 0;
 }
 
+// what the 16-bit and the f16x3 blob of ins_seg open with (W: InsSegLpW / InsSegX3W): the fp32 first layer, the folded
+// biases in the order the kernels read them, the per-crop part of dconv1. dconv5 is a row-major fp32 layer of the 16-bit
+// decoder (bias_dec + 576: dw5, + 832: db5) and a fragment layer of the f16x3 one (bias_dec + 576: db5)
+template <class W>
+static int pack_ins_seg_16_open(const dal3_layer* L, int c_in, const W& w, bool x3, hipStream_t s) {
+    float* be = mut(w.bias_enc);
+    float* bd = mut(w.bias_dec);
+    HIP_TRY(launch_pack_weight(L[0], PACK_FIRST, 0, c_in, 2, 2, mut(w.w1), s));
+    HIP_TRY(launch_pack_bias(L[0], mut(w.b1), s));
+    HIP_TRY(launch_pack_bias(L[1], be, s));
+    HIP_TRY(launch_pack_bias(L[2], be + 64, s));
+    HIP_TRY(launch_pack_bias(L[3], be + 128, s));
+    HIP_TRY(launch_pack_bias(L[4], be + 256, s));
+    HIP_TRY(launch_pack_bias(L[1], bd, s));
+    HIP_TRY(launch_pack_bias(L[6], bd + 64, s));
+    HIP_TRY(launch_pack_bias(L[7], bd + 320, s));
+    HIP_TRY(launch_pack_bias(L[8], bd + 448, s));
+    if (!x3) HIP_TRY(launch_pack_weight(L[9], PACK_ROWMAJOR, 0, 128, 0, 0, bd + 576, s));
+    HIP_TRY(launch_pack_bias(L[9], bd + (x3 ? 576 : 832), s));        // db5: 2 real rows, padded to 32
+    HIP_TRY(launch_pack_weight(L[5], PACK_ROWMAJOR, 64, 1024, 0, 0, mut(w.dw1g), s));
+    HIP_TRY(launch_pack_bias(L[5], mut(w.db1), s));
+    return 0;
+}
+
+// what every point head's blob opens with: the fp32 first layer and the folded biases of conv1 .. conv4
+static int pack_head_open(const dal3_layer* L, int c_in, int ks, int c1, const float* w1, const float* b1, const float* b2,
+                          const float* b3, const float* b4, hipStream_t s) {
+    HIP_TRY(launch_pack_weight(L[0], PACK_FIRST, 0, c_in, c1 / 32, ks, mut(w1), s));
+    HIP_TRY(launch_pack_bias(L[0], mut(b1), s));
+    HIP_TRY(launch_pack_bias(L[1], mut(b2), s));
+    HIP_TRY(launch_pack_bias(L[2], mut(b3), s));
+    HIP_TRY(launch_pack_bias(L[3], mut(b4), s));
+    return 0;
+}
+
 extern "C" int dal3_pack_weights(int head_kind, const dal3_layer* L, int n_layers, int dtype, void* packed_dev,
                                  size_t* bytes_inout, dal3_stream stream) {
     if (dtype != DAL3_F32 && dtype != DAL3_BF16 && dtype != DAL3_F16 && dtype != DAL3_F16X3)
@@ -311,20 +256,23 @@ extern "C" int dal3_pack_weights(int head_kind, const dal3_layer* L, int n_layer
     if (!bytes_inout) return fail(DAL3_EINVAL, "dal3_pack_weights: bytes_inout is NULL");
     const bool x3 = dtype == DAL3_F16X3;
     const bool lp = dtype != DAL3_F32 && !x3;
-    size_t need;
+    size_t floats;                                          // (the blobs a ring reads end in a tail; the 16-bit rings' do not)
     switch (head_kind) {
         case DAL3_HEAD_INS_SEG:
-            need = x3 ? ins_seg_x3_packed_bytes() : lp ? ins_seg_lp_packed_bytes() : ins_seg_packed_floats(0) * sizeof(float);
+            floats = x3 ? measure(ins_seg_16_walk<InsSegX3W>) + DAL3_BLOB_TAIL_FLOATS
+                        : lp ? measure(ins_seg_16_walk<InsSegLpW>) : measure(ins_seg_walk) + DAL3_BLOB_TAIL_FLOATS;
             break;
         case DAL3_HEAD_STATIC_BOX_EST:
         case DAL3_HEAD_POINT_EMB:
         case DAL3_HEAD_BOX_EMB:
-            need = x3 ? point_head_x3_packed_bytes(head_kind)
-                      : lp ? point_head_lp_packed_bytes(head_kind) : point_head_packed_floats(head_kind) * sizeof(float);
+            floats = x3 ? measure(point_head_16_walk, head_kind, true) + DAL3_BLOB_TAIL_FLOATS
+                        : lp ? measure(point_head_16_walk, head_kind, false)
+                             : measure(point_head_walk, head_kind) + DAL3_BLOB_TAIL_FLOATS;
             break;
-        case DAL3_HEAD_DYNAMIC_BOX_EST: need = fc_head_packed_floats() * sizeof(float); break;   // FC only: fp32 in every dtype
+        case DAL3_HEAD_DYNAMIC_BOX_EST: floats = measure(fc_head_walk); break;   // FC only: fp32 in every dtype
         default: return fail(DAL3_EINVAL, "dal3_pack_weights: unknown head_kind %d", head_kind);
     }
+    const size_t need = floats * sizeof(float);
     if (!packed_dev) {
         *bytes_inout = need;
         return 0;
@@ -333,7 +281,6 @@ extern "C" int dal3_pack_weights(int head_kind, const dal3_layer* L, int n_layer
     if (!L) return fail(DAL3_EINVAL, "dal3_pack_weights: layers is NULL");
     if (reinterpret_cast<uintptr_t>(packed_dev) & 255) return fail(DAL3_EINVAL, "packed_dev must be 256-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const float* base = static_cast<const float*>(packed_dev);
     HIP_TRY(hipMemsetAsync(packed_dev, 0, need, s));
 
     if (head_kind == DAL3_HEAD_INS_SEG) {
@@ -343,26 +290,12 @@ extern "C" int dal3_pack_weights(int head_kind, const dal3_layer* L, int n_layer
         static const int co[10] = {64, 64, 64, 128, 1024, 512, 256, 128, 128, 2};
         static const int ci[10] = {0, 64, 64, 64, 128, 1088, 512, 256, 128, 128};
         for (int i = 0; i < 10; ++i) TRY(check_layer(L[i], i == 0 ? c_in : ci[i], co[i], "ins_seg layer"));
+        const int64_t F = 512;                                        // 16-bit elements per fragment
         if (x3) {
-            const InsSegX3W w = ins_seg_x3_view(packed_dev);
+            const InsSegX3W w = view(packed_dev, ins_seg_16_walk<InsSegX3W>);
             uint16_t* enc = const_cast<uint16_t*>(w.enc_stream);
             uint16_t* dec = const_cast<uint16_t*>(w.dec_stream);
-            float* be = mut(w.bias_enc);
-            float* bd = mut(w.bias_dec);
-            const int64_t F = 512;                                    // 16-bit elements per fragment
-            HIP_TRY(launch_pack_weight(L[0], PACK_FIRST, 0, c_in, 2, 2, mut(w.w1), s));
-            HIP_TRY(launch_pack_bias(L[0], mut(w.b1), s));
-            HIP_TRY(launch_pack_bias(L[1], be, s));
-            HIP_TRY(launch_pack_bias(L[2], be + 64, s));
-            HIP_TRY(launch_pack_bias(L[3], be + 128, s));
-            HIP_TRY(launch_pack_bias(L[4], be + 256, s));
-            HIP_TRY(launch_pack_bias(L[1], bd, s));
-            HIP_TRY(launch_pack_bias(L[6], bd + 64, s));
-            HIP_TRY(launch_pack_bias(L[7], bd + 320, s));
-            HIP_TRY(launch_pack_bias(L[8], bd + 448, s));
-            HIP_TRY(launch_pack_bias(L[9], bd + 576, s));             // db5: 2 real rows, padded to 32
-            HIP_TRY(launch_pack_weight(L[5], PACK_ROWMAJOR, 64, 1024, 0, 0, mut(w.dw1g), s));
-            HIP_TRY(launch_pack_bias(L[5], mut(w.db1), s));
+            TRY(pack_ins_seg_16_open(L, c_in, w, true, s));
             // encode stream (fragments): conv2 @0 (16) | conv3 @16 (16) | conv4 @32 (32) | conv5 @64 (512)
             HIP_TRY(launch_pack_weight_x3(L[1], 0, 0, 64, 2, 2, enc, s));
             HIP_TRY(launch_pack_weight_x3(L[2], 0, 0, 64, 2, 2, enc + 16 * F, s));
@@ -372,34 +305,18 @@ extern "C" int dal3_pack_weights(int head_kind, const dal3_layer* L, int n_layer
             // 15 x { A_{c+1} @24+40c (8), D_c @32+40c (32) } | D_15 @624 (32) | dconv3 @656 (128) | dconv4 @784 (64) |
             // dconv5 @848 (16: one out-tile, rows 0, 1 real)
             HIP_TRY(launch_pack_weight_x3(L[1], 0, 0, 64, 2, 2, dec, s));
-            HIP_TRY(launch_pack_weight_x3(L[5], 0, 0, 64, 16, 2, dec, s, 2, 16 * F, 24 * F, 40 * F));
-            HIP_TRY(launch_pack_weight_x3(L[6], 1, 0, 512, 8, 16, dec, s, 8, 32 * F, 72 * F, 40 * F, 624 * F));
+            HIP_TRY(launch_pack_weight_x3(L[5], 0, 0, 64, 16, 2, dec, s, PackGroups{2, 16 * F, 24 * F, 40 * F}));
+            HIP_TRY(launch_pack_weight_x3(L[6], 1, 0, 512, 8, 16, dec, s, PackGroups{8, 32 * F, 72 * F, 40 * F, 624 * F}));
             HIP_TRY(launch_pack_weight_x3(L[7], 0, 0, 256, 4, 8, dec + 656 * F, s));
             HIP_TRY(launch_pack_weight_x3(L[8], 0, 0, 128, 4, 4, dec + 784 * F, s));
             HIP_TRY(launch_pack_weight_x3(L[9], 0, 0, 128, 1, 4, dec + 848 * F, s));
             return 0;
         }
         if (lp) {
-            const InsSegLpW w = ins_seg_lp_view(packed_dev);
+            const InsSegLpW w = view(packed_dev, ins_seg_16_walk<InsSegLpW>);
             uint16_t* enc = const_cast<uint16_t*>(w.enc_stream);
             uint16_t* dec = const_cast<uint16_t*>(w.dec_stream);
-            float* be = mut(w.bias_enc);
-            float* bd = mut(w.bias_dec);
-            const int64_t F = 512;                                    // 16-bit elements per fragment
-            HIP_TRY(launch_pack_weight(L[0], PACK_FIRST, 0, c_in, 2, 2, mut(w.w1), s));
-            HIP_TRY(launch_pack_bias(L[0], mut(w.b1), s));
-            HIP_TRY(launch_pack_bias(L[1], be, s));
-            HIP_TRY(launch_pack_bias(L[2], be + 64, s));
-            HIP_TRY(launch_pack_bias(L[3], be + 128, s));
-            HIP_TRY(launch_pack_bias(L[4], be + 256, s));
-            HIP_TRY(launch_pack_bias(L[1], bd, s));
-            HIP_TRY(launch_pack_bias(L[6], bd + 64, s));
-            HIP_TRY(launch_pack_bias(L[7], bd + 320, s));
-            HIP_TRY(launch_pack_bias(L[8], bd + 448, s));
-            HIP_TRY(launch_pack_weight(L[9], PACK_ROWMAJOR, 0, 128, 0, 0, bd + 576, s));
-            HIP_TRY(launch_pack_bias(L[9], bd + 832, s));
-            HIP_TRY(launch_pack_weight(L[5], PACK_ROWMAJOR, 64, 1024, 0, 0, mut(w.dw1g), s));
-            HIP_TRY(launch_pack_bias(L[5], mut(w.db1), s));
+            TRY(pack_ins_seg_16_open(L, c_in, w, false, s));
             // encode stream (fragments): conv2 @0 | conv3 @8 | conv4 @16 | conv5 @32
             HIP_TRY(launch_pack_weight_lp(L[1], dtype, 0, 0, 64, 2, 2, enc, s));
             HIP_TRY(launch_pack_weight_lp(L[2], dtype, 0, 0, 64, 2, 2, enc + 8 * F, s));
@@ -407,14 +324,14 @@ extern "C" int dal3_pack_weights(int head_kind, const dal3_layer* L, int n_layer
             HIP_TRY(launch_pack_weight_lp(L[4], dtype, 0, 0, 128, 32, 4, enc + 32 * F, s));
             // decode stream, segments of 40: [conv2 @0, 1a(0) @8] ; 1a(c>=1) @40+20(c-1) ; 2(c) @44+20c ; dconv3 @360,@400 ; dconv4 @440, dconv5 @472
             HIP_TRY(launch_pack_weight_lp(L[1], dtype, 0, 0, 64, 2, 2, dec, s));
-            HIP_TRY(launch_pack_weight_lp(L[5], dtype, 0, 0, 64, 16, 2, dec, s, 2, 8 * F, 40 * F, 20 * F));
-            HIP_TRY(launch_pack_weight_lp(L[6], dtype, 1, 0, 512, 8, 16, dec, s, 8, 44 * F, 64 * F, 20 * F));
-            HIP_TRY(launch_pack_weight_lp(L[7], dtype, 0, 0, 256, 4, 8, dec, s, 16, 360 * F, 400 * F, 40 * F));
+            HIP_TRY(launch_pack_weight_lp(L[5], dtype, 0, 0, 64, 16, 2, dec, s, PackGroups{2, 8 * F, 40 * F, 20 * F}));
+            HIP_TRY(launch_pack_weight_lp(L[6], dtype, 1, 0, 512, 8, 16, dec, s, PackGroups{8, 44 * F, 64 * F, 20 * F}));
+            HIP_TRY(launch_pack_weight_lp(L[7], dtype, 0, 0, 256, 4, 8, dec, s, PackGroups{16, 360 * F, 400 * F, 40 * F}));
             HIP_TRY(launch_pack_weight_lp(L[8], dtype, 0, 0, 128, 4, 4, dec + 440 * F, s));
             HIP_TRY(launch_pack_weight_lp(L[9], dtype, 0, 0, 128, 1, 4, dec + 472 * F, s));   // dconv5: rows 0, 1 of one out-tile
             return 0;
         }
-        InsSegW w = ins_seg_view(base, c_in);
+        const InsSegW w = view(packed_dev, ins_seg_walk);
         HIP_TRY(launch_pack_weight(L[0], PACK_FIRST, 0, c_in, 2, 2, mut(w.w1), s));
         HIP_TRY(launch_pack_bias(L[0], mut(w.b1), s));
         // encode stream: conv2 | conv3 | conv4 | conv5
@@ -424,11 +341,11 @@ extern "C" int dal3_pack_weights(int head_kind, const dal3_layer* L, int n_layer
         TRY(pack_frag(L[4], PACK_FRAG_MT_MAJOR, 0, 128, w.enc_stream, ENC_W5, w.b5, s));
         // decode stream: conv2 | dconv1a(0) | { dconv1a(c+1), dconv2(c) } | dconv3 | dconv4 (fragments of 256 floats)
         TRY(pack_frag(L[1], PACK_FRAG_MT_MAJOR, 0, 64, w.dec_stream, DEC_W2, nullptr, s));
-        TRY(pack_frag(L[5], PACK_FRAG_MT_MAJOR, 0, 64, w.dec_stream, DEC_MIX, w.db1, s, /*chunk = 2 blocks*/ 2,
-                      0, 8 * 256, 40 * 256));                                              // columns of out2
+        TRY(pack_frag(L[5], PACK_FRAG_MT_MAJOR, 0, 64, w.dec_stream, DEC_MIX, w.db1, s,
+                      PackGroups{/*chunk = 2 blocks*/ 2, 0, 8 * 256, 40 * 256}));          // columns of out2
         HIP_TRY(launch_pack_weight(L[5], PACK_ROWMAJOR, 64, 1024, 0, 0, mut(w.dw1g), s));   // columns of g
-        TRY(pack_frag(L[6], PACK_FRAG_KT_MAJOR, 0, 512, w.dec_stream, DEC_MIX, w.db2, s, /*chunk = 8 blocks*/ 8,
-                      16 * 256, 56 * 256, 40 * 256));
+        TRY(pack_frag(L[6], PACK_FRAG_KT_MAJOR, 0, 512, w.dec_stream, DEC_MIX, w.db2, s,
+                      PackGroups{/*chunk = 8 blocks*/ 8, 16 * 256, 56 * 256, 40 * 256}));
         TRY(pack_frag(L[7], PACK_FRAG_MT_MAJOR, 0, 256, w.dec_stream, DEC_W3, w.db3, s));
         TRY(pack_frag(L[8], PACK_FRAG_MT_MAJOR, 0, 128, w.dec_stream, DEC_W4, w.db4, s));
         // the same dconv1a / dconv2 out-tile major, for the latency kernels
@@ -439,11 +356,12 @@ extern "C" int dal3_pack_weights(int head_kind, const dal3_layer* L, int n_layer
         // the screened encoder's copies of conv5: fp32 rows, fp16 fragments, per-channel error-bound coefficients
         HIP_TRY(launch_pack_weight(L[4], PACK_ROWMAJOR, 0, 128, 0, 0, mut(w.w5row), s));
         HIP_TRY(launch_pack_weight_lp(L[4], DAL3_F16, 0, 0, 128, 32, 4, reinterpret_cast<uint16_t*>(mut(w.w5h)), s));
-        HIP_TRY(launch_pack_enc_screen(L[4], mut(w.scr_pq), reinterpret_cast<int32_t*>(mut(w.scr_flag)), s));
+        HIP_TRY(launch_pack_screen_bound(L[4], mut(w.scr_pq), const_cast<int32_t*>(w.scr_flag), s));
         // the compacted dconv2 - dconv4's chain-ordered copies and their guard flag
-        HIP_TRY(launch_pack_dec_sparse(L[6], w.db2, mut(w.dw2c), reinterpret_cast<int32_t*>(const_cast<int32_t*>(w.dec_flag)), s));
-        HIP_TRY(launch_pack_dec_queue(L[7], 256, w.db3, mut(w.dw3c), reinterpret_cast<int32_t*>(const_cast<int32_t*>(w.dec_flag)), s));
-        HIP_TRY(launch_pack_dec_queue(L[8], 128, w.db4, mut(w.dw4c), reinterpret_cast<int32_t*>(const_cast<int32_t*>(w.dec_flag)), s));
+        int32_t* dec_flag = const_cast<int32_t*>(w.dec_flag);
+        HIP_TRY(launch_pack_dec_chain(L[6], w.db2, mut(w.dw2c), dec_flag, s));
+        HIP_TRY(launch_pack_dec_chain(L[7], w.db3, mut(w.dw3c), dec_flag, s));
+        HIP_TRY(launch_pack_dec_chain(L[8], w.db4, mut(w.dw4c), dec_flag, s));
         // dconv1's crop-dead channels: the chain-ordered fp32 copy, the fp16 fragments and the bound's coefficients
         HIP_TRY(launch_pack_weight_lp(L[5], DAL3_F16, 0, 0, 64, 16, 2, reinterpret_cast<uint16_t*>(mut(w.w1h)), s));
         HIP_TRY(launch_pack_dec_prune(L[5], mut(w.dw1c), mut(w.prn_pq), const_cast<uint32_t*>(w.dec_ident),
@@ -452,58 +370,44 @@ extern "C" int dal3_pack_weights(int head_kind, const dal3_layer* L, int n_layer
     }
     if (head_kind == DAL3_HEAD_DYNAMIC_BOX_EST) {
         if (n_layers != 3) return fail(DAL3_EINVAL, "dynamic box_est expects 3 layers, got %d", n_layers);
-        return pack_fc(L, fc_head_view(base), s);
+        return pack_fc(L, view(packed_dev, fc_head_walk), s);
     }
     int c_in, ks, c[4], n_fc, fi[3], fo[3];
     point_head_dims(head_kind, &c_in, &ks, c, &n_fc, fi, fo);
     if (n_layers != 4 + n_fc) return fail(DAL3_EINVAL, "head %d expects %d layers, got %d", head_kind, 4 + n_fc, n_layers);
     TRY(check_layer(L[0], c_in, c[0], "conv1"));
     for (int i = 1; i < 4; ++i) TRY(check_layer(L[i], c[i - 1], c[i], "conv"));
-    if (x3) {
-        const PointHeadX3W w = point_head_x3_view(packed_dev, head_kind);
-        HIP_TRY(launch_pack_weight(L[0], PACK_FIRST, 0, c_in, c[0] / 32, ks, mut(w.w1), s));
-        HIP_TRY(launch_pack_bias(L[0], mut(w.b1), s));
-        HIP_TRY(launch_pack_bias(L[1], mut(w.bias), s));
-        HIP_TRY(launch_pack_bias(L[2], mut(w.bias) + c[1], s));
-        HIP_TRY(launch_pack_bias(L[3], mut(w.bias) + c[1] + c[2], s));
-        uint16_t* st = const_cast<uint16_t*>(w.stream);          // conv2 | conv3 | conv4, out-tile major, back to back
+    if (x3 || lp) {
+        const PointHeadLpW w = view(packed_dev, point_head_16_walk, head_kind, x3);
+        TRY(pack_head_open(L, c_in, ks, c[0], w.w1, w.b1, w.bias, w.bias + c[1], w.bias + c[1] + c[2], s));
+        uint16_t* st = const_cast<uint16_t*>(w.stream);
+        const int64_t SEGE = (int64_t)LP_HEAD_SEG * 512;           // 16-bit: elements per ring segment
         int64_t off = 0;
+        int seg = 0;
         for (int l = 1; l < 4; ++l) {
             const int kt = c[l - 1] / 32, mt = c[l] / 32;
-            HIP_TRY(launch_pack_weight_x3(L[l], 0, 0, c[l - 1], mt, kt, st + off, s));
-            off += (int64_t)mt * kt * 2048;
+            if (x3) {                                              // conv2 | conv3 | conv4, out-tile major, back to back
+                HIP_TRY(launch_pack_weight_x3(L[l], 0, 0, c[l - 1], mt, kt, st + off, s));
+                off += (int64_t)mt * kt * 2048;
+            } else {                                               // each layer: TPS out-tiles per segment
+                const int tps = lp_tps(kt, mt);
+                HIP_TRY(launch_pack_weight_lp(L[l], dtype, 0, 0, c[l - 1], mt, kt, st, s,
+                                              PackGroups{tps * kt, seg * SEGE, (seg + 1) * SEGE, SEGE}));
+                seg += mt / tps;
+            }
         }
         return pack_fc(L + 4, w.fc, s);
     }
-    if (lp) {
-        const PointHeadLpW w = point_head_lp_view(packed_dev, head_kind);
-        HIP_TRY(launch_pack_weight(L[0], PACK_FIRST, 0, c_in, c[0] / 32, ks, mut(w.w1), s));
-        HIP_TRY(launch_pack_bias(L[0], mut(w.b1), s));
-        HIP_TRY(launch_pack_bias(L[1], mut(w.bias), s));
-        HIP_TRY(launch_pack_bias(L[2], mut(w.bias) + c[1], s));
-        HIP_TRY(launch_pack_bias(L[3], mut(w.bias) + c[1] + c[2], s));
-        uint16_t* st = const_cast<uint16_t*>(w.stream);
-        const int64_t SEGE = (int64_t)LP_HEAD_SEG * 512;           // elements per ring segment
-        int seg = 0;
-        for (int l = 1; l < 4; ++l) {                              // each layer: TPS out-tiles per segment
-            const int kt = c[l - 1] / 32, mt = c[l] / 32, tps = lp_tps(kt, mt);
-            HIP_TRY(launch_pack_weight_lp(L[l], dtype, 0, 0, c[l - 1], mt, kt, st, s, tps * kt, seg * SEGE,
-                                          (seg + 1) * SEGE, SEGE));
-            seg += mt / tps;
-        }
-        return pack_fc(L + 4, w.fc, s);
-    }
-    PointHeadW w = point_head_view(base, head_kind);
-    HIP_TRY(launch_pack_weight(L[0], PACK_FIRST, 0, c_in, c[0] / 32, ks, mut(w.w1), s));
-    HIP_TRY(launch_pack_bias(L[0], mut(w.b1), s));
+    const PointHeadW w = view(packed_dev, point_head_walk, head_kind);
+    TRY(pack_head_open(L, c_in, ks, c[0], w.w1, w.b1, w.b2, w.b3, w.b4, s));
     const int f3 = (c[1] / 32) * (c[0] / 32) * 4, f4 = f3 + (c[2] / 32) * (c[1] / 32) * 4;   // fragment offsets
-    TRY(pack_frag(L[1], PACK_FRAG_MT_MAJOR, 0, c[0], w.stream, 0, w.b2, s));
-    TRY(pack_frag(L[2], PACK_FRAG_MT_MAJOR, 0, c[1], w.stream, f3, w.b3, s));
-    TRY(pack_frag(L[3], PACK_FRAG_MT_MAJOR, 0, c[2], w.stream, f4, w.b4, s));
+    TRY(pack_frag(L[1], PACK_FRAG_MT_MAJOR, 0, c[0], w.stream, 0, nullptr, s));
+    TRY(pack_frag(L[2], PACK_FRAG_MT_MAJOR, 0, c[1], w.stream, f3, nullptr, s));
+    TRY(pack_frag(L[3], PACK_FRAG_MT_MAJOR, 0, c[2], w.stream, f4, nullptr, s));
     if (w.w4row) {
         HIP_TRY(launch_pack_weight(L[3], PACK_ROWMAJOR, 0, 256, 0, 0, mut(w.w4row), s));
         HIP_TRY(launch_pack_weight_lp(L[3], DAL3_F16, 0, 0, 256, 16, 8, reinterpret_cast<uint16_t*>(mut(w.w4h)), s));
-        HIP_TRY(launch_pack_head_screen(L[3], mut(w.scr_pq), reinterpret_cast<int32_t*>(mut(w.scr_flag)), s));
+        HIP_TRY(launch_pack_screen_bound(L[3], mut(w.scr_pq), const_cast<int32_t*>(w.scr_flag), s));
     }
     return pack_fc(L + 4, w.fc, s);
 }
@@ -588,7 +492,7 @@ static int ins_seg_run(const void* packed, int dtype, int c_in, const dal3_bcn& 
     const BCN x = to_bcn(pts);
     HIP_TRY(launch_nonfinite_rows(x, B, N, c_in, ws.g, 1024, s));      // g = 0 (NaN for a crop with a non-finite coordinate)
     if (dtype == DAL3_F32) {
-        const InsSegW w = ins_seg_view(static_cast<const float*>(packed), c_in);
+        const InsSegW w = view(packed, ins_seg_walk);
         // the screened encoder and the compacted decoder both run: dconv1's channels that are dead for a whole crop are
         // proved so from the encoder's fp16 maxima and the decoder leaves them out (DESIGN.md "Crop-dead channels of dconv1")
         const bool plan = dec_plan_route(x.flags, B, N);
@@ -600,12 +504,12 @@ static int ins_seg_run(const void* packed, int dtype, int c_in, const dal3_bcn& 
         HIP_TRY(launch_ins_seg_decode(w, x, c_in, B, N, ws.gb, logits, mask, s,
                                       plan ? DecPlan{ws.plan_k, ws.plan_gbc, ws.plan_nch} : DecPlan{nullptr, nullptr, nullptr}));
     } else if (dtype == DAL3_F16X3) {
-        const InsSegX3W w = ins_seg_x3_view(packed);
+        const InsSegX3W w = view(packed, ins_seg_16_walk<InsSegX3W>);
         HIP_TRY(launch_ins_seg_encode_x3(w, x, c_in, B, N, ws.g, s));
         HIP_TRY(launch_fc(w.dw1g, w.db1, ws.g, 1024, ws.gb, 512, B, 1024, 512, 0, s));
         HIP_TRY(launch_ins_seg_decode_x3(w, x, c_in, B, N, ws.gb, logits, mask, s));
     } else {
-        const InsSegLpW w = ins_seg_lp_view(packed);
+        const InsSegLpW w = view(packed, ins_seg_16_walk<InsSegLpW>);
         HIP_TRY(launch_ins_seg_encode_lp(dtype, w, x, c_in, B, N, ws.g, s));
         HIP_TRY(launch_fc(w.dw1g, w.db1, ws.g, 1024, ws.gb, 512, B, 1024, 512, 0, s));
         HIP_TRY(launch_ins_seg_decode_lp(dtype, w, x, c_in, B, N, ws.gb, logits, mask, s));
@@ -634,12 +538,12 @@ extern "C" int dal3_ins_seg_encode(const void* packed, int dtype, int c_in, dal3
     TRY(check_bcn(pts, "pts"));
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (dtype == DAL3_F32)
-        HIP_TRY(launch_ins_seg_encode(ins_seg_view(static_cast<const float*>(packed), c_in), to_bcn(pts), c_in, B, N,
+        HIP_TRY(launch_ins_seg_encode(view(packed, ins_seg_walk), to_bcn(pts), c_in, B, N,
                                       global_feat, s));
     else if (dtype == DAL3_F16X3)
-        HIP_TRY(launch_ins_seg_encode_x3(ins_seg_x3_view(packed), to_bcn(pts), c_in, B, N, global_feat, s));
+        HIP_TRY(launch_ins_seg_encode_x3(view(packed, ins_seg_16_walk<InsSegX3W>), to_bcn(pts), c_in, B, N, global_feat, s));
     else
-        HIP_TRY(launch_ins_seg_encode_lp(dtype, ins_seg_lp_view(packed), to_bcn(pts), c_in, B, N, global_feat, s));
+        HIP_TRY(launch_ins_seg_encode_lp(dtype, view(packed, ins_seg_16_walk<InsSegLpW>), to_bcn(pts), c_in, B, N, global_feat, s));
     return 0;
 }
 
@@ -648,10 +552,11 @@ extern "C" int dal3_ins_seg_global_bias(const void* packed, int dtype, const flo
     TRY(check_dtype(dtype));
     if (!packed || !global_feat || !gbias) return fail(DAL3_EINVAL, "ins_seg_global_bias: bad argument");
     TRY(check_extent(B, 1, "ins_seg_global_bias"));
-    const float* dw1g = dtype == DAL3_F32 ? ins_seg_view(static_cast<const float*>(packed), 3).dw1g
-                        : dtype == DAL3_F16X3 ? ins_seg_x3_view(packed).dw1g : ins_seg_lp_view(packed).dw1g;
-    const float* db1 = dtype == DAL3_F32 ? ins_seg_view(static_cast<const float*>(packed), 3).db1
-                       : dtype == DAL3_F16X3 ? ins_seg_x3_view(packed).db1 : ins_seg_lp_view(packed).db1;
+    const float *dw1g, *db1;                                // (the same two sections of every dtype's blob)
+    auto sections = [&](const auto& w) { dw1g = w.dw1g, db1 = w.db1; };
+    if (dtype == DAL3_F32) sections(view(packed, ins_seg_walk));
+    else if (dtype == DAL3_F16X3) sections(view(packed, ins_seg_16_walk<InsSegX3W>));
+    else sections(view(packed, ins_seg_16_walk<InsSegLpW>));
     HIP_TRY(launch_fc(dw1g, db1, global_feat, 1024, gbias, 512, B, 1024, 512, 0, static_cast<hipStream_t>(stream)));
     return 0;
 }
@@ -664,12 +569,12 @@ extern "C" int dal3_ins_seg_decode(const void* packed, int dtype, int c_in, dal3
     TRY(check_bcn(pts, "pts"));
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (dtype == DAL3_F32)
-        HIP_TRY(launch_ins_seg_decode(ins_seg_view(static_cast<const float*>(packed), c_in), to_bcn(pts), c_in, B, N,
+        HIP_TRY(launch_ins_seg_decode(view(packed, ins_seg_walk), to_bcn(pts), c_in, B, N,
                                       gbias, logits, mask, s));
     else if (dtype == DAL3_F16X3)
-        HIP_TRY(launch_ins_seg_decode_x3(ins_seg_x3_view(packed), to_bcn(pts), c_in, B, N, gbias, logits, mask, s));
+        HIP_TRY(launch_ins_seg_decode_x3(view(packed, ins_seg_16_walk<InsSegX3W>), to_bcn(pts), c_in, B, N, gbias, logits, mask, s));
     else
-        HIP_TRY(launch_ins_seg_decode_lp(dtype, ins_seg_lp_view(packed), to_bcn(pts), c_in, B, N, gbias, logits, mask, s));
+        HIP_TRY(launch_ins_seg_decode_lp(dtype, view(packed, ins_seg_16_walk<InsSegLpW>), to_bcn(pts), c_in, B, N, gbias, logits, mask, s));
     return 0;
 }
 
@@ -782,16 +687,16 @@ static int point_head_run(int head_kind, const void* packed, int dtype, const da
     int c_in, ks, c[4], n_fc, fi[3], fo[3];
     point_head_dims(head_kind, &c_in, &ks, c, &n_fc, fi, fo);
     if (dtype == DAL3_F16X3) {
-        const PointHeadX3W w = point_head_x3_view(packed, head_kind);
+        const PointHeadX3W w = view(packed, point_head_16_walk, head_kind, true);
         HIP_TRY(launch_point_head_x3(head_kind, w, to_bcn(x), c_in, B, M, ws.feat, distinct, s));
         return fc_chain(w.fc, ws.feat, 512, out, out_stride, B, ws.t1, ws.t2, s, dec);
     }
     if (dtype != DAL3_F32) {
-        const PointHeadLpW w = point_head_lp_view(packed, head_kind);
+        const PointHeadLpW w = view(packed, point_head_16_walk, head_kind, false);
         HIP_TRY(launch_point_head_lp(dtype, head_kind, w, to_bcn(x), c_in, B, M, ws.feat, distinct, s));
         return fc_chain(w.fc, ws.feat, 512, out, out_stride, B, ws.t1, ws.t2, s, dec);
     }
-    const PointHeadW w = point_head_view(static_cast<const float*>(packed), head_kind);
+    const PointHeadW w = view(packed, point_head_walk, head_kind);
     HIP_TRY(launch_point_head(head_kind, w, to_bcn(x), c_in, B, M, ws.feat, distinct, s, ws.work, ws.work_bytes));
     return fc_chain(w.fc, ws.feat, 512, out, out_stride, B, ws.t1, ws.t2, s, dec);
 }
@@ -826,15 +731,15 @@ extern "C" int dal3_point_head_pool(int head_kind, const void* packed, int dtype
     int c_in, ks, c[4], n_fc, fi[3], fo[3];
     point_head_dims(head_kind, &c_in, &ks, c, &n_fc, fi, fo);
     if (dtype == DAL3_F16X3) {
-        HIP_TRY(launch_point_head_x3(head_kind, point_head_x3_view(packed, head_kind), to_bcn(x), c_in, B, M, feat, n_distinct, s));
+        HIP_TRY(launch_point_head_x3(head_kind, view(packed, point_head_16_walk, head_kind, true), to_bcn(x), c_in, B, M, feat, n_distinct, s));
         return 0;
     }
     if (dtype != DAL3_F32) {
-        const PointHeadLpW w = point_head_lp_view(packed, head_kind);
+        const PointHeadLpW w = view(packed, point_head_16_walk, head_kind, false);
         HIP_TRY(launch_point_head_lp(dtype, head_kind, w, to_bcn(x), c_in, B, M, feat, n_distinct, s));
         return 0;
     }
-    const PointHeadW w = point_head_view(static_cast<const float*>(packed), head_kind);
+    const PointHeadW w = view(packed, point_head_walk, head_kind);
     HIP_TRY(launch_point_head(head_kind, w, to_bcn(x), c_in, B, M, feat, n_distinct, s, workspace, workspace_bytes));
     return 0;
 }
@@ -849,7 +754,7 @@ extern "C" int dal3_dynamic_box_est_forward(const void* packed, const float* emb
     Carver c(workspace, workspace_bytes);
     const HeadWs ws = carve_head(c, B);
     if (!c.ok) return fail(DAL3_EWORKSPACE, "dynamic_box_est: workspace needs %zu bytes, got %zu", c.off, workspace_bytes);
-    return fc_chain(fc_head_view(static_cast<const float*>(packed)), embedding, 384, box_pred, 39, B, ws.t1, ws.t2,
+    return fc_chain(view(packed, fc_head_walk), embedding, 384, box_pred, 39, B, ws.t1, ws.t2,
                     static_cast<hipStream_t>(stream));
 }
 
@@ -2448,7 +2353,7 @@ extern "C" int dal3_dynamic_forward(const dal3_dynamic_args* a, int phases, dal3
     // forward() adds nothing to the centre; the eval driver adds init_box[:, :3] and yaw init_box[:, -2]
     const DecodeArgs dd{a->box_pred, nullptr, 0, 0, a->init_box8, 8, a->init_box8 ? a->init_box8 + 6 : nullptr, 8,
                         a->heading_residuals, a->size_residuals, nullptr, a->boxes7};
-    TRY(fc_chain(fc_head_view(static_cast<const float*>(a->w_box_est)), a->embedding, 384, a->box_pred, 39, B,
+    TRY(fc_chain(view(a->w_box_est, fc_head_walk), a->embedding, 384, a->box_pred, 39, B,
                  ws.head.t1, ws.head.t2, s, &dd));
     return 0;
 }

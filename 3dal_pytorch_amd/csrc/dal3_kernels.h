@@ -120,6 +120,14 @@ enum {                        // stream geometry in fragments of 256 floats
     LAT_W1A = 0, LAT_W2 = 128, LAT_FRAGS = 128 + 512
 };
 
+// Where the fragment packers (launch_pack_weight*) write a layer whose (mt,kt) blocks are consumed in groups of `blocks`
+// blocks: group 0 at out + a0, group g >= 1 at out + a1 + (g - 1) * stride (elements of the stream); last >= 0: the last
+// group sits at out + last instead. blocks == 0: block after block from out.
+struct PackGroups {
+    int blocks = 0;
+    int64_t a0 = 0, a1 = 0, stride = 0, last = -1;
+};
+
 struct FcW {
     const float* w[3];   // row-major (c_out, c_in), BN folded
     const float* b[3];
@@ -199,26 +207,16 @@ struct InsSegX3W {
     const uint16_t* enc_stream;   // 18 segments of 32 fragments
     const uint16_t* dec_stream;   // 27 segments
 };
-size_t ins_seg_x3_packed_bytes();
-InsSegX3W ins_seg_x3_view(const void* base);
 hipError_t launch_ins_seg_encode_x3(const InsSegX3W& w, BCN pts, int c_in, int B, int N, float* g, hipStream_t s);
 hipError_t launch_ins_seg_decode_x3(const InsSegX3W& w, BCN pts, int c_in, int B, int N, const float* gbias, float* logits,
                                     uint8_t* mask, hipStream_t s);
-size_t point_head_x3_packed_bytes(int head_kind);
-PointHeadX3W point_head_x3_view(const void* base, int head_kind);
 int point_head_x3_segments(int head_kind);
 hipError_t launch_point_head_x3(int head_kind, const PointHeadX3W& w, BCN x, int c_in, int B, int M, float* feat,
                                 const int32_t* distinct, hipStream_t s);
 // (hi, lo) fragment pairs of a layer, out-tile major: [mt][kt][k-step][hi | lo][64 lanes][8]; element order as
 // launch_pack_weight_lp; kt_major: [kt][mt][...] (a K-major layer consumed chunk by chunk)
 hipError_t launch_pack_weight_x3(const dal3_layer& L, int kt_major, int col_off, int n_cols, int mt_n, int kt_n, uint16_t* out,
-                                 hipStream_t s, int grp_blocks = 0, int64_t grp_a0 = 0, int64_t grp_a1 = 0,
-                                 int64_t grp_stride = 0, int64_t grp_last = -1);
-size_t ins_seg_lp_packed_bytes();
-InsSegLpW ins_seg_lp_view(const void* base);
-size_t point_head_lp_packed_bytes(int head_kind);
-PointHeadLpW point_head_lp_view(const void* base, int head_kind);
-int point_head_lp_segments(int head_kind);
+                                 hipStream_t s, PackGroups G = PackGroups{});
 hipError_t launch_ins_seg_encode_lp(int dtype, const InsSegLpW& w, BCN pts, int c_in, int B, int N, float* g, hipStream_t s);
 hipError_t launch_ins_seg_decode_lp(int dtype, const InsSegLpW& w, BCN pts, int c_in, int B, int N, const float* gbias,
                                     float* logits, uint8_t* mask, hipStream_t s);
@@ -226,16 +224,9 @@ hipError_t launch_point_head_lp(int dtype, int head_kind, const PointHeadLpW& w,
                                 float* feat, const int32_t* distinct, hipStream_t s);
 // 16-bit fragment packing: element j of lane l of fragment (mt,kt,s) = W'[32mt + (l&31)][32kt + 16s + 8(j>>2) + 4(l>>5) + (j&3)]
 hipError_t launch_pack_weight_lp(const dal3_layer& L, int dtype, int kt_major, int col_off, int n_cols, int mt_n, int kt_n,
-                                 uint16_t* out, hipStream_t s, int grp_blocks = 0, int64_t grp_a0 = 0, int64_t grp_a1 = 0,
-                                 int64_t grp_stride = 0);
+                                 uint16_t* out, hipStream_t s, PackGroups G = PackGroups{});
 
-// layout (offsets in floats from the blob start); all sections 256-byte aligned
-size_t ins_seg_packed_floats(int c_in);
-InsSegW ins_seg_view(const float* base, int c_in);
-size_t point_head_packed_floats(int head_kind);
-PointHeadW point_head_view(const float* base, int head_kind);
-size_t fc_head_packed_floats();
-FcW fc_head_view(const float* base);
+// the blobs' layouts (all sections 256-byte aligned) are the walks of dal3_api.hip
 void point_head_dims(int head_kind, int* c_in, int* ks, int c[4], int* n_fc, int fc_in[3], int fc_out[3]);
 
 // ---- launchers (all asynchronous on s)
@@ -251,10 +242,10 @@ hipError_t launch_pack_dec_prune(const dal3_layer& L, float* dw1c, float* pq, ui
 // plan_k (B, DEC_PLAN_LD), plan_gbc (B, 512), plan_nch (B): see DecPlan
 hipError_t launch_dec_plan(const InsSegW& w, const float* gb, const uint32_t* prune, int B, uint32_t* plan_k, float* plan_gbc,
                            int32_t* plan_nch, hipStream_t s);
-hipError_t launch_pack_enc_screen(const dal3_layer& L, float* pq, int32_t* flag, hipStream_t s);
-// db2: the layer's packed bias (written earlier on s)
-hipError_t launch_pack_dec_sparse(const dal3_layer& L, const float* db2, float* dw2c, int32_t* flag, hipStream_t s);
-hipError_t launch_pack_dec_queue(const dal3_layer& L, int c_in, const float* bias, float* wcopy, int32_t* flag, hipStream_t s);
+// the bound coefficients (pq) and fp16-range flag of a screened layer: the encoder's conv5 (128 -> 1024) or a head's conv4 (256 -> 512)
+hipError_t launch_pack_screen_bound(const dal3_layer& L, float* pq, int32_t* flag, hipStream_t s);
+// the chain-ordered copy of dconv2 / dconv3 / dconv4 and its guard; bias: the layer's packed bias (written earlier on s)
+hipError_t launch_pack_dec_chain(const dal3_layer& L, const float* bias, float* wcopy, int32_t* flag, hipStream_t s);
 hipError_t launch_ins_seg_decode(const InsSegW& w, BCN pts, int c_in, int B, int N, const float* gbias,
                                  float* logits, uint8_t* mask, hipStream_t s, DecPlan plan = DecPlan{nullptr, nullptr, nullptr});
 // distinct (B) i32 or NULL: only the first distinct[b] points of item b are distinct (the rest duplicate them)
@@ -296,11 +287,9 @@ hipError_t launch_fc(const float* W, const float* bias, const float* x, int64_t 
                      int c_in, int c_out, int relu, hipStream_t s);
 
 enum { PACK_FRAG_MT_MAJOR = 0, PACK_FRAG_KT_MAJOR = 1, PACK_FIRST = 2, PACK_ROWMAJOR = 3 };
-// grp_blocks > 0: the (mt,kt) blocks are written in groups of grp_blocks; group 0 at out + grp_a0, group g >= 1 at
-// out + grp_a1 + (g-1)*grp_stride (floats). grp_blocks == 0: dense.
+// G: the fragment modes only (offsets in floats)
 hipError_t launch_pack_weight(const dal3_layer& L, int mode, int col_off, int n_cols, int mt_n, int kt_n, float* out,
-                              hipStream_t s, int grp_blocks = 0, int64_t grp_a0 = 0, int64_t grp_a1 = 0,
-                              int64_t grp_stride = 0);
+                              hipStream_t s, PackGroups G = PackGroups{});
 hipError_t launch_pack_bias(const dal3_layer& L, float* out, hipStream_t s);
 
 hipError_t launch_static_crop_prep(const double* points, const int64_t* offsets, const int32_t* choice, const double* pose,

@@ -17,9 +17,18 @@ __device__ __forceinline__ float folded_w(const dal3_layer& L, int row, int col,
     return L.weight[(int64_t)row * L.c_in + col_off + col] * bn_scale(L, row);
 }
 
+// A layer whose blocks go to a stream in GROUPS of `blocks` blocks: group 0 at element a0, group g >= 1 at a1 + (g - 1) *
+// stride; last >= 0: the last group sits there instead (PackGroups, dal3_kernels.h). blocks == 0: block after block, o = i.
+__device__ __forceinline__ int64_t grouped_offset(const PackGroups& G, int64_t i, int blk, int blk_elems, int n_blocks) {
+    if (G.blocks <= 0) return i;
+    const int g = blk / G.blocks;
+    const bool last = G.last >= 0 && g == n_blocks / G.blocks - 1;
+    return (last ? G.last : g == 0 ? G.a0 : G.a1 + (int64_t)(g - 1) * G.stride) + (int64_t)(blk % G.blocks) * blk_elems +
+           i % blk_elems;
+}
+
 __global__ void pack_weight_kernel(dal3_layer L, int mode, int col_off, int n_cols, int mt_n, int kt_n,
-                                   float* __restrict__ out, int64_t total, int grp_blocks, int64_t grp_a0,
-                                   int64_t grp_a1, int64_t grp_stride) {
+                                   float* __restrict__ out, int64_t total, PackGroups G) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
     if (mode == PACK_ROWMAJOR) {
@@ -34,28 +43,28 @@ __global__ void pack_weight_kernel(dal3_layer L, int mode, int col_off, int n_co
         const int blk = (int)(i >> 10);
         const int mt = mode == PACK_FRAG_MT_MAJOR ? blk / kt_n : blk % mt_n;
         const int kt = mode == PACK_FRAG_MT_MAJOR ? blk % kt_n : blk / mt_n;
-        int64_t o = i;
-        if (grp_blocks > 0) {
-            const int g = blk / grp_blocks;
-            o = (g == 0 ? grp_a0 : grp_a1 + (int64_t)(g - 1) * grp_stride) + (int64_t)(blk % grp_blocks) * 1024 + (i & 1023);
-        }
-        out[o] = folded_w(L, 32 * mt + (lane & 31), 32 * kt + tile_chan(4 * q + e, lane >> 5), col_off, n_cols);
+        out[grouped_offset(G, i, blk, 1024, mt_n * kt_n)] =
+            folded_w(L, 32 * mt + (lane & 31), 32 * kt + tile_chan(4 * q + e, lane >> 5), col_off, n_cols);
     }
 }
 
-// 16-bit fragments for v_mfma_f32_32x32x16_{bf16,f16}: a block (mt,kt) is two 1-KiB fragments (k-steps s = 0,1)
-// of [64 lanes][8 elements]; the k order inside a step matches the C/D layout of the producing MFMA (dal3_lp.h).
+// 16-bit fragments for v_mfma_f32_32x32x16_{bf16,f16}: [64 lanes][8 elements] per k-step s = 0, 1 of a block (mt, kt); the
+// k order inside a step matches the C/D layout of the producing MFMA (dal3_lp.h). Element j of lane `lane`:
+__device__ __forceinline__ float frag16_weight(const dal3_layer& L, int blk, int s, int lane, int j, int kt_major, int col_off,
+                                               int n_cols, int mt_n, int kt_n) {
+    const int mt = kt_major ? blk % mt_n : blk / kt_n;
+    const int kt = kt_major ? blk / mt_n : blk % kt_n;
+    return folded_w(L, 32 * mt + (lane & 31), 32 * kt + 16 * s + 8 * (j >> 2) + 4 * (lane >> 5) + (j & 3), col_off, n_cols);
+}
+
+// bf16 / fp16: a block is its two 1-KiB fragments
 __global__ void pack_weight_lp_kernel(dal3_layer L, int dtype, int kt_major, int col_off, int n_cols, int mt_n, int kt_n,
-                                      uint16_t* __restrict__ out, int64_t total, int grp_blocks, int64_t grp_a0,
-                                      int64_t grp_a1, int64_t grp_stride) {
+                                      uint16_t* __restrict__ out, int64_t total, PackGroups G) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
     const int j = (int)(i & 7), lane = (int)((i >> 3) & 63), s = (int)((i >> 9) & 1);
     const int blk = (int)(i >> 10);
-    const int mt = kt_major ? blk % mt_n : blk / kt_n;
-    const int kt = kt_major ? blk / mt_n : blk % kt_n;
-    const float v = folded_w(L, 32 * mt + (lane & 31), 32 * kt + 16 * s + 8 * (j >> 2) + 4 * (lane >> 5) + (j & 3), col_off,
-                             n_cols);
+    const float v = frag16_weight(L, blk, s, lane, j, kt_major, col_off, n_cols, mt_n, kt_n);
     uint16_t bits;
     if (dtype == DAL3_BF16) {
         const __bf16 h = (__bf16)v;
@@ -64,54 +73,37 @@ __global__ void pack_weight_lp_kernel(dal3_layer L, int dtype, int kt_major, int
         const _Float16 h = (_Float16)v;
         bits = __builtin_bit_cast(uint16_t, h);
     }
-    int64_t o = i;
-    if (grp_blocks > 0) {
-        const int g = blk / grp_blocks;
-        o = (g == 0 ? grp_a0 : grp_a1 + (int64_t)(g - 1) * grp_stride) + (int64_t)(blk % grp_blocks) * 1024 + (i & 1023);
-    }
-    out[o] = bits;
+    out[grouped_offset(G, i, blk, 1024, mt_n * kt_n)] = bits;
 }
 
 // "f16x3" fragments: every k-step of a block as a PAIR of fp16 fragments, hi = fp16(w), lo = fp16(w - hi). A block (mt, kt)
 // is four 1-KiB fragments [k-step 0: hi, lo][k-step 1: hi, lo]; element order inside a fragment as above.
 __global__ void pack_weight_x3_kernel(dal3_layer L, int kt_major, int col_off, int n_cols, int mt_n, int kt_n,
-                                      uint16_t* __restrict__ out, int64_t total, int grp_blocks, int64_t grp_a0,
-                                      int64_t grp_a1, int64_t grp_stride, int64_t grp_last) {
+                                      uint16_t* __restrict__ out, int64_t total, PackGroups G) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
     const int j = (int)(i & 7), lane = (int)((i >> 3) & 63), half = (int)((i >> 9) & 1), s = (int)((i >> 10) & 1);
     const int blk = (int)(i >> 11);
-    const int mt = kt_major ? blk % mt_n : blk / kt_n;
-    const int kt = kt_major ? blk / mt_n : blk % kt_n;
-    const float v = folded_w(L, 32 * mt + (lane & 31), 32 * kt + 16 * s + 8 * (j >> 2) + 4 * (lane >> 5) + (j & 3), col_off,
-                             n_cols);
+    const float v = frag16_weight(L, blk, s, lane, j, kt_major, col_off, n_cols, mt_n, kt_n);
     // a folded weight beyond fp16's range (dal3.h, DAL3_F16X3) is packed as NaN: the head's outputs are NaN, not silently wrong
     const _Float16 hi = fabsf(v) < 65504.0f ? (_Float16)v : (_Float16)__builtin_nanf("");
     const _Float16 lo = (_Float16)(v - (float)hi);
-    int64_t o = i;
-    if (grp_blocks > 0) {
-        const int g = blk / grp_blocks;
-        // (grp_last >= 0: the last group sits there instead — the decoder's D_15, which has no A block in front of it)
-        const bool last = grp_last >= 0 && g == mt_n * kt_n / grp_blocks - 1;
-        o = (last ? grp_last : g == 0 ? grp_a0 : grp_a1 + (int64_t)(g - 1) * grp_stride) + (int64_t)(blk % grp_blocks) * 2048 + (i & 2047);
-    }
-    out[o] = __builtin_bit_cast(uint16_t, half ? lo : hi);
+    // (G.last: the decoder's D_15, which has no A block in front of it)
+    out[grouped_offset(G, i, blk, 2048, mt_n * kt_n)] = __builtin_bit_cast(uint16_t, half ? lo : hi);
 }
 hipError_t launch_pack_weight_x3(const dal3_layer& L, int kt_major, int col_off, int n_cols, int mt_n, int kt_n, uint16_t* out,
-                                 hipStream_t s, int grp_blocks, int64_t grp_a0, int64_t grp_a1, int64_t grp_stride,
-                                 int64_t grp_last) {
+                                 hipStream_t s, PackGroups G) {
     const int64_t total = (int64_t)mt_n * kt_n * 2048;
     hipLaunchKernelGGL(pack_weight_x3_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, L, kt_major, col_off, n_cols,
-                       mt_n, kt_n, out, total, grp_blocks, grp_a0, grp_a1, grp_stride, grp_last);
+                       mt_n, kt_n, out, total, G);
     return hipGetLastError();
 }
 
 hipError_t launch_pack_weight_lp(const dal3_layer& L, int dtype, int kt_major, int col_off, int n_cols, int mt_n, int kt_n,
-                                 uint16_t* out, hipStream_t s, int grp_blocks, int64_t grp_a0, int64_t grp_a1,
-                                 int64_t grp_stride) {
+                                 uint16_t* out, hipStream_t s, PackGroups G) {
     const int64_t total = (int64_t)mt_n * kt_n * 1024;
     hipLaunchKernelGGL(pack_weight_lp_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, L, dtype, kt_major,
-                       col_off, n_cols, mt_n, kt_n, out, total, grp_blocks, grp_a0, grp_a1, grp_stride);
+                       col_off, n_cols, mt_n, kt_n, out, total, G);
     return hipGetLastError();
 }
 
@@ -128,88 +120,77 @@ __global__ void pack_bias_kernel(dal3_layer L, float* __restrict__ out, int padd
 }
 
 hipError_t launch_pack_weight(const dal3_layer& L, int mode, int col_off, int n_cols, int mt_n, int kt_n, float* out,
-                              hipStream_t s, int grp_blocks, int64_t grp_a0, int64_t grp_a1, int64_t grp_stride) {
+                              hipStream_t s, PackGroups G) {
     int64_t total;
     if (mode == PACK_ROWMAJOR) total = (int64_t)L.c_out * n_cols;
     else if (mode == PACK_FIRST) total = (int64_t)mt_n * kt_n * 64;
     else total = (int64_t)mt_n * kt_n * 1024;
     hipLaunchKernelGGL(pack_weight_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, L, mode, col_off,
-                       n_cols, mt_n, kt_n, out, total, grp_blocks, grp_a0, grp_a1, grp_stride);
+                       n_cols, mt_n, kt_n, out, total, G);
     return hipGetLastError();
 }
 
-// Error-bound coefficients of the screened encoder (DESIGN.md "Screened conv5"): for a point with ||x||_2 <= X,
+// Error-bound coefficients of a layer screened on the fp16 MFMA over K input channels (DESIGN.md "Screened conv5", "Screened
+// conv4 of the point heads", "Crop-dead channels of dconv1"): for a point with ||x||_2 <= X,
 //   |fp16-MFMA score(c) - fp32 chain(c)| <= X * P_c + Q_c,
-//   P_c = kappa ||w_c||_2 + 2^-24 sqrt(128),  Q_c = 2^-24 ||w_c||_1 + 2^-40,  kappa = 1.02 * 2^-10 + 128 * 2^-23,
+//   P_c = kappa ||w_c||_2 + 2^-24 sqrt(K),  Q_c = 2^-24 ||w_c||_1 + 2^-40,  kappa = 1.02 * 2^-10 + K * 2^-23,
 // evaluated in double and rounded to fp32 with a relative margin of 1e-6 (>> 2^-24). flag: a weight that fp16 cannot hold.
-__global__ void pack_enc_screen_kernel(dal3_layer L, float* __restrict__ pq, int32_t* __restrict__ flag) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= 1024) return;
+// sqrt(K) is the literal the proofs' bounds were checked with (K = 128: above the true root, not the double nearest to it).
+template <int K>
+__device__ __forceinline__ void bound_coefficients(const dal3_layer& L, int c, float* __restrict__ pq, int32_t* __restrict__ flag) {
+    static_assert(K == 64 || K == 128 || K == 256, "sqrt(K) is a table");
+    constexpr double sqrt_k = K == 64 ? 8.0 : K == 128 ? 11.3137085 : 16.0;
     double s2 = 0.0, s1 = 0.0;
     bool bad = false;
-    for (int k = 0; k < 128; ++k) {
-        const float v = folded_w(L, c, k, 0, 128);
+    for (int k = 0; k < K; ++k) {
+        const float v = folded_w(L, c, k, 0, K);
         bad |= !(fabsf(v) < 65504.0f);
         s2 += (double)v * (double)v;
         s1 += fabs((double)v);
     }
-    const double kappa = 1.02 * 0x1p-10 + 128.0 * 0x1p-23;
-    pq[2 * c] = (float)((kappa * sqrt(s2) + 0x1p-24 * 11.3137085) * (1.0 + 1e-6));
+    const double kappa = 1.02 * 0x1p-10 + (double)K * 0x1p-23;
+    pq[2 * c] = (float)((kappa * sqrt(s2) + 0x1p-24 * sqrt_k) * (1.0 + 1e-6));
     pq[2 * c + 1] = (float)((0x1p-24 * s1 + 0x1p-40) * (1.0 + 1e-6));
     if (bad) atomicOr(flag, 1);
 }
-hipError_t launch_pack_enc_screen(const dal3_layer& L, float* pq, int32_t* flag, hipStream_t s) {
-    hipLaunchKernelGGL(pack_enc_screen_kernel, dim3(4), dim3(256), 0, s, L, pq, flag);
-    return hipGetLastError();
-}
-
-// The same coefficients for conv4 (256 -> 512) of the point heads (DESIGN.md "Screened conv4 of the point heads"): K = 256,
-//   P_c = kappa ||w_c||_2 + 2^-24 sqrt(256),  Q_c = 2^-24 ||w_c||_1 + 2^-40,  kappa = 1.02 * 2^-10 + 256 * 2^-23.
-__global__ void pack_head_screen_kernel(dal3_layer L, float* __restrict__ pq, int32_t* __restrict__ flag) {
+// conv5 of the encoder (K = 128, 1024 channels) and conv4 of the point heads (K = 256, 512 channels)
+template <int K, int CHANNELS>
+__global__ void pack_screen_bound_kernel(dal3_layer L, float* __restrict__ pq, int32_t* __restrict__ flag) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= 512) return;
-    double s2 = 0.0, s1 = 0.0;
-    bool bad = false;
-    for (int k = 0; k < 256; ++k) {
-        const float v = folded_w(L, c, k, 0, 256);
-        bad |= !(fabsf(v) < 65504.0f);
-        s2 += (double)v * (double)v;
-        s1 += fabs((double)v);
-    }
-    const double kappa = 1.02 * 0x1p-10 + 256.0 * 0x1p-23;
-    pq[2 * c] = (float)((kappa * sqrt(s2) + 0x1p-24 * 16.0) * (1.0 + 1e-6));
-    pq[2 * c + 1] = (float)((0x1p-24 * s1 + 0x1p-40) * (1.0 + 1e-6));
-    if (bad) atomicOr(flag, 1);
+    if (c < CHANNELS) bound_coefficients<K>(L, c, pq, flag);
 }
-hipError_t launch_pack_head_screen(const dal3_layer& L, float* pq, int32_t* flag, hipStream_t s) {
-    hipLaunchKernelGGL(pack_head_screen_kernel, dim3(2), dim3(256), 0, s, L, pq, flag);
+hipError_t launch_pack_screen_bound(const dal3_layer& L, float* pq, int32_t* flag, hipStream_t s) {
+    if (L.c_in == 128 && L.c_out == 1024) hipLaunchKernelGGL((pack_screen_bound_kernel<128, 1024>), dim3(4), dim3(256), 0, s, L, pq, flag);
+    else if (L.c_in == 256 && L.c_out == 512) hipLaunchKernelGGL((pack_screen_bound_kernel<256, 512>), dim3(2), dim3(256), 0, s, L, pq, flag);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
-// The compacted dconv2's weight copy (dal3_kernels.h::InsSegW::dw2c) and its guard: skipping a dead channel's term is
-// exact only while 0 * w is a zero (w finite) and no accumulator chain starts from -0 (DESIGN.md "Compacted dconv2").
-__global__ void pack_dec_sparse_kernel(dal3_layer L, const float* __restrict__ db2, float* __restrict__ out,
-                                       int32_t* __restrict__ flag) {
+// The compacted decoder's chain-ordered weight copies (dal3_kernels.h::InsSegW::dw2c, dw3c, dw4c) of dconv2 (512 -> 256),
+// dconv3 (256 -> 128) and dconv4 (128 -> 128): [k][row 0..31][out-tile], W'[32 mt + row][32 c + tile_chan(r, h)] at chain index
+// k = 32 c + 2 r + h. Their guard: skipping a dead channel's term is exact only while 0 * w is a zero (w finite) and no
+// accumulator chain starts from -0 (DESIGN.md "Compacted dconv2"). bias: the layer's packed bias (written earlier on s).
+__global__ void pack_dec_chain_kernel(dal3_layer L, const float* __restrict__ bias, float* __restrict__ out,
+                                      int32_t* __restrict__ flag) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= 512 * 256) return;
-    const int mt = i & 7, row = (i >> 3) & 31, k = i >> 8;
+    if (i >= L.c_in * L.c_out) return;
+    const int mt_n = L.c_out / 32;
+    const int mt = i % mt_n, row = (i / mt_n) & 31, k = i / L.c_out;
     const int c = k >> 5, r = (k & 31) >> 1, h = k & 1;
-    const float v = folded_w(L, 32 * mt + row, 32 * c + tile_chan(r, h), 0, 512);
+    const float v = folded_w(L, 32 * mt + row, 32 * c + tile_chan(r, h), 0, L.c_in);
     out[i] = v;
     bool bad = (__float_as_uint(v) & 0x7F800000u) == 0x7F800000u;
-    if (i < 256) bad |= __float_as_uint(db2[i]) == 0x80000000u;
+    if (i < L.c_out) bad |= __float_as_uint(bias[i]) == 0x80000000u;
     if (bad) atomicOr(flag, 1);
 }
-hipError_t launch_pack_dec_sparse(const dal3_layer& L, const float* db2, float* dw2c, int32_t* flag, hipStream_t s) {
-    hipLaunchKernelGGL(pack_dec_sparse_kernel, dim3(512), dim3(256), 0, s, L, db2, dw2c, flag);
+hipError_t launch_pack_dec_chain(const dal3_layer& L, const float* bias, float* wcopy, int32_t* flag, hipStream_t s) {
+    hipLaunchKernelGGL(pack_dec_chain_kernel, dim3(L.c_in * L.c_out / 256), dim3(256), 0, s, L, bias, wcopy, flag);
     return hipGetLastError();
 }
 
 // dconv1's crop-dead channels (DESIGN.md "Crop-dead channels of dconv1"): the chain-ordered copy of dconv1a that the compacted
-// decoder reads its A operands from (InsSegW::dw1c), the plan of a crop with nothing flagged, and the coefficients of
-//   |s16(c,p) - (chain32(c,p) - gb_c)| <= X P_c + Q_c + 2 K 2^-24 |gb_c|,   K = 64,
-//   P_c = kappa ||w_c||_2 + 2^-24 sqrt(64),  Q_c = 2^-24 ||w_c||_1 + 2^-40,  kappa = 1.02 * 2^-10 + 64 * 2^-23,
-// in double with the 1e-6 margin, as pack_enc_screen_kernel. flag: a weight that fp16 cannot hold.
+// decoder reads its A operands from (InsSegW::dw1c), the plan of a crop with nothing flagged, and bound_coefficients of
+//   |s16(c,p) - (chain32(c,p) - gb_c)| <= X P_c + Q_c + 2 K 2^-24 |gb_c|,   K = 64.
 __global__ void pack_dec_prune_kernel(dal3_layer L, float* __restrict__ dw1c, float* __restrict__ pq, uint32_t* __restrict__ ident,
                                       int32_t* __restrict__ flag) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -219,19 +200,7 @@ __global__ void pack_dec_prune_kernel(dal3_layer L, float* __restrict__ dw1c, fl
         dw1c[i] = k < DEC_NULL_K ? folded_w(L, ch, 32 * (f >> 4) + tile_chan(f & 15, hh), 0, 64) : 0.0f;
     }
     if (i < DEC_PLAN_LD) ident[i] = i < DEC_NULL_K ? (uint32_t)i : (uint32_t)DEC_NULL_K;
-    if (i >= 512) return;
-    double s2 = 0.0, s1 = 0.0;
-    bool bad = false;
-    for (int k = 0; k < 64; ++k) {
-        const float v = folded_w(L, i, k, 0, 64);
-        bad |= !(fabsf(v) < 65504.0f);
-        s2 += (double)v * (double)v;
-        s1 += fabs((double)v);
-    }
-    const double kappa = 1.02 * 0x1p-10 + 64.0 * 0x1p-23;
-    pq[2 * i] = (float)((kappa * sqrt(s2) + 0x1p-24 * 8.0) * (1.0 + 1e-6));
-    pq[2 * i + 1] = (float)((0x1p-24 * s1 + 0x1p-40) * (1.0 + 1e-6));
-    if (bad) atomicOr(flag, 1);
+    if (i < 512) bound_coefficients<64>(L, i, pq, flag);
 }
 hipError_t launch_pack_dec_prune(const dal3_layer& L, float* dw1c, float* pq, uint32_t* ident, int32_t* flag, hipStream_t s) {
     hipLaunchKernelGGL(pack_dec_prune_kernel, dim3(((DEC_NULL_K + 1) * 64 + 255) / 256), dim3(256), 0, s, L, dw1c, pq, ident, flag);
@@ -288,24 +257,6 @@ hipError_t launch_dec_plan(const InsSegW& w, const float* gb, const uint32_t* pr
                            int32_t* plan_nch, hipStream_t s) {
     hipLaunchKernelGGL(dec_plan_kernel, dim3((unsigned)B), dim3(512), 0, s, gb, prune, w.prn_pq, w.prn_flag, w.dec_flag, plan_k,
                        plan_gbc, plan_nch);
-    return hipGetLastError();
-}
-
-// The same for the queue layers dconv3 (c_in 256) and dconv4 (c_in 128), 128 outputs each: [k][row][out-tile 0..3]
-__global__ void pack_dec_queue_kernel(dal3_layer L, int c_in, const float* __restrict__ bias, float* __restrict__ out,
-                                      int32_t* __restrict__ flag) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= c_in * 128) return;
-    const int mt = i & 3, row = (i >> 2) & 31, k = i >> 7;
-    const int kt = k >> 5, r = (k & 31) >> 1, h = k & 1;
-    const float v = folded_w(L, 32 * mt + row, 32 * kt + tile_chan(r, h), 0, c_in);
-    out[i] = v;
-    bool bad = (__float_as_uint(v) & 0x7F800000u) == 0x7F800000u;
-    if (i < 128) bad |= __float_as_uint(bias[i]) == 0x80000000u;
-    if (bad) atomicOr(flag, 1);
-}
-hipError_t launch_pack_dec_queue(const dal3_layer& L, int c_in, const float* bias, float* wcopy, int32_t* flag, hipStream_t s) {
-    hipLaunchKernelGGL(pack_dec_queue_kernel, dim3(c_in * 128 / 256), dim3(256), 0, s, L, c_in, bias, wcopy, flag);
     return hipGetLastError();
 }
 

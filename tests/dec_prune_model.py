@@ -17,11 +17,12 @@ and the plan's layout, and holds the JUDGE that the tests turn on planted faults
 import numpy as np
 import torch
 
+import bound_model
+from bound_model import fold as _fold
 from dec_sparse_model import fmaf, tile_chan
-from oracle import ref_heads as R
 
 K = 64
-KAPPA = 1.02 * 2.0 ** -10 + K * 2.0 ** -23
+KAPPA = bound_model.kappa(K)
 F16_GUARD = 60000.0                                       # an x2 entry above this: the crop has no bound
 NULL_K = 512                                              # DEC_NULL_K
 PLAN_LD = 640                                             # DEC_PLAN_LD
@@ -29,11 +30,6 @@ MIN_DEAD = 64                                             # DAL3_DEC_MIN_DEAD
 CHAIN = np.array([32 * c + tile_chan(r, h) for c in range(16) for r in range(16) for h in (0, 1)])   # chain index -> channel
 K_ORDER = np.array([32 * kt + tile_chan(r, h) for kt in range(2) for r in range(16) for h in (0, 1)])  # dconv1's own k order
 f32 = lambda v: torch.tensor(v, dtype=torch.float32)
-
-
-def _fold(sd, p, layer, bn):
-    w, b = R.fold_bn(sd, p, layer, bn)
-    return w.float(), b.float()
 
 
 def layers(sd, pts, p="ins_seg"):
@@ -54,10 +50,7 @@ def layers(sd, pts, p="ins_seg"):
 
 
 def coefficients(w1a):
-    w = w1a.double()
-    P = (KAPPA * w.norm(dim=1) + 2.0 ** -24 * np.sqrt(K)) * (1 + 1e-6)
-    Q = (2.0 ** -24 * w.abs().sum(1) + 2.0 ** -40) * (1 + 1e-6)
-    return P, Q
+    return bound_model.coefficients(w1a, K)
 
 
 def scores(w1a, x2):

@@ -18,7 +18,7 @@ dropped zero terms, not about the last bit of one fmaf.
 import numpy as np
 import torch
 
-from oracle import ref_heads as R
+from bound_model import fold as _fold
 
 TILE = 32                                                  # points per wave tile (DAL3_DEC_T = 1)
 
@@ -79,11 +79,6 @@ def compact_chain(w2, b2, act):
         steps_all.append(steps)
         dense_all.append(dense)
     return acc, np.array(steps_all), np.array(dense_all)
-
-
-def _fold(sd, p, layer, bn):
-    w, b = R.fold_bn(sd, p, layer, bn)
-    return w.float(), b.float()
 
 
 def decoder_inputs(sd, pts, p="ins_seg"):

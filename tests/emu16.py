@@ -21,6 +21,7 @@ precision accumulate) fails, however generous the absolute bar.
 """
 import torch
 
+from bound_model import fold as _fold
 from oracle import ref_heads as R
 
 DT = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}     # ("fp32": no rounding — the structure check)
@@ -31,11 +32,6 @@ RMS_SLACK = 1.15                                           # ... for rms errors 
 def q(x, prec):
     """round to the 16-bit type and back (RNE), exactly what a 16-bit MFMA operand holds"""
     return x.to(DT[prec]).float()
-
-
-def _fold(sd, p, layer, bn):
-    w, b = R.fold_bn(sd, p, layer, bn)
-    return w.float(), b.float()
 
 
 def _lin32(w, b, x):

@@ -9,7 +9,7 @@ specifies), its distance to the dense kernel's value chain32 (a k-ordered fp32 f
   E(c, tile) = X * P_c + Q_c,  X = max ||x_p||_2 over the tile's 32 points,
   P_c = KAPPA ||w_c||_2 + 2^-24 sqrt(K),  Q_c = 2^-24 ||w_c||_1 + 2^-40,  KAPPA = 1.02 * 2^-10 + K * 2^-23,  K = 256
 
-(DESIGN.md "Screened conv4 of the point heads"; dal3_misc.hip, pack_head_screen_kernel), and only the pairs with
+(DESIGN.md "Screened conv4 of the point heads"; dal3_misc.hip, bound_coefficients), and only the pairs with
   s16 > thr = fl(fl(G - b_c) - fl(E + 2^-22 (|G| + |b_c|))),   G = the seed tiles' exact maximum of the channel,
 are recomputed exactly. (The kernel's G may be larger — other waves' and the run's own exact maxima — which only
 removes candidates; the model keeps the rule of the design's table.) float64 on the fp32 operands stands in for the
@@ -18,19 +18,16 @@ exact chain; the chain's own rounding (<= K 2^-24 sum|w||x|) is part of KAPPA.
 import numpy as np
 import torch
 
+import bound_model
+from bound_model import fold as _fold
 from oracle import ref_heads as R
 
 K = 256
-KAPPA = 1.02 * 2.0 ** -10 + K * 2.0 ** -23
+KAPPA = bound_model.kappa(K)
 TILE = 32
 F16_GUARD = 60000.0                                       # activations above this: the tile takes the dense layer
 SCR_CAP = 1024                                            # candidate entries per 32-point tile (HEAD_SCR_CAP)
 STRIDE = 4                                                # DAL3_HEAD_SCR_STRIDE as shipped
-
-
-def _fold(sd, p, layer, bn):
-    w, b = R.fold_bn(sd, p, layer, bn)
-    return w.float(), b.float()
 
 
 def activations(sd, x, p="box_est"):
@@ -56,10 +53,7 @@ def effective_points(x, distinct):
 
 
 def coefficients(w4):
-    w = w4.double()
-    P = (KAPPA * w.norm(dim=1) + 2.0 ** -24 * np.sqrt(K)) * (1 + 1e-6)
-    Q = (2.0 ** -24 * w.abs().sum(1) + 2.0 ** -40) * (1 + 1e-6)
-    return P, Q
+    return bound_model.coefficients(w4, K)
 
 
 def check(w4, b4, x3, live, real, stride=STRIDE, what="", proof=True):

@@ -10,25 +10,21 @@ layers so that a wrong bound is found without a GPU:
   eps_l2(c,p) = KAPPA * ||w_c||_2 ||x_p||_2,   eps_l1(c,p) = KAPPA * sum_k |w_ck| |x_pk|      (the two bounds
   KAPPA       = 1.02 * 2^-10 + K * 2^-23,  K = 128                                              of the issue's table)
   E(c, wave)  = X * P_c + Q_c,  X = max ||x_p||_2 over the wave's 64 points                      (what the kernels evaluate:
-  P_c = KAPPA ||w_c||_2 + 2^-24 sqrt(K),  Q_c = 2^-24 ||w_c||_1 + 2^-40                           dal3_misc.hip, pack_enc_screen_kernel)
+  P_c = KAPPA ||w_c||_2 + 2^-24 sqrt(K),  Q_c = 2^-24 ||w_c||_1 + 2^-40                           dal3_misc.hip, bound_coefficients)
 
 float64 on the fp32 operands stands in for the exact chain; the chain's own rounding (<= K 2^-24 sum|w||x|) is part of KAPPA.
 """
 import numpy as np
 import torch
 
-from oracle import ref_heads as R
+import bound_model
+from bound_model import fold as _fold
 
 K = 128
-KAPPA = 1.02 * 2.0 ** -10 + K * 2.0 ** -23
+KAPPA = bound_model.kappa(K)
 WAVE_POINTS = 64                                          # DAL3_ENC_T = 2 tiles of 32 points per wave
 F16_GUARD = 60000.0                                       # activations above this: the wave takes the dense layer
 SCR_CAP = 1024                                            # candidate entries per wave and 32-point tile
-
-
-def _fold(sd, p, layer, bn):
-    w, b = R.fold_bn(sd, p, layer, bn)
-    return w.float(), b.float()
 
 
 def activations(sd, pts, p="ins_seg"):
@@ -57,10 +53,7 @@ def eps_point(w5, x4, bound):
 
 
 def coefficients(w5):
-    w = w5.double()
-    P = (KAPPA * w.norm(dim=1) + 2.0 ** -24 * np.sqrt(K)) * (1 + 1e-6)
-    Q = (2.0 ** -24 * w.abs().sum(1) + 2.0 ** -40) * (1 + 1e-6)
-    return P, Q
+    return bound_model.coefficients(w5, K)
 
 
 def _waves(t, N):
