@@ -25,11 +25,13 @@ vp = C.c_void_p
 
 
 class Layer(C.Structure):
+    """dal3_layer"""
     _fields_ = [("weight", vp), ("bias", vp), ("bn_weight", vp), ("bn_bias", vp), ("bn_mean", vp),
                 ("bn_var", vp), ("c_in", C.c_int32), ("c_out", C.c_int32)]
 
 
 class PackItem(C.Structure):
+    """dal3_tr_pack_item"""
     _fields_ = [("W", vp), ("ldw", C.c_int64), ("transpose_w", C.c_int32), ("c_out", C.c_int32), ("c_in", C.c_int32),
                 ("mtb", C.c_int32), ("out", vp)]
 
@@ -40,11 +42,13 @@ class WgradPart(C.Structure):
 
 
 class BCN(C.Structure):
+    """dal3_bcn"""
     _fields_ = [("data", vp), ("stride_b", C.c_int64), ("stride_c", C.c_int64), ("stride_n", C.c_int64),
                 ("dtype", C.c_int32), ("flags", C.c_int32)]
 
 
 class StaticArgs(C.Structure):
+    """dal3_static_args"""
     _fields_ = [("B", C.c_int32), ("N", C.c_int32), ("two_stage", C.c_int32), ("sampler", C.c_int32),
                 ("dtype", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64), ("item_offset", C.c_int64), ("pts", BCN),
                 ("init_box", vp), ("bbox_gt", vp), ("choice", vp),
@@ -59,6 +63,7 @@ class StaticArgs(C.Structure):
 
 
 class DynamicArgs(C.Structure):
+    """dal3_dynamic_args"""
     _fields_ = [("B", C.c_int32), ("N", C.c_int32), ("n_box", C.c_int32), ("sampler", C.c_int32),
                 ("dtype", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64), ("item_offset", C.c_int64), ("pts", BCN), ("box", BCN),
                 ("init_box8", vp), ("choice", vp),

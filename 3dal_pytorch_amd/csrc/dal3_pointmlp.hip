@@ -705,9 +705,6 @@ __device__ __forceinline__ void ins_seg_decode_tile(const InsSegW& w, const BCN&
 // compact loop ran once per chunk (LEDGER_r12.md, section 3). With nothing dead it still loses 5 %: the dense body stays.
 // A crop with a plan (DESIGN.md "Crop-dead channels of dconv1") is counted on the plan's flags, by dec_plan_kernel, against the
 // same number: at exactly 64 flags the planned call is level with the unplanned one, at 128 it gains 0.35 ms (LEDGER_r14.md).
-#ifndef DAL3_DEC_MIN_DEAD
-#define DAL3_DEC_MIN_DEAD 64
-#endif
 template <int T>
 __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_decode_kernel(InsSegW w, BCN pts, int c_in, int n_pts,
                                                              int tiles_per_item, const float* __restrict__ gbias,

@@ -1,5 +1,6 @@
 """Shared helpers for the parity tests: rebuild the deterministic inputs/weights the golden
 vectors were generated on (3dal_pytorch_amd/synth.py) and load the fixtures."""
+import ctypes
 import importlib
 import os
 import sys
@@ -15,6 +16,15 @@ pkg = importlib.import_module("3dal_pytorch_amd")
 synth = importlib.import_module("3dal_pytorch_amd.synth")
 arch = importlib.import_module("3dal_pytorch_amd.arch")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+
+def dec_min_dead():
+    """DAL3_DEC_MIN_DEAD (csrc/dal3_kernels.h) as the built library hands it out: dal3_ins_seg_plan_layout runs on the host
+    alone. The one number that the models and generated inputs of the tests go by."""
+    hip = importlib.import_module("3dal_pytorch_amd._hip")
+    off, min_dead = (ctypes.c_size_t * 4)(), ctypes.c_int(-1)
+    hip.check(hip.lib().dal3_ins_seg_plan_layout(1, off, ctypes.byref(min_dead)))
+    return min_dead.value
 
 
 def golden(name):

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 import bound_model
+from _common import dec_min_dead
 from bound_model import fold as _fold
 from dec_sparse_model import fmaf, tile_chan
 
@@ -26,7 +27,7 @@ KAPPA = bound_model.kappa(K)
 F16_GUARD = 60000.0                                       # an x2 entry above this: the crop has no bound
 NULL_K = 512                                              # DEC_NULL_K
 PLAN_LD = 640                                             # DEC_PLAN_LD
-MIN_DEAD = 64                                             # DAL3_DEC_MIN_DEAD
+MIN_DEAD = dec_min_dead()                                 # DAL3_DEC_MIN_DEAD
 CHAIN = np.array([32 * c + tile_chan(r, h) for c in range(16) for r in range(16) for h in (0, 1)])   # chain index -> channel
 K_ORDER = np.array([32 * kt + tile_chan(r, h) for kt in range(2) for r in range(16) for h in (0, 1)])  # dconv1's own k order
 f32 = lambda v: torch.tensor(v, dtype=torch.float32)

@@ -7,10 +7,10 @@ import numpy as np
 import torch
 
 import f64_ref as F
-from _common import positions_from_indices, synth
+from _common import dec_min_dead, positions_from_indices, synth
 from oracle import ref_heads as R
 
-DEC_MIN_DEAD = 160                                         # DAL3_DEC_MIN_DEAD (csrc/dal3_kernels.h)
+DEC_MIN_DEAD = dec_min_dead()                              # DAL3_DEC_MIN_DEAD (csrc/dal3_kernels.h)
 
 
 def with_dconv1_bias(seed, shift):

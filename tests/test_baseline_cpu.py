@@ -1,13 +1,12 @@
 """CPU-side checks of the baseline runs (3dal_pytorch_amd/baseline.py; dal3_score_tracks / dal3_best_gt_iou): the sample
 recipe against what the reference's tools/static_init.py, tools/dynamic_init.py and tools/eval.py recorded
-(tests/golden/baseline.npz, written by tests/golden/gen_baseline.py), the host flattening, the C ABI's structs and
+(tests/golden/baseline.npz, written by tests/golden/gen_baseline.py), the host flattening, the C ABI's entries and
 argument checks, and the code object's scratch use. No GPU compute here."""
 import ctypes
 import importlib
 import os
 import pickle
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -113,24 +112,6 @@ def test_entries_are_declared_bound_and_exported():
     assert hip.lib().dal3_score_workspace_bytes(0) == 0
     assert hip.lib().dal3_score_workspace_bytes(256) * 2 == hip.lib().dal3_score_workspace_bytes(257)
     assert hip.lib().dal3_score_workspace_bytes(1 << 20) == 4096 * hip.lib().dal3_score_workspace_bytes(1)
-
-
-def test_ctypes_structs_have_the_headers_layout(tmp_path):
-    """sizeof and every field offset of the three structs, as a C compiler lays out include/dal3.h"""
-    cc = shutil.which("gcc") or shutil.which("cc") or shutil.which("clang") or "/opt/rocm/lib/llvm/bin/clang"
-    structs = {"dal3_score_acc": hip.ScoreAcc, "dal3_score_args": hip.ScoreArgs, "dal3_best_gt_args": hip.BestGtArgs}
-    body = "".join(f'printf("{c} %zu\\n", sizeof({c}));\n' + "".join(
-        f'printf("{c}.{f[0]} %zu\\n", offsetof({c}, {f[0]}));\n' for f in t._fields_) for c, t in structs.items())
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "dal3.h"\nint main(void) {\n' + body + "return 0; }\n")
-    exe = tmp_path / "layout"
-    subprocess.run([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    for c, t in structs.items():
-        assert int(got[c]) == ctypes.sizeof(t), c
-        for f in t._fields_:
-            assert int(got[f"{c}.{f[0]}"]) == getattr(t, f[0]).offset, (c, f[0])
-    assert ctypes.sizeof(hip.ScoreAcc) == 72
 
 
 def _score_args(**kw):

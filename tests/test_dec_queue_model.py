@@ -119,7 +119,7 @@ def test_the_bench_tools_threshold_is_the_kernels():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sys.path.insert(0, os.path.join(root, "tools"))
     import bench_kernels
-    src = open(os.path.join(root, "3dal_pytorch_amd", "csrc", "dal3_pointmlp.hip")).read()
-    assert bench_kernels.DEC_MIN_DEAD == int(re.search(r"^#define DAL3_DEC_MIN_DEAD (\d+)", src, re.M).group(1))
+    from _common import dec_min_dead
+    assert bench_kernels.DEC_MIN_DEAD == dec_min_dead()
     hdr = open(os.path.join(root, "3dal_pytorch_amd", "csrc", "dal3_kernels.h")).read()
     assert bench_kernels.BLOB_TAIL_BYTES == 4 * int(re.search(r"^#define DAL3_BLOB_TAIL_FLOATS (\d+)", hdr, re.M).group(1))

@@ -1,12 +1,10 @@
 """CPU-side checks of the detector post-processing (3dal_pytorch_amd/nms.py, detect.py; dal3_nms / dal3_center_decode):
 the NumPy restatement of tests/nms_ref.py against what the reference's own rotate_nms_pcdet, circle_nms and
-CenterHead.predict recorded (tests/golden/nms.npz, written by tests/golden/gen_nms.py), the C ABI's structs and argument
+CenterHead.predict recorded (tests/golden/nms.npz, written by tests/golden/gen_nms.py), the C ABI's entries and argument
 checks, and the refusals that need no device. No GPU compute here."""
 import ctypes
 import importlib
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -88,22 +86,6 @@ def test_entries_are_declared_bound_and_exported():
     # O(K): twice the rows, twice the bytes (to the 256-byte sections)
     one, two = hip.lib().dal3_nms_workspace_bytes(1 << 16, 0), hip.lib().dal3_nms_workspace_bytes(1 << 17, 0)
     assert two == 2 * one and hip.lib().dal3_nms_workspace_bytes(1 << 16, 1) > one
-
-
-def test_ctypes_structs_have_the_headers_layout(tmp_path):
-    cc = shutil.which("gcc") or shutil.which("cc") or shutil.which("clang") or "/opt/rocm/lib/llvm/bin/clang"
-    structs = {"dal3_nms_args": hip.NmsArgs, "dal3_map": hip.Map, "dal3_center_decode_args": hip.CenterDecodeArgs}
-    body = "".join(f'printf("{c} %zu\\n", sizeof({c}));\n' + "".join(
-        f'printf("{c}.{f[0]} %zu\\n", offsetof({c}, {f[0]}));\n' for f in t._fields_) for c, t in structs.items())
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "dal3.h"\nint main(void) {\n' + body + "return 0; }\n")
-    exe = tmp_path / "layout"
-    subprocess.run([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    for c, t in structs.items():
-        assert int(got[c]) == ctypes.sizeof(t), c
-        for f in t._fields_:
-            assert int(got[f"{c}.{f[0]}"]) == getattr(t, f[0]).offset, (c, f[0])
 
 
 FAKE = 0x1000                                   # never dereferenced: every case fails before a launch

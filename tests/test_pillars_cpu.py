@@ -2,13 +2,11 @@
 dal3_pillar_scatter, dal3_voxel_mean): the sort-based NumPy restatement of tests/pillars_ref.py against what the reference's
 own points_to_voxel recorded (tests/golden/pillars.npz, written by tests/golden/gen_pillars.py) — which pins that the parallel
 formulation equals the sequential loop, cap included —, the float64 restatement of the feature net against the reference
-module's .double() output, the planted faults against the GPU test's bars, the C ABI's structs, workspace sizes and
+module's .double() output, the planted faults against the GPU test's bars, the C ABI's entries, workspace sizes and
 argument checks, and the refusals that need no device. No GPU compute here."""
 import ctypes
 import importlib
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -235,22 +233,6 @@ def test_workspace_sizes_are_the_carve():
     assert lib.dal3_voxelize_workspace_bytes(1, 1000) == carve(1, 1000) == 26368
     assert lib.dal3_voxelize_workspace_bytes(4, 720000) == carve(4, 720000) == 17472000
     assert lib.dal3_voxelize_workspace_bytes(-1, 0) == 0 and lib.dal3_voxelize_workspace_bytes(0, 1 << 25) == 0
-
-
-def test_ctypes_structs_have_the_headers_layout(tmp_path):
-    cc = shutil.which("gcc") or shutil.which("cc") or shutil.which("clang") or "/opt/rocm/lib/llvm/bin/clang"
-    structs = {"dal3_voxelize_args": hip.VoxelizeArgs, "dal3_pillar_feature_args": hip.PillarFeatureArgs}
-    body = "".join(f'printf("{c} %zu\\n", sizeof({c}));\n' + "".join(
-        f'printf("{c}.{f[0]} %zu\\n", offsetof({c}, {f[0]}));\n' for f in t._fields_) for c, t in structs.items())
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "dal3.h"\nint main(void) {\n' + body + "return 0; }\n")
-    exe = tmp_path / "layout"
-    subprocess.run([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    for c, t in structs.items():
-        assert int(got[c]) == ctypes.sizeof(t), c
-        for f in t._fields_:
-            assert int(got[f"{c}.{f[0]}"]) == getattr(t, f[0]).offset, (c, f[0])
 
 
 FAKE = 0x1000                                   # never dereferenced: every case fails before a launch

@@ -1,14 +1,12 @@
 """CPU-side checks of the detector's dense stage (3dal_pytorch_amd/rpn.py, detector.py; dal3_conv2d_pack / dal3_conv2d):
 the float64 restatement of tests/rpn_ref.py against what the reference's own RPN and CenterHead recorded (tests/golden/
 rpn.npz, written by tests/golden/gen_rpn.py), the planted faults against the GPU tests' bars, the modules' keys against the
-reference's, the stock-torch composite against the recorded fp32 outputs bit for bit, the C ABI's declarations, struct
-layout and argument checks, and the FLOP count of tools/bench_detector.py. No GPU compute here."""
+reference's, the stock-torch composite against the recorded fp32 outputs bit for bit, the C ABI's declarations
+and argument checks, and the FLOP count of tools/bench_detector.py. No GPU compute here."""
 import ctypes
 import importlib
 import importlib.util
 import os
-import shutil
-import subprocess
 import zlib
 
 import numpy as np
@@ -177,21 +175,6 @@ def test_pack_sizes_follow_the_layout():
     assert f(hip.CONV2D_DECONV2, 128, 128) == 512 + 16 * 16 * 256
     assert f(hip.CONV2D_DECONV4, 256, 128) == 2048 + 64 * 32 * 256
     assert f(4, 64, 64) == 0 and f(-1, 64, 64) == 0 and f(0, 0, 64) == 0 and f(0, 64, 0) == 0 and f(0, 4097, 1) == 0
-
-
-def test_ctypes_struct_has_the_headers_layout(tmp_path):
-    cc = shutil.which("gcc") or shutil.which("cc") or shutil.which("clang") or "/opt/rocm/lib/llvm/bin/clang"
-    c, t = "dal3_conv2d_args", hip.Conv2dArgs
-    body = f'printf("{c} %zu\\n", sizeof({c}));\n' + "".join(
-        f'printf("{c}.{f[0]} %zu\\n", offsetof({c}, {f[0]}));\n' for f in t._fields_)
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "dal3.h"\nint main(void) {\n' + body + "return 0; }\n")
-    exe = tmp_path / "layout"
-    subprocess.run([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(got[c]) == ctypes.sizeof(t)
-    for f in t._fields_:
-        assert int(got[f"{c}.{f[0]}"]) == getattr(t, f[0]).offset, f[0]
 
 
 FAKE = 0x1000                                   # never dereferenced: every case fails before a launch

@@ -1,12 +1,10 @@
 """CPU-side checks of the double-flip test-time augmentation (dal3_flip4_points, dal3_center_decode_flip4; detect.
 DoubleFlipPost, pillars.double_flip): the NumPy restatement of tests/tta_ref.py against what the reference's own
 CenterHead.predict with double_flip and its DoubleFlip recorded (tests/golden/tta.npz, written by tests/golden/gen_tta.py),
-the C ABI's struct and argument checks, and the refusals that need no device. No GPU compute here."""
+the C ABI's entries and argument checks, and the refusals that need no device. No GPU compute here."""
 import ctypes
 import importlib
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -95,25 +93,6 @@ def test_workspace_bytes_formula_at_two_sizes():
         assert lib.dal3_center_decode_flip4_workspace_bytes(B, H, W) == want == lib.dal3_center_decode_workspace_bytes(B, H, W)
     assert lib.dal3_center_decode_flip4_workspace_bytes(-1, 4, 4) == 0
     assert lib.dal3_center_decode_flip4_workspace_bytes(1, 1 << 13, 1 << 13) == 0
-
-
-def test_ctypes_struct_has_the_headers_layout(tmp_path):
-    cc = shutil.which("gcc") or shutil.which("cc") or shutil.which("clang") or "/opt/rocm/lib/llvm/bin/clang"
-    lines = ['printf("size %zu\\n", sizeof(dal3_center_decode_flip4_args));',
-             'printf("decode %zu\\n", offsetof(dal3_center_decode_flip4_args, decode));']
-    lines += [f'printf("decode.{f[0]} %zu\\n", offsetof(dal3_center_decode_flip4_args, decode.{f[0]}));'
-              for f in hip.CenterDecodeArgs._fields_]
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "dal3.h"\nint main(void) {\n' + "\n".join(lines) +
-                   "\nreturn 0; }\n")
-    exe = tmp_path / "layout"
-    subprocess.run([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    t = hip.CenterDecodeFlip4Args
-    assert [f[0] for f in t._fields_] == ["decode"]
-    assert int(got["size"]) == ctypes.sizeof(t) and int(got["decode"]) == t.decode.offset
-    for f in hip.CenterDecodeArgs._fields_:
-        assert int(got[f"decode.{f[0]}"]) == t.decode.offset + getattr(hip.CenterDecodeArgs, f[0]).offset, f[0]
 
 
 FAKE = 0x1000                                   # never dereferenced: every case fails before a launch

@@ -24,7 +24,7 @@ DNAME = {"fp32": "f32", "bf16": "bf16", "fp16": "f16", "f16x3": "f16x3 (fp16 MFM
 EXEC_MULT = {"fp32": 1, "bf16": 1, "fp16": 1, "f16x3": 3}
 
 
-DEC_MIN_DEAD = 64                # DAL3_DEC_MIN_DEAD of csrc/dal3_pointmlp.hip (tests/test_dec_queue_model.py holds the two together)
+DEC_MIN_DEAD = 64                # DAL3_DEC_MIN_DEAD of csrc/dal3_kernels.h (tests/test_dec_queue_model.py holds the two together)
 BLOB_TAIL_BYTES = 32768          # DAL3_BLOB_TAIL_FLOATS * 4 (csrc/dal3_kernels.h)
 
 
