@@ -129,6 +129,11 @@ struct WRing {
         if (CYC && soff == len) soff = 0;                  // scalar compare + select
         return __builtin_bit_cast(f32x4, v);
     }
+    // The fragment at byte offset `off` of the stream, `soff` left alone: for a consumer whose position in the stream is
+    // a function of its loop counters, so that no offset is carried from tile to tile (dal3_head_screen.hip).
+    __device__ __forceinline__ f32x4 fetch_at(uint32_t off) const {
+        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, off, 0));
+    }
     __device__ __forceinline__ void init(const f32x4* stream, int lane, uint32_t bytes = 0) {
         rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<f32x4*>(stream), 0, 0x7fffffff, 0x00020000);
         voff = (uint32_t)lane * 16u;

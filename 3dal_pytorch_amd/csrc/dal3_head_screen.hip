@@ -55,6 +55,35 @@ extern "C" int dal3_debug_head_screen_counts(unsigned long long* out, int reset)
 #define HSCR_COUNT(k, v)
 #endif
 
+// Diagnostic build only (-DDAL3_STAMP, tools/stamps_head.py): a persistent wave sums the s_memtime ticks of its tiles' phases
+// and leaves them, 16 words per wave, in a buffer of their own (dal3_debug_set_head_stamps): [0] conv1..conv3 with the next
+// tile's entry and points, [1] norm, pack and range test, [2] the fp16 sweep, [3] list building, [4] / [5] the recompute's
+// halves, [6] flush, entry and turnover, [7] a dense conv4 (range, flag or overflow), [8] tiles, [9] tiles that stayed
+// screened. No stamp executes in the shipped library.
+#ifdef DAL3_STAMP
+__device__ unsigned long long* g_head_stamps = nullptr;
+extern "C" int dal3_debug_set_head_stamps(void* p) {
+    return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_head_stamps), &p, sizeof(p));
+}
+#define HSTAMP_NOW(t)                                                               \
+    do {                                                                            \
+        __builtin_amdgcn_sched_barrier(0);                                          \
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory"); \
+        __builtin_amdgcn_sched_barrier(0);                                          \
+    } while (0)
+#define HSTAMP(k)                                \
+    do {                                         \
+        unsigned long long t_;                   \
+        HSTAMP_NOW(t_);                          \
+        st_acc[k] += (uint32_t)(t_ - st_prev);   \
+        st_prev = t_;                            \
+    } while (0)
+#define HSTAMP_ADD(k, v) st_acc[k] += (v)
+#else
+#define HSTAMP(k)
+#define HSTAMP_ADD(k, v)
+#endif
+
 template <int KS, int C1, int C2, int C3>
 __global__ __launch_bounds__(64) void point_head_screen_kernel(PointHeadW w, BCN x, int c_in, float* __restrict__ feat,
                                                                uint32_t* __restrict__ ctl, const u32x4* __restrict__ list) {
@@ -95,8 +124,14 @@ __global__ __launch_bounds__(64) void point_head_screen_kernel(PointHeadW w, BCN
     constexpr uint32_t FRAGS23 = ((C2 / 32) * (C1 / 32) + (C3 / 32) * (C2 / 32)) * 4u;   // conv2 | conv3 fragments
     WRing<DAL3_PF, true> ring;                         // conv2 | conv3, cyclic: conv4's fp32 fragments are the fallback's
     ring.init(w.stream, lane, FRAGS23 * 1024u);
-    WRing<8, true> r16;                                // conv4's fp16 fragments [16 out-tiles][8 kt][2 s] of 1 KiB, cyclic
-    r16.init(w.w4h, lane, 16u * KT * 2u * 1024u);
+    // conv4's fp16 fragments [16 out-tiles][8 kt][2 s] of 1 KiB. A sweep consumes the whole stream exactly, so the ring
+    // stands at the stream's start (fragments 0..7 in the slots) at every tile boundary, whichever way the tile went,
+    // and the fetch behind use i of block mt is fragment (16 mt + i + 8) mod 256: a function of the counters, nothing
+    // carried round the tile loop. (A carried offset meets the dense routes' epilogue at the loop's join, a divergent
+    // branch the compiler merges from both routes, is taken for divergent there, and every fetch of the sweep gets a
+    // waterfall loop: profiles/LEDGER_r17.md.)
+    WRing<8> r16;
+    r16.init(w.w4h, lane);
     f32x16 bias = tile_from_channels(w.b2, h);
     u32x4 e = list[cur];
     float in[T][KS];
@@ -121,6 +156,11 @@ __global__ __launch_bounds__(64) void point_head_screen_kernel(PointHeadW w, BCN
         conv_max_layer<KT, T>(r32, s_b4, x3, reinterpret_cast<float*>(s_run), 16, lane);
     };
     enter((int64_t)e[0]);
+#ifdef DAL3_STAMP
+    uint32_t st_acc[10] = {};
+    unsigned long long st_prev;
+    HSTAMP_NOW(st_prev);
+#endif
     for (;;) {
         const int64_t b = (int64_t)e[0];
         const int e_t = (int)e[1], e_n = (int)e[2];    // this tile's index and the item's distinct points
@@ -152,6 +192,8 @@ __global__ __launch_bounds__(64) void point_head_screen_kernel(PointHeadW w, BCN
             load_points<KS, T>(x, (int64_t)e[0], (int)e[1] * 32, (int)e[2], c_in, in_n, lane);
         }
         HSCR_COUNT(0, 1);
+        HSTAMP(0);
+        HSTAMP_ADD(8, 1u);
 
         // fp16 holds every activation of the tile? (x3 >= +0 after the ReLU: the integer order of the bit patterns is the
         // order of the values, and a NaN / Inf pattern lies above the limit.)
@@ -167,6 +209,7 @@ __global__ __launch_bounds__(64) void point_head_screen_kernel(PointHeadW w, BCN
         if (blob_dense || __builtin_amdgcn_ballot_w64(xm > HEAD_SCR_XMAX_BITS) != 0) {
             HSCR_COUNT(1, 1);
             dense_tile(x3);
+            HSTAMP(7);
         } else {
             // X >= ||x_p||_2 for every point of the tile (lane half h holds 128 of a point's 256 channels)
             float ss = 0.0f;
@@ -197,6 +240,7 @@ __global__ __launch_bounds__(64) void point_head_screen_kernel(PointHeadW w, BCN
             }
             // Per 32-channel block one constant per lane (= channel): the threshold on the fp16 score.
             // chain32 <= s16 + E; s16 <= thr <= G - b - E  ==>  chain32 + b <= G  ==>  fl(chain32 + b) <= G.
+            HSTAMP(1);
             auto block_const = [&](int mt) -> float {
                 const int c = 32 * mt + (lane & 31);
                 const f32x2 pq = s_pq[c];
@@ -218,12 +262,12 @@ __global__ __launch_bounds__(64) void point_head_screen_kernel(PointHeadW w, BCN
                 hits.park_block(s_stage, mt, hb & vmask, lane);
             };
             // transposed tile, as conv_max_layer: points on the registers, channels on the lanes
-            auto mm = [&](f32x16& acc, auto side) {
+            auto mm = [&](f32x16& acc, int mt, auto side) {
                 acc = f32x16{};
 #pragma unroll
                 for (int i = 0; i < 2 * KT; ++i) {
                     const f16x8_t a = __builtin_bit_cast(f16x8_t, r16.slot[i & 7]);
-                    r16.slot[i & 7] = r16.fetch();
+                    r16.slot[i & 7] = r16.fetch_at(((16u * (uint32_t)mt + (uint32_t)i + 8u) & 255u) * 1024u);
                     acc = FP16::mfma(xh[i >> 1].k[i & 1], a, acc);
                     DAL3_SCHED_FENCE();
                     side(i);
@@ -232,30 +276,33 @@ __global__ __launch_bounds__(64) void point_head_screen_kernel(PointHeadW w, BCN
             };
             f32x16 accA, accB;
             float kA = block_const(0), kB;
-            mm(accA, NoSide());                                                    // block 0
+            mm(accA, 0, NoSide());                                                 // block 0
             int mt = 1;
             for (; mt + 1 < 16; mt += 2) {             // (two whole blocks per trip and nothing else: see conv_max_layer)
                 kB = block_const(mt);
-                mm(accB, [&](int i) { if (i < 8) ep_slice(accA, i, kA); });
+                mm(accB, mt, [&](int i) { if (i < 8) ep_slice(accA, i, kA); });
                 ep_finish(mt - 1);
                 kA = block_const(mt + 1);
-                mm(accA, [&](int i) { if (i < 8) ep_slice(accB, i, kB); });
+                mm(accA, mt + 1, [&](int i) { if (i < 8) ep_slice(accB, i, kB); });
                 ep_finish(mt);
             }
             kB = block_const(mt);                                                  // mt == 15
-            mm(accB, [&](int i) { if (i < 8) ep_slice(accA, i, kA); });
+            mm(accB, mt, [&](int i) { if (i < 8) ep_slice(accA, i, kA); });
             ep_finish(mt - 1);
 #pragma unroll
             for (int i = 0; i < 8; ++i) ep_slice(accB, i, kB);                     // last block: nothing left to hide under
             ep_finish(mt);
+            HSTAMP(2);
             uint32_t cnt1[T];
             const bool overflow = scr_build_lists<T, 16, HEAD_SCR_CAP>(s_stage, s_list, hits, cnt1, lane);
             const uint32_t cnt = cnt1[0];
             HSCR_COUNT(3, cnt);
+            HSTAMP(3);
 
             if (overflow) {                            // the list does not hold the tile's candidates: the dense layer, exact
                 HSCR_COUNT(2, 1);
                 dense_tile(x3);
+                HSTAMP(7);
             } else {
                 // One candidate per lane: the dense kernel's chain. v_mfma_f32_32x32x2_f32 from a zero accumulator is, per
                 // output, fma(a1, b1, fma(a0, b0, acc)) over its k-steps in issue order, k = 0 from lane half 0: channels
@@ -292,19 +339,29 @@ __global__ __launch_bounds__(64) void point_head_screen_kernel(PointHeadW w, BCN
                                 if (live && bits > 0) atomicMax(&s_run[c], bits);
                             }
                         });
+                    HSTAMP(4 + half);
                 }
+                HSTAMP_ADD(9, 1u);
             }
         }
         const bool more = ncur < n_live;
         const bool leave = !more || (int64_t)e[0] != b;
         if (leave) flush(b);                           // (the wave's own LDS operations are in order: no barrier)
+        HSTAMP(6);
         if (!more) break;
         if (leave) enter((int64_t)e[0]);
+        HSTAMP(6);
         cur = ncur;
         run_end = nend;
 #pragma unroll
         for (int k = 0; k < KS; ++k) in[0][k] = in_n[0][k];
     }
+#ifdef DAL3_STAMP
+    if (lane == 0 && blockIdx.x < 1024) {
+#pragma unroll
+        for (int k = 0; k < 10; ++k) g_head_stamps[blockIdx.x * 16 + k] = st_acc[k];
+    }
+#endif
 }
 
 hipError_t launch_point_head_screen(int head_kind, const PointHeadW& w, BCN x, int c_in, float* feat, uint32_t* ctl,

@@ -55,6 +55,9 @@ __device__ __forceinline__ void lat_block(WRing<8>& ring, int KT, const float* _
 
 // one layer: Y[:, 32 mt ..] = relu(W' X + init) for the out-tiles mt = wave, wave + 16, ...; `frags` = the layer's
 // fragments [MT][KT][4][64] f32x4; init (LDS) = the folded bias, or the crop's dconv1 term
+// `wave` must be in a scalar register (the kernels take it through readfirstlane): the ring's buffer descriptor is built
+// from frags + mt, and with mt derived from threadIdx.x the compiler holds the descriptor in vector registers and wraps
+// every fetch in a loop over its distinct values (four v_readfirstlane_b32 and a branch per load).
 __device__ __forceinline__ void lat_layer(const f32x4* __restrict__ frags, int KT, int MT, const float* __restrict__ init,
                                           const float* __restrict__ X, int ldx, float* __restrict__ Y, int ldy, int lane,
                                           int wave) {
@@ -113,7 +116,7 @@ __global__ __launch_bounds__(64 * LAT_WAVES) void ins_seg_encode_lat_kernel(InsS
     float* bufA = lat_smem;
     float* bufB = bufA + 32 * LAT_LDA;
     float* s_b = bufB + 32 * LAT_LDB;                   // b1 64 | b2 64 | b3 64 | b4 128 | b5 1024
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // (scalar: see lat_layer)
     const int64_t b = blockIdx.x / tiles_per_item;
     const int n0 = (blockIdx.x % tiles_per_item) * 32;
     lat_copy(s_b, w.b1, 64);
@@ -143,7 +146,7 @@ __global__ __launch_bounds__(64 * LAT_WAVES) void ins_seg_decode_lat_kernel(InsS
     float* bufA = lat_smem;
     float* bufB = bufA + 32 * LAT_LDA;
     float* s_b = bufB + 32 * LAT_LDB;                   // b1 64 | b2 64 | gb 512 | db2 256 | db3 128 | db4 128 | dw5 256 | db5 2
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // (scalar: see lat_layer)
     const int m = lane & 31, h = lane >> 5;
     const int64_t b = blockIdx.x / tiles_per_item;
     const int n0 = (blockIdx.x % tiles_per_item) * 32;
@@ -209,7 +212,7 @@ __global__ __launch_bounds__(64 * LAT_WAVES) void point_head_lat_kernel(PointHea
     float* bufA = lat_smem;
     float* bufB = bufA + 32 * LAT_LDA;
     float* s_b = bufB + 32 * LAT_LDB;                   // b1 C1 | b2 C2 | b3 C3 | b4 512
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // (scalar: see lat_layer)
     const int64_t b = blockIdx.x / tiles_per_item;
     const int n0 = (blockIdx.x % tiles_per_item) * 32;
     if (distinct) {                                     // copies beyond the first distinct[b] points: see point_head_kernel
