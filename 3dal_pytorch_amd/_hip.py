@@ -426,6 +426,7 @@ SIGNATURES = {
     "dal3_point_head_forward": (_i, [_i, vp, _i, BCN, _i, _i, vp, _i64, vp, _sz, vp]),
     "dal3_point_head_pool_workspace_bytes": (_sz, [_i, _i]),
     "dal3_point_head_screen_min_tiles": (_i, []),
+    "dal3_point_head_route": (_i, [_i, _i, _i, _i]),
     "dal3_point_head_screen_stride": (_i, []),
     "dal3_point_head_pool": (_i, [_i, vp, _i, BCN, _i, _i, vp, vp, vp, _sz, vp]),
     "dal3_dynamic_box_est_forward": (_i, [vp, vp, _i, vp, vp, _sz, vp]),
@@ -651,7 +652,9 @@ STORAGE = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 BCN_NO_SMALL_JOB_KERNELS, BCN_NO_WORKLIST, BCN_NO_LDS_SAMPLER = 1, 2, 4
 BCN_NO_DEC_PLAN = 16
 BCN_NO_ENC_RESIDENT = 32
+BCN_NO_HEAD_RESIDENT = 64
 ENC_ROUTE_LATENCY, ENC_ROUTE_DENSE, ENC_ROUTE_TWO_LAUNCH, ENC_ROUTE_RESIDENT = 0, 1, 2, 3      # dal3_ins_seg_encoder_route
+HEAD_ROUTE_LATENCY, HEAD_ROUTE_PER_TILE, HEAD_ROUTE_PERSISTENT, HEAD_ROUTE_TWO_LAUNCH, HEAD_ROUTE_RESIDENT = 0, 1, 2, 3, 4      # dal3_point_head_route
 # dal3_bcn.flags of every view bcn() builds (include/dal3.h, DAL3_BCN_*). 0 in normal use; A/B measurements and the
 # tests that pin "both kernel families give the same bits" set it around a call (binding-side, the library has no switch).
 DISPATCH_FLAGS = 0

@@ -278,6 +278,12 @@ hipError_t launch_point_head(int head_kind, const PointHeadW& w, BCN x, int c_in
 static_assert(DAL3_HEAD_SCR_STRIDE >= 2, "stride 1 leaves no tile to screen");
 hipError_t launch_point_head_screen(int head_kind, const PointHeadW& w, BCN x, int c_in, float* feat, uint32_t* ctl,
                                     const u32x4* list, int64_t max_tiles, int64_t slots, hipStream_t s);
+// The item-resident route (dal3_head_screen.hip): a workgroup of DAL3_WG_WAVES waves per CU takes whole items from a
+// cursor, every live tile screened.
+bool head_resident_route(int flags, int head_kind, int B, int M);
+int head_route(int flags, int head_kind, int B, int M);    // which point-head kernels run: DAL3_HEAD_ROUTE_* (dal3.h)
+hipError_t launch_point_head_resident(int head_kind, const PointHeadW& w, BCN x, int c_in, int B, int M, float* feat,
+                                      const int32_t* distinct, hipStream_t s, void* cursor, int cus);
 hipError_t launch_pack_head_screen(const dal3_layer& L, float* pq, int32_t* flag, hipStream_t s);
 hipError_t launch_generic_layer(const f32x4* wf, const float* w1, const float* bias, int kt_n, int ks_n, int mt_n,
                                 int relu, BCN x, int c_in, int B, int N, float* y, hipStream_t s);

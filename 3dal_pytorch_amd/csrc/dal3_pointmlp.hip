@@ -1082,20 +1082,58 @@ static int head_slots() {
     return 4 * v;
 }
 
+// The screened conv4 as one item-resident launch (dal3_head_screen.hip, point_head_resident_kernel): the heads with conv4
+// 256 -> 512, items of more than one tile, when the job has at least DAL3_HEAD_RES_MIN_PER_CU items per CU of the current
+// device; below that the two launches and their DAL3_HEAD_SCR_MIN_TILES, as before. A pure function of the job, the CU
+// count and the caller's flags (dal3.h: DAL3_BCN_NO_HEAD_RESIDENT selects the two launches for any job). Both give the
+// same bits. The constants are MEASURED (profiles/LEDGER_r18.md, "route constant"; 256 CUs, ms resident / two launches,
+// bench mix of distinct points). box_est at B x 512: a CU takes whole items one after the other, so a batch a little above
+// a whole number of items per CU pays for one more — with one workgroup per item 257 0.346 / 0.277 and 513 0.518 / 0.439
+// lose (256 0.198 / 0.273 and 512 0.387 / 0.436 win); from 3 per CU, with the cursor grid, nothing measured loses: 768
+// 0.553 / 0.608, 769 0.555 / 0.610, 1023 0.695 / 0.784, 1025 0.696 / 0.791, 4096 2.434 / 2.758. point_emb at B x 2560 (80
+// tiles an item, one workgroup per item): 768 1.876 / 1.794 and 769 2.135 / 1.813 lose, 1024 2.468 / 2.489 is level within
+// its spread of 0.024: from 4 per CU.
+#ifndef DAL3_HEAD_RES_MIN_PER_CU
+#define DAL3_HEAD_RES_MIN_PER_CU 3
+#endif
+#ifndef DAL3_HEAD_RES_MIN_PER_CU_EMB
+#define DAL3_HEAD_RES_MIN_PER_CU_EMB 4
+#endif
+bool head_resident_route(int flags, int head_kind, int B, int M) {
+    if (!DAL3_HEAD_SCREEN || DAL3_HEAD_T != 1 || (flags & (DAL3_BCN_NO_HEAD_RESIDENT | DAL3_BCN_NO_WORKLIST))) return false;
+    if ((head_kind != 1 && head_kind != 2) || (M + 31) / 32 <= 1) return false;
+    if (lat_use((int64_t)B * ((M + 31) / 32), flags, DAL3_LAT_MAX_TILES_HEAD)) return false;
+    return (int64_t)B >= (int64_t)(head_kind == 1 ? DAL3_HEAD_RES_MIN_PER_CU : DAL3_HEAD_RES_MIN_PER_CU_EMB) * (head_slots() / 4);
+}
+// Which kernels launch_point_head takes when it is given a worklist (dal3.h: dal3_point_head_route), in the order it decides.
+int head_route(int flags, int head_kind, int B, int M) {
+    const int64_t tiles = (int64_t)B * ((M + 31) / 32);
+    if (lat_use(tiles, flags, DAL3_LAT_MAX_TILES_HEAD)) return DAL3_HEAD_ROUTE_LATENCY;
+    if ((flags & DAL3_BCN_NO_WORKLIST) || DAL3_HEAD_T != 1) return DAL3_HEAD_ROUTE_PER_TILE;
+    if (head_resident_route(flags, head_kind, B, M)) return DAL3_HEAD_ROUTE_RESIDENT;
+    if (DAL3_HEAD_SCREEN && (head_kind == 1 || head_kind == 2) && tiles >= DAL3_HEAD_SCR_MIN_TILES && (M + 31) / 32 > 1)
+        return DAL3_HEAD_ROUTE_TWO_LAUNCH;
+    return DAL3_HEAD_ROUTE_PERSISTENT;
+}
+
 hipError_t launch_point_head(int head_kind, const PointHeadW& w, BCN x, int c_in, int B, int M, float* feat,
                              const int32_t* distinct, hipStream_t s, void* worklist, size_t worklist_bytes) {
     constexpr int T = DAL3_HEAD_T;
     const int tpi = (M + 32 * T - 1) / (32 * T);       // one-wave workgroups
     const bool lat = lat_use((int64_t)B * ((M + 31) / 32), x.flags, DAL3_LAT_MAX_TILES_HEAD);
     const bool pers = !lat && worklist && worklist_bytes >= point_head_worklist_bytes(B, M) && !(x.flags & DAL3_BCN_NO_WORKLIST) && T == 1;
-    // conv4 screened (dal3_head_screen.hip): the persistent route of a head with conv4 256 -> 512 from
-    // DAL3_HEAD_SCR_MIN_TILES tiles upward, and items of more than one seed's worth of tiles
-    const bool screen = DAL3_HEAD_SCREEN && pers && (head_kind == 1 || head_kind == 2) && w.w4row &&
+    // conv4 screened (dal3_head_screen.hip): whole items per workgroup where the job fills the chip with them (they read
+    // `distinct` themselves: no worklist is built, its first word is the item cursor) ...
+    const bool resident = pers && w.w4row && head_resident_route(x.flags, head_kind, B, M);
+    // ... else the persistent route of a head with conv4 256 -> 512 from DAL3_HEAD_SCR_MIN_TILES tiles upward, and items
+    // of more than one seed's worth of tiles
+    const bool screen = DAL3_HEAD_SCREEN && pers && !resident && (head_kind == 1 || head_kind == 2) && w.w4row &&
                         (int64_t)B * tpi >= DAL3_HEAD_SCR_MIN_TILES && tpi > 1;
     // feat = 0 (NaN rows for items with a non-finite input, dal3.h) and, for the persistent kernel, the worklist
-    hipError_t e0 = launch_nonfinite_rows(x, B, M, c_in, feat, 512, s, distinct, pers ? worklist : nullptr,
+    hipError_t e0 = launch_nonfinite_rows(x, B, M, c_in, feat, 512, s, distinct, pers && !resident ? worklist : nullptr,
                                           screen ? DAL3_HEAD_SCR_STRIDE : 0);
     if (e0 != hipSuccess) return e0;
+    if (resident) return launch_point_head_resident(head_kind, w, x, c_in, B, M, feat, distinct, s, worklist, head_slots() / 4);
     if (lat) return launch_point_head_lat(head_kind, w, x, c_in, B, M, feat, distinct, s);
     if (pers) {
         uint32_t* ctl = static_cast<uint32_t*>(worklist);

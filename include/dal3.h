@@ -143,9 +143,12 @@ typedef struct {
  *                                  crop (large jobs only; 8 is not a flag and stays refused)
  *   DAL3_BCN_NO_ENC_RESIDENT       fp32 instance segmentation: the screened encoder as its two launches (bound, then
  *                                  candidates; four workgroups per 1024 points) instead of one workgroup per crop, which
- *                                  jobs of many crops take (dal3_ins_seg_encoder_route) */
+ *                                  jobs of many crops take (dal3_ins_seg_encoder_route)
+ *   DAL3_BCN_NO_HEAD_RESIDENT      fp32 static box_est / point_emb heads: the screened conv4 as its two launches (dense
+ *                                  seed tiles, then the other tiles) instead of one workgroup per item, which jobs of
+ *                                  many items take (dal3_point_head_route) */
 enum { DAL3_BCN_NO_SMALL_JOB_KERNELS = 1, DAL3_BCN_NO_WORKLIST = 2, DAL3_BCN_NO_LDS_SAMPLER = 4, DAL3_BCN_NO_DEC_PLAN = 16,
-       DAL3_BCN_NO_ENC_RESIDENT = 32 };
+       DAL3_BCN_NO_ENC_RESIDENT = 32, DAL3_BCN_NO_HEAD_RESIDENT = 64 };
 
 /* ---- PointNetInstanceSeg.forward (static_model.py:271-296, dynamic_model.py:187-212) plus
  * the mask of point_cloud_masking (static_model.py:59). logits (B,N,2) fp32, mask (B,N) u8.
@@ -233,6 +236,13 @@ int dal3_point_head_pool(int head_kind, const void* packed, int dtype, dal3_bcn 
  * `stride`-th live tile of an item is its dense seed. Dispatch facts for tests and measurements. */
 int dal3_point_head_screen_min_tiles(void);
 int dal3_point_head_screen_stride(void);
+/* Which kernels a DAL3_F32 point-head job of B items x M points takes with `flags` (DAL3_BCN_*) on the current device, a
+ * workspace given: the small-job family, one workgroup per (item, tile), the dense persistent waves, the screened conv4's
+ * two launches, or its item-resident single launch. A pure function of its arguments and the device's CU count; negative
+ * (DAL3_EINVAL) for a bad argument. For tests and measurements: results are bit-identical on every route. */
+enum { DAL3_HEAD_ROUTE_LATENCY = 0, DAL3_HEAD_ROUTE_PER_TILE = 1, DAL3_HEAD_ROUTE_PERSISTENT = 2, DAL3_HEAD_ROUTE_TWO_LAUNCH = 3,
+       DAL3_HEAD_ROUTE_RESIDENT = 4 };
+int dal3_point_head_route(int head_kind, int B, int M, int flags);
 
 /* ---- dynamic PointNetEstimation.forward (dynamic_model.py:300-312): (B,384) -> (B,39). */
 int dal3_dynamic_box_est_forward(const void* packed, const float* embedding, int B, float* box_pred,

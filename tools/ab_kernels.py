@@ -4,8 +4,8 @@ three shared-MLP kernels, median and min per build, outputs cross-checked agains
 `seg` is dal3_ins_seg_forward — encoder, per-crop FC, the decoder's plan where the build has one, decoder — as a step runs
 them (`dec` alone is the stand-alone entry, which never has a plan); `seg0` the same call with DAL3_BCN_NO_DEC_PLAN.
 `enc2` / `seg2` are `enc` / `seg` with DAL3_BCN_NO_ENC_RESIDENT (the screened encoder's two launches) where the build knows
-that flag, the same call as `enc` / `seg` where it does not. A -DDAL3_SCREEN_COUNT build prints the screen's counters of one
-`seg` and one `seg2` call.
+that flag, the same call as `enc` / `seg` where it does not; `head2` likewise is `head` with DAL3_BCN_NO_HEAD_RESIDENT (the
+screened point head's two launches). A -DDAL3_SCREEN_COUNT build prints the screen's counters of one `seg` and one `seg2` call.
 
   python tools/ab_kernels.py build_a.so build_b.so ... [--B 4096] [--N 1024] [--rounds 7]
 """
@@ -118,6 +118,15 @@ for name, lib in libs:
                                                             hip.ptr(d["logits"]), hip.ptr(d["mask"]), st)
     d["head"] = lambda lib=lib, d=d: lib.dal3_point_head_forward(hip.HEAD_STATIC_BOX_EST, hip.ptr(d["w_box"]), DT, xo, B, 512,
                                                                  hip.ptr(d["bp"]), 39, hip.ptr(d["ws"]), d["ws"].numel(), st)
+    d["has_head_res"] = hasattr(lib, "dal3_point_head_route")
+    xo2 = hip.bcn(obj)
+    xo2.flags |= hip.BCN_NO_HEAD_RESIDENT if d["has_head_res"] else 0
+    d["bp2"] = torch.empty((B, 39), device=dev)
+    d["head2"] = lambda lib=lib, d=d, xo2=xo2: lib.dal3_point_head_forward(hip.HEAD_STATIC_BOX_EST, hip.ptr(d["w_box"]), DT, xo2, B, 512,
+                                                                          hip.ptr(d["bp2"]), 39, hip.ptr(d["ws"]), d["ws"].numel(), st)
+    if d["has_head_res"]:
+        print(f"{name}: point head route {lib.dal3_point_head_route(hip.HEAD_STATIC_BOX_EST, B, 512, 0)} "
+              f"(with DAL3_BCN_NO_HEAD_RESIDENT {lib.dal3_point_head_route(hip.HEAD_STATIC_BOX_EST, B, 512, hip.BCN_NO_HEAD_RESIDENT)})")
     assert d["enc"]() == 0, lib.dal3_last_error()
     assert lib.dal3_ins_seg_global_bias(hip.ptr(w_seg), DT, hip.ptr(g), B, hip.ptr(gb), st) == 0
     if hasattr(lib, "dal3_debug_dec_counts"):         # a -DDAL3_DEC_COUNT build: what the compacted dconv2 saw in ONE launch
@@ -174,8 +183,10 @@ torch.cuda.synchronize()
 ref = state[0]
 for (name, _), d in zip(libs, state):
     same = (torch.equal(d["g"], ref["g"]), torch.equal(d["logits"], ref["logits"]), torch.equal(d["bp"], ref["bp"]))
-    assert d["enc2"]() == 0 and d["seg2"]() == 0, _.dal3_last_error()
+    assert d["enc2"]() == 0 and d["seg2"]() == 0 and d["head2"]() == 0, _.dal3_last_error()
     torch.cuda.synchronize()
+    print(f"{name}: point head under DAL3_BCN_NO_HEAD_RESIDENT bitwise-equal to the first build (box_pred) = "
+          f"{torch.equal(d['bp2'].view(torch.int32), ref['bp'].view(torch.int32))}")
     print(f"{name}: two-launch encoder bitwise-equal to the first build (g of enc2, g / logits / mask of seg2) = "
           f"{(torch.equal(d['g'], ref['g']), torch.equal(d['g_seg'].view(torch.int32), ref['g_seg'].view(torch.int32)), torch.equal(d['lg_seg'].view(torch.int32), ref['lg_seg0'].view(torch.int32)), torch.equal(d['mk_seg'], ref['mk_seg0']))}")
     bits = lambda t: t.view(torch.int32)
@@ -197,7 +208,7 @@ def timed(fn, iters=5):
     return a.elapsed_time(b) / iters
 
 
-KINDS = ("enc", "enc2", "dec", "head", "seg", "seg2", "seg0")
+KINDS = ("enc", "enc2", "dec", "head", "head2", "seg", "seg2", "seg0")
 res = {(n, k): [] for n, _ in libs for k in KINDS}
 for r in range(args.rounds):
     for k in KINDS:

@@ -190,7 +190,9 @@ def kernel_table(model, inputs, static, B, N, iters):
         granule = 256 if lp else 32
         exe_pts = arch.head_executed_points(cnt, m, granule) if distinct is not None else B * arch._pad(m, granule)
         pers = not lp and B * ((m + 31) // 32) > 512            # fp32 throughput family: persistent waves over the live-tile worklist
-        row(f"point_head{'_pers' if pers else ''}{sfx}[{name}]", t, arch.head_point_mac(table) * B * m, arch.head_point_mac(table, True) * exe_pts,
+        # ... or, for jobs of many items, the item-resident screened kernel (csrc/dal3_head_screen.hip): ask the library
+        res = prec == "fp32" and lib.dal3_point_head_route(mod.HEAD_KIND, B, m, hip.DISPATCH_FLAGS) == hip.HEAD_ROUTE_RESIDENT
+        row(f"point_head{'_resident' if res else '_pers' if pers else ''}{sfx}[{name}]", t, arch.head_point_mac(table) * B * m, arch.head_point_mac(table, True) * exe_pts,
             note=f"{exe_pts / (B * m):.3f} of the {m} object points per item are computed"
                  + (" (copies skipped)" if distinct is not None else " (padding)"))
     return out, float(cnt.mean())
