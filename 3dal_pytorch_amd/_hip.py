@@ -242,6 +242,14 @@ class Conv2dArgs(C.Structure):
                 ("H", C.c_int64), ("W", C.c_int64), ("x", Map), ("y", Map), ("packed", vp)]
 
 
+class Conv2dLpArgs(C.Structure):
+    """dal3_conv2d_lp_args"""
+    _fields_ = [("kind", C.c_int32), ("stride", C.c_int32), ("relu", C.c_int32), ("c_in", C.c_int32), ("c_out", C.c_int32),
+                ("y_channels", C.c_int32), ("y_channel_offset", C.c_int32), ("max_workgroups", C.c_int32), ("dtype", C.c_int32),
+                ("reserved", C.c_int32), ("B", C.c_int64), ("H", C.c_int64), ("W", C.c_int64), ("x", Map), ("y", Map),
+                ("packed", vp)]
+
+
 SP_OVERFLOW, SP_BAD_COORD, SP_DUPLICATE, SP_BAD_WEIGHT = 256, 512, 1024, 2048
 _i3 = C.c_int32 * 3
 
@@ -470,6 +478,9 @@ SIGNATURES = {
     "dal3_conv2d_pack_floats": (_sz, [_i, _i, _i]),
     "dal3_conv2d_pack": (_i, [C.POINTER(Layer), _i, C.c_double, vp, vp]),
     "dal3_conv2d": (_i, [C.POINTER(Conv2dArgs), vp]),
+    "dal3_conv2d_lp_pack_bytes": (_sz, [_i, _i, _i]),
+    "dal3_conv2d_lp_pack": (_i, [C.POINTER(Layer), _i, C.c_double, _i, vp, vp]),
+    "dal3_conv2d_lp": (_i, [C.POINTER(Conv2dLpArgs), vp]),
     "dal3_sp_sort_workspace_bytes": (_sz, [_i64]),
     "dal3_sp_sort": (_i, [C.POINTER(SpSortArgs), vp]),
     "dal3_sp_downsample_workspace_bytes": (_sz, [_i64, _i]),

@@ -1315,24 +1315,58 @@ extern "C" int dal3_conv2d_pack(const dal3_layer* layer, int kind, double eps, f
     return 0;
 }
 
-extern "C" int dal3_conv2d(const dal3_conv2d_args* args, dal3_stream stream) {
-    if (!args) return fail(DAL3_EINVAL, "conv2d: null args");
-    const dal3_conv2d_args& a = *args;
-    if (!conv2d_kind_ok(a.kind)) return fail(DAL3_EINVAL, "conv2d: kind %d is no DAL3_CONV2D_* form", (int)a.kind);
+// what dal3_conv2d and dal3_conv2d_lp ask of the fields their args structs share
+template <class Args>
+static int check_conv2d_args(const char* who, const Args& a) {
+    if (!conv2d_kind_ok(a.kind)) return fail(DAL3_EINVAL, "%s: kind %d is no DAL3_CONV2D_* form", who, (int)a.kind);
     const int want = a.kind == DAL3_CONV2D_DECONV2 ? 2 : a.kind == DAL3_CONV2D_DECONV4 ? 4 : 1;
     if (a.stride != want && !(a.kind == DAL3_CONV2D_3X3 && a.stride == 2))
-        return fail(DAL3_EINVAL, "conv2d: stride %d (3x3: 1 or 2; 1x1: 1; a transposed convolution: its kernel size, 2 or 4)",
+        return fail(DAL3_EINVAL, "%s: stride %d (3x3: 1 or 2; 1x1: 1; a transposed convolution: its kernel size, 2 or 4)", who,
                     (int)a.stride);
-    if ((a.relu != 0 && a.relu != 1) || a.max_workgroups < 0) return fail(DAL3_EINVAL, "conv2d: bad relu (0 or 1) / max_workgroups (>= 0)");
-    if (a.c_in < 1 || a.c_in > 4096 || a.c_out < 1 || a.c_out > 4096) return fail(DAL3_EINVAL, "conv2d: bad c_in / c_out (1 .. 4096)");
+    if ((a.relu != 0 && a.relu != 1) || a.max_workgroups < 0) return fail(DAL3_EINVAL, "%s: bad relu (0 or 1) / max_workgroups (>= 0)", who);
+    if (a.c_in < 1 || a.c_in > 4096 || a.c_out < 1 || a.c_out > 4096) return fail(DAL3_EINVAL, "%s: bad c_in / c_out (1 .. 4096)", who);
     if (a.B < 0 || a.H < 0 || a.W < 0 || a.B > 65535 || a.H > 65535 || a.W > 65535)
-        return fail(DAL3_EINVAL, "conv2d: bad B / H / W (0 .. 65535)");
+        return fail(DAL3_EINVAL, "%s: bad B / H / W (0 .. 65535)", who);
     if (a.y_channel_offset < 0 || a.y_channels < 1 || (int64_t)a.y_channel_offset + a.c_out > a.y_channels)
-        return fail(DAL3_EINVAL, "conv2d: channels %d .. %lld lie outside the output's %d", (int)a.y_channel_offset,
+        return fail(DAL3_EINVAL, "%s: channels %d .. %lld lie outside the output's %d", who, (int)a.y_channel_offset,
                     (long long)a.y_channel_offset + a.c_out, (int)a.y_channels);
-    if (!a.x.data || !a.y.data) return fail(DAL3_EINVAL, "conv2d: null x / y");
-    if (!a.packed || (reinterpret_cast<uintptr_t>(a.packed) & 15)) return fail(DAL3_EINVAL, "conv2d: packed is null or not 16-byte aligned");
+    if (!a.x.data || !a.y.data) return fail(DAL3_EINVAL, "%s: null x / y", who);
+    if (!a.packed || (reinterpret_cast<uintptr_t>(a.packed) & 15)) return fail(DAL3_EINVAL, "%s: packed is null or not 16-byte aligned", who);
+    return 0;
+}
+
+extern "C" int dal3_conv2d(const dal3_conv2d_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "conv2d: null args");
+    TRY(check_conv2d_args("conv2d", *args));
     HIP_TRY(launch_conv2d(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+// ... and on 16-bit MFMA operands (dal3_conv2d_lp.hip)
+static bool conv2d_lp_dtype_ok(int dtype) { return dtype == DAL3_F16 || dtype == DAL3_BF16; }
+
+extern "C" size_t dal3_conv2d_lp_pack_bytes(int kind, int c_in, int c_out) {
+    if (!conv2d_kind_ok(kind) || c_in < 1 || c_in > 4096 || c_out < 1 || c_out > 4096) return 0;
+    return conv2d_lp_pack_bytes(kind, c_in, c_out);
+}
+
+extern "C" int dal3_conv2d_lp_pack(const dal3_layer* layer, int kind, double eps, int dtype, void* out, dal3_stream stream) {
+    if (!layer || !out) return fail(DAL3_EINVAL, "conv2d_lp_pack: null layer / out");
+    if (!conv2d_kind_ok(kind)) return fail(DAL3_EINVAL, "conv2d_lp_pack: kind %d is no DAL3_CONV2D_* form", kind);
+    if (!conv2d_lp_dtype_ok(dtype)) return fail(DAL3_EINVAL, "conv2d_lp_pack: dtype %d (DAL3_F16 or DAL3_BF16)", dtype);
+    if (layer->c_in < 1 || layer->c_in > 4096 || layer->c_out < 1 || layer->c_out > 4096)
+        return fail(DAL3_EINVAL, "conv2d_lp_pack: bad c_in / c_out (1 .. 4096)");
+    TRY(check_fold_layer("conv2d_lp_pack", layer, -1, eps, static_cast<const float*>(out)));
+    HIP_TRY(launch_conv2d_lp_pack(FoldLayer(*layer, eps), kind, dtype, out, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+extern "C" int dal3_conv2d_lp(const dal3_conv2d_lp_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "conv2d_lp: null args");
+    if (!conv2d_lp_dtype_ok(args->dtype)) return fail(DAL3_EINVAL, "conv2d_lp: dtype %d (DAL3_F16 or DAL3_BF16)", (int)args->dtype);
+    if (args->reserved != 0) return fail(DAL3_EINVAL, "conv2d_lp: reserved must be 0");
+    TRY(check_conv2d_args("conv2d_lp", *args));
+    HIP_TRY(launch_conv2d_lp(args, static_cast<hipStream_t>(stream)));
     return 0;
 }
 

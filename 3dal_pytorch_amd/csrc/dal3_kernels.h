@@ -375,6 +375,10 @@ size_t conv2d_pack_floats(int kind, int c_in, int c_out);
 // (internal: any c_in / c_out the format can hold, not only the public entry's 4096; the RoI head packs its sections here)
 hipError_t launch_conv2d_pack(const FoldLayer& layer, int kind, float* out, hipStream_t s);
 hipError_t launch_conv2d(const dal3_conv2d_args* a, hipStream_t s);
+// ... and on 16-bit MFMA operands (dal3_conv2d_lp.hip); dtype DAL3_F16 or DAL3_BF16, checked by the caller
+size_t conv2d_lp_pack_bytes(int kind, int c_in, int c_out);
+hipError_t launch_conv2d_lp_pack(const FoldLayer& layer, int kind, int dtype, void* out, hipStream_t s);
+hipError_t launch_conv2d_lp(const dal3_conv2d_lp_args* a, hipStream_t s);
 // the VoxelNet detector's sparse 3-D middle (dal3_spconv.hip): site bookkeeping on the chunked radix sort, gather-GEMM convolutions
 size_t sp_sort_workspace_bytes(int64_t capacity);
 hipError_t launch_sp_sort(const dal3_sp_sort_args* a, hipStream_t s);

@@ -57,6 +57,20 @@ class SingleStageDetector(nn.Module):
     def with_neck(self):
         return self.neck is not None
 
+    @property
+    def precision(self):
+        """the MFMA operand type of the dense stage's eval-mode kernels: 'fp32' (the default) | 'fp16' | 'bf16'. Setting it
+        sets the neck's and the head's `precision` (rpn.RPN, rpn.CenterHead), whose maps stay float32 either way. The reader
+        (PillarFeatureNet / the voxel mean) and the sparse 3-D middle stay fp32, and so do the decode and the NMS."""
+        return self.bbox_head.precision
+
+    @precision.setter
+    def precision(self, value):
+        rpn.check_precision(value)
+        for m in (self.neck, self.bbox_head):
+            if m is not None:
+                m.precision = value
+
     def init_weights(self, pretrained):
         """a checkpoint path: its `state_dict` (or the file itself) must hold exactly this model's keys"""
         ckpt = torch.load(pretrained, map_location="cpu")

@@ -10,6 +10,10 @@ and the tensors' version stamps); the three upsampled maps are written into chan
 head's maps (they are views, not NCHW-contiguous tensors). `composite()` is the same definition in stock torch ops: it
 runs in train mode and for whatever the kernel does not serve (a strided-convolution deblock, GroupNorm, other kernel
 sizes). There is no quiet fallback on the GPU route: a module that `hip_serves()` raises if its inputs are not on the GPU.
+
+`precision` on `RPN` and `CenterHead` ("fp32", the default, | "fp16" | "bf16") picks the MFMA operand type of that kernel
+route: with a 16-bit one every layer runs dal3_conv2d_lp on weights rounded once at pack time and activations rounded as
+they are staged, accumulating in fp32; the maps stay float32 either way.
 """
 import copy
 
@@ -17,7 +21,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import _hip
+from . import _heads, _hip
 
 KIND_TAPS = {_hip.CONV2D_3X3: 9, _hip.CONV2D_1X1: 1, _hip.CONV2D_DECONV2: 1, _hip.CONV2D_DECONV4: 1}
 KIND_SUB = {_hip.CONV2D_3X3: 1, _hip.CONV2D_1X1: 1, _hip.CONV2D_DECONV2: 4, _hip.CONV2D_DECONV4: 16}
@@ -56,12 +60,55 @@ def _norm_ok(bn):
     return bn is None or (isinstance(bn, nn.BatchNorm2d) and bn.affine and bn.track_running_stats)
 
 
-def pack_layer(conv, bn, kind):
-    """fold and pack one layer -> a float32 device tensor (dal3_conv2d_pack)"""
+PRECISIONS = ("fp32", "fp16", "bf16")
+_TORCH16 = {"fp16": torch.float16, "bf16": torch.bfloat16}
+
+
+def check_precision(precision):
+    """'fp32' | 'fp16' | 'bf16' -> the DAL3_* dtype (_heads.dtype_of's names and mapping); 'f16x3' belongs to the point
+    heads and is refused here"""
+    dtype = _heads.dtype_of(precision)
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision {precision!r}: the detector's dense stage runs on 'fp32', 'fp16' or 'bf16' MFMA operands "
+                         "('f16x3' is an arithmetic of the point heads only)")
+    return dtype
+
+
+def _lp_fragments(buf, kind, c_out, precision):
+    """the fragment part of a dal3_conv2d_lp_pack blob (behind the float32 biases of its whole 32-row tiles) as the 16-bit type"""
+    n_tiles = -(-c_out * KIND_SUB[kind] // 32)
+    return buf[n_tiles * 32 * 4:].view(_TORCH16[precision])
+
+
+def refuse_nonfinite_weights(packs, layers, precision):
+    """packs: dal3_conv2d_lp_pack blobs; layers: their (kind, c_out, name). A folded weight that is not finite in the 16-bit
+    type is refused here, on the PACKED values (so exactly what the kernel would read), with one device->host sync for all
+    the blobs of a packing, as _hip.check_f16x3_range refuses its range once per packing: the kernel would carry an
+    infinity on in silence"""
+    with torch.no_grad():
+        ok = torch.stack([torch.isfinite(_lp_fragments(p, kind, c_out, precision)).all() for p, (kind, c_out, _) in zip(packs, layers)])
+        for good, (_, _, name) in zip(ok.cpu().tolist(), layers):
+            if not good:
+                raise ValueError(f"precision {precision!r}: a folded weight of {name or 'the layer'} is not finite as {precision}"
+                                 + (f" (fp16's range ends at {_hip.F16_MAX:g})" if precision == "fp16" else "")
+                                 + "; this layer cannot run on 16-bit operands (use precision 'fp32' or 'bf16')")
+
+
+def pack_layer(conv, bn, kind, precision="fp32", name=None, check=True):
+    """fold and pack one layer -> a device tensor: float32 (dal3_conv2d_pack), or for 'fp16' / 'bf16' the uint8 blob of
+    dal3_conv2d_lp_pack. `name`: what a refusal calls the layer; check=False leaves refuse_nonfinite_weights to the caller,
+    who packs several layers and checks them with one synchronisation."""
+    dtype = check_precision(precision)
     L = _hip.fold_layer_struct(conv, bn)
-    lib = _hip.lib()
-    buf = torch.empty(lib.dal3_conv2d_pack_floats(kind, L.c_in, L.c_out), dtype=torch.float32, device=conv.weight.device)
-    _hip.check(lib.dal3_conv2d_pack(L, kind, float(bn.eps) if bn is not None else 1e-5, _hip.ptr(buf), _hip.stream()))
+    lib, eps = _hip.lib(), float(bn.eps) if bn is not None else 1e-5
+    if precision == "fp32":
+        buf = torch.empty(lib.dal3_conv2d_pack_floats(kind, L.c_in, L.c_out), dtype=torch.float32, device=conv.weight.device)
+        _hip.check(lib.dal3_conv2d_pack(L, kind, eps, _hip.ptr(buf), _hip.stream()))
+        return buf
+    buf = torch.empty(lib.dal3_conv2d_lp_pack_bytes(kind, L.c_in, L.c_out), dtype=torch.uint8, device=conv.weight.device)
+    _hip.check(lib.dal3_conv2d_lp_pack(L, kind, eps, dtype, _hip.ptr(buf), _hip.stream()))
+    if check:
+        refuse_nonfinite_weights([buf], [(kind, L.c_out, name)], precision)
     return buf
 
 
@@ -76,9 +123,11 @@ def out_size(kind, stride, H, W):
 _nchw_map = _hip.nchw_map
 
 
-def conv2d(x, packed, kind, stride, relu, c_out, out=None, channel_offset=0, max_workgroups=0):
+def conv2d(x, packed, kind, stride, relu, c_out, out=None, channel_offset=0, max_workgroups=0, precision="fp32"):
     """one layer: x (B, c_in, H, W) float32 CUDA, any strides -> channels [channel_offset, channel_offset + c_out) of `out`
-    (B, >= channel_offset + c_out, OH, OW) (allocated when None), returned as a view. Enqueued on the current stream."""
+    (B, >= channel_offset + c_out, OH, OW) (allocated when None), returned as a view. Enqueued on the current stream.
+    `precision`: what `packed` was packed as ('fp16' / 'bf16': dal3_conv2d_lp; x and out stay float32)."""
+    dtype = check_precision(precision)
     if not torch.is_tensor(x):
         raise TypeError("x must be a tensor")
     _hip.require_gpu(x, "x")
@@ -92,13 +141,18 @@ def conv2d(x, packed, kind, stride, relu, c_out, out=None, channel_offset=0, max
         _hip.require_gpu(out, "out")
         if out.dtype != torch.float32 or out.dim() != 4 or out.shape[0] != B or tuple(out.shape[2:]) != (OH, OW) or out.device != x.device:
             raise ValueError(f"out must be float32 ({B}, channels, {OH}, {OW}) on {x.device}, got {out.dtype} {tuple(out.shape)}")
-    if packed.numel() != _hip.lib().dal3_conv2d_pack_floats(kind, c_in, c_out) or packed.device != x.device:
-        raise ValueError(f"the packed weights are not those of a {c_in} -> {c_out} layer of kind {kind} on {x.device}")
-    a = _hip.Conv2dArgs(kind=kind, stride=stride, relu=1 if relu else 0, c_in=c_in, c_out=c_out, y_channels=out.shape[1],
-                        y_channel_offset=channel_offset, max_workgroups=int(max_workgroups), B=B, H=H, W=W, x=_nchw_map(x),
-                        y=_nchw_map(out), packed=_hip.ptr(packed))
+    lib, lp = _hip.lib(), precision != "fp32"
+    want = lib.dal3_conv2d_lp_pack_bytes(kind, c_in, c_out) if lp else lib.dal3_conv2d_pack_floats(kind, c_in, c_out)
+    if packed.dtype != (torch.uint8 if lp else torch.float32) or packed.numel() != want or packed.device != x.device:
+        raise ValueError(f"the packed weights are not those of a {c_in} -> {c_out} layer of kind {kind} in {precision} on {x.device}")
+    fields = dict(kind=kind, stride=stride, relu=1 if relu else 0, c_in=c_in, c_out=c_out, y_channels=out.shape[1],
+                  y_channel_offset=channel_offset, max_workgroups=int(max_workgroups), B=B, H=H, W=W, x=_nchw_map(x),
+                  y=_nchw_map(out), packed=_hip.ptr(packed))
     if B and H and W:
-        _hip.check(_hip.lib().dal3_conv2d(a, _hip.stream()))
+        if lp:
+            _hip.check(lib.dal3_conv2d_lp(_hip.Conv2dLpArgs(dtype=dtype, **fields), _hip.stream()))
+        else:
+            _hip.check(lib.dal3_conv2d(_hip.Conv2dArgs(**fields), _hip.stream()))
     return out[:, channel_offset:channel_offset + c_out]
 
 
@@ -112,12 +166,24 @@ def conv2d_flop(kind, stride, c_in, c_out, H, W, B=1):
     return algo, 2 * B * up(ph, 8) * up(pw, 32) * rows * k * taps
 
 
+def conv2d_lp_flop(kind, stride, c_in, c_out, H, W, B=1):
+    """conv2d_flop for the 16-bit kernel, whose tiles differ in one extent: 16 input channels a k-step, not 8"""
+    taps, sub = KIND_TAPS[kind], KIND_SUB[kind]
+    ph, pw = out_size(kind, stride, H, W) if kind == _hip.CONV2D_3X3 else (H, W)
+    rows, k, up = -(-c_out * sub // 32) * 32, -(-c_in // 16) * 16, lambda v, m: -(-v // m) * m
+    return conv2d_flop(kind, stride, c_in, c_out, H, W, B)[0], 2 * B * up(ph, 8) * up(pw, 32) * rows * k * taps
+
+
 class _PackedLayers(nn.Module):
-    """the packed-weights cache of a module whose `_plan()` lists its kernel layers as (conv, bn, kind, stride, relu)"""
+    """the packed-weights cache of a module whose `_plan()` lists its kernel layers as (conv, bn, kind, stride, relu);
+    `_pack_key()` is whatever else the pack depends on"""
 
     def __init__(self):
         super().__init__()
         self._packed, self._stamp = None, None
+
+    def _pack_key(self):
+        return None
 
     def invalidate_packed(self):
         """after writes that bypass the tensors' version counters (`.data` writes, raw pointers)"""
@@ -141,13 +207,42 @@ class _PackedLayers(nn.Module):
     def packed(self):
         plan = self._plan()
         ts = [t for conv, bn, *_ in plan for t in list(conv.parameters()) + (list(bn.parameters()) + list(bn.buffers()) if bn is not None else [])]
-        stamp = tuple((t.data_ptr(), t._version, t.device) for t in ts)
+        stamp = (self._pack_key(), tuple((t.data_ptr(), t._version, t.device) for t in ts))
         if self._packed is None or stamp != self._stamp:
             self._packed, self._stamp = self._pack(plan), stamp
         return self._packed
 
     def _pack(self, plan):
         return [pack_layer(conv, bn, kind) for conv, bn, kind, _, _ in plan]
+
+
+class _DenseLayers(_PackedLayers):
+    """_PackedLayers of the dense stage's two modules. `precision` ('fp32', the default, | 'fp16' | 'bf16') is the MFMA
+    operand type of the eval-mode kernel route; it is part of the cache's key, so changing it repacks. Train mode and a
+    module the kernel does not serve run the composite, whatever it says."""
+
+    def __init__(self):
+        super().__init__()
+        self._precision = "fp32"
+
+    @property
+    def precision(self):
+        return self._precision
+
+    @precision.setter
+    def precision(self, value):
+        check_precision(value)
+        self._precision = value
+
+    def _pack_key(self):
+        return self._precision
+
+    def _pack(self, plan):
+        names = {m: n for n, m in self.named_modules()}
+        packs = [pack_layer(conv, bn, kind, self._precision, names.get(conv), check=False) for conv, bn, kind, _, _ in plan]
+        if self._precision != "fp32":
+            refuse_nonfinite_weights(packs, [(kind, conv.out_channels, names.get(conv)) for conv, _, kind, _, _ in plan], self._precision)
+        return packs
 
 
 def _split(seq):
@@ -163,7 +258,7 @@ def _split(seq):
     return out
 
 
-class RPN(_PackedLayers):
+class RPN(_DenseLayers):
     """det3d/models/necks/rpn.py. forward(x (B, num_input_features, H, W)) -> (B, sum(us_num_filters), H', W')."""
 
     def __init__(self, layer_nums, ds_layer_strides, ds_num_filters, us_layer_strides, us_num_filters, num_input_features,
@@ -240,13 +335,13 @@ class RPN(_PackedLayers):
         if self.training or not self.hip_serves():
             return self.composite(x)
         with torch.no_grad():
-            packed, plan = self.packed(), self._plan()
+            packed, plan, prec = self.packed(), self._plan(), self._precision
             at, n_block_layers = 0, sum(len(_split(b)) for b in self.blocks)
             ups, offset, out = [], 0, None
             for i, block in enumerate(self.blocks):
                 for _ in _split(block):
                     conv, _, kind, stride, relu = plan[at]
-                    x = conv2d(x, packed[at], kind, stride, relu, conv.out_channels, max_workgroups=max_workgroups)
+                    x = conv2d(x, packed[at], kind, stride, relu, conv.out_channels, max_workgroups=max_workgroups, precision=prec)
                     at += 1
                 j = i - self._upsample_start_idx
                 if j >= 0:
@@ -257,7 +352,7 @@ class RPN(_PackedLayers):
                     elif tuple(out.shape[2:]) != size:
                         raise RuntimeError(f"the upsampled maps differ in size ({tuple(out.shape[2:])} and {size}): torch.cat would refuse them")
                     conv2d(x, packed[n_block_layers + j], kind, stride, relu, conv.out_channels, out=out, channel_offset=offset,
-                           max_workgroups=max_workgroups)
+                           max_workgroups=max_workgroups, precision=prec)
                     offset += conv.out_channels
             return out
 
@@ -292,7 +387,7 @@ class SepHead(nn.Module):
         return {head: self.__getattr__(head)(x) for head in self.heads}
 
 
-class CenterHead(_PackedLayers):
+class CenterHead(_DenseLayers):
     """center_head.py:167-244 and `predict` (through detect.CenterHeadPost). forward(x) -> one dict per task of logical
     (B, c, H, W) maps; on the kernel route they are channel slices of one tensor per task."""
 
@@ -347,6 +442,8 @@ class CenterHead(_PackedLayers):
                 first = [packs[at + sum(n[:i])] for i in range(len(n))]
                 rows = [plan[at + sum(n[:i])][0].out_channels for i in range(len(n))]
                 # a pack is [bias of every GEMM row | fragments by out tile]: the fused layer's is both parts concatenated
+                # (a 16-bit pack is a byte blob with the same two parts, its biases float32)
+                rows = [r * (1 if self._precision == "fp32" else 4) for r in rows]
                 fused.append(torch.cat([p[:r] for p, r in zip(first, rows)] + [p[r:] for p, r in zip(first, rows)]))
             else:
                 fused.append(None)
@@ -362,11 +459,11 @@ class CenterHead(_PackedLayers):
         if self.training or not self.hip_serves():
             return self.composite(x)
         with torch.no_grad():
-            (packed, fused), plan = self.packed(), self._plan()
+            (packed, fused), plan, prec = self.packed(), self._plan(), self._precision
 
             def run(at, x, **kw):
                 conv, _, kind, stride, relu = plan[at]
-                return conv2d(x, packed[at], kind, stride, relu, conv.out_channels, max_workgroups=max_workgroups, **kw)
+                return conv2d(x, packed[at], kind, stride, relu, conv.out_channels, max_workgroups=max_workgroups, precision=prec, **kw)
 
             x = run(0, x)
             at, ret = 1, []
@@ -377,7 +474,7 @@ class CenterHead(_PackedLayers):
                 mid = None
                 if fused[t] is not None:
                     widths = [plan[at + sum(n[:i])][0].out_channels for i in range(len(n))]
-                    mid = conv2d(x, fused[t], _hip.CONV2D_3X3, 1, True, sum(widths), max_workgroups=max_workgroups)
+                    mid = conv2d(x, fused[t], _hip.CONV2D_3X3, 1, True, sum(widths), max_workgroups=max_workgroups, precision=prec)
                 d, offset = {}, 0
                 for i, head in enumerate(task.heads):
                     y = x

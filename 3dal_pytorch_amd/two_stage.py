@@ -527,6 +527,16 @@ class TwoStageDetector(nn.Module):
 
     to_prediction = staticmethod(CenterHeadPost.to_prediction)
 
+    @property
+    def precision(self):
+        """`single_det.precision`: the first stage's neck and head on 'fp32' | 'fp16' | 'bf16' MFMA operands. The BEV
+        feature extractor reads the neck's float32 map as before, and the RoI head stays fp32."""
+        return self.single_det.precision
+
+    @precision.setter
+    def precision(self, value):
+        self.single_det.precision = value
+
     def post(self):
         if self._post is None or self._post[0] is not self.test_cfg:
             self._post = (self.test_cfg, CenterHeadPost(self.test_cfg, self.bbox_head.num_classes))

@@ -993,6 +993,42 @@ size_t dal3_conv2d_pack_floats(int kind, int c_in, int c_out);
 int dal3_conv2d_pack(const dal3_layer* layer, int kind, double eps, float* out, dal3_stream stream);
 int dal3_conv2d(const dal3_conv2d_args* args, dal3_stream stream);
 
+/* The same layers on 16-bit MFMA operands (v_mfma_f32_32x32x16_f16 / _bf16; additions only, nothing above changes).
+ * dtype is DAL3_F16 or DAL3_BF16 at both entries; anything else returns DAL3_EINVAL and nothing is launched. The forms,
+ * the strides, the channel slice, the pixel-shuffle store, max_workgroups and every limit are dal3_conv2d's. The
+ * arithmetic, which is the contract:
+ *   - W' of the fold above (float64, rounded once to float32) is rounded once more to the 16-bit type by
+ *     dal3_conv2d_lp_pack, round to nearest even; b' stays float32;
+ *   - every input activation is rounded to the 16-bit type, round to nearest even, as the kernel stages it;
+ *   - the products (exact in float32: at most 22 significant bits) are summed in the MFMA's float32 accumulator, which
+ *     starts at b'; ReLU and the store are float32. x and y stay float32 maps: only the OPERANDS are 16-bit.
+ * As above the order of the summation is not part of the definition: a layer is judged against the float64 evaluation
+ * of the ROUNDED operands under the float32 kernel's own bars, and a chain of layers against tests/rpn_lp_model.py.
+ * Range: DAL3_F16 turns an activation with |x| > 65504 into an infinity, and a folded weight beyond that has no fp16
+ * value: both are outside the contract, as for the DAL3_F16 point heads (the binding refuses such a weight at pack
+ * time, naming the layer). DAL3_BF16 has float32's range and no such limit.
+ * packed: dal3_conv2d_lp_pack_bytes(kind, c_in, c_out) bytes (0 for bad arguments), 16-byte aligned, the same for both
+ * types: [float32 b' of every GEMM row, rounded up to whole tiles of 32 | 1 KiB fragments by out tile, 16 input
+ * channels and tap]. A blob packed as one type must be run as that type. */
+typedef struct dal3_conv2d_lp_args {
+    int32_t kind;                        /* DAL3_CONV2D_* */
+    int32_t stride;                      /* 3X3: 1 or 2; 1X1: 1; DECONV2: 2; DECONV4: 4 */
+    int32_t relu;                        /* 0 or 1 */
+    int32_t c_in, c_out;
+    int32_t y_channels;                  /* channels of the tensor y.data starts */
+    int32_t y_channel_offset;            /* first channel this layer writes */
+    int32_t max_workgroups;              /* 0: no cap */
+    int32_t dtype;                       /* DAL3_F16 | DAL3_BF16: what packed was packed as */
+    int32_t reserved;                    /* 0 (anything else: DAL3_EINVAL) */
+    int64_t B, H, W;                     /* of the INPUT */
+    dal3_map x, y;
+    const void* packed;                  /* dal3_conv2d_lp_pack's */
+} dal3_conv2d_lp_args;
+
+size_t dal3_conv2d_lp_pack_bytes(int kind, int c_in, int c_out);
+int dal3_conv2d_lp_pack(const dal3_layer* layer, int kind, double eps, int dtype, void* out, dal3_stream stream);
+int dal3_conv2d_lp(const dal3_conv2d_lp_args* args, dal3_stream stream);
+
 /* ---- the VoxelNet detector's sparse 3-D middle: SpMiddleResNetFHD (det3d/models/backbones/scn.py), which the reference
  * delegates to spconv 1.x: SubMConv3d (kernel 3), SparseConv3d, BatchNorm1d (folded), ReLU, SparseBasicBlock's residual and
  * the .dense().view(N, C * D, H, W) at the end. float32, eval mode. (Additions only; DAL3_VERSION stays, as for the entries

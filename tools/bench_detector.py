@@ -12,6 +12,15 @@ the two routes' outputs, and the compiler's register / scratch / LDS counts of e
 to a file (after every batch size, so that an interrupted run leaves what it measured).
     python tools/bench_detector.py [--batches 1 4 --window 1.0 --out profiles/bench_detector.json]
 
+--precision fp16 | bf16 (default fp32: everything above, unchanged) times three routes in one job instead, alternating:
+  hip_fp32        the fp32 kernel route (dal3_conv2d)
+  hip_<precision> the same modules with `precision` set: dal3_conv2d_lp on 16-bit MFMA operands, float32 maps
+  half_composite  `composite()` of .half() copies on a .half() canvas: stock PyTorch-ROCm half-precision convolutions
+and records the ratios, the 16-bit kernel's executed FLOP (16 input channels a k-step), the compiler's resources of
+csrc/dal3_conv2d_lp.hip, the output difference of the two kernel routes, and for the seeded sweep of --double-flip
+(`PointPillars.detect`, --points points) how many kept boxes differ between "fp32" and the 16-bit precision.
+    python tools/bench_detector.py --precision fp16 --out profiles/bench_detector_lp.json
+
 --double-flip measures the test-time augmentation instead (profiles/bench_tta.json): `PointPillars.detect` on one seeded
 sweep of --points points over the same 468 x 468 grid, with and without test_cfg.double_flip, and the merge of the four
 views alone two ways on the head's own outputs:
@@ -42,14 +51,16 @@ PEAK_TFLOPS = 157.3                             # fp32 MFMA: 256 CUs x 4 SIMDs x
 SIZE = 468
 
 
-def flop(neck, head, H, W, B=1):
-    """(algorithmic, executed) FLOP of neck + head on a (B, C, H, W) canvas, layer by layer from the modules' own plans"""
+def flop(neck, head, H, W, B=1, layer_flop=None):
+    """(algorithmic, executed) FLOP of neck + head on a (B, C, H, W) canvas, layer by layer from the modules' own plans;
+    layer_flop: rpn.conv2d_flop (the default) or rpn.conv2d_lp_flop"""
     algo = executed = 0
+    layer_flop = layer_flop or rpn.conv2d_flop
 
     def add(plan_row, h, w):
         nonlocal algo, executed
         conv, _, kind, stride, _ = plan_row
-        a, e = rpn.conv2d_flop(kind, stride, conv.in_channels, conv.out_channels, h, w, B)
+        a, e = layer_flop(kind, stride, conv.in_channels, conv.out_channels, h, w, B)
         algo, executed = algo + a, executed + e
         return rpn.out_size(kind, stride, h, w)
 
@@ -83,12 +94,12 @@ def window(fn, seconds):
     return a.elapsed_time(b) / n, n
 
 
-def kernel_resources():
-    """registers, scratch and LDS of every kernel of csrc/dal3_conv2d.hip from the compiler's own remarks, or None"""
+def kernel_resources(source="dal3_conv2d.hip"):
+    """registers, scratch and LDS of every kernel of csrc/<source> from the compiler's own remarks, or None"""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         return None
-    src = os.path.join(ROOT, "3dal_pytorch_amd", "csrc", "dal3_conv2d.hip")
+    src = os.path.join(ROOT, "3dal_pytorch_amd", "csrc", source)
     cmd = [hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "--cuda-device-only", "-c", src, "-o", os.devnull,
            "-Rpass-analysis=kernel-resource-usage"]
     try:
@@ -101,8 +112,9 @@ def kernel_resources():
     for line in text.splitlines():
         m = re.search(r"remark:\s+Function Name: (\S+)", line)
         if m:
-            m2 = re.search(r"\d+([a-z0-9_]+_kernel)(?:ILi(\d)ELi(\d)ELb([01])ELi(\d)E)?", m.group(1))
-            cur = (m2.group(1) + (f"<{m2.group(2)},{m2.group(3)},{m2.group(4)},{m2.group(5)}>" if m2.group(2) else "")) if m2 else m.group(1)
+            m2 = re.search(r"\d+([a-z0-9_]+_kernel)(?:I(?:\d([A-Z0-9]+?))?(?:Li(\d)ELi(\d)ELb([01])ELi(\d)E)?E)?", m.group(1))
+            args = [g for g in (m2.groups()[1:] if m2 else ()) if g is not None]
+            cur = (m2.group(1) + (f"<{','.join(args)}>" if args else "")) if m2 else m.group(1)
             out[cur] = {}
             continue
         m = re.search(r"remark:\s+([A-Za-z ]+(?:\[[^\]]+\])?): (\d+)", line)
@@ -153,15 +165,12 @@ def composite_merge(preds_dicts):
     return out
 
 
-def double_flip_bench(a):
-    """--double-flip: see the module's docstring"""
+def sweep_model_and_points(n, dev):
+    """the seeded PointPillars detector over the 468 x 468 grid and the seeded sweep of n points -> (model, points, offsets)"""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import pillars_ref as P
     import rpn_ref as R
     detector = importlib.import_module("3dal_pytorch_amd.detector")
-    detect = importlib.import_module("3dal_pytorch_amd.detect")
-    pillars = importlib.import_module("3dal_pytorch_amd.pillars")
-    dev = torch.device("cuda")
     model = detector.PointPillars(
         reader=dict(type="PillarFeatureNet", num_filters=[64, 64], num_input_features=5, with_distance=False,
                     voxel_size=TTA_VOXEL, pc_range=TTA_RANGE),
@@ -171,12 +180,94 @@ def double_flip_bench(a):
     sd.update({"neck." + k: v for k, v in R.neck_weights().items()})
     sd.update({"bbox_head." + k: v for k, v in R.head_weights().items()})
     model.load_state_dict({k: torch.as_tensor(np.asarray(v)) for k, v in sd.items()}, strict=True)
-    model = model.to(dev).eval()
     rng = np.random.default_rng(0)
-    n = a.points
     pts = np.concatenate([np.clip(rng.normal(0, 30, (n, 2)), -74.8, 74.8), rng.uniform(-2, 4, (n, 1)), rng.uniform(0, 1, (n, 2))],
                          1).astype(np.float32)
-    dpts, off = torch.from_numpy(pts).to(dev), np.asarray([0, n], np.int64)
+    return model.to(dev).eval(), torch.from_numpy(pts).to(dev), np.asarray([0, n], np.int64)
+
+
+def kept_boxes_that_differ(a, dev):
+    """`detect` on the seeded sweep with "fp32" and with a.precision: a kept box of one run has a partner in the other when
+    a box of the same label lies within one pillar (0.32 m) of its centre -> the counts (a record, not a bar)"""
+    model, dpts, off = sweep_model_and_points(a.points, dev)
+    with torch.no_grad():
+        want = model.detect(dpts, off)[0]
+        model.precision = a.precision
+        got = model.detect(dpts, off)[0]
+
+    def unmatched(p, q):
+        if not p["scores"].numel() or not q["scores"].numel():
+            return int(p["scores"].numel())
+        d = torch.cdist(p["box3d_lidar"][:, :2].double(), q["box3d_lidar"][:, :2].double())
+        d[p["label_preds"][:, None] != q["label_preds"][None, :]] = float("inf")
+        return int((d.min(1).values > 0.32).sum())
+
+    return {"points": a.points, "kept_fp32": int(want["scores"].numel()), f"kept_{a.precision}": int(got["scores"].numel()),
+            f"{a.precision}_without_fp32_partner": unmatched(got, want), f"fp32_without_{a.precision}_partner": unmatched(want, got)}
+
+
+def lp_bench(a):
+    """--precision fp16 | bf16: see the module's docstring"""
+    import copy
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import rpn_ref as R
+    dev, prec = torch.device("cuda"), a.precision
+    neck, head = rpn.RPN(**R.NECK), rpn.CenterHead(**R.HEAD)
+    neck.load_state_dict({k: torch.as_tensor(v) for k, v in R.neck_weights().items()}, strict=True)
+    head.load_state_dict({k: torch.as_tensor(v) for k, v in R.head_weights().items()}, strict=True)
+    neck, head = neck.to(dev).eval(), head.to(dev).eval()
+    neck16, head16 = copy.deepcopy(neck), copy.deepcopy(head)
+    neck16.precision = head16.precision = prec
+    neck_h, head_h = copy.deepcopy(neck).half(), copy.deepcopy(head).half()
+    res = {"bench": "detector_lp", "precision": prec, "size": a.size, "device": torch.cuda.get_device_name(0), "window_s": a.window,
+           "kernel_resources": kernel_resources("dal3_conv2d_lp.hip"), "batches": {}}
+    routes = {"hip_fp32": lambda x, xh: head(neck(x)), f"hip_{prec}": lambda x, xh: head16(neck16(x)),
+              "half_composite": lambda x, xh: head_h.composite(neck_h.composite(xh))}
+    for B in a.batches:
+        x = torch.from_numpy(R.canvas(f"bench{B}", (B, 64, a.size, a.size))).to(dev)
+        xh = x.half()
+        algo, executed = flop(neck, head, a.size, a.size, B, rpn.conv2d_lp_flop)
+        row = {"algorithmic_flop": algo, "executed_flop": executed, "occupied": float((x != 0).any(1).float().mean())}
+        with torch.no_grad():
+            outs = {k: fn(x, xh) for k, fn in routes.items()}               # warm, twice
+            for fn in routes.values():
+                fn(x, xh)
+            want, scale = outs["hip_fp32"][0], max(float(v.abs().max()) for v in outs["hip_fp32"][0].values())
+            row["max_abs_value"] = scale
+            for k in (f"hip_{prec}", "half_composite"):
+                row[f"{k}_max_abs_diff_to_fp32"] = max(float((outs[k][0][h].float() - want[h]).abs().max()) for h in want)
+            del outs
+            torch.cuda.synchronize()
+            times = {k: [] for k in routes}
+            for _ in range(a.windows):
+                for k, fn in routes.items():
+                    times[k].append(window(lambda: fn(x, xh), a.window))
+        for k, w in times.items():
+            row[f"{k}_ms"] = float(np.median([t for t, _ in w]))
+            row[f"{k}_windows"] = [[round(t, 3), n] for t, n in w]
+        row[f"hip_{prec}_algorithmic_tflops"] = algo / (row[f"hip_{prec}_ms"] * 1e-3) / 1e12
+        row[f"hip_{prec}_over_hip_fp32_time"] = row[f"hip_{prec}_ms"] / row["hip_fp32_ms"]
+        row[f"hip_{prec}_over_half_composite_time"] = row[f"hip_{prec}_ms"] / row["half_composite_ms"]
+        res["batches"][str(B)] = row
+        print(f"B={B}: {json.dumps(row)}", file=sys.stderr, flush=True)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(json.dumps(res) + "\n")
+    del x, xh
+    res["kept_boxes"] = kept_boxes_that_differ(a, dev)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res) + "\n")
+    print(json.dumps(res))
+
+
+def double_flip_bench(a):
+    """--double-flip: see the module's docstring"""
+    detect = importlib.import_module("3dal_pytorch_amd.detect")
+    pillars = importlib.import_module("3dal_pytorch_amd.pillars")
+    dev, n = torch.device("cuda"), a.points
+    model, dpts, off = sweep_model_and_points(n, dev)
     off_dev = torch.from_numpy(off).to(dev)
     flip_cfg = dict(TTA_CFG, double_flip=True)
     res = {"bench": "double_flip", "size": a.size, "points": n, "device": torch.cuda.get_device_name(0), "window_s": a.window}
@@ -233,9 +324,14 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--double-flip", action="store_true", help="time the test-time augmentation instead (see above)")
     ap.add_argument("--points", type=int, default=180000, help="points of the --double-flip sweep")
+    ap.add_argument("--precision", choices=["fp32", "fp16", "bf16"], default="fp32",
+                    help="fp16 / bf16: time the fp32 kernels, the 16-bit kernels and stock half convolutions in one job (see above)")
     a = ap.parse_args()
     if a.double_flip:
         return double_flip_bench(a)
+    if a.precision != "fp32":
+        a.out = a.out or os.path.join(ROOT, "profiles", "bench_detector_lp.json")
+        return lp_bench(a)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import rpn_ref as R
     dev = torch.device("cuda")
