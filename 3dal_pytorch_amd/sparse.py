@@ -43,11 +43,14 @@ def safe_capacity(in_capacity, batch_size, shape, kernel, stride, padding):
 
 
 def _check_grid(batch_size, shape):
+    """the library's own bound (sp_grid_ok of csrc/dal3_api.hip), term for term: what passes here is never refused there"""
     if batch_size < 1 or any(n < 1 for n in shape):
         raise ValueError(f"batch_size {batch_size} and spatial_shape {tuple(shape)} must be positive")
-    if batch_size * int(np.prod([int(n) for n in shape], dtype=np.int64)) >= 2 ** 31 - 1:
-        raise ValueError(f"B * D * H * W = {batch_size} * {int(np.prod(shape, dtype=np.int64))} does not fit the 31-bit (sample, cell) "
-                         "key: split the batch")
+    if batch_size > 65535 or any(n > 65536 for n in shape):
+        raise ValueError(f"batch_size {batch_size} must be at most 65535 and every axis of {tuple(shape)} at most 65536 cells")
+    cells = int(np.prod([int(n) for n in shape], dtype=np.int64))
+    if cells >= (2 ** 31 - 1) // batch_size:    # the library's integer division: one cell stricter than B * cells < 2^31 - 1
+        raise ValueError(f"B * D * H * W = {batch_size} * {cells} does not fit the 31-bit (sample, cell) key: split the batch")
 
 
 class SparseConvTensor:

@@ -1,4 +1,4 @@
-"""What tests/test_gpu_sparse.py and tests/test_gpu_voxelnet.py share: sparse tensors and single layers on the device,
+"""What tests/test_gpu_sparse.py, tests/test_gpu_sparse_edges.py and tests/test_gpu_voxelnet.py share: sparse tensors and single layers on the device,
 the bookkeeping walked level by level next to sparse_ref's rulebook, references computed once, and the record of every
 figure held under DAL3_SPARSE_RECORD=<path> (how profiles/sparse_measured.json is made: run both files in one session)."""
 import functools
@@ -105,14 +105,15 @@ def windows(shape):
     return out
 
 
-def book_ref(idx, B, shape):
-    """every level's integers by sparse_ref: [(name, indices, shape, the 27-tap table, the strided table or None)]"""
+def book_ref(idx, B, shape, table=S.table):
+    """every level's integers by sparse_ref: [(name, indices, shape, the 27-tap table, the strided table or None)].
+    table: S.table, or S.table_sorted for levels of thousands of sites"""
     idx = np.asarray(idx, np.int32).reshape(-1, 4)
-    levels = [("res0", idx, tuple(shape), S.table(idx, idx, B, shape, shape, (3, 3, 3), (1, 1, 1), (1, 1, 1)), None)]
+    levels = [("res0", idx, tuple(shape), table(idx, idx, B, shape, shape, (3, 3, 3), (1, 1, 1), (1, 1, 1)), None)]
     for name, kernel, stride, padding, osh in windows(shape):
         o, _ = S.downsample(idx, B, shape, kernel, stride, padding)
-        down = S.table(o, idx, B, shape, osh, kernel, stride, padding)
-        levels.append((name, o, osh, S.table(o, o, B, osh, osh, (3, 3, 3), (1, 1, 1), (1, 1, 1)), down))
+        down = table(o, idx, B, shape, osh, kernel, stride, padding)
+        levels.append((name, o, osh, table(o, o, B, osh, osh, (3, 3, 3), (1, 1, 1), (1, 1, 1)), down))
         idx, shape = o, osh
     return levels
 
@@ -129,9 +130,11 @@ class Guarded:
 
 
 @torch.no_grad()
-def book_gpu(x, caps=None, max_workgroups=0):
+def book_gpu(x, caps=None, max_workgroups=0, inverse=None):
     """the same walk on the device through sparse.py's bookkeeping, every output in a guarded, sentinel-filled buffer ->
-    [(name, indices, n, shape, table27, strided table or None, capacity)] as host arrays, and whether every guard is intact"""
+    [(name, indices, n, shape, table27, strided table or None, capacity)] as host arrays, and whether every guard is intact.
+    inverse: a list that takes every strided level's transposed table, (name, (taps, input capacity) host array), built in a
+    guarded buffer too"""
     caps, bufs = caps or {}, []
     levels = [("res0", x.indices.cpu().numpy(), None if x.n is None else int(x.n.item()), x.spatial_shape,
                sparse.subm_table(x, None, max_workgroups).cpu().numpy(), None, x.capacity)]
@@ -148,6 +151,11 @@ def book_gpu(x, caps=None, max_workgroups=0):
         g27 = Guarded(27 * cap, 0)
         t27 = sparse.neighbour_table(y, indices, n_out, cap, shape, (3, 3, 3), (1, 1, 1), (1, 1, 1), max_workgroups, g27.view.view(27, cap))
         bufs += [gi, gk, gt, g27]
+        if inverse is not None:
+            gv = Guarded(taps * x.capacity, 0)
+            inv = sparse.transposed_table(x, keys, n_out, cap, shape, kernel, stride, padding, max_workgroups, gv.view.view(taps, x.capacity))
+            inverse.append((name, inv.cpu().numpy()))
+            bufs.append(gv)
         levels.append((name, indices.cpu().numpy(), int(n_out.item()), shape, t27.cpu().numpy(), down.cpu().numpy(), cap))
         x = y
     return levels, all(b.intact() for b in bufs)

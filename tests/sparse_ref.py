@@ -184,33 +184,61 @@ def table(out_idx, in_idx, B, in_shape, osh, kernel, stride, padding):
     return t
 
 
+def table_sorted(out_idx, in_idx, B, in_shape, osh, kernel, stride, padding):
+    """`table` without the dict: one np.searchsorted per tap over the valid input keys in a stable ascending order. The
+    same signature and the same result (of input rows that share a key the last one answers, as the dict's later entry
+    replaces the earlier one; -1 for a bad output row and for a tap outside the input grid): what a level of tens of
+    thousands of sites is compared with."""
+    ik = keys_of(in_idx, B, in_shape)
+    rows = np.nonzero(ik >= 0)[0]
+    rows = rows[np.argsort(ik[rows], kind="stable")]
+    sk = ik[rows]
+    o = np.asarray(out_idx, np.int64).reshape(-1, 4)
+    good = keys_of(o, B, osh) >= 0
+    t = np.full((int(np.prod(kernel)), o.shape[0]), -1, np.int32)
+    tap = 0
+    for kz in range(kernel[0]):
+        for ky in range(kernel[1]):
+            for kx in range(kernel[2]):
+                c = o[:, 1:] * np.asarray(stride) - np.asarray(padding) + np.asarray([kz, ky, kx])
+                k = keys_of(np.concatenate([o[:, :1], c], 1), B, in_shape)
+                if sk.size:
+                    at = np.searchsorted(sk, k, side="right") - 1
+                    hit = good & (k >= 0) & (at >= 0) & (sk[np.maximum(at, 0)] == k)
+                    t[tap, hit] = rows[at[hit]]
+                tap += 1
+    return t
+
+
 # ------------------------------------------------------------------------------------- the two formulations
 class Rulebook:
-    """x = (features (n, C) float64, indices (n, 4), shape); `tables` / `sites` record the integers by level"""
+    """x = (features (n, C) of `dtype`, indices (n, 4), shape); `record` holds the integers by level. dtype float32 is the
+    same gather evaluated in fp32: the yardstick on a grid too large for the dense formulation. table: `table` or its
+    vectorised twin `table_sorted`."""
 
-    def __init__(self, B, fault=None):
-        self.B, self.fault, self.cache, self.record = B, fault, {}, {}
+    def __init__(self, B, fault=None, dtype=np.float64, table=table):
+        self.B, self.fault, self.cache, self.record, self.dtype, self.table = B, fault, {}, {}, dtype, table
 
     def start(self, feats, idx, shape):
-        f = np.asarray(feats, np.float64).copy()
+        f = np.asarray(feats, self.dtype).copy()
         f[keys_of(idx, self.B, shape) < 0] = 0.0
         return f, np.asarray(idx, np.int32), tuple(shape)
 
     def conv(self, x, w, kernel, stride, padding, subm, key):
         f, idx, shape = x
-        w = np.asarray(w, np.float64)
+        w = np.asarray(w, self.dtype)
         if self.fault == "taps_flipped":
             w = w[::-1, ::-1, ::-1]
         if subm:
             if key not in self.cache:
-                self.cache[key] = table(idx, idx, self.B, shape, shape, (3, 3, 3), (1, 1, 1), (1, 1, 1))
+                self.cache[key] = self.table(idx, idx, self.B, shape, shape, (3, 3, 3), (1, 1, 1), (1, 1, 1))
             t, oidx, osh = self.cache[key], idx, shape
         else:
             oidx, osh = downsample(idx, self.B, shape, kernel, stride, padding)
-            t = table(oidx, idx, self.B, shape, osh, kernel, stride, padding)
+            t = self.table(oidx, idx, self.B, shape, osh, kernel, stride, padding)
         self.record[key] = dict(indices=oidx, shape=osh, table=t)
         w = w.reshape(-1, w.shape[3], w.shape[4])
-        y = np.zeros((oidx.shape[0], w.shape[2]))
+        y = np.zeros((oidx.shape[0], w.shape[2]), self.dtype)
         for tap in range(t.shape[0]):
             has = t[tap] >= 0
             if has.any():
@@ -220,7 +248,7 @@ class Rulebook:
 
     def post(self, x, fn):
         y, idx, shape = x
-        return np.where(self.valid, fn(y, lambda v: np.asarray(v, np.float64)[None, :]), 0.0), idx, shape
+        return np.where(self.valid, fn(y, lambda v: np.asarray(v, self.dtype)[None, :]), self.dtype(0)), idx, shape
 
     def feats(self, x):
         return x[0]
@@ -302,6 +330,14 @@ def layer(be, feats, idx, shape, w, bias, bn, kernel, stride, padding, subm, rel
     x = be.start(feats, idx, shape)
     y = be.conv(x, w, kernel, stride, padding, subm, "layer")
     return np.asarray(be.dense(_post(be, y, bias, bn, eps, relu, be.feats(x) if residual else None)))
+
+
+def layer_rows(be, feats, idx, shape, w, bias, bn, kernel, stride, padding, subm, relu, eps=EPS):
+    """`layer` on a Rulebook without the dense map, for a grid no dense array can hold -> (rows (n_out, c_out), output
+    indices (n_out, 4), output shape): a submanifold layer's rows in the input's order, a strided one's in key order"""
+    x = be.start(feats, idx, shape)
+    y, oidx, osh = _post(be, be.conv(x, w, kernel, stride, padding, subm, "layer"), bias, bn, eps, relu)
+    return y, oidx, osh
 
 
 def backbone(be, sd, feats, idx, shape):

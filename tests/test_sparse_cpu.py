@@ -93,6 +93,75 @@ def test_the_integers_of_the_two_formulations_agree_exactly():
     assert (key[idx.shape[0]:] == B * int(np.prod(shape))).all() and np.array_equal(idx[pos[:idx.shape[0]]], S.unkey(key[:idx.shape[0]], shape))
 
 
+def _both_tables(idx, B, shape, kernel, stride, padding, what):
+    """the dict walk and its vectorised twin, on the strided window and on the 27-tap table of its output -> count of hits"""
+    idx = np.asarray(idx, np.int32)
+    o, osh = S.downsample(idx, B, shape, kernel, stride, padding)
+    hits = 0
+    for args in ((idx, idx, B, shape, shape, (3, 3, 3), (1, 1, 1), (1, 1, 1)), (o, idx, B, shape, osh, kernel, stride, padding),
+                 (o, o, B, osh, osh, (3, 3, 3), (1, 1, 1), (1, 1, 1))):
+        slow, fast = S.table(*args), S.table_sorted(*args)
+        assert slow.dtype == fast.dtype == np.int32 and slow.shape == fast.shape and np.array_equal(slow, fast), what
+        hits += int((slow >= 0).sum())
+    return hits
+
+
+def test_the_vectorised_table_is_the_dict_walk():
+    import sparse_book_cases as K
+    import sparse_train_ref as T
+    from test_gpu_sparse import BOOK_CASES
+    k3s2 = ((3, 3, 3), (2, 2, 2), (1, 1, 1))
+    for name, (idx, B, shape) in BOOK_CASES.items():
+        for _, _, kernel, stride, padding in S.STEMS[1:len(K.levels(shape))]:      # every level the bookkeeping test walks
+            assert _both_tables(idx, B, shape, kernel, stride, padding, name) > 0
+            idx, shape = S.downsample(idx, B, shape, kernel, stride, padding)
+    idx, B, shape = BOOK_CASES["n65"]
+    bad = idx.copy()
+    bad[10, 3], bad[50, 0], bad[7, 1] = shape[2], B, -1                     # past the grid, past the batch, negative
+    _both_tables(bad, B, shape, *k3s2, "bad coordinate")
+    t = S.table_sorted(bad, bad, B, shape, shape, (3, 3, 3), (1, 1, 1), (1, 1, 1))
+    assert (t[:, [7, 10, 50]] == -1).all() and not np.isin(t, [7, 10, 50]).any()       # a bad row has no tap and is nobody's neighbour
+    dup = idx.copy()
+    dup[20], dup[41] = dup[3], dup[3]
+    _both_tables(dup, B, shape, *k3s2, "duplicate")
+    t = S.table_sorted(dup, dup, B, shape, shape, (3, 3, 3), (1, 1, 1), (1, 1, 1))
+    assert (t[13, [3, 20, 41]] == 41).all()                                 # the last row of a key answers, as in the dict
+    idx, B, shape = K.window_sites()
+    for kernel, stride, padding in K.window_cases():
+        assert _both_tables(idx, B, shape, kernel, stride, padding, (kernel, stride, padding)) > 0
+        # and the transposed table that scales (sparse_train_ref.inverse_table) is the forward one read backwards
+        o, osh = S.downsample(idx, B, shape, kernel, stride, padding)
+        fwd = S.table_sorted(o, idx, B, shape, osh, kernel, stride, padding)
+        assert np.array_equal(T.inverse_table(idx, o, B, shape, osh, kernel, stride, padding), T.inverse_brute(fwd, idx.shape[0]))
+
+
+def test_check_grid_is_sp_grid_ok():
+    """sparse._check_grid and the library's sp_grid_ok on the largest grid and on the first one refused. The library compares
+    cells with floor((2^31 - 1) / B); the product B * cells < 2^31 - 1 that _check_grid used to take admits one more cell count
+    for every B >= 2 (2^31 - 1 is prime), which the library then refused. _check_grid now divides as the library does."""
+    import sparse_book_cases as K
+    lib = hip.lib()
+    sort = lambda B, shape: hip.SpSortArgs(B=B, shape=I3(*shape), capacity=0, status=FAKE)       # capacity 0: nothing is launched
+    B, shape = K.WIDTH_GRIDS["largest"]
+    sparse._check_grid(B, shape)
+    assert lib.dal3_sp_sort(sort(B, shape), None) == hip.OK
+    B, shape = K.FIRST_REFUSED
+    assert B * int(np.prod(shape, dtype=np.int64)) == 2 ** 31 - 2 and not K.admissible(B, shape)
+    _err(lib.dal3_sp_sort(sort(B, shape), None), "2^31 - 1")
+    with pytest.raises(ValueError, match="31-bit"):
+        sparse._check_grid(B, shape)
+    for B, shape in ((1, (2, 32767, 32768)), (1, (1, 46341, 46340)), (65535, (1, 1, 32768)), (65535, (1, 1, 32769)), (65536, (1, 1, 1)),
+                     (1, (1, 1, 65537)), (1, (65536, 1, 1)), (3, (5, 7, 9)), *K.WIDTH_GRIDS.values()):
+        rc = lib.dal3_sp_sort(sort(B, shape), None)
+        assert rc in (hip.OK, hip.EINVAL)
+        if rc == hip.OK:
+            sparse._check_grid(B, shape)
+        else:
+            with pytest.raises(ValueError):
+                sparse._check_grid(B, shape)
+        assert K.admissible(B, shape) == (rc == hip.OK), (B, shape)
+
+
 def test_planted_faults_are_caught_at_ten_times_the_bars():
     feats, idx, B, shape, sd, _, _, _, truth = case()
     f32 = S.backbone(S.Dense(B, torch.float32), sd, feats, idx, shape)
