@@ -285,6 +285,11 @@ class SpConvArgs(C.Structure):
                 ("max_workgroups", C.c_int64)]
 
 
+class SpConvLpArgs(C.Structure):
+    """dal3_sp_conv_lp_args"""
+    _fields_ = SpConvArgs._fields_ + [("dtype", C.c_int32), ("x16", vp), ("y16", vp)]
+
+
 SP_WGRAD_SLICE = 1024                           # DAL3_SP_WGRAD_SLICE: the sites of one partial sum of dal3_sp_wgrad
 
 
@@ -489,6 +494,9 @@ SIGNATURES = {
     "dal3_sp_conv_pack_floats": (_sz, [_i, _i, _i]),
     "dal3_sp_conv_pack": (_i, [C.POINTER(Layer), _i, C.c_double, vp, vp, vp]),
     "dal3_sp_conv": (_i, [C.POINTER(SpConvArgs), vp]),
+    "dal3_sp_conv_lp_pack_bytes": (_sz, [_i, _i, _i]),
+    "dal3_sp_conv_lp_pack": (_i, [C.POINTER(Layer), _i, C.c_double, _i, vp, vp, vp]),
+    "dal3_sp_conv_lp": (_i, [C.POINTER(SpConvLpArgs), vp]),
     "dal3_sp_table_transposed": (_i, [C.POINTER(SpTableTransposedArgs), vp]),
     "dal3_sp_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i64]),
     "dal3_sp_wgrad": (_i, [C.POINTER(SpWgradArgs), vp]),

@@ -1500,6 +1500,59 @@ extern "C" int dal3_sp_conv(const dal3_sp_conv_args* args, dal3_stream stream) {
     return 0;
 }
 
+// ... and on 16-bit MFMA operands (dal3_spconv_lp.hip)
+extern "C" size_t dal3_sp_conv_lp_pack_bytes(int taps, int c_in, int c_out) {
+    if (taps < 1 || taps > 27 || !sp_channels_ok(c_in, c_out)) return 0;
+    return sp_conv_lp_pack_bytes(taps, c_in, c_out);
+}
+
+extern "C" int dal3_sp_conv_lp_pack(const dal3_layer* layer, int taps, double eps, int dtype, void* out, int32_t* status,
+                                    dal3_stream stream) {
+    if (!layer || !out) return fail(DAL3_EINVAL, "sp_conv_lp_pack: null layer / out");
+    if (!conv2d_lp_dtype_ok(dtype)) return fail(DAL3_EINVAL, "sp_conv_lp_pack: dtype %d (DAL3_F16 or DAL3_BF16)", dtype);
+    if (taps < 1 || taps > 27) return fail(DAL3_EINVAL, "sp_conv_lp_pack: %d taps (1 .. 27)", taps);
+    if (!sp_channels_ok(layer->c_in, layer->c_out))
+        return fail(DAL3_EINVAL, "sp_conv_lp_pack: %d -> %d channels (c_in 1 .. 8, 16, 32, 64, 128; c_out 16, 32, 64, 128)",
+                    (int)layer->c_in, (int)layer->c_out);
+    TRY(check_fold_layer("sp_conv_lp_pack", layer, -1, eps, static_cast<const float*>(out)));
+    HIP_TRY(launch_sp_conv_lp_pack(FoldLayer(*layer, eps), taps, dtype, out, status, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+extern "C" int dal3_sp_conv_lp(const dal3_sp_conv_lp_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "sp_conv_lp: null args");
+    const dal3_sp_conv_lp_args& a = *args;
+    if (!conv2d_lp_dtype_ok(a.dtype)) return fail(DAL3_EINVAL, "sp_conv_lp: dtype %d (DAL3_F16 or DAL3_BF16)", (int)a.dtype);
+    if (a.taps < 1 || a.taps > 27 || !sp_channels_ok(a.c_in, a.c_out))
+        return fail(DAL3_EINVAL, "sp_conv_lp: %d taps, %d -> %d channels (taps 1 .. 27; c_in 1 .. 8, 16, 32, 64, 128; c_out 16, 32, 64, 128)",
+                    (int)a.taps, (int)a.c_in, (int)a.c_out);
+    if ((a.relu != 0 && a.relu != 1) || a.center_tap < -1 || a.center_tap >= a.taps || a.max_workgroups < 0 || a.reserved || a.reserved2)
+        return fail(DAL3_EINVAL, "sp_conv_lp: bad relu (0 or 1) / center_tap (-1 .. taps - 1) / max_workgroups (>= 0) / reserved");
+    if (!sp_cap_ok(a.in_capacity) || !sp_cap_ok(a.out_capacity) || !sp_cap_ok(a.out_capacity * 27)) return fail(DAL3_EINVAL, "sp_conv_lp: bad capacity");
+    if (!a.status) return fail(DAL3_EINVAL, "sp_conv_lp: null status");
+    if (!a.packed || (reinterpret_cast<uintptr_t>(a.packed) & 15)) return fail(DAL3_EINVAL, "sp_conv_lp: packed is null or not 16-byte aligned");
+    if (a.x && a.x16) return fail(DAL3_EINVAL, "sp_conv_lp: both x and x16 are given (exactly one)");
+    if (a.x16 && a.c_in <= 8) return fail(DAL3_EINVAL, "sp_conv_lp: x16 needs c_in 16, 32, 64 or 128 (c_in %d comes as float32 x)", (int)a.c_in);
+    if (a.canvas) {
+        if (!a.out_indices && a.out_capacity > 0) return fail(DAL3_EINVAL, "sp_conv_lp: a canvas needs out_indices");
+        if (a.canvas_B < 1 || a.canvas_B > 65535 || a.canvas_shape[0] < 1 || a.canvas_shape[1] < 1 || a.canvas_shape[2] < 1 ||
+            a.canvas_shape[0] > 65536 || a.canvas_shape[1] > 65536 || a.canvas_shape[2] > 65536 ||
+            a.canvas_B * a.c_out * a.canvas_shape[0] * a.canvas_shape[1] * a.canvas_shape[2] > ((int64_t)1 << 40))
+            return fail(DAL3_EINVAL, "sp_conv_lp: bad canvas shape (canvas_B, D, H, W >= 1)");
+    } else if (a.out_capacity > 0 && !a.y && !a.y16) {
+        return fail(DAL3_EINVAL, "sp_conv_lp: no output (y, y16 and canvas are NULL)");
+    }
+    if (a.out_capacity > 0) {
+        if (!a.table) return fail(DAL3_EINVAL, "sp_conv_lp: null table");
+        if (a.in_capacity > 0 && !a.x && !a.x16) return fail(DAL3_EINVAL, "sp_conv_lp: neither x nor x16 is given (exactly one)");
+        if (((a.c_in > 8 ? reinterpret_cast<uintptr_t>(a.x) : 0) | reinterpret_cast<uintptr_t>(a.x16) | reinterpret_cast<uintptr_t>(a.y) |
+             reinterpret_cast<uintptr_t>(a.y16) | reinterpret_cast<uintptr_t>(a.residual)) & 15)
+            return fail(DAL3_EINVAL, "sp_conv_lp: x (with 16 or more channels), x16, y, y16 and residual must be 16-byte aligned");
+    }
+    HIP_TRY(launch_sp_conv_lp(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 extern "C" int dal3_sp_table_transposed(const dal3_sp_table_transposed_args* args, dal3_stream stream) {
     if (!args) return fail(DAL3_EINVAL, "sp_table_transposed: null args");
     const dal3_sp_table_transposed_args& a = *args;

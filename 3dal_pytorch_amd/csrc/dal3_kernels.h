@@ -389,6 +389,10 @@ hipError_t launch_sp_table(const dal3_sp_table_args* a, hipStream_t s);
 size_t sp_conv_pack_floats(int taps, int c_in, int c_out);
 hipError_t launch_sp_conv_pack(const FoldLayer& layer, int taps, float* out, int32_t* status, hipStream_t s);
 hipError_t launch_sp_conv(const dal3_sp_conv_args* a, hipStream_t s);
+// ... and its convolutions on 16-bit MFMA operands (dal3_spconv_lp.hip); dtype DAL3_F16 or DAL3_BF16, checked by the caller
+size_t sp_conv_lp_pack_bytes(int taps, int c_in, int c_out);
+hipError_t launch_sp_conv_lp_pack(const FoldLayer& layer, int taps, int dtype, void* out, int32_t* status, hipStream_t s);
+hipError_t launch_sp_conv_lp(const dal3_sp_conv_lp_args* a, hipStream_t s);
 hipError_t launch_sp_table_transposed(const dal3_sp_table_transposed_args* a, hipStream_t s);
 size_t sp_wgrad_workspace_bytes(int taps, int c_in, int c_out, int64_t out_capacity);
 hipError_t launch_sp_wgrad(const dal3_sp_wgrad_args* a, hipStream_t s);

@@ -71,6 +71,21 @@ class SingleStageDetector(nn.Module):
             if m is not None:
                 m.precision = value
 
+    @property
+    def sparse_precision(self):
+        """the MFMA operand type of the sparse 3-D middle's eval-mode convolutions (sparse.SpMiddleResNetFHD.sparse_precision):
+        'fp32' (the default) | 'fp16' | 'bf16'. A knob of its own: `precision` does not touch it, and it does not touch
+        `precision`. A backbone without one (PointPillarsScatter) reads 'fp32' and refuses to be set."""
+        return getattr(self.backbone, "sparse_precision", "fp32")
+
+    @sparse_precision.setter
+    def sparse_precision(self, value):
+        rpn.check_precision(value)
+        if not hasattr(self.backbone, "sparse_precision"):
+            raise ValueError(f"{type(self.backbone).__name__} has no sparse convolutions: sparse_precision belongs to a detector "
+                             "with a sparse 3-D middle (VoxelNet)")
+        self.backbone.sparse_precision = value
+
     def init_weights(self, pretrained):
         """a checkpoint path: its `state_dict` (or the file itself) must hold exactly this model's keys"""
         ckpt = torch.load(pretrained, map_location="cpu")

@@ -11,6 +11,12 @@ capacity-sized, and a level that would exceed its capacity sets _hip.SP_OVERFLOW
 the differentiable one: every convolution is a torch.autograd.Function around dal3_sp_conv whose backward runs the data
 gradient on the same kernel (the transposed pack on the inverse table) and the weight gradient through dal3_sp_wgrad;
 BatchNorm over the live rows (`batch_norm_rows`), ReLU and the residual are stock torch ops. There is no CPU route.
+
+`sparse_precision` on the layers, the block and the backbone ("fp32", the default, | "fp16" | "bf16") picks the MFMA operand
+type of the eval-mode convolutions: with a 16-bit one every layer runs dal3_sp_conv_lp on weights rounded once at pack time;
+the first layer rounds the float32 voxel features as it stages them, every later layer gathers the 16-bit rows its
+producer stored beside (or instead of) the float32 ones (`SparseConvTensor.features16`). Residuals, the returned levels and
+the BEV map stay float32; the bookkeeping is the same either way, and `train_forward` ignores the knob.
 """
 from types import SimpleNamespace
 
@@ -20,7 +26,7 @@ from torch import nn
 
 from . import _hip
 from .pillars import _device_ints
-from .rpn import _PackedLayers
+from .rpn import _TORCH16, _PackedLayers, check_precision
 
 
 def _triple(v):
@@ -57,24 +63,34 @@ class SparseConvTensor:
     """features (capacity, C) float32 and indices (capacity, 4) int32 rows [b, z, y, x] on the GPU, spatial_shape (D, H, W),
     batch_size. n: a device int64 (1) tensor, the rows in use (None: all of them). status: the int32 (1) word the kernels OR
     problems into (_hip.SP_*). `sorted` (keys, rows; rows None = the identity) and `indice_dict` are the bookkeeping the
-    layers share."""
+    layers share. features16: optionally the same rows rounded to torch.float16 or torch.bfloat16, (capacity, C), as a
+    16-bit layer stores them for the next one to gather; a layer whose float32 rows nobody reads has `features` None."""
 
-    def __init__(self, features, indices, spatial_shape, batch_size, n=None, status=None):
+    def __init__(self, features, indices, spatial_shape, batch_size, n=None, status=None, features16=None):
         for t, what in ((features, "features"), (indices, "indices")):
-            if not torch.is_tensor(t):
+            if not torch.is_tensor(t) and not (t is None and what == "features" and features16 is not None):
                 raise TypeError(f"{what} must be a tensor")
-        if features.dim() != 2 or features.dtype != torch.float32:
+        rows = (features if features is not None else features16).shape[0]
+        if features is not None and (features.dim() != 2 or features.dtype != torch.float32):
             raise ValueError(f"features must be float32 (n, C), got {features.dtype} {tuple(features.shape)}")
-        if indices.shape != (features.shape[0], 4) or indices.dtype != torch.int32:
-            raise ValueError(f"indices must be int32 ({features.shape[0]}, 4), got {indices.dtype} {tuple(indices.shape)}")
-        _hip.require_gpu(features, "features")
+        if indices.shape != (rows, 4) or indices.dtype != torch.int32:
+            raise ValueError(f"indices must be int32 ({rows}, 4), got {indices.dtype} {tuple(indices.shape)}")
+        if features16 is not None:
+            if not torch.is_tensor(features16) or features16.dtype not in (torch.float16, torch.bfloat16) or features16.dim() != 2 or \
+                    features16.shape[0] != rows or (features is not None and features16.shape != features.shape):
+                raise ValueError("features16 must be a float16 or bfloat16 tensor of the features' shape (capacity, C)")
+            _hip.require_gpu(features16, "features16")
+            features16 = features16.contiguous()
+        if features is not None:
+            _hip.require_gpu(features, "features")
         _hip.require_gpu(indices, "indices")
-        self.features, self.indices = features.contiguous(), indices.contiguous()
+        self.features, self.indices = None if features is None else features.contiguous(), indices.contiguous()
+        self.features16 = features16
         self.spatial_shape, self.batch_size = tuple(int(v) for v in spatial_shape), int(batch_size)
         if len(self.spatial_shape) != 3:
             raise ValueError("spatial_shape must be (D, H, W)")
         _check_grid(self.batch_size, self.spatial_shape)
-        dev = features.device
+        dev = indices.device
         self.n = _device_ints(n, "n", torch.int64, 1, dev)
         self.status = _device_ints(status, "status", torch.int32, 1, dev)
         if self.status is None:
@@ -83,11 +99,11 @@ class SparseConvTensor:
 
     @property
     def capacity(self):
-        return self.features.shape[0]
+        return self.indices.shape[0]
 
-    def like(self, features):
-        """the same sites with other features (what a submanifold layer returns)"""
-        out = SparseConvTensor(features, self.indices, self.spatial_shape, self.batch_size, self.n, self.status)
+    def like(self, features, features16=None):
+        """the same sites with other features (what a submanifold layer returns); features16 is the caller's or none"""
+        out = SparseConvTensor(features, self.indices, self.spatial_shape, self.batch_size, self.n, self.status, features16)
         out.sorted, out.indice_dict = self.sorted, self.indice_dict
         return out
 
@@ -114,7 +130,7 @@ def _i3(v):
 def sort_sites(x, max_workgroups=0):
     """x.sorted = (keys, rows) of the tensor's sites by ascending key (dal3_sp_sort); flags bad and duplicate rows"""
     if x.sorted is None:
-        cap, dev = x.capacity, x.features.device
+        cap, dev = x.capacity, x.indices.device
         key = torch.empty(cap, dtype=torch.int32, device=dev)
         pos = torch.empty(cap, dtype=torch.int32, device=dev)
         lib = _hip.lib()
@@ -133,7 +149,7 @@ def neighbour_table(x, out_indices, out_n, out_capacity, shape_out, kernel, stri
     key, pos = sort_sites(x, max_workgroups)
     taps = int(np.prod(kernel))
     if table is None:
-        table = torch.empty((taps, out_capacity), dtype=torch.int32, device=x.features.device)
+        table = torch.empty((taps, out_capacity), dtype=torch.int32, device=x.indices.device)
     a = _hip.SpTableArgs(B=x.batch_size, in_shape=_i3(x.spatial_shape), out_shape=_i3(shape_out), kernel=_i3(kernel),
                          stride=_i3(stride), padding=_i3(padding), out_capacity=out_capacity, n_out=_hip.ptr(out_n),
                          out_indices=_hip.ptr(out_indices), in_capacity=x.capacity, n_in=_hip.ptr(x.n), in_key=_hip.ptr(key),
@@ -163,7 +179,7 @@ def downsample(x, kernel, stride, padding, capacity=None, max_workgroups=0, indi
     cap = safe_capacity(x.capacity, x.batch_size, x.spatial_shape, kernel, stride, padding) if capacity is None else int(capacity)
     if cap < 0:
         raise ValueError("capacity must be >= 0")
-    dev = x.features.device
+    dev = x.indices.device
     if indices is None:
         indices = torch.empty((cap, 4), dtype=torch.int32, device=dev)
     if keys is None:
@@ -182,9 +198,11 @@ def downsample(x, kernel, stride, padding, capacity=None, max_workgroups=0, indi
 
 
 # ------------------------------------------------------------------------------------- the convolution
-def pack_layer(conv, bn, status=None):
-    """fold and pack one layer -> a float32 device tensor (dal3_sp_conv_pack). conv: SubMConv3d / SparseConv3d; bn:
-    nn.BatchNorm1d or None"""
+def pack_layer(conv, bn, status=None, precision="fp32"):
+    """fold and pack one layer -> a float32 device tensor (dal3_sp_conv_pack), or for 'fp16' / 'bf16' the uint8 blob of
+    dal3_sp_conv_lp_pack. conv: SubMConv3d / SparseConv3d; bn: nn.BatchNorm1d or None. A folded weight that is not finite
+    (in the 16-bit type, for a 16-bit pack) sets SP_BAD_WEIGHT in `status` on the device; nothing synchronises."""
+    dtype = check_precision(precision)
     L = _hip.fold_layer_struct(conv, bn)
     if bn is not None and not (isinstance(bn, nn.BatchNorm1d) and bn.affine and bn.track_running_stats):
         raise RuntimeError("the norm layer must be an affine nn.BatchNorm1d with running statistics")
@@ -194,16 +212,33 @@ def pack_layer(conv, bn, status=None):
     if not floats:
         raise ValueError(f"the kernel serves c_in 1 .. 8, 16, 32, 64, 128 and c_out 16, 32, 64, 128, not {conv.in_channels} -> "
                          f"{conv.out_channels}")
+    eps = float(bn.eps) if bn is not None else 1e-3
+    if precision != "fp32":
+        buf = torch.empty(lib.dal3_sp_conv_lp_pack_bytes(taps, conv.in_channels, conv.out_channels), dtype=torch.uint8,
+                          device=conv.weight.device)
+        _hip.check(lib.dal3_sp_conv_lp_pack(L, taps, eps, dtype, _hip.ptr(buf), _hip.ptr(status), _hip.stream()))
+        return buf
     buf = torch.empty(floats, dtype=torch.float32, device=conv.weight.device)
-    _hip.check(lib.dal3_sp_conv_pack(L, taps, float(bn.eps) if bn is not None else 1e-3, _hip.ptr(buf), _hip.ptr(status), _hip.stream()))
+    _hip.check(lib.dal3_sp_conv_pack(L, taps, eps, _hip.ptr(buf), _hip.ptr(status), _hip.stream()))
     return buf
 
 
 def conv(features, table, n_out, packed, c_in, c_out, status, relu=False, residual=None, center_tap=-1, canvas=None,
-         out_indices=None, canvas_shape=None, out=None, max_workgroups=0):
+         out_indices=None, canvas_shape=None, out=None, max_workgroups=0, precision="fp32", features16=None, out16=False,
+         rows=True):
     """one dal3_sp_conv launch: features (in_capacity, c_in), table (taps, out_capacity) -> (out_capacity, c_out) rows, or, with
-    `canvas` (B, c_out * D, H, W), the BEV store (the rows are then not kept)"""
+    `canvas` (B, c_out * D, H, W), the BEV store (the rows are then not kept).
+    precision 'fp16' / 'bf16': dal3_sp_conv_lp on a pack of that precision. The input is `features` (float32, rounded as it is
+    staged) or `features16` (the producer's 16-bit rows; c_in >= 16), exactly one of them. out16: True (allocate) or a
+    (out_capacity, c_out) tensor of the 16-bit type that takes q(y); the call then returns (rows or canvas, y16).
+    rows=False keeps no float32 rows (out16 is then the only output)."""
     taps, out_cap = table.shape
+    if precision != "fp32":
+        return _conv_lp(features, table, n_out, packed, c_in, c_out, status, relu, residual, center_tap, canvas, out_indices,
+                        canvas_shape, out, max_workgroups, precision, features16, out16, rows)
+    check_precision(precision)
+    if features16 is not None or out16 is not False or not rows:
+        raise ValueError("features16, out16 and rows=False belong to the 16-bit precisions")
     dev = features.device
     if packed.numel() != _hip.lib().dal3_sp_conv_pack_floats(taps, c_in, c_out) or packed.device != dev:
         raise ValueError(f"the packed weights are not those of a {taps}-tap {c_in} -> {c_out} layer on {dev}")
@@ -225,6 +260,49 @@ def conv(features, table, n_out, packed, c_in, c_out, status, relu=False, residu
     return canvas if canvas is not None else out
 
 
+def _conv_lp(features, table, n_out, packed, c_in, c_out, status, relu, residual, center_tap, canvas, out_indices, canvas_shape,
+             out, max_workgroups, precision, features16, out16, rows):
+    """`conv` on 16-bit MFMA operands"""
+    dtype, t16 = check_precision(precision), _TORCH16[precision]
+    taps, out_cap = table.shape
+    dev, lib = table.device, _hip.lib()
+    if packed.dtype != torch.uint8 or packed.numel() != lib.dal3_sp_conv_lp_pack_bytes(taps, c_in, c_out) or packed.device != dev:
+        raise ValueError(f"the packed weights are not those of a {taps}-tap {c_in} -> {c_out} layer in {precision} on {dev}")
+    if (features is None) == (features16 is None):
+        raise ValueError("exactly one of features (float32) and features16 is the layer's input")
+    if features is not None and (features.shape[1] != c_in or features.dtype != torch.float32 or not features.is_contiguous()):
+        raise ValueError(f"features must be contiguous float32 (n, {c_in}), got {features.dtype} {tuple(features.shape)}")
+    if features16 is not None and (features16.dim() != 2 or features16.shape[1] != c_in or features16.dtype != t16 or
+                                   not features16.is_contiguous() or c_in < 16):
+        raise ValueError(f"features16 must be contiguous {t16} (n, {c_in}) with 16 or more channels, got {features16.dtype} "
+                         f"{tuple(features16.shape)}")
+    if residual is not None and (residual.shape != (out_cap, c_out) or not residual.is_contiguous() or residual.dtype != torch.float32):
+        raise ValueError(f"residual must be contiguous float32 ({out_cap}, {c_out})")
+    if canvas is None and out is None and rows:
+        out = torch.empty((out_cap, c_out), dtype=torch.float32, device=dev)
+    y16 = None
+    if out16 is True:
+        y16 = torch.empty((out_cap, c_out), dtype=t16, device=dev)
+    elif out16 is not False:
+        y16 = out16
+        if not torch.is_tensor(y16) or y16.shape != (out_cap, c_out) or y16.dtype != t16 or not y16.is_contiguous() or y16.device != dev:
+            raise ValueError(f"out16 must be a contiguous {t16} ({out_cap}, {c_out}) tensor on {dev}")
+    if canvas is None and out is None and y16 is None:
+        raise ValueError("the layer has no output: rows=False needs out16 or a canvas")
+    x = features if features is not None else features16
+    a = _hip.SpConvLpArgs(taps=taps, c_in=c_in, c_out=c_out, relu=1 if relu else 0, center_tap=center_tap, in_capacity=x.shape[0],
+                          x=_hip.ptr(features), out_capacity=out_cap, n_out=_hip.ptr(n_out), table=_hip.ptr(table),
+                          packed=_hip.ptr(packed), residual=_hip.ptr(residual), y=_hip.ptr(out), canvas=_hip.ptr(canvas),
+                          out_indices=_hip.ptr(out_indices), status=_hip.ptr(status), max_workgroups=int(max_workgroups),
+                          dtype=dtype, x16=_hip.ptr(features16), y16=_hip.ptr(y16))
+    if canvas is not None:
+        a.canvas_B = canvas.shape[0]
+        a.canvas_shape[:] = [int(v) for v in canvas_shape]
+    _hip.check(lib.dal3_sp_conv_lp(a, _hip.stream()))
+    first = canvas if canvas is not None else out
+    return first if out16 is False else (first, y16)
+
+
 # ------------------------------------------------------------------------------------- the backward pass
 DGRAD_WIDTHS = (16, 32, 64, 128)                # the kernel's output widths: a data gradient has the layer's c_in channels
 
@@ -234,7 +312,7 @@ def transposed_table(x, out_keys, out_n, out_capacity, shape_out, kernel, stride
     (dal3_sp_table_transposed). out_keys: `downsample`'s ascending keys of the output sites"""
     taps = int(np.prod(kernel))
     if table is None:
-        table = torch.empty((taps, x.capacity), dtype=torch.int32, device=x.features.device)
+        table = torch.empty((taps, x.capacity), dtype=torch.int32, device=x.indices.device)
     a = _hip.SpTableTransposedArgs(B=x.batch_size, in_shape=_i3(x.spatial_shape), out_shape=_i3(shape_out), kernel=_i3(kernel),
                                    stride=_i3(stride), padding=_i3(padding), in_capacity=x.capacity, n_in=_hip.ptr(x.n),
                                    in_indices=_hip.ptr(x.indices), out_capacity=out_capacity, n_out=_hip.ptr(out_n),
@@ -350,7 +428,35 @@ def batch_norm_rows(bn, features, n=None):
     return y if mask is None else torch.where(mask, y, torch.zeros((), dtype=y.dtype, device=y.device))
 
 
-class _SparseConv(_PackedLayers):
+class _SparseLayers(_PackedLayers):
+    """_PackedLayers of the sparse middle's modules. `sparse_precision` ('fp32', the default, | 'fp16' | 'bf16') is the MFMA
+    operand type of the eval-mode convolutions; it is part of the cache's key, so changing it repacks, and a container sets
+    its children. (Not `precision`: that name is the dense stage's knob, which leaves this stage alone.) train_forward
+    ignores it."""
+
+    def __init__(self):
+        super().__init__()
+        self._sparse_precision = "fp32"
+
+    @property
+    def sparse_precision(self):
+        return self._sparse_precision
+
+    @sparse_precision.setter
+    def sparse_precision(self, value):
+        check_precision(value)
+        for m in self.modules():
+            if isinstance(m, _SparseLayers):
+                m._sparse_precision = value
+
+    def _pack_key(self):
+        return self._sparse_precision
+
+    def _pack(self, plan):
+        return [pack_layer(c, bn, precision=self._sparse_precision) for c, bn in plan]
+
+
+class _SparseConv(_SparseLayers):
     """a parameter container with spconv 1.x's shapes: weight (kD, kH, kW, c_in, c_out), bias (c_out) or None"""
     subm = False
 
@@ -376,12 +482,11 @@ class _SparseConv(_PackedLayers):
     def _plan(self):
         return [(self, None)]
 
-    def _pack(self, plan):
-        return [pack_layer(c, bn) for c, bn in plan]
-
-    def run(self, x, packed, relu=False, residual=None, capacity=None, max_workgroups=0, canvas=False):
+    def run(self, x, packed, relu=False, residual=None, capacity=None, max_workgroups=0, canvas=False, rows=True, out16=False):
         """the layer on x with the given pack (its own, or one with a BatchNorm folded in) -> SparseConvTensor, or the
-        (B, c_out * D, H, W) BEV map with canvas=True"""
+        (B, c_out * D, H, W) BEV map with canvas=True. With a 16-bit `sparse_precision` (which `packed` must be of) the layer
+        gathers x.features16 where x has them (and 16 or more channels), x.features otherwise; out16: the output also carries
+        features16 = q(features); rows=False: only those."""
         if self.subm:
             if self.kernel_size != (3, 3, 3) or self.stride != (1, 1, 1):
                 raise NotImplementedError("SubMConv3d is served with kernel 3 and stride 1")
@@ -392,15 +497,27 @@ class _SparseConv(_PackedLayers):
             table = neighbour_table(x, indices, n_out, cap, shape, self.kernel_size, self.stride, self.padding, max_workgroups)
             center = -1
         kw = dict(relu=relu, residual=residual, center_tap=center, max_workgroups=max_workgroups)
+        feats, y16 = x.features, None
+        if self._sparse_precision != "fp32":
+            f16 = x.features16 if self.in_channels >= 16 else None
+            if f16 is not None:
+                feats = None
+            kw.update(precision=self._sparse_precision, features16=f16)
+            if not canvas:
+                kw.update(out16=bool(out16), rows=rows)
+        elif out16 or not rows:
+            raise ValueError("out16 and rows=False belong to a 16-bit sparse_precision")
         if canvas:
             D, H, W = shape
-            bev = torch.empty((x.batch_size, self.out_channels * D, H, W), dtype=torch.float32, device=x.features.device)
-            return conv(x.features, table, n_out, packed, self.in_channels, self.out_channels, x.status, canvas=bev,
+            bev = torch.empty((x.batch_size, self.out_channels * D, H, W), dtype=torch.float32, device=x.indices.device)
+            return conv(feats, table, n_out, packed, self.in_channels, self.out_channels, x.status, canvas=bev,
                         out_indices=indices, canvas_shape=shape, **kw)
-        y = conv(x.features, table, n_out, packed, self.in_channels, self.out_channels, x.status, **kw)
+        y = conv(feats, table, n_out, packed, self.in_channels, self.out_channels, x.status, **kw)
+        if out16:
+            y, y16 = y
         if self.subm:
-            return x.like(y)
-        out = SparseConvTensor(y, indices, shape, x.batch_size, n_out, x.status)
+            return x.like(y, y16)
+        out = SparseConvTensor(y, indices, shape, x.batch_size, n_out, x.status, y16)
         out.sorted = (keys, None)               # emitted in key order
         return out
 
@@ -461,7 +578,7 @@ def _norm(cfg, c):
     return nn.BatchNorm1d(c, eps=cfg.get("eps", 1e-5), momentum=cfg.get("momentum", 0.1))
 
 
-class SparseBasicBlock(_PackedLayers):
+class SparseBasicBlock(_SparseLayers):
     """scn.py:37-80: relu(bn2(conv2(relu(bn1(conv1(x))))) + x); both convolutions are submanifold and have a bias"""
     expansion = 1
 
@@ -479,13 +596,16 @@ class SparseBasicBlock(_PackedLayers):
     def _plan(self):
         return [(self.conv1, self.bn1), (self.conv2, self.bn2)]
 
-    def _pack(self, plan):
-        return [pack_layer(c, bn) for c, bn in plan]
-
     def forward(self, x, max_workgroups=0):
         _refuse_training(self)
         with torch.no_grad():
             p1, p2 = self.packed()
+            if self._sparse_precision != "fp32":
+                if x.features is None:
+                    raise ValueError("the block's residual is its input's float32 rows: the input has none")
+                # conv1's rows are read by conv2 alone: 16-bit only; conv2's are the next residual and the next input
+                out = self.conv1.run(x, p1, relu=True, max_workgroups=max_workgroups, rows=False, out16=True)
+                return self.conv2.run(out, p2, relu=True, residual=x.features, max_workgroups=max_workgroups, out16=True)
             out = self.conv1.run(x, p1, relu=True, max_workgroups=max_workgroups)
             return self.conv2.run(out, p2, relu=True, residual=x.features, max_workgroups=max_workgroups)
 
@@ -499,7 +619,7 @@ class SparseBasicBlock(_PackedLayers):
         return x.like(f if mask is None else torch.where(mask, f, torch.zeros((), dtype=f.dtype, device=f.device)))
 
 
-class SpMiddleResNetFHD(_PackedLayers):
+class SpMiddleResNetFHD(_SparseLayers):
     """scn.py:83-177. forward(voxel_features, coors, batch_size, input_shape, n_voxels=None) -> (bev (B, 128 * D', H', W'),
     {conv1 .. conv4: SparseConvTensor}). n_voxels: a device int64 (1) tensor (VoxelizeResult.n_pillars), the rows in use;
     without it every row is a voxel. `capacities`: {"conv2" | "conv3" | "conv4" | "extra_conv": rows} for the strided
@@ -531,9 +651,6 @@ class SpMiddleResNetFHD(_PackedLayers):
     def _plan(self):
         return [(getattr(self, s)[0], getattr(self, s)[1]) for s in self.STEMS]
 
-    def _pack(self, plan):
-        return [pack_layer(c, bn) for c, bn in plan]
-
     def forward(self, voxel_features, coors, batch_size, input_shape, n_voxels=None, capacities=None, max_workgroups=0):
         _refuse_training(self)
         with torch.no_grad():
@@ -545,13 +662,15 @@ class SpMiddleResNetFHD(_PackedLayers):
             caps = dict(self.capacities or {}, **(capacities or {}))
             packs = dict(zip(self.STEMS, self.packed()))
             kw = dict(max_workgroups=max_workgroups)
-            x = self.conv_input[0].run(x, packs["conv_input"], relu=True, **kw)
+            # on 16-bit operands a stem writes its float32 rows (the next residual) and their 16-bit twin (the next input)
+            stem = dict(kw, out16=True) if self._sparse_precision != "fp32" else kw
+            x = self.conv_input[0].run(x, packs["conv_input"], relu=True, **stem)
             out = {}
             for name in ("conv1", "conv2", "conv3", "conv4"):
                 seq = getattr(self, name)
                 blocks = list(seq)
                 if name != "conv1":
-                    x = seq[0].run(x, packs[name], relu=True, capacity=caps.get(name), **kw)
+                    x = seq[0].run(x, packs[name], relu=True, capacity=caps.get(name), **stem)
                     blocks = blocks[3:]
                 for b in blocks:
                     x = b(x, **kw)

@@ -537,6 +537,15 @@ class TwoStageDetector(nn.Module):
     def precision(self, value):
         self.single_det.precision = value
 
+    @property
+    def sparse_precision(self):
+        """`single_det.sparse_precision`: the first stage's sparse 3-D middle on 'fp32' | 'fp16' | 'bf16' MFMA operands"""
+        return self.single_det.sparse_precision
+
+    @sparse_precision.setter
+    def sparse_precision(self, value):
+        self.single_det.sparse_precision = value
+
     def post(self):
         if self._post is None or self._post[0] is not self.test_cfg:
             self._post = (self.test_cfg, CenterHeadPost(self.test_cfg, self.bbox_head.num_classes))

@@ -1155,6 +1155,59 @@ size_t dal3_sp_conv_pack_floats(int taps, int c_in, int c_out);
 int dal3_sp_conv_pack(const dal3_layer* layer, int taps, double eps, float* out, int32_t* status, dal3_stream stream);
 int dal3_sp_conv(const dal3_sp_conv_args* args, dal3_stream stream);
 
+/* The same convolutions on 16-bit MFMA operands (v_mfma_f32_32x32x16_f16 / _bf16; additions only, nothing above changes;
+ * the bookkeeping entries serve both). dtype is DAL3_F16 or DAL3_BF16 at both entries; anything else returns DAL3_EINVAL
+ * and nothing is launched. The arithmetic is the dense stage's contract (above dal3_conv2d_lp_args) applied to
+ * dal3_sp_conv's definition; q is one rounding to the 16-bit type, to nearest even:
+ *   - W' of the fold (float64, rounded once to float32) is rounded once more, with q, by dal3_sp_conv_lp_pack; b' stays
+ *     float32;
+ *   - every gathered input activation is q(x). It comes one of two ways: from float32 rows `x`, rounded as they are
+ *     staged, or from 16-bit rows `x16` that the producing layer stored through its `y16` = q(y), y being its float32
+ *     result after residual and ReLU. Both hold the same values, so both give THE SAME OUTPUT BITS;
+ *   - the products are summed in the MFMA's float32 accumulator; the order is not part of the definition, but the bits
+ *     depend on neither the grid, max_workgroups nor the capacities, and there are no floating-point atomics;
+ *   - the residual is float32 rows, unrounded; b', the residual, ReLU (keeps a NaN, -0 -> +0), the center_tap rule
+ *     (absent -> row +0) and the canvas store are float32 and behave as in dal3_sp_conv;
+ *   - an absent neighbour contributes exactly zero; a NaN or Inf feature reaches exactly the outputs whose receptive
+ *     field holds it.
+ * Range: DAL3_F16 turns an activation with |x| > 65504 into an infinity: outside the contract, as for the dense stage. A
+ * folded weight that is not finite AFTER q marks the pack and sets DAL3_SP_BAD_WEIGHT in *status (optional); dal3_sp_conv_lp
+ * on such a pack writes nothing and sets the same bit. Pack time does not synchronise.
+ * Widths: dal3_sp_conv_pack's. packed: dal3_sp_conv_lp_pack_bytes(taps, c_in, c_out) bytes (0 for bad arguments), 16-byte
+ * aligned, the same for both types: [64 words, the first one the flag | float32 b' of every out tile of 32 | 1 KiB
+ * fragments by tap, 16 input channels and out tile]. A blob packed as one type must be run as that type.
+ * The struct is dal3_sp_conv_args plus dtype, x16 and y16. Exactly one of x and x16 is non-NULL; x16 rows have c_in 16-bit
+ * elements, are 16-byte aligned and need c_in 16, 32, 64 or 128 (c_in 1 .. 8 comes as float32 x only, zero-padded to one
+ * k-step). y (float32 rows), y16 (c_out 16-bit elements a row, = q(y) exactly) and canvas are each optional; at least one
+ * must be given. Bad combinations return DAL3_EINVAL and nothing is launched. */
+typedef struct dal3_sp_conv_lp_args {
+    int32_t taps, c_in, c_out, relu;
+    int32_t center_tap;                  /* -1, or the tap whose absence makes a row +0 */
+    int32_t reserved;                    /* 0 */
+    int64_t in_capacity;
+    const float* x;                      /* (in_capacity, c_in) float32, or NULL with x16 */
+    int64_t out_capacity;
+    const int64_t* n_out;                /* optional device (1) */
+    const int32_t* table;                /* (taps, out_capacity) */
+    const void* packed;                  /* dal3_sp_conv_lp_pack's */
+    const float* residual;               /* optional (out_capacity, c_out) float32 */
+    float* y;                            /* optional (out_capacity, c_out) */
+    float* canvas;                       /* optional (canvas_B, c_out * D, H, W) */
+    const int32_t* out_indices;          /* (out_capacity, 4), with a canvas */
+    int64_t canvas_B;
+    int32_t canvas_shape[3];             /* D, H, W */
+    int32_t reserved2;                   /* 0 */
+    int32_t* status;                     /* (1) OR-ed */
+    int64_t max_workgroups;
+    int32_t dtype;                       /* DAL3_F16 | DAL3_BF16: what packed was packed as */
+    const void* x16;                     /* (in_capacity, c_in) 16-bit, or NULL with x */
+    void* y16;                           /* optional (out_capacity, c_out) 16-bit */
+} dal3_sp_conv_lp_args;
+
+size_t dal3_sp_conv_lp_pack_bytes(int taps, int c_in, int c_out);
+int dal3_sp_conv_lp_pack(const dal3_layer* layer, int taps, double eps, int dtype, void* out, int32_t* status, dal3_stream stream);
+int dal3_sp_conv_lp(const dal3_sp_conv_lp_args* args, dal3_stream stream);
+
 /* ---- the backward pass of the sparse convolutions (training the backbone).
  *
  * The data gradient needs no entry of its own: dx[j] = sum over taps k of dy[inv[k][j]] . W[k]^T is dal3_sp_conv with
