@@ -250,6 +250,22 @@ class Conv2dLpArgs(C.Structure):
                 ("packed", vp)]
 
 
+CONV2D_WGRAD_SLICE = 4096                       # DAL3_CONV2D_WGRAD_SLICE: the pixels of one partial sum of dal3_conv2d_wgrad
+
+
+class Conv2dDgradArgs(C.Structure):
+    """dal3_conv2d_dgrad_args"""
+    _fields_ = [("kind", C.c_int32), ("stride", C.c_int32), ("c_in", C.c_int32), ("c_out", C.c_int32), ("max_workgroups", C.c_int32),
+                ("reserved", C.c_int32), ("B", C.c_int64), ("H", C.c_int64), ("W", C.c_int64), ("dy", Map), ("dx", Map), ("packed", vp)]
+
+
+class Conv2dWgradArgs(C.Structure):
+    """dal3_conv2d_wgrad_args"""
+    _fields_ = [("kind", C.c_int32), ("stride", C.c_int32), ("c_in", C.c_int32), ("c_out", C.c_int32), ("max_workgroups", C.c_int32),
+                ("reserved", C.c_int32), ("B", C.c_int64), ("H", C.c_int64), ("W", C.c_int64), ("x", Map), ("dy", Map), ("dw", vp),
+                ("db", vp), ("workspace", vp), ("workspace_bytes", C.c_size_t)]
+
+
 SP_OVERFLOW, SP_BAD_COORD, SP_DUPLICATE, SP_BAD_WEIGHT = 256, 512, 1024, 2048
 _i3 = C.c_int32 * 3
 
@@ -486,6 +502,11 @@ SIGNATURES = {
     "dal3_conv2d_lp_pack_bytes": (_sz, [_i, _i, _i]),
     "dal3_conv2d_lp_pack": (_i, [C.POINTER(Layer), _i, C.c_double, _i, vp, vp]),
     "dal3_conv2d_lp": (_i, [C.POINTER(Conv2dLpArgs), vp]),
+    "dal3_conv2d_dgrad_pack_floats": (_sz, [_i, _i, _i]),
+    "dal3_conv2d_dgrad_pack": (_i, [vp, _i, _i, _i, vp, vp]),
+    "dal3_conv2d_dgrad": (_i, [C.POINTER(Conv2dDgradArgs), vp]),
+    "dal3_conv2d_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i64, _i64, _i64]),
+    "dal3_conv2d_wgrad": (_i, [C.POINTER(Conv2dWgradArgs), vp]),
     "dal3_sp_sort_workspace_bytes": (_sz, [_i64]),
     "dal3_sp_sort": (_i, [C.POINTER(SpSortArgs), vp]),
     "dal3_sp_downsample_workspace_bytes": (_sz, [_i64, _i]),

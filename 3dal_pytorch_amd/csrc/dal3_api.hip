@@ -1370,6 +1370,82 @@ extern "C" int dal3_conv2d_lp(const dal3_conv2d_lp_args* args, dal3_stream strea
     return 0;
 }
 
+// ... and their backward pass (dal3_conv2d_train.hip)
+static bool conv2d_dgrad_kind_ok(int kind) { return kind == DAL3_CONV2D_3X3 || kind == DAL3_CONV2D_DECONV2 || kind == DAL3_CONV2D_DECONV4; }
+static bool conv2d_width_ok(int c) { return c >= 1 && c <= 4096; }
+static bool conv2d_extent_ok(int64_t v) { return v >= 0 && v <= 65535; }
+
+extern "C" size_t dal3_conv2d_dgrad_pack_floats(int kind, int c_in, int c_out) {
+    if (!conv2d_dgrad_kind_ok(kind) || !conv2d_width_ok(c_in) || !conv2d_width_ok(c_out)) return 0;
+    return conv2d_dgrad_pack_floats(kind, c_in, c_out);
+}
+
+extern "C" int dal3_conv2d_dgrad_pack(const float* weight, int kind, int c_in, int c_out, float* out, dal3_stream stream) {
+    if (!weight || !out) return fail(DAL3_EINVAL, "conv2d_dgrad_pack: null weight / out");
+    if (!conv2d_dgrad_kind_ok(kind))
+        return fail(DAL3_EINVAL, "conv2d_dgrad_pack: kind %d (DAL3_CONV2D_3X3 of stride 2, _DECONV2 or _DECONV4: the other forms' data "
+                    "gradient is dal3_conv2d on the transposed pack)", kind);
+    if (!conv2d_width_ok(c_in) || !conv2d_width_ok(c_out)) return fail(DAL3_EINVAL, "conv2d_dgrad_pack: bad c_in / c_out (1 .. 4096)");
+    if (reinterpret_cast<uintptr_t>(out) & 15) return fail(DAL3_EINVAL, "conv2d_dgrad_pack: out must be 16-byte aligned");
+    HIP_TRY(launch_conv2d_dgrad_pack(weight, kind, c_in, c_out, out, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+extern "C" int dal3_conv2d_dgrad(const dal3_conv2d_dgrad_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "conv2d_dgrad: null args");
+    const dal3_conv2d_dgrad_args& a = *args;
+    if (!conv2d_dgrad_kind_ok(a.kind))
+        return fail(DAL3_EINVAL, "conv2d_dgrad: kind %d (DAL3_CONV2D_3X3 of stride 2, _DECONV2 or _DECONV4: the other forms' data gradient "
+                    "is dal3_conv2d on the transposed pack)", (int)a.kind);
+    if (a.stride != (a.kind == DAL3_CONV2D_DECONV4 ? 4 : 2))
+        return fail(DAL3_EINVAL, "conv2d_dgrad: stride %d (3x3: 2; a transposed convolution: its kernel size, 2 or 4)", (int)a.stride);
+    if (a.max_workgroups < 0 || a.reserved) return fail(DAL3_EINVAL, "conv2d_dgrad: bad max_workgroups (>= 0) / reserved");
+    if (!conv2d_width_ok(a.c_in) || !conv2d_width_ok(a.c_out)) return fail(DAL3_EINVAL, "conv2d_dgrad: bad c_in / c_out (1 .. 4096)");
+    if (!conv2d_extent_ok(a.B) || !conv2d_extent_ok(a.H) || !conv2d_extent_ok(a.W)) return fail(DAL3_EINVAL, "conv2d_dgrad: bad B / H / W (0 .. 65535)");
+    if (a.kind != DAL3_CONV2D_3X3 && (a.H * a.stride > 65535 || a.W * a.stride > 65535))
+        return fail(DAL3_EINVAL, "conv2d_dgrad: dy's extent exceeds 65535");
+    if (!a.dy.data || !a.dx.data) return fail(DAL3_EINVAL, "conv2d_dgrad: null dy / dx");
+    if (!a.packed || (reinterpret_cast<uintptr_t>(a.packed) & 15)) return fail(DAL3_EINVAL, "conv2d_dgrad: packed is null or not 16-byte aligned");
+    HIP_TRY(launch_conv2d_dgrad(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+static bool conv2d_wgrad_form_ok(int kind, int stride) {
+    if (!conv2d_kind_ok(kind)) return false;
+    const int want = kind == DAL3_CONV2D_DECONV2 ? 2 : kind == DAL3_CONV2D_DECONV4 ? 4 : 1;
+    return stride == want || (kind == DAL3_CONV2D_3X3 && stride == 2);
+}
+
+extern "C" size_t dal3_conv2d_wgrad_workspace_bytes(int kind, int stride, int c_in, int c_out, int64_t B, int64_t H, int64_t W) {
+    if (!conv2d_wgrad_form_ok(kind, stride) || !conv2d_width_ok(c_in) || !conv2d_width_ok(c_out) || !conv2d_extent_ok(B) ||
+        !conv2d_extent_ok(H) || !conv2d_extent_ok(W))
+        return 0;
+    return conv2d_wgrad_workspace_bytes(kind, stride, c_in, c_out, B, H, W);
+}
+
+extern "C" int dal3_conv2d_wgrad(const dal3_conv2d_wgrad_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "conv2d_wgrad: null args");
+    const dal3_conv2d_wgrad_args& a = *args;
+    if (!conv2d_wgrad_form_ok(a.kind, a.stride))
+        return fail(DAL3_EINVAL, "conv2d_wgrad: kind %d with stride %d (3x3: 1 or 2; 1x1: 1; a transposed convolution: its kernel size, 2 or 4)",
+                    (int)a.kind, (int)a.stride);
+    if (a.max_workgroups < 0 || a.reserved) return fail(DAL3_EINVAL, "conv2d_wgrad: bad max_workgroups (>= 0) / reserved");
+    if (!conv2d_width_ok(a.c_in) || !conv2d_width_ok(a.c_out)) return fail(DAL3_EINVAL, "conv2d_wgrad: bad c_in / c_out (1 .. 4096)");
+    if (!conv2d_extent_ok(a.B) || !conv2d_extent_ok(a.H) || !conv2d_extent_ok(a.W)) return fail(DAL3_EINVAL, "conv2d_wgrad: bad B / H / W (0 .. 65535)");
+    if (a.kind >= DAL3_CONV2D_DECONV2 && (a.H * a.stride > 65535 || a.W * a.stride > 65535))
+        return fail(DAL3_EINVAL, "conv2d_wgrad: dy's extent exceeds 65535");
+    if (!a.dw) return fail(DAL3_EINVAL, "conv2d_wgrad: null dw");
+    if (a.B > 0 && a.H > 0 && a.W > 0) {
+        if (!a.x.data || !a.dy.data) return fail(DAL3_EINVAL, "conv2d_wgrad: null x / dy");
+        if (!a.workspace) return fail(DAL3_EINVAL, "conv2d_wgrad: null workspace");
+        if (a.workspace_bytes < conv2d_wgrad_workspace_bytes(a.kind, a.stride, a.c_in, a.c_out, a.B, a.H, a.W))
+            return fail(DAL3_EWORKSPACE, "conv2d_wgrad: workspace too small (dal3_conv2d_wgrad_workspace_bytes)");
+        if (reinterpret_cast<uintptr_t>(a.workspace) & 7) return fail(DAL3_EINVAL, "conv2d_wgrad: workspace must be 8-byte aligned");
+    }
+    HIP_TRY(launch_conv2d_wgrad(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------- the sparse 3-D middle
 static int sp_grid_ok(const char* who, int64_t B, const int32_t* shape) {
     if (B < 1 || B > 65535) return fail(DAL3_EINVAL, "%s: bad B (1 .. 65535)", who);

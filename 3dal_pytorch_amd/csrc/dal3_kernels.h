@@ -379,6 +379,12 @@ hipError_t launch_conv2d(const dal3_conv2d_args* a, hipStream_t s);
 size_t conv2d_lp_pack_bytes(int kind, int c_in, int c_out);
 hipError_t launch_conv2d_lp_pack(const FoldLayer& layer, int kind, int dtype, void* out, hipStream_t s);
 hipError_t launch_conv2d_lp(const dal3_conv2d_lp_args* a, hipStream_t s);
+// ... and their backward pass (dal3_conv2d_train.hip); the arguments are checked by the caller
+size_t conv2d_dgrad_pack_floats(int kind, int c_in, int c_out);
+hipError_t launch_conv2d_dgrad_pack(const float* weight, int kind, int c_in, int c_out, float* out, hipStream_t s);
+hipError_t launch_conv2d_dgrad(const dal3_conv2d_dgrad_args* a, hipStream_t s);
+size_t conv2d_wgrad_workspace_bytes(int kind, int stride, int c_in, int c_out, int64_t B, int64_t H, int64_t W);
+hipError_t launch_conv2d_wgrad(const dal3_conv2d_wgrad_args* a, hipStream_t s);
 // the VoxelNet detector's sparse 3-D middle (dal3_spconv.hip): site bookkeeping on the chunked radix sort, gather-GEMM convolutions
 size_t sp_sort_workspace_bytes(int64_t capacity);
 hipError_t launch_sp_sort(const dal3_sp_sort_args* a, hipStream_t s);

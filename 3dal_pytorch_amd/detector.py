@@ -12,8 +12,8 @@ the current stream; the read-back of the kept boxes inside `predict` is the only
 `detect` makes the views itself. The loss is not built: `return_loss=True` is refused. `VoxelNet` has the same two doors
 with the 3-D grid, VoxelFeatureExtractorV3 and the sparse middle (sparse.SpMiddleResNetFHD) in front of the neck.
 `VoxelNet.first_stage_loss(example)` is the training step up to the loss: the reader, the backbone's differentiable
-`train_forward`, the neck's and the head's stock-torch routes and `CenterHead.loss` (`forward(return_loss=True)` stays
-refused). `forward_two_stage` stays refused: the two-stage model is two_stage.TwoStageDetector, which wraps either detector, runs
+`train_forward`, the neck's and the head's stock-torch routes (or, with `dense="hip"`, their `train_forward` on the HIP
+convolution kernels) and `CenterHead.loss` (`forward(return_loss=True)` stays refused). `forward_two_stage` stays refused: the two-stage model is two_stage.TwoStageDetector, which wraps either detector, runs
 its stages up to the head itself and keeps the kept boxes on the device for the RoI head.
 """
 import torch
@@ -26,6 +26,7 @@ READERS = {"PillarFeatureNet": pillars.PillarFeatureNet, "VoxelFeatureExtractorV
 BACKBONES = {"PointPillarsScatter": pillars.PointPillarsScatter, "SpMiddleResNetFHD": sparse.SpMiddleResNetFHD}
 NECKS = {"RPN": rpn.RPN}
 HEADS = {"CenterHead": rpn.CenterHead}
+DENSE_ROUTES = ("composite", "hip")             # how the neck and the head train (VoxelNet.first_stage_loss)
 
 
 def _build(cfg, table, what):
@@ -181,28 +182,33 @@ class VoxelNet(SingleStageDetector):
         x, _ = self.extract_feat(data)
         return self.bbox_head.predict(example, self.bbox_head(x), self.test_cfg)
 
-    def first_stage_loss(self, example):
-        """the first stage's training step up to its loss: reader -> backbone.train_forward -> the neck's and the head's
-        stock-torch composite routes (BatchNorm by its mode) -> CenterHead.loss. example: the voxeliser's entries (voxels,
-        coordinates, num_points, num_voxels, shape; optionally n_voxels, the device count of a capacity-sized batch) and
-        the lists of center_loss.center_targets -> CenterHead.loss's dictionary; `loss` carries the graph to every
-        parameter of the backbone, the neck and the head."""
+    def first_stage_loss(self, example, dense="composite"):
+        """the first stage's training step up to its loss: reader -> backbone.train_forward -> the neck and the head
+        (BatchNorm by its mode) -> CenterHead.loss. dense: the neck's and the head's route, "composite" (the default:
+        stock torch ops and stock autograd) | "hip" (their `train_forward`: every convolution and its backward on the HIP
+        kernels, float32 whatever `precision` says). example: the voxeliser's entries (voxels, coordinates, num_points,
+        num_voxels, shape; optionally n_voxels, the device count of a capacity-sized batch) and the lists of
+        center_loss.center_targets -> CenterHead.loss's dictionary; `loss` carries the graph to every parameter of the
+        backbone, the neck and the head."""
+        if dense not in DENSE_ROUTES:
+            raise ValueError(f"dense {dense!r}: the neck and the head train through 'composite' (stock torch) or 'hip'")
         n_voxels = example.get("n_voxels")
         feats = self.reader(example["voxels"], example["num_points"], n_pillars=n_voxels)
         x, _ = self.backbone.train_forward(feats, example["coordinates"], len(example["num_voxels"]), example["shape"][0],
                                            n_voxels=n_voxels, capacities=self.sparse_capacities)
+        hip = dense == "hip"
         if self.with_neck:
-            x = self.neck.composite(x)
-        return self.bbox_head.loss(example, self.bbox_head.composite(x))
+            x = self.neck.train_forward(x) if hip else self.neck.composite(x)
+        return self.bbox_head.loss(example, self.bbox_head.train_forward(x) if hip else self.bbox_head.composite(x))
 
     def set_train_input(self, preprocess, assigner):
         """the stages `train_step_from_sweeps` feeds the loss with: an augment.Preprocess and a center_loss.AssignLabel"""
         self.train_input = (preprocess, assigner)
 
-    def train_step_from_sweeps(self, points, point_offsets, annotations, draws=None):
+    def train_step_from_sweeps(self, points, point_offsets, annotations, draws=None, dense="composite"):
         """resident sweeps and annotations -> CenterHead.loss's dictionary, on the current stream with no host
         synchronisation: augment.train_example (GT paste, augmentation, shuffle; voxelisation; AssignLabel) and then
-        first_stage_loss. points (N, F) float32 CUDA, point_offsets (B + 1) on the host, annotations: {gt_boxes (B, max_gt, 9)
+        first_stage_loss (`dense`: its route for the neck and the head). points (N, F) float32 CUDA, point_offsets (B + 1) on the host, annotations: {gt_boxes (B, max_gt, 9)
         CUDA, gt_classes, gt_counts} as augment.Preprocess takes them; draws: the step's augment.Draws (None: drawn on the
         device). `last_example` keeps the example."""
         if getattr(self, "train_input", None) is None:
@@ -216,7 +222,7 @@ class VoxelNet(SingleStageDetector):
                                         max_points=self.max_points, max_voxels=self.max_voxels, draws=draws,
                                         candidates=annotations.get("candidates"))
         self.last_example = example
-        return self.first_stage_loss(example)
+        return self.first_stage_loss(example, dense=dense)
 
     def forward_two_stage(self, example, return_loss=False, **kwargs):
         raise NotImplementedError("VoxelNet.forward_two_stage: the second stage is not built into this method: two_stage."

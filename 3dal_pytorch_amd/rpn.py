@@ -14,6 +14,11 @@ sizes). There is no quiet fallback on the GPU route: a module that `hip_serves()
 `precision` on `RPN` and `CenterHead` ("fp32", the default, | "fp16" | "bf16") picks the MFMA operand type of that kernel
 route: with a 16-bit one every layer runs dal3_conv2d_lp on weights rounded once at pack time and activations rounded as
 they are staged, accumulating in fp32; the maps stay float32 either way.
+
+`RPN.train_forward` / `CenterHead.train_forward` are `composite()`'s graph with every convolution on the HIP kernels, forward
+and backward (`_Conv2dFunction`: dal3_conv2d on the raw pack, dal3_conv2d_dgrad, dal3_conv2d_wgrad), float32, BatchNorm /
+ReLU / torch.cat stock: the opt-in training route (`dense="hip"` of detector.VoxelNet.first_stage_loss). `forward()` in train
+mode stays the composite.
 """
 import copy
 
@@ -154,6 +159,160 @@ def conv2d(x, packed, kind, stride, relu, c_out, out=None, channel_offset=0, max
         else:
             _hip.check(lib.dal3_conv2d(_hip.Conv2dArgs(**fields), _hip.stream()))
     return out[:, channel_offset:channel_offset + c_out]
+
+
+# ------------------------------------------------------------------------------------- training: the backward pass
+_DECONVS = (_hip.CONV2D_DECONV2, _hip.CONV2D_DECONV4)
+
+
+def layer_widths(weight, kind):
+    """(c_in, c_out) of a Conv2d's (c_out, c_in, k, k) or a ConvTranspose2d's (c_in, c_out, s, s) weight"""
+    return (weight.shape[0], weight.shape[1]) if kind in _DECONVS else (weight.shape[1], weight.shape[0])
+
+
+def _check_map(t, what, shape=None):
+    if not torch.is_tensor(t):
+        raise TypeError(f"{what} must be a tensor")
+    _hip.require_gpu(t, what)
+    if t.dim() != 4 or t.dtype != torch.float32 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise ValueError(f"{what} must be float32 {'(B, C, H, W)' if shape is None else tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+
+
+def pack_raw(weight, bias, kind, c_in, c_out):
+    """dal3_conv2d_pack without a fold: a contiguous float32 weight of c_in -> c_out in the form's own layout, its bias or None"""
+    for t in (weight, bias):
+        if t is not None:
+            _hip.require_gpu(t, "the layer's parameters")
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise RuntimeError("weights must be contiguous fp32")
+    lib = _hip.lib()
+    L = _hip.Layer(_hip.ptr(weight), _hip.ptr(bias), None, None, None, None, c_in, c_out)
+    buf = torch.empty(lib.dal3_conv2d_pack_floats(kind, c_in, c_out), dtype=torch.float32, device=weight.device)
+    _hip.check(lib.dal3_conv2d_pack(L, kind, 1e-5, _hip.ptr(buf), _hip.stream()))
+    return buf
+
+
+def conv2d_dgrad(dy, weight, kind, stride, in_size, out=None, max_workgroups=0):
+    """the data gradient of one layer: dy (B, c_out, OH, OW) float32 CUDA of any strides and the layer's weight -> dx
+    (B, c_in, H, W), in_size = (H, W) (a stride-2 layer's output does not determine it). `out`: a (B, c_in, H, W) view to
+    write (allocated with torch.empty when None; every element is written). 3x3 of stride 1 and 1x1 are dal3_conv2d on the
+    transposed pack; 3x3 of stride 2 and the transposed convolutions are dal3_conv2d_dgrad. Enqueued on the current stream."""
+    c_in, c_out = layer_widths(weight, kind)
+    H, W = in_size
+    B = dy.shape[0] if torch.is_tensor(dy) and dy.dim() == 4 else 0
+    _check_map(dy, "dy", (B, c_out, *out_size(kind, stride, H, W)))
+    if out is None:
+        out = torch.empty((B, c_in, H, W), dtype=torch.float32, device=dy.device)
+    _check_map(out, "out", (B, c_in, H, W))
+    w = weight.detach()
+    if kind == _hip.CONV2D_1X1 or (kind == _hip.CONV2D_3X3 and stride == 1):
+        wt = (w.flip(2, 3) if kind == _hip.CONV2D_3X3 else w).transpose(0, 1).contiguous()
+        conv2d(dy, pack_raw(wt, None, kind, c_out, c_in), kind, 1, False, c_in, out=out, max_workgroups=max_workgroups)
+        return out
+    lib = _hip.lib()
+    w = w.contiguous()
+    _hip.require_gpu(w, "the layer's weight")
+    packed = torch.empty(lib.dal3_conv2d_dgrad_pack_floats(kind, c_in, c_out), dtype=torch.float32, device=dy.device)
+    _hip.check(lib.dal3_conv2d_dgrad_pack(_hip.ptr(w), kind, c_in, c_out, _hip.ptr(packed), _hip.stream()))
+    if B and H and W:
+        a = _hip.Conv2dDgradArgs(kind=kind, stride=stride, c_in=c_in, c_out=c_out, max_workgroups=int(max_workgroups), B=B, H=H, W=W,
+                                 dy=_nchw_map(dy), dx=_nchw_map(out), packed=_hip.ptr(packed))
+        _hip.check(lib.dal3_conv2d_dgrad(a, _hip.stream()))
+    return out
+
+
+def conv2d_wgrad_workspace_bytes(kind, stride, c_in, c_out, B, H, W):
+    return _hip.lib().dal3_conv2d_wgrad_workspace_bytes(kind, stride, c_in, c_out, B, H, W)
+
+
+def conv2d_wgrad(x, dy, kind, stride, weight_shape, bias=True, dw=None, db=None, max_workgroups=0):
+    """one dal3_conv2d_wgrad call: the layer's input x (B, c_in, H, W) and the incoming gradient dy (B, c_out, OH, OW), float32
+    CUDA of any strides -> (dW in the parameter's own layout, db (c_out) or None). `dw` / `db`: contiguous tensors to write
+    (allocated when None)."""
+    weight_shape = tuple(weight_shape)
+    c_in, c_out = (weight_shape[0], weight_shape[1]) if kind in _DECONVS else (weight_shape[1], weight_shape[0])
+    _check_map(x, "x")
+    B, _, H, W = x.shape
+    _check_map(x, "x", (B, c_in, H, W))
+    _check_map(dy, "dy", (B, c_out, *out_size(kind, stride, H, W)))
+    dev, lib = x.device, _hip.lib()
+    if dw is None:
+        dw = torch.empty(weight_shape, dtype=torch.float32, device=dev)
+    if db is None and bias:
+        db = torch.empty(c_out, dtype=torch.float32, device=dev)
+    for t, shape in ((dw, weight_shape), (db, (c_out,))):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape or t.device != dev):
+            raise ValueError(f"a gradient buffer must be contiguous float32 {shape} on {dev}, got {t.dtype} {tuple(t.shape)}")
+    nbytes = lib.dal3_conv2d_wgrad_workspace_bytes(kind, stride, c_in, c_out, B, H, W)
+    ws = _hip.workspace(nbytes, dev)
+    a = _hip.Conv2dWgradArgs(kind=kind, stride=stride, c_in=c_in, c_out=c_out, max_workgroups=int(max_workgroups), B=B, H=H, W=W,
+                             x=_nchw_map(x), dy=_nchw_map(dy), dw=_hip.ptr(dw), db=_hip.ptr(db if bias else None),
+                             workspace=_hip.ptr(ws), workspace_bytes=nbytes)
+    _hip.check(lib.dal3_conv2d_wgrad(a, _hip.stream()))
+    return dw, (db if bias else None)
+
+
+class _Conv2dFunction(torch.autograd.Function):
+    """y = dal3_conv2d(x; weight, bias) on the raw pack (no fold, no ReLU). The backward: dx by the form's route
+    (conv2d_dgrad), (dW, db) through dal3_conv2d_wgrad; each is skipped when nothing asks for it. The maps are read through
+    their strides, nothing synchronises and everything is enqueued on the current stream."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, kind, stride, max_workgroups):
+        c_in, c_out = layer_widths(weight, kind)
+        packed = pack_raw(weight.detach(), None if bias is None else bias.detach(), kind, c_in, c_out)
+        y = conv2d(x, packed, kind, stride, False, c_out, max_workgroups=max_workgroups)
+        ctx.save_for_backward(x, weight)
+        ctx.form, ctx.has_bias = (kind, stride, max_workgroups), bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        kind, stride, mw = ctx.form
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = conv2d_dgrad(dy, weight, kind, stride, x.shape[2:], max_workgroups=mw)
+        want_db = ctx.has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1] or want_db:
+            dw, db = conv2d_wgrad(x, dy, kind, stride, weight.shape, bias=want_db, max_workgroups=mw)
+        return dx, dw, db, None, None, None
+
+
+def conv2d_train(x, conv, max_workgroups=0):
+    """an nn.Conv2d / nn.ConvTranspose2d that dal3_conv2d serves (layer_kind), differentiable on the HIP kernels"""
+    form = layer_kind(conv)
+    if form is None:
+        raise NotImplementedError(f"{conv}: dal3_conv2d serves Conv 3x3 of stride 1 or 2, Conv 1x1 and ConvTranspose k = s in (2, 4)")
+    return _Conv2dFunction.apply(x, conv.weight, conv.bias, form[0], form[1], int(max_workgroups))
+
+
+def _train_sequence(seq, x, max_workgroups):
+    """a reference Sequential in training: every convolution through _Conv2dFunction (which pads a 3x3 itself: a
+    ZeroPad2d in front of it is skipped, as `_split` does), every norm layer as the stock module, ReLU stock"""
+    for m in seq:
+        if isinstance(m, (nn.Conv2d, nn.ConvTranspose2d)):
+            x = conv2d_train(x, m, max_workgroups)
+        elif isinstance(m, nn.ReLU):
+            x = torch.relu(x)
+        elif not isinstance(m, nn.ZeroPad2d):
+            x = m(x)
+    return x
+
+
+def _refuse_train_forward(module, sequences, x):
+    """what `train_forward` refuses, in words"""
+    name = type(module).__name__
+    for seq in sequences:
+        for _, bn, _ in _split(seq):
+            if not _norm_ok(bn):
+                raise NotImplementedError(f"{name}.train_forward: the norm layer {bn} is not an affine nn.BatchNorm2d with running statistics")
+    if not module.hip_serves():
+        raise NotImplementedError(f"{name}.train_forward: this configuration has a layer that dal3_conv2d does not serve (hip_serves() is "
+                                  "False): train it through composite()")
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise RuntimeError(f"{name}.train_forward runs only on the GPU through lib3dal_hip.so (x lives on "
+                           f"{x.device if torch.is_tensor(x) else type(x).__name__}); composite() is the stock-torch route")
 
 
 def conv2d_flop(kind, stride, c_in, c_out, H, W, B=1):
@@ -331,6 +490,20 @@ class RPN(_DenseLayers):
                 ups.append(self.deblocks[i - self._upsample_start_idx](x))
         return torch.cat(ups, dim=1) if ups else x
 
+    def train_forward(self, x, max_workgroups=0):
+        """composite()'s graph with every convolution on the HIP kernels (_Conv2dFunction: dal3_conv2d forward, the data and
+        weight gradients of dal3_conv2d_dgrad / dal3_conv2d_wgrad), float32 whatever `precision` says. Every norm layer is
+        called as the stock module, so it acts by its own mode (batch statistics and running-stat updates in train mode,
+        the running statistics when frozen); ReLU and torch.cat are stock. Refuses, in words, a configuration that
+        hip_serves() refuses, a norm layer that is no affine nn.BatchNorm2d with running statistics, and a CPU tensor."""
+        _refuse_train_forward(self, list(self.blocks) + list(self.deblocks), x)
+        ups = []
+        for i, block in enumerate(self.blocks):
+            x = _train_sequence(block, x, max_workgroups)
+            if i - self._upsample_start_idx >= 0:
+                ups.append(_train_sequence(self.deblocks[i - self._upsample_start_idx], x, max_workgroups))
+        return torch.cat(ups, dim=1)
+
     def forward(self, x, max_workgroups=0):
         if self.training or not self.hip_serves():
             return self.composite(x)
@@ -454,6 +627,13 @@ class CenterHead(_DenseLayers):
         """the same definition in stock torch ops (the reference's forward)"""
         x = self.shared_conv(x)
         return [task(x) for task in self.tasks]
+
+    def train_forward(self, x, max_workgroups=0):
+        """composite()'s graph with every convolution on the HIP kernels (RPN.train_forward's contract and refusals) -> one
+        dict per task of (B, c, H, W) maps. The heads' first layers are not fused in training: each is a launch of its own."""
+        _refuse_train_forward(self, self._sequences(), x)
+        x = _train_sequence(self.shared_conv, x, max_workgroups)
+        return [{head: _train_sequence(getattr(task, head), x, max_workgroups) for head in task.heads} for task in self.tasks]
 
     def forward(self, x, *kwargs, max_workgroups=0):
         if self.training or not self.hip_serves():

@@ -1029,6 +1029,83 @@ size_t dal3_conv2d_lp_pack_bytes(int kind, int c_in, int c_out);
 int dal3_conv2d_lp_pack(const dal3_layer* layer, int kind, double eps, int dtype, void* out, dal3_stream stream);
 int dal3_conv2d_lp(const dal3_conv2d_lp_args* args, dal3_stream stream);
 
+/* ---- the backward pass of the dense stage (training the neck and the head), float32. (Additions only.) The forms, the
+ * strides and the limits (B, H, W <= 65535, c_in, c_out <= 4096) are dal3_conv2d's; B, H, W, c_in and c_out are always
+ * those of the layer's FORWARD input x and output y, and dy has y's extent. Every map is float32, read and written through
+ * the element strides of its dal3_map with offsets formed in 64 bits: the gradient of a torch.cat is a channel-slice view
+ * and a channels-last map is read as it lies; no copy of a map is made. Invalid arguments return DAL3_EINVAL and nothing
+ * is launched. Built with IEEE NaN semantics. The order of every sum is a function of the argument shapes alone, there
+ * are no floating-point atomics, and the bits are the same for every max_workgroups and from run to run.
+ *
+ * The forward in train mode needs no entry of its own: it is dal3_conv2d on the raw pack (dal3_conv2d_pack without a
+ * BatchNorm, relu = 0, the convolution's own bias if it has one).
+ *
+ * The data gradient of DAL3_CONV2D_3X3 with stride 1 and of DAL3_CONV2D_1X1 needs no entry of its own either: it is
+ * dal3_conv2d of the same form on x = dy with the pack of the transposed weight (c_in, c_out, k, k), spatially flipped
+ * for 3x3 (W^T[ci,co,ky,kx] = W[co,ci,2-ky,2-kx]), without bias, BatchNorm or ReLU.
+ *
+ * dal3_conv2d_dgrad serves the three forms whose data gradient is no forward form:
+ *   DAL3_CONV2D_3X3, stride 2     dx[b,ci,iy,ix] = sum over co, ky, kx of W[co,ci,ky,kx] * dy[b,co,(iy+1-ky)/2,(ix+1-kx)/2]
+ *                                 over the taps where both divisions are exact and the output pixel exists. By the parity of
+ *                                 (iy, ix) there are four phases of 1, 2, 2 and 4 taps; a workgroup's pixel grid is one
+ *                                 phase's sub-grid, the phase is part of the work index (one launch), and only the taps
+ *                                 that are present are multiplied.
+ *   DAL3_CONV2D_DECONV2 / _DECONV4   dx[b,ci,y,x] = sum over co, dy, dx of W[ci,co,dy,dx] * g[b,co,y*s+dy,x*s+dx]: the 1x1
+ *                                 form with K = c_out * s * s and a pixel-unshuffle load.
+ * Any other form or stride is DAL3_EINVAL. Every element of the (B, c_in, H, W) view dx is written, +0 where nothing
+ * reaches it, and nothing outside it. The sums run on the fp32 MFMA (dx channels on its rows, 32 pixels on its columns)
+ * from +0; the order is not part of the definition. dy and dx must not overlap. No workspace.
+ * packed: dal3_conv2d_dgrad_pack_floats(kind, c_in, c_out) floats (0 for bad arguments), 16-byte aligned, written by
+ * dal3_conv2d_dgrad_pack from the parameter in its own layout ((c_out, c_in, 3, 3), or (c_in, c_out, s, s)), a device
+ * pointer; there is no fold.
+ *
+ * dal3_conv2d_wgrad serves all five form / stride pairs and writes the gradients in the parameter's own layout:
+ *   DAL3_CONV2D_3X3 / _1X1        dw[co,ci,ky,kx] = sum over b, oy, ox of dy[b,co,oy,ox] * x[b,ci,oy*s+ky-1,ox*s+kx-1], zeros
+ *                                 outside the image (1x1: x[b,ci,oy,ox]);
+ *   DAL3_CONV2D_DECONV2 / _DECONV4   dw[ci,co,dy,dx] = sum over b, y, x of x[b,ci,y,x] * g[b,co,y*s+dy,x*s+dx];
+ *   db[co] = the sum of dy[b,co,.,.], added in float64 in a fixed order and rounded once; db may be NULL.
+ * A GEMM on the fp32 MFMA with the pixels as the contraction. The pixel grid (y's for a convolution, x's for a transposed
+ * one) is cut into tiles of 4 rows x TC columns (TC = 16 for DAL3_CONV2D_DECONV4, 32 otherwise), in (b, row, column)
+ * order, and a slice is the DAL3_CONV2D_WGRAD_SLICE / (4 * TC) consecutive tiles that cover at most
+ * DAL3_CONV2D_WGRAD_SLICE pixels. Every (32 x 32 channel tile, kernel row, slice) writes its partial sums to the
+ * workspace and a second kernel adds the slices in ascending slice order. c_out of 1, 2 and 3 and every c_in up to the
+ * limit are served (a tile of 32 channels is zero-padded).
+ * workspace: dal3_conv2d_wgrad_workspace_bytes(kind, stride, c_in, c_out, B, H, W) bytes (0 for bad arguments), 8-byte
+ * aligned: 4 * |dw| * ceil(B * ceil(PH / 4) * ceil(PW / TC) / (DAL3_CONV2D_WGRAD_SLICE / (4 * TC))), (PH, PW) the pixel
+ * grid above, |dw| the parameter's element count. */
+enum { DAL3_CONV2D_WGRAD_SLICE = 4096 };
+
+typedef struct dal3_conv2d_dgrad_args {
+    int32_t kind;                        /* DAL3_CONV2D_3X3 (stride 2), _DECONV2, _DECONV4 */
+    int32_t stride;                      /* 3X3: 2; DECONV2: 2; DECONV4: 4 */
+    int32_t c_in, c_out;                 /* of the layer */
+    int32_t max_workgroups;              /* 0: no cap */
+    int32_t reserved;                    /* 0 */
+    int64_t B, H, W;                     /* of the layer's INPUT, which is dx's */
+    dal3_map dy, dx;
+    const float* packed;                 /* dal3_conv2d_dgrad_pack's */
+} dal3_conv2d_dgrad_args;
+
+typedef struct dal3_conv2d_wgrad_args {
+    int32_t kind;                        /* DAL3_CONV2D_* */
+    int32_t stride;                      /* 3X3: 1 or 2; 1X1: 1; DECONV2: 2; DECONV4: 4 */
+    int32_t c_in, c_out;
+    int32_t max_workgroups;              /* 0: no cap */
+    int32_t reserved;                    /* 0 */
+    int64_t B, H, W;                     /* of the layer's INPUT x */
+    dal3_map x, dy;
+    float* dw;                           /* the weight's own layout, contiguous */
+    float* db;                           /* (c_out), or NULL */
+    void* workspace;
+    size_t workspace_bytes;
+} dal3_conv2d_wgrad_args;
+
+size_t dal3_conv2d_dgrad_pack_floats(int kind, int c_in, int c_out);
+int dal3_conv2d_dgrad_pack(const float* weight, int kind, int c_in, int c_out, float* out, dal3_stream stream);
+int dal3_conv2d_dgrad(const dal3_conv2d_dgrad_args* args, dal3_stream stream);
+size_t dal3_conv2d_wgrad_workspace_bytes(int kind, int stride, int c_in, int c_out, int64_t B, int64_t H, int64_t W);
+int dal3_conv2d_wgrad(const dal3_conv2d_wgrad_args* args, dal3_stream stream);
+
 /* ---- the VoxelNet detector's sparse 3-D middle: SpMiddleResNetFHD (det3d/models/backbones/scn.py), which the reference
  * delegates to spconv 1.x: SubMConv3d (kernel 3), SparseConv3d, BatchNorm1d (folded), ReLU, SparseBasicBlock's residual and
  * the .dense().view(N, C * D, H, W) at the end. float32, eval mode. (Additions only; DAL3_VERSION stays, as for the entries
