@@ -232,6 +232,22 @@ class PillarFeatureArgs(C.Structure):
                 ("canvas_B", C.c_int64), ("ny", C.c_int64), ("nx", C.c_int64), ("max_workgroups", C.c_int64)]
 
 
+PILLAR_TRAIN_SLICE = 128                        # DAL3_PILLAR_TRAIN_SLICE: the pillars of one partial sum of the reader's training step
+PILLAR_TRAIN_SAVED_FLOATS = 512
+_p2 = vp * 2
+
+
+class PillarTrainArgs(C.Structure):
+    """dal3_pillar_train_args"""
+    _fields_ = [("P", C.c_int64), ("n_pillars", vp), ("voxels", vp), ("num_points", vp), ("coordinates", vp), ("C", C.c_int32),
+                ("max_points", C.c_int32), ("n_layers", C.c_int32), ("c_out", C.c_int32), ("vx", C.c_float), ("vy", C.c_float),
+                ("x_offset", C.c_float), ("y_offset", C.c_float), ("layers", C.POINTER(Layer)), ("eps", C.c_double),
+                ("momentum", C.c_double * 2), ("running_mean", _p2), ("running_var", _p2), ("num_batches_tracked", _p2),
+                ("saved", vp), ("features", vp), ("canvas", vp), ("canvas_B", C.c_int64), ("ny", C.c_int64), ("nx", C.c_int64),
+                ("grad", vp), ("grad_stride", C.c_int64 * 4), ("dW", _p2), ("dgamma", _p2), ("dbeta", _p2),
+                ("max_workgroups", C.c_int64), ("workspace", vp), ("workspace_bytes", C.c_size_t)]
+
+
 CONV2D_3X3, CONV2D_1X1, CONV2D_DECONV2, CONV2D_DECONV4 = range(4)
 
 
@@ -494,6 +510,9 @@ SIGNATURES = {
     "dal3_voxelize": (_i, [C.POINTER(VoxelizeArgs), vp]),
     "dal3_pillar_pack": (_i, [C.POINTER(Layer), _i, _i, C.c_double, vp, vp]),
     "dal3_pillar_features": (_i, [C.POINTER(PillarFeatureArgs), vp]),
+    "dal3_pillar_train_workspace_bytes": (_sz, [_i64, _i]),
+    "dal3_pillar_train_forward": (_i, [C.POINTER(PillarTrainArgs), vp]),
+    "dal3_pillar_train_backward": (_i, [C.POINTER(PillarTrainArgs), vp]),
     "dal3_pillar_scatter": (_i, [vp, vp, _i64, vp, _i, vp, _i64, _i64, _i64, vp]),
     "dal3_voxel_mean": (_i, [vp, vp, _i64, vp, _i, _i, vp, vp]),
     "dal3_conv2d_pack_floats": (_sz, [_i, _i, _i]),

@@ -1265,6 +1265,58 @@ extern "C" int dal3_pillar_features(const dal3_pillar_feature_args* args, dal3_s
     return 0;
 }
 
+static int pillar_train_ok(const char* who, const dal3_pillar_train_args& a) {
+    if (a.P < 0 || a.P > DAL3_MAX_ITEMS || a.max_workgroups < 0) return fail(DAL3_EINVAL, "%s: bad P / max_workgroups", who);
+    if (a.C < 3 || a.C > 8 || a.max_points < 1 || a.max_points > 64) return fail(DAL3_EINVAL, "%s: bad C (3 .. 8) / max_points (1 .. 64)", who);
+    if ((a.n_layers != 1 && a.n_layers != 2) || a.c_out != 64) return fail(DAL3_EINVAL, "%s: n_layers 1 or 2, c_out 64", who);
+    if (!a.layers || !(a.eps > 0.0)) return fail(DAL3_EINVAL, "%s: null layers / eps (> 0)", who);
+    const int want_in[2] = {a.C + 5, 64}, want_out[2] = {a.n_layers == 1 ? 64 : 32, 64};
+    for (int i = 0; i < a.n_layers; ++i) {
+        const dal3_layer& L = a.layers[i];
+        if (L.c_in != want_in[i] || L.c_out != want_out[i])
+            return fail(DAL3_EINVAL, "%s: layer %d is %d -> %d, the kernels serve %d -> %d", who, i, (int)L.c_in, (int)L.c_out, want_in[i],
+                        want_out[i]);
+        if (!L.weight || L.bias || !L.bn_weight || !L.bn_bias) return fail(DAL3_EINVAL, "%s: layer %d needs weight, bn_weight, bn_bias and no bias", who, i);
+    }
+    if (!a.saved || (reinterpret_cast<uintptr_t>(a.saved) & 15)) return fail(DAL3_EINVAL, "%s: saved is null or not 16-byte aligned", who);
+    if (a.P > 0 && (!a.voxels || !a.num_points || !a.coordinates)) return fail(DAL3_EINVAL, "%s: null voxels / num_points / coordinates", who);
+    if (!a.workspace || (reinterpret_cast<uintptr_t>(a.workspace) & 7)) return fail(DAL3_EINVAL, "%s: workspace is null or not 8-byte aligned", who);
+    if (a.workspace_bytes < pillar_train_workspace_bytes(a.P, a.n_layers))
+        return fail(DAL3_EWORKSPACE, "%s: workspace too small (dal3_pillar_train_workspace_bytes)", who);
+    return 0;
+}
+
+extern "C" size_t dal3_pillar_train_workspace_bytes(int64_t P, int n_layers) {
+    if (P < 0 || P > DAL3_MAX_ITEMS || (n_layers != 1 && n_layers != 2)) return 0;
+    return pillar_train_workspace_bytes(P, n_layers);
+}
+
+extern "C" int dal3_pillar_train_forward(const dal3_pillar_train_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "pillar_train_forward: null args");
+    const dal3_pillar_train_args& a = *args;
+    TRY(pillar_train_ok("pillar_train_forward", a));
+    for (int i = 0; i < a.n_layers; ++i) {
+        if (!(a.momentum[i] >= 0.0 && a.momentum[i] <= 1.0)) return fail(DAL3_EINVAL, "pillar_train_forward: momentum outside [0, 1]");
+        if (!a.running_mean[i] != !a.running_var[i]) return fail(DAL3_EINVAL, "pillar_train_forward: running_mean and running_var go together");
+    }
+    if (a.canvas) TRY(canvas_ok("pillar_train_forward", a.c_out, a.canvas, a.canvas_B, a.ny, a.nx));
+    else if (a.P > 0 && !a.features) return fail(DAL3_EINVAL, "pillar_train_forward: no output (features and canvas are NULL)");
+    HIP_TRY(launch_pillar_train_forward(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+extern "C" int dal3_pillar_train_backward(const dal3_pillar_train_args* args, dal3_stream stream) {
+    if (!args) return fail(DAL3_EINVAL, "pillar_train_backward: null args");
+    const dal3_pillar_train_args& a = *args;
+    TRY(pillar_train_ok("pillar_train_backward", a));
+    if (a.canvas && (a.canvas_B < 1 || a.ny < 1 || a.nx < 1)) return fail(DAL3_EINVAL, "pillar_train_backward: bad canvas shape");
+    if (a.P > 0 && !a.grad) return fail(DAL3_EINVAL, "pillar_train_backward: null grad");
+    for (int i = 0; i < a.n_layers; ++i)
+        if (!a.dW[i] || !a.dgamma[i] || !a.dbeta[i]) return fail(DAL3_EINVAL, "pillar_train_backward: null dW / dgamma / dbeta of layer %d", i);
+    HIP_TRY(launch_pillar_train_backward(args, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 extern "C" int dal3_pillar_scatter(const float* features, const int32_t* coordinates, int64_t P, const int64_t* n_pillars, int c_out,
                                    float* canvas, int64_t canvas_B, int64_t ny, int64_t nx, dal3_stream stream) {
     if (P < 0 || P > DAL3_MAX_ITEMS || c_out < 1 || c_out > 4096) return fail(DAL3_EINVAL, "pillar_scatter: bad P / c_out");

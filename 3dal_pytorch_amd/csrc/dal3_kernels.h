@@ -370,6 +370,10 @@ hipError_t launch_pillar_scatter(const float* features, const int32_t* coordinat
                                  float* canvas, int64_t canvas_B, int64_t ny, int64_t nx, hipStream_t s);
 hipError_t launch_voxel_mean(const float* voxels, const int32_t* num_points, int64_t P, const int64_t* n_pillars, int max_points,
                              int C, float* out, hipStream_t s);
+// ... and its training step (dal3_pillars_train.hip); the arguments are checked by the caller
+size_t pillar_train_workspace_bytes(int64_t P, int n_layers);
+hipError_t launch_pillar_train_forward(const dal3_pillar_train_args* a, hipStream_t s);
+hipError_t launch_pillar_train_backward(const dal3_pillar_train_args* a, hipStream_t s);
 // the detector's dense stage (dal3_conv2d.hip): 3x3 / 1x1 / transposed convolutions as one implicit GEMM on the fp32 MFMA
 size_t conv2d_pack_floats(int kind, int c_in, int c_out);
 // (internal: any c_in / c_out the format can hold, not only the public entry's 4096; the RoI head packs its sections here)

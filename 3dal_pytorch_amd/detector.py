@@ -7,9 +7,12 @@ or configs/waymo/voxelnet/waymo_centerpoint_voxelnet_3x.py.
 `forward(example, return_loss=False)` takes the reference's collated example (voxels, coordinates, num_points, num_voxels,
 shape, metadata) and returns `CenterHead.predict`'s list. `detect(points, point_offsets, metadata=None)` starts from the
 raw sweep instead: voxelise -> pillar features into the canvas -> RPN -> CenterHead -> decode + NMS, everything enqueued on
-the current stream; the read-back of the kept boxes inside `predict` is the only host synchronisation. A `test_cfg` with
+the current stream; the read-back of the kept boxes inside `predict` is the only host synchronisation. `PointPillars.
+first_stage_loss(example, reader="hip")` and `train_step_from_sweeps` are its training step up to the loss, the reader on
+its HIP training kernels. A `test_cfg` with
 `double_flip` (test-time augmentation) is served by both: `forward` takes the reference's batch of four views per sample,
-`detect` makes the views itself. The loss is not built: `return_loss=True` is refused. `VoxelNet` has the same two doors
+`detect` makes the views itself. Only `forward(return_loss=True)` is refused: the loss is reached through
+`first_stage_loss`, not through `forward`. `VoxelNet` has the same two doors
 with the 3-D grid, VoxelFeatureExtractorV3 and the sparse middle (sparse.SpMiddleResNetFHD) in front of the neck.
 `VoxelNet.first_stage_loss(example)` is the training step up to the loss: the reader, the backbone's differentiable
 `train_forward`, the neck's and the head's stock-torch routes (or, with `dense="hip"`, their `train_forward` on the HIP
@@ -26,7 +29,8 @@ READERS = {"PillarFeatureNet": pillars.PillarFeatureNet, "VoxelFeatureExtractorV
 BACKBONES = {"PointPillarsScatter": pillars.PointPillarsScatter, "SpMiddleResNetFHD": sparse.SpMiddleResNetFHD}
 NECKS = {"RPN": rpn.RPN}
 HEADS = {"CenterHead": rpn.CenterHead}
-DENSE_ROUTES = ("composite", "hip")             # how the neck and the head train (VoxelNet.first_stage_loss)
+DENSE_ROUTES = ("composite", "hip")             # how the neck and the head train (first_stage_loss)
+READER_ROUTES = ("composite", "hip")            # how the pillar reader trains (PointPillars.first_stage_loss)
 
 
 def _build(cfg, table, what):
@@ -111,6 +115,23 @@ class SingleStageDetector(nn.Module):
         self.last = r
         return r
 
+    def set_train_input(self, preprocess, assigner):
+        """the stages `train_step_from_sweeps` feeds the loss with: an augment.Preprocess and a center_loss.AssignLabel"""
+        self.train_input = (preprocess, assigner)
+
+    def _example_from_sweeps(self, points, point_offsets, annotations, draws):
+        """augment.train_example on this detector's grid: the capacity-sized example of `train_step_from_sweeps`"""
+        if getattr(self, "train_input", None) is None:
+            raise RuntimeError("train_step_from_sweeps needs set_train_input(preprocess, assigner) first")
+        if self.voxel_size is None:
+            raise RuntimeError("train_step_from_sweeps needs the reader's voxel_size and pc_range: build the model with them")
+        from . import augment
+        preprocess, assigner = self.train_input
+        return augment.train_example(preprocess, assigner, points, point_offsets, annotations["gt_boxes"], annotations["gt_classes"],
+                                     annotations["gt_counts"], voxel_size=self.voxel_size, pc_range=self.pc_range,
+                                     max_points=self.max_points, max_voxels=self.max_voxels, draws=draws,
+                                     candidates=annotations.get("candidates"))
+
     to_prediction = staticmethod(CenterHeadPost.to_prediction)
 
 
@@ -137,6 +158,44 @@ class PointPillars(SingleStageDetector):
                     batch_size=len(example["num_voxels"]), input_shape=example["shape"][0])
         preds = self.bbox_head(self.extract_feat(data))
         return self.bbox_head.predict(example, preds, self.test_cfg)
+
+    def first_stage_loss(self, example, reader="hip", dense="composite"):
+        """the training step up to the loss: reader -> canvas -> the neck and the head (BatchNorm by its mode) ->
+        CenterHead.loss. reader: "hip" (the default: PillarFeatureNet.train_forward_canvas, the reader's forward and
+        backward on the HIP kernels; it honours example["n_voxels"], the device count of a capacity-sized batch) |
+        "composite" (stock torch ops, stock autograd and an index_put scatter). dense: the neck's and the head's route, as
+        VoxelNet.first_stage_loss takes it. example: the voxeliser's entries (voxels, coordinates, num_points, num_voxels,
+        shape; optionally n_voxels) and the lists of center_loss.center_targets -> CenterHead.loss's dictionary; `loss`
+        carries the graph to every parameter of the reader, the neck and the head."""
+        if reader not in READER_ROUTES:
+            raise ValueError(f"reader {reader!r}: the pillar reader trains through 'hip' (its kernels) or 'composite' (stock torch)")
+        if dense not in DENSE_ROUTES:
+            raise ValueError(f"dense {dense!r}: the neck and the head train through 'composite' (stock torch) or 'hip'")
+        n_voxels, B, shape = example.get("n_voxels"), len(example["num_voxels"]), example["shape"][0]
+        voxels, num, co = example["voxels"], example["num_points"], example["coordinates"]
+        if reader == "hip":
+            x = self.reader.train_forward_canvas(voxels, num, co, B, shape, n_pillars=n_voxels)
+        else:
+            if n_voxels is not None:
+                raise ValueError("reader='composite' cannot take a capacity-sized batch (n_voxels): the rows behind the live count "
+                                 "have num_points 0, the composite divides by it, and the 0 / 0 = NaN goes into BatchNorm's batch "
+                                 "statistics. Slice the example to its live rows and drop n_voxels (a host read-back), or use "
+                                 "reader='hip'")
+            feats = self.reader.composite(voxels, num, co)
+            at = co.long()
+            x = feats.new_zeros((B, feats.shape[1], int(shape[1]), int(shape[0])))
+            x[at[:, 0], :, at[:, 2], at[:, 3]] = feats
+        hip = dense == "hip"
+        if self.with_neck:
+            x = self.neck.train_forward(x) if hip else self.neck.composite(x)
+        return self.bbox_head.loss(example, self.bbox_head.train_forward(x) if hip else self.bbox_head.composite(x))
+
+    def train_step_from_sweeps(self, points, point_offsets, annotations, draws=None, reader="hip", dense="composite"):
+        """VoxelNet.train_step_from_sweeps's contract on the pillar grid: resident sweeps and annotations ->
+        CenterHead.loss's dictionary on the current stream with no host synchronisation (augment.train_example, then
+        first_stage_loss with `reader` and `dense`). `last_example` keeps the example."""
+        self.last_example = self._example_from_sweeps(points, point_offsets, annotations, draws)
+        return self.first_stage_loss(self.last_example, reader=reader, dense=dense)
 
     @torch.no_grad()
     def detect(self, points, point_offsets, metadata=None, point_offsets_device=None):
@@ -201,26 +260,13 @@ class VoxelNet(SingleStageDetector):
             x = self.neck.train_forward(x) if hip else self.neck.composite(x)
         return self.bbox_head.loss(example, self.bbox_head.train_forward(x) if hip else self.bbox_head.composite(x))
 
-    def set_train_input(self, preprocess, assigner):
-        """the stages `train_step_from_sweeps` feeds the loss with: an augment.Preprocess and a center_loss.AssignLabel"""
-        self.train_input = (preprocess, assigner)
-
     def train_step_from_sweeps(self, points, point_offsets, annotations, draws=None, dense="composite"):
         """resident sweeps and annotations -> CenterHead.loss's dictionary, on the current stream with no host
         synchronisation: augment.train_example (GT paste, augmentation, shuffle; voxelisation; AssignLabel) and then
         first_stage_loss (`dense`: its route for the neck and the head). points (N, F) float32 CUDA, point_offsets (B + 1) on the host, annotations: {gt_boxes (B, max_gt, 9)
         CUDA, gt_classes, gt_counts} as augment.Preprocess takes them; draws: the step's augment.Draws (None: drawn on the
         device). `last_example` keeps the example."""
-        if getattr(self, "train_input", None) is None:
-            raise RuntimeError("train_step_from_sweeps needs set_train_input(preprocess, assigner) first")
-        if self.voxel_size is None:
-            raise RuntimeError("train_step_from_sweeps needs the reader's voxel_size and pc_range: build the model with them")
-        from . import augment
-        preprocess, assigner = self.train_input
-        example = augment.train_example(preprocess, assigner, points, point_offsets, annotations["gt_boxes"], annotations["gt_classes"],
-                                        annotations["gt_counts"], voxel_size=self.voxel_size, pc_range=self.pc_range,
-                                        max_points=self.max_points, max_voxels=self.max_voxels, draws=draws,
-                                        candidates=annotations.get("candidates"))
+        example = self._example_from_sweeps(points, point_offsets, annotations, draws)
         self.last_example = example
         return self.first_stage_loss(example, dense=dense)
 

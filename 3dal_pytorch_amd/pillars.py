@@ -245,7 +245,8 @@ def _checked_voxels(features, num_voxels, coors):
 class PillarFeatureNet(nn.Module):
     """pillar_encoder.py:58-153. Eval mode with num_filters (64,) or (64, 64), with_distance=False, max_points <= 64 and
     3 .. 8 point features runs dal3_pillar_features (BatchNorm folded at packing time with the layers' own eps); anything
-    else, and train mode, runs the stock-torch composite. forward -> (P, C_out) always (no squeeze)."""
+    else, and train mode, runs the stock-torch composite. forward -> (P, C_out) always (no squeeze). The training step on
+    the HIP kernels is opt-in: `train_forward` / `train_forward_canvas` (dal3_pillar_train_forward / _backward)."""
 
     def __init__(self, num_input_features=4, num_filters=(64,), with_distance=False, voxel_size=(0.2, 0.2, 4),
                  pc_range=(0, -40, -3, 70.4, 40, 1), norm_cfg=None):
@@ -356,6 +357,110 @@ class PillarFeatureNet(nn.Module):
         canvas = torch.empty((int(batch_size), 64, int(input_shape[1]), int(input_shape[0])), dtype=torch.float32,
                              device=features.device)
         return self._launch(features, num_voxels, coors, n_pillars, canvas)
+
+    # ------------------------------------------------------------------ the training step (dal3_pillar_train_*)
+    def _train_checked(self, features, num_voxels, coors, n_pillars, route):
+        if not self.training:
+            raise RuntimeError(f"PillarFeatureNet.{route} is the training step: the module is in eval mode (call .train(); "
+                               "forward / forward_canvas serve eval mode)")
+        if features.dim() != 3 or features.shape[2] != self.num_input or not self.hip_serves(features.shape[1]):
+            raise RuntimeError(f"PillarFeatureNet.{route}: hip_serves does not serve this shape (units [64] or [32, 64], "
+                               f"3 <= C <= 8, max_points <= 64, one eps, with_distance=False); got units "
+                               f"{[l.units for l in self.pfn_layers]}, features {tuple(features.shape)}, "
+                               f"num_input_features {self.num_input}, with_distance {self._with_distance}")
+        features, num_voxels, coors = _checked_voxels(features, num_voxels, coors)
+        if features.shape[0] * features.shape[1] < 2:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size "
+                             f"{[features.shape[0] * features.shape[1], self.pfn_layers[0].units]}")
+        for t in self._tensors():
+            _hip.require_gpu(t, "PillarFeatureNet's parameters")
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise RuntimeError("weights must be contiguous fp32")
+        return features, num_voxels, coors, _device_ints(n_pillars, "n_pillars", torch.int64, 1, features.device)
+
+    def train_forward(self, features, num_voxels, coors, n_pillars=None, *, max_workgroups=0):
+        """train mode on the HIP kernels -> (P, 64), differentiable with respect to every linear.weight, norm.weight and
+        norm.bias (not the voxels). The BatchNorms use the batch statistics of the first min(*n_pillars, P) pillars' rows
+        and update running_mean / running_var / num_batches_tracked in place, on the device; rows behind the live count
+        are zero and nothing of them is read. No host synchronisation."""
+        features, num_voxels, coors, n_pillars = self._train_checked(features, num_voxels, coors, n_pillars, "train_forward")
+        params = [t for l in self.pfn_layers for t in (l.linear.weight, l.norm.weight, l.norm.bias)]
+        return _PillarTrain.apply(self, features, num_voxels, coors, n_pillars, None, int(max_workgroups), *params)
+
+    def train_forward_canvas(self, features, num_voxels, coors, batch_size, input_shape, n_pillars=None, *, max_workgroups=0):
+        """the fused training route -> the differentiable (batch_size, 64, ny, nx) canvas, the bits of train_forward +
+        PointPillarsScatter; the backward reads the canvas cotangent through its strides, the (P, 64) tensors never exist.
+        input_shape = [nx, ny, ...]."""
+        features, num_voxels, coors, n_pillars = self._train_checked(features, num_voxels, coors, n_pillars, "train_forward_canvas")
+        params = [t for l in self.pfn_layers for t in (l.linear.weight, l.norm.weight, l.norm.bias)]
+        shape = (int(batch_size), 64, int(input_shape[1]), int(input_shape[0]))
+        return _PillarTrain.apply(self, features, num_voxels, coors, n_pillars, shape, int(max_workgroups), *params)
+
+    def _train_args(self, features, num_voxels, coors, n_pillars, params, saved, ws, max_workgroups):
+        P, max_points, C = features.shape
+        layers = (_hip.Layer * len(self.pfn_layers))(*[
+            _hip.Layer(_hip.ptr(params[3 * i]), None, _hip.ptr(params[3 * i + 1]), _hip.ptr(params[3 * i + 2]), None, None,
+                       params[3 * i].shape[1], params[3 * i].shape[0]) for i in range(len(self.pfn_layers))])
+        a = _hip.PillarTrainArgs(P=P, n_pillars=_hip.ptr(n_pillars), voxels=_hip.ptr(features), num_points=_hip.ptr(num_voxels),
+                                 coordinates=_hip.ptr(coors), C=C, max_points=max_points, n_layers=len(self.pfn_layers), c_out=64,
+                                 vx=self.vx, vy=self.vy, x_offset=self.x_offset, y_offset=self.y_offset, layers=layers,
+                                 eps=float(self.pfn_layers[0].norm.eps), saved=_hip.ptr(saved), max_workgroups=max_workgroups,
+                                 workspace=_hip.ptr(ws), workspace_bytes=ws.numel())
+        return a, layers                # (the caller keeps `layers` alive over the call)
+
+
+class _PillarTrain(torch.autograd.Function):
+    """dal3_pillar_train_forward / dal3_pillar_train_backward: params = (linear.weight, norm.weight, norm.bias) per layer"""
+
+    @staticmethod
+    def forward(ctx, net, features, num_voxels, coors, n_pillars, canvas_shape, max_workgroups, *params):
+        dev = features.device
+        params = [p.detach() for p in params]
+        lib = _hip.lib()
+        ws = _hip.workspace(lib.dal3_pillar_train_workspace_bytes(features.shape[0], len(net.pfn_layers)), dev)
+        saved = torch.empty(_hip.PILLAR_TRAIN_SAVED_FLOATS, dtype=torch.float32, device=dev)
+        a, keep = net._train_args(features, num_voxels, coors, n_pillars, params, saved, ws, max_workgroups)
+        for i, l in enumerate(net.pfn_layers):
+            # momentum None is torch's cumulative average: not what the reference's configs use, and not served
+            if l.norm.momentum is None:
+                raise RuntimeError("PillarFeatureNet.train_forward: BatchNorm momentum=None (a cumulative average) is not served")
+            a.momentum[i] = float(l.norm.momentum)
+            a.running_mean[i], a.running_var[i] = l.norm.running_mean.data_ptr(), l.norm.running_var.data_ptr()
+            a.num_batches_tracked[i] = l.norm.num_batches_tracked.data_ptr()
+        if canvas_shape is None:
+            out = torch.empty((features.shape[0], 64), dtype=torch.float32, device=dev)
+            a.features = out.data_ptr()
+        else:
+            out = torch.empty(canvas_shape, dtype=torch.float32, device=dev)
+            a.canvas, a.canvas_B, a.ny, a.nx = out.data_ptr(), canvas_shape[0], canvas_shape[2], canvas_shape[3]
+        _hip.check(lib.dal3_pillar_train_forward(a, _hip.stream()))
+        net.invalidate_packed()         # the kernels wrote the running statistics through raw pointers
+        ctx.net, ctx.canvas_shape, ctx.max_workgroups, ctx.n_pillars = net, canvas_shape, max_workgroups, n_pillars
+        ctx.save_for_backward(features, num_voxels, coors, saved, *params)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        features, num_voxels, coors, saved, *params = ctx.saved_tensors
+        net, dev = ctx.net, features.device
+        lib = _hip.lib()
+        if grad.dtype != torch.float32:
+            raise TypeError(f"PillarFeatureNet.train_forward: the cotangent must be float32, got {grad.dtype}")
+        ws = _hip.workspace(lib.dal3_pillar_train_workspace_bytes(features.shape[0], len(net.pfn_layers)), dev)
+        a, keep = net._train_args(features, num_voxels, coors, ctx.n_pillars, params, saved, ws, ctx.max_workgroups)
+        a.grad = grad.data_ptr()
+        if ctx.canvas_shape is None:
+            a.grad_stride[:] = [grad.stride(0), grad.stride(1), 0, 0]
+        else:
+            a.canvas = grad.data_ptr()
+            a.canvas_B, a.ny, a.nx = ctx.canvas_shape[0], ctx.canvas_shape[2], ctx.canvas_shape[3]
+            a.grad_stride[:] = list(grad.stride())
+        grads = [torch.empty_like(p) for p in params]
+        for i in range(len(net.pfn_layers)):
+            a.dW[i], a.dgamma[i], a.dbeta[i] = (g.data_ptr() for g in grads[3 * i:3 * i + 3])
+        _hip.check(lib.dal3_pillar_train_backward(a, _hip.stream()))
+        return (None,) * 7 + tuple(grads)
 
 
 class PointPillarsScatter(nn.Module):

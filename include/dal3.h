@@ -944,6 +944,79 @@ int dal3_pillar_scatter(const float* features, const int32_t* coordinates, int64
 int dal3_voxel_mean(const float* voxels, const int32_t* num_points, int64_t P, const int64_t* n_pillars, int max_points, int C,
                     float* out, dal3_stream stream);
 
+/* ---- the reader's training step: PFNLayer in train mode (det3d/models/readers/pillar_encoder.py:40-55), forward and
+ * backward, on the rows dal3_pillar_features defines above (the same mean, decoration and padding mask), float32 inputs,
+ * products on the fp32 MFMA, every sum over pillars in float64.
+ *
+ * Live pillars. live = min(*n_pillars, P) with n_pillars, else P; the BatchNorm sees n = live * max_points samples.
+ * Nothing of a pillar behind `live` is read, counted or written: its voxels and num_points may hold anything, NaN included.
+ * Forward, per layer, x the layer's input row:
+ *   z = W x (no bias); mean_c and var_c (biased) over all n rows. PADDING ROWS COUNT: their layer-1 z is exactly 0, so they
+ *   add nothing to the sums but are part of n. xhat = (z - mean) / sqrt(var + eps), a = gamma xhat + beta (evaluated as one
+ *   fused multiply-add z * (gamma istd) + (beta - mean gamma istd)), y = relu(a); top = the max of y over all max_points
+ *   rows, padding rows included. A middle layer passes on [y | top repeated], the last layer passes on top.
+ *   Shapes: units [64] or [32, 64], 3 <= C <= 8, 1 <= max_points <= 64, one eps.
+ * Running statistics (optional: running_mean[l] NULL leaves layer l's alone), on the device, in float64, rounded once:
+ *   r = (1 - momentum) r + momentum * stat, the variance unbiased: var * n / max(n - 1, 1); num_batches_tracked += 1.
+ *   live == 0 gives mean 0 and var 0.
+ * Backward, from the cotangent of the last layer's top:
+ *   da = dy [a > 0]; dbeta = sum da, dgamma = sum da xhat; dz = gamma / sqrt(var + eps) (da - dbeta / n - xhat dgamma / n)
+ *   for EVERY row of every live pillar: a padding row has a non-zero dz and, in layer 2, the non-zero input
+ *   [y1_pad | top1], so it contributes to dW2 and to what flows back into layer 1. dW = sum over rows dz (x) x,
+ *   dx = W^T dz. The max sends its cotangent to the lowest row that attains it; a middle layer's top receives the sum
+ *   of its repeated columns' dx over the pillar's rows. Rows that tie exactly are at y = 0 (the ReLU gate stops the
+ *   cotangent) or have identical inputs (the same terms whichever is picked): the choice shows in no parameter gradient.
+ *   No gradient with respect to the voxels is produced.
+ * Sums. Every sum over pillars (sum z, sum z^2, dbeta, dgamma, dW) is taken over slices of DAL3_PILLAR_TRAIN_SLICE
+ * consecutive pillars, in pillar order, into float64; every slice's partial is stored and the partials are added in
+ * ascending slice order, in float64. No floating-point atomic: the bits are the same for every max_workgroups and every
+ * run. MFMA columns beyond max_points (a repeated row) are masked out of every sum. Nothing of P * max_points * channels
+ * elements is written to memory. Nothing synchronises.
+ * Outputs. forward: `features` (P, 64), first filled with +0 (rows behind live stay 0), or, with `canvas`, the
+ * (canvas_B, 64, ny, nx) map of dal3_pillar_features (zero-filled first; a pillar outside the canvas is not written), and
+ * `saved`, DAL3_PILLAR_TRAIN_SAVED_FLOATS floats, 16-byte aligned: per layer mean | istd | gamma istd | beta - mean gamma
+ * istd, 64 each. backward: the same geometry, parameters and `saved`; `grad` is the cotangent of features (element strides
+ * grad_stride[0] per row, [1] per channel) or, when `canvas` is non-NULL (only its being set is used), of the canvas with
+ * strides grad_stride[0..3] per (b, c, y, x): a channels-last or sliced cotangent is read as it lies, a pillar outside
+ * the canvas has a zero cotangent. dW[l] (units, c_in), dgamma[l], dbeta[l] (units) are written, not added to.
+ * layers: a HOST array of n_layers dal3_layer with device pointers weight, bn_weight, bn_bias (bias NULL; bn_mean, bn_var unused).
+ * workspace: dal3_pillar_train_workspace_bytes(P, n_layers), 8-byte aligned; the backward does not need the forward's. */
+#define DAL3_PILLAR_TRAIN_SLICE 128
+#define DAL3_PILLAR_TRAIN_SAVED_FLOATS 512
+
+typedef struct dal3_pillar_train_args {
+    int64_t P;                           /* rows of voxels / features */
+    const int64_t* n_pillars;            /* optional device (1): pillars in use */
+    const float* voxels;                 /* (P, max_points, C) */
+    const int32_t* num_points;           /* (P) */
+    const int32_t* coordinates;          /* (P, 4) [b, z, y, x] */
+    int32_t C, max_points;
+    int32_t n_layers, c_out;             /* 1 or 2; 64 */
+    float vx, vy, x_offset, y_offset;
+    const dal3_layer* layers;            /* HOST (n_layers) */
+    double eps;
+    double momentum[2];
+    float* running_mean[2];              /* forward: optional, per layer (units) */
+    float* running_var[2];
+    int64_t* num_batches_tracked[2];     /* forward: optional, per layer (1) */
+    float* saved;                        /* (DAL3_PILLAR_TRAIN_SAVED_FLOATS): forward writes, backward reads */
+    float* features;                     /* forward: (P, c_out), or NULL with a canvas */
+    float* canvas;                       /* optional (canvas_B, c_out, ny, nx); backward: non-NULL selects the canvas cotangent */
+    int64_t canvas_B, ny, nx;
+    const float* grad;                   /* backward: the cotangent */
+    int64_t grad_stride[4];              /* elements: (row, channel, -, -) or (b, c, y, x) */
+    float* dW[2];                        /* backward outputs, per layer */
+    float* dgamma[2];
+    float* dbeta[2];
+    int64_t max_workgroups;              /* 0: no cap */
+    void* workspace;
+    size_t workspace_bytes;
+} dal3_pillar_train_args;
+
+size_t dal3_pillar_train_workspace_bytes(int64_t P, int n_layers);
+int dal3_pillar_train_forward(const dal3_pillar_train_args* args, dal3_stream stream);
+int dal3_pillar_train_backward(const dal3_pillar_train_args* args, dal3_stream stream);
+
 /* ---- the detector's dense stage: the 2-D convolutions of RPN (det3d/models/necks/rpn.py) and of CenterHead.forward /
  * SepHead (det3d/models/bbox_heads/center_head.py:65-110, 167-244), float32, eval mode.
  *
