@@ -459,6 +459,7 @@ SIGNATURES = {
     "dal3_ins_seg_workspace_bytes": (_sz, [_i]),
     "dal3_ins_seg_plan_layout": (_i, [_i, C.POINTER(_sz), C.POINTER(_i)]),
     "dal3_ins_seg_encoder_route": (_i, [_i, _i, _i]),
+    "dal3_ins_seg_decode_route": (_i, [vp, _i, _i, _i]),
     "dal3_ins_seg_forward": (_i, [vp, _i, _i, BCN, _i, _i, vp, vp, vp, vp, _sz, vp]),
     "dal3_ins_seg_encode": (_i, [vp, _i, _i, BCN, _i, _i, vp, vp]),
     "dal3_ins_seg_global_bias": (_i, [vp, _i, vp, _i, vp, vp]),
@@ -712,7 +713,9 @@ BCN_NO_SMALL_JOB_KERNELS, BCN_NO_WORKLIST, BCN_NO_LDS_SAMPLER = 1, 2, 4
 BCN_NO_DEC_PLAN = 16
 BCN_NO_ENC_RESIDENT = 32
 BCN_NO_HEAD_RESIDENT = 64
+BCN_NO_DEC_PAIR = 128
 ENC_ROUTE_LATENCY, ENC_ROUTE_DENSE, ENC_ROUTE_TWO_LAUNCH, ENC_ROUTE_RESIDENT = 0, 1, 2, 3      # dal3_ins_seg_encoder_route
+DEC_ROUTE_LATENCY, DEC_ROUTE_ONE_WAVE, DEC_ROUTE_PAIR = 0, 1, 2      # dal3_ins_seg_decode_route
 HEAD_ROUTE_LATENCY, HEAD_ROUTE_PER_TILE, HEAD_ROUTE_PERSISTENT, HEAD_ROUTE_TWO_LAUNCH, HEAD_ROUTE_RESIDENT = 0, 1, 2, 3, 4      # dal3_point_head_route
 # dal3_bcn.flags of every view bcn() builds (include/dal3.h, DAL3_BCN_*). 0 in normal use; A/B measurements and the
 # tests that pin "both kernel families give the same bits" set it around a call (binding-side, the library has no switch).

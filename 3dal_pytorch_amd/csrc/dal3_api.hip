@@ -420,7 +420,7 @@ static int check_bcn(const dal3_bcn& t, const char* what) {
     if (t.dtype != DAL3_F32 && t.dtype != DAL3_BF16 && t.dtype != DAL3_F16)
         return fail(DAL3_EINVAL, "%s: storage dtype %d is none of DAL3_F32 / DAL3_BF16 / DAL3_F16", what, t.dtype);
     if (t.dtype != DAL3_F32 && (reinterpret_cast<uintptr_t>(t.data) & 1)) return fail(DAL3_EINVAL, "%s: 16-bit data must be 2-byte aligned", what);
-    if (t.flags & ~(DAL3_BCN_NO_SMALL_JOB_KERNELS | DAL3_BCN_NO_WORKLIST | DAL3_BCN_NO_LDS_SAMPLER | DAL3_BCN_NO_DEC_PLAN | DAL3_BCN_NO_ENC_RESIDENT | DAL3_BCN_NO_HEAD_RESIDENT)) return fail(DAL3_EINVAL, "%s: unknown bits in flags (%d)", what, t.flags);
+    if (t.flags & ~(DAL3_BCN_NO_SMALL_JOB_KERNELS | DAL3_BCN_NO_WORKLIST | DAL3_BCN_NO_LDS_SAMPLER | DAL3_BCN_NO_DEC_PLAN | DAL3_BCN_NO_ENC_RESIDENT | DAL3_BCN_NO_HEAD_RESIDENT | DAL3_BCN_NO_DEC_PAIR)) return fail(DAL3_EINVAL, "%s: unknown bits in flags (%d)", what, t.flags);
     return 0;
 }
 
@@ -471,9 +471,18 @@ extern "C" int dal3_ins_seg_plan_layout(int B, size_t off[4], int* min_dead) {
 
 extern "C" int dal3_ins_seg_encoder_route(int B, int N, int flags) {
     TRY(check_extent(B, N, "ins_seg_encoder_route"));
-    if (flags & ~(DAL3_BCN_NO_SMALL_JOB_KERNELS | DAL3_BCN_NO_WORKLIST | DAL3_BCN_NO_LDS_SAMPLER | DAL3_BCN_NO_DEC_PLAN | DAL3_BCN_NO_ENC_RESIDENT | DAL3_BCN_NO_HEAD_RESIDENT))
+    if (flags & ~(DAL3_BCN_NO_SMALL_JOB_KERNELS | DAL3_BCN_NO_WORKLIST | DAL3_BCN_NO_LDS_SAMPLER | DAL3_BCN_NO_DEC_PLAN | DAL3_BCN_NO_ENC_RESIDENT | DAL3_BCN_NO_HEAD_RESIDENT | DAL3_BCN_NO_DEC_PAIR))
         return fail(DAL3_EINVAL, "ins_seg_encoder_route: unknown bits in flags (%d)", flags);
     return enc_route(flags, B, N);
+}
+
+extern "C" int dal3_ins_seg_decode_route(const void* packed, int B, int N, int flags) {
+    TRY(check_extent(B, N, "ins_seg_decode_route"));
+    if (flags & ~(DAL3_BCN_NO_SMALL_JOB_KERNELS | DAL3_BCN_NO_WORKLIST | DAL3_BCN_NO_LDS_SAMPLER | DAL3_BCN_NO_DEC_PLAN | DAL3_BCN_NO_ENC_RESIDENT | DAL3_BCN_NO_HEAD_RESIDENT | DAL3_BCN_NO_DEC_PAIR))
+        return fail(DAL3_EINVAL, "ins_seg_decode_route: unknown bits in flags (%d)", flags);
+    int32_t guard = 0;
+    if (packed) HIP_TRY(hipMemcpy(&guard, view(packed, ins_seg_walk).dec_flag, sizeof(guard), hipMemcpyDeviceToHost));
+    return dec_route(flags, B, N, guard != 0);
 }
 
 static int check_dtype(int dtype) {
@@ -749,7 +758,7 @@ extern "C" int dal3_point_head_screen_stride(void) { return DAL3_HEAD_SCR_STRIDE
 extern "C" int dal3_point_head_route(int head_kind, int B, int M, int flags) {
     TRY(check_extent(B, M, "point_head_route"));
     if (head_kind < 1 || head_kind > 3) return fail(DAL3_EINVAL, "point_head_route: unknown head kind %d", head_kind);
-    if (flags & ~(DAL3_BCN_NO_SMALL_JOB_KERNELS | DAL3_BCN_NO_WORKLIST | DAL3_BCN_NO_LDS_SAMPLER | DAL3_BCN_NO_DEC_PLAN | DAL3_BCN_NO_ENC_RESIDENT | DAL3_BCN_NO_HEAD_RESIDENT))
+    if (flags & ~(DAL3_BCN_NO_SMALL_JOB_KERNELS | DAL3_BCN_NO_WORKLIST | DAL3_BCN_NO_LDS_SAMPLER | DAL3_BCN_NO_DEC_PLAN | DAL3_BCN_NO_ENC_RESIDENT | DAL3_BCN_NO_HEAD_RESIDENT | DAL3_BCN_NO_DEC_PAIR))
         return fail(DAL3_EINVAL, "point_head_route: unknown bits in flags (%d)", flags);
     return head_route(flags, head_kind, B, M);
 }

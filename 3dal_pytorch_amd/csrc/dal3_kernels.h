@@ -238,6 +238,8 @@ hipError_t launch_ins_seg_encode_screen(const InsSegW& w, BCN pts, int c_in, int
 bool dec_plan_route(int flags, int B, int N);
 int enc_route(int flags, int B, int N);                     // which fp32 encoder runs: DAL3_ENC_ROUTE_* (dal3.h)
 bool enc_resident_route(int flags, int B, int N);           // the screened encoder as ONE crop-resident launch (dal3_pointmlp.hip)
+bool dec_pair_route(int flags, int B, int N);               // the throughput decoder as pairs of waves (dal3_pointmlp.hip)
+int dec_route(int flags, int B, int N, bool guarded);       // which fp32 decoder runs: DAL3_DEC_ROUTE_* (dal3.h)
 hipError_t launch_pack_dec_prune(const dal3_layer& L, float* dw1c, float* pq, uint32_t* ident, int32_t* flag, hipStream_t s);
 // plan_k (B, DEC_PLAN_LD), plan_gbc (B, 512), plan_nch (B): see DecPlan
 hipError_t launch_dec_plan(const InsSegW& w, const float* gb, const uint32_t* prune, int B, uint32_t* plan_k, float* plan_gbc,

@@ -11,7 +11,8 @@
 //
 // One wave owns T tiles of 32 points; waves never talk to each other (no LDS, no barrier): the
 // cross-wave max is an atomic on g / feat. Weights stream from L2 as 1-KiB coalesced dwordx4
-// fragments shared by all waves of the chip.
+// fragments shared by all waves of the chip. The one exception is ins_seg_decode_pair_kernel, the
+// throughput decoder of large fp32 jobs: a pair of waves shares a tile, its row queue and barriers.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -762,6 +763,453 @@ __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_decode_kernel(InsS
 }
 
 // ------------------------------------------------------------------------------------------------
+// Two waves per tile (DESIGN.md "Two waves per tile"; tests/dec_pair_model.py is the schedule's CPU model). A workgroup is
+// a PAIR of waves that owns one 32-point tile and runs the compacted body only; at 128 threads and at most 256 registers a
+// CU holds four pairs, two waves on every SIMD, so the instructions one wave issues between its fp32 MFMAs lie beside the
+// MFMAs of another. The two waves split every layer's OUTPUT tiles — dconv2's 4 w .. 4 w + 3 of eight, dconv3's and
+// dconv4's 2 w, 2 w + 1 of four — and each runs the compact loop over the WHOLE list for its half: no output's chain is
+// divided and every chain keeps the one-wave order, so the bits are ins_seg_decode_kernel's. What they share:
+//   rows      dconv1's chunk j of the plan is computed by wave j mod 2 and written to rows 128 (g mod 2) + 32 u + 2 r + h
+//             (group g = j / 4, place u = j mod 4): two buffers, rows 0 .. 127 and 128 .. 255. dconv3: wave w writes the
+//             rows of its own four k-tiles (128 w ..), dconv4: of its own two (64 w ..). Wave 0 writes the row of zeros.
+//   masks     a chunk's (k-tile's) producer leaves its mask word at a place of its own; dconv2's are double-buffered too.
+//   barriers  one per group between its production and its consumption: produce(0) | B | consume(0) produce(1) | B | ... —
+//             the producer of group g + 2 reaches buffer g mod 2 only after the barrier both waves pass once group g is
+//             consumed. Then B | dconv3's rows | B | its loop | B | dconv4's rows | B | its loop, dconv5's first half | B |
+//             dconv5's second half and the store. The pairs of a CU are separate workgroups and drift apart.
+// Each wave has a list and a leftover row of ITS OWN (DEC_P_PRIV floats behind the shared rows): a shared leftover row
+// would be overwritten by the faster wave's next odd group while the slower one still reads it as its list's entry 0.
+// dconv5: one chain per logit and lane half in the one-wave order — wave 0 adds k-tiles 0, 1 from zero and hands the
+// partial sums over in LDS, wave 1 CONTINUES them with k-tiles 2, 3, adds the lane halves and the bias, and stores.
+// Each wave computes conv1 and conv2 for itself (68 of a tile's 1970 MFMAs twice). The ReLU, rows and ballots of a
+// wave's second chunk of a group are not hidden under MFMAs of its own: the partner's are beside them.
+// A blob whose guard flag is set is not for this kernel (every workgroup leaves at once): launch_ins_seg_decode puts
+// ins_seg_decode_guarded_kernel behind it, which runs the dense body for such a blob and leaves at once for any other.
+#define DEC_P_PRIV 612                                     // dconv2's list (dconv3's / dconv4's lie over it) | the leftover row
+#define DEC_P_PEND_OFF (2 * (1 + 256 + DEC_Q_OVER))
+#define DEC_P_LIST0 ((DEC_Q_ZERO + 1) * 32)
+#define DEC_P_MASK (DEC_P_LIST0 + 2 * DEC_P_PRIV)          // 2 x 4 words of dconv2's groups, 8 of dconv3, 4 of dconv4
+#define DEC_P_FLOATS (DEC_P_MASK + 32)
+#define DEC_P_L5 (128 * 32)                                // dconv5's partial sums: rows that dconv4 does not use
+static_assert(DEC_P_PEND_OFF + 32 <= DEC_P_PRIV && DEC_P_PRIV % 2 == 0 && DAL3_DEC_GROUP == 4, "the pair's LDS layout");
+#ifdef DAL3_STAMP
+// words per wave (blockIdx.x < 4096, wave 0 / 1): 0 start, 1 prologue done, 2 dconv2 done, 6 dconv3 done, 3 dconv4 done,
+// 4 end; 8 ticks spent in barriers, 9 barriers, 10 k-steps of dconv2, 15 = 1 (tools/stamps.py --pair)
+#define PSTAMP(k)                                                                                 \
+    do {                                                                                          \
+        __builtin_amdgcn_sched_barrier(0);                                                        \
+        unsigned long long t_;                                                                    \
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");               \
+        __builtin_amdgcn_sched_barrier(0);                                                        \
+        if (lane == 0 && blockIdx.x < 4096) g_stamps[(blockIdx.x * 2 + wv) * 16 + (k)] = t_;      \
+    } while (0)
+#define PBARRIER()                                                                                \
+    do {                                                                                          \
+        unsigned long long t0_, t1_;                                                              \
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t0_)::"memory");              \
+        __syncthreads();                                                                          \
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t1_)::"memory");              \
+        bar_wait += t1_ - t0_, ++bar_n;                                                           \
+    } while (0)
+#else
+#define PSTAMP(k)
+#define PBARRIER() __syncthreads()
+#endif
+struct PStep {                          // operands of one compact k-step of dconv2 for four out-tiles
+    f32x4 a;
+    float b;
+};
+struct PQStep {                         // ... of dconv3 / dconv4 for two out-tiles
+    f32x2 a;
+    float b;
+};
+// dconv3 / dconv4 for wave wv of a pair: X its KT / 2 k-tiles of the input, Y its two out-tiles. kl: the wave's own list;
+// mw: the layer's KT mask words. (dec_queue_layer with the rows and the out-tiles halved, and two barriers.)
+template <int KT>
+__device__ __forceinline__ void dec_pair_queue_layer(const f32x16 (&X)[KT / 2], f32x16 (&Y)[2], const float* __restrict__ bvec,
+                                                     const float* __restrict__ wcopy, float* q, uint32_t* kl, uint32_t* mw, int lane,
+                                                     uint32_t wv, uint32_t& n_steps, uint32_t& n_live, unsigned long long& bar_wait,
+                                                     uint32_t& bar_n) {
+    static_assert(KT % 4 == 0, "two k-tiles per 64-bit mask word, half of them per wave");
+    const uint32_t h = (uint32_t)lane >> 5, pt = (uint32_t)lane & 31u;
+    const __amdgpu_buffer_rsrc_t wq = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wcopy), 0, KT * 32 * 512, 0x00020000);
+    f32x16 acc[2];
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt) acc[mt] = tile_from_channels(bvec + 32 * (2 * wv + mt), (int)h);
+    PBARRIER();                                        // the partner has read what lay in these rows before
+    float* qo = q + (KT / 2) * 1024 * wv + lane;       // the wave's own k-tiles: rows 32 (KT / 2 wv + i) + 2 r (+ 1: the high half)
+#pragma unroll
+    for (int i = 0; i < KT / 2; ++i) {
+        uint32_t halves = 0;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float v = X[i][r];
+            qo[(32 * i + 2 * r) * 32] = v;
+            note_halves(halves, live_ballot(v), r);
+        }
+        const uint32_t word = live_word(halves);
+        if (lane == 0) mw[(KT / 2) * wv + i] = word;
+    }
+    PBARRIER();
+    uint32_t m[KT];
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt) m[kt] = __builtin_amdgcn_readfirstlane(mw[kt]);
+    uint32_t cnt = 0;
+#pragma unroll
+    for (int j = 0; j < KT / 2; ++j) {
+        const uint32_t below = __builtin_amdgcn_mbcnt_hi(m[2 * j + 1], __builtin_amdgcn_mbcnt_lo(m[2 * j], 0u));
+        const uint32_t word = h ? m[2 * j + 1] : m[2 * j];
+        if ((word >> pt) & 1u) kl[cnt + below] = 64u * j + (uint32_t)lane;
+        cnt += __builtin_popcount(m[2 * j]) + __builtin_popcount(m[2 * j + 1]);
+    }
+    if (lane < DEC_Q_OVER) kl[cnt + (uint32_t)lane] = DEC_Q_ZERO;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t steps = (cnt + 1u) >> 1;
+    n_steps += steps, n_live += cnt;
+    auto mma = [&](const PQStep& S) {
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) acc[mt] = mfma32(S.a[mt], S.b, acc[mt]);
+    };
+    auto issue = [&](PQStep& S, uint32_t k) {          // row k and its weights of the wave's two out-tiles
+        S.b = q[k * 32u + pt];
+        S.a = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(wq, k * 512u + pt * 16u + 8u * wv, 0, 0));
+    };
+    const uint32_t* kp = kl + h;
+    PQStep S[DAL3_DEC_QNB];
+    uint32_t K[DAL3_DEC_QNB];
+#pragma unroll
+    for (int u = 0; u < DAL3_DEC_QNB; ++u) K[u] = kp[2 * u];
+#pragma unroll
+    for (int u = 0; u < DAL3_DEC_QNB; ++u) {
+        issue(S[u], K[u]);
+        K[u] = kp[2 * (DAL3_DEC_QNB + u)];
+    }
+    uint32_t s = 0;
+    for (; s + DAL3_DEC_QNB <= steps; s += DAL3_DEC_QNB) {
+        kp += 2 * DAL3_DEC_QNB;
+#pragma unroll
+        for (int u = 0; u < DAL3_DEC_QNB; ++u) {
+            mma(S[u]);
+            issue(S[u], K[u]);
+            K[u] = kp[2 * (DAL3_DEC_QNB + u)];
+            DAL3_SCHED_FENCE();
+        }
+    }
+#pragma unroll
+    for (int u = 0; u + 1 < DAL3_DEC_QNB; ++u) {
+        if (s + u < steps) mma(S[u]);
+    }
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt) Y[mt] = relu16(acc[mt]);
+}
+
+__global__ __launch_bounds__(128, 2) void ins_seg_decode_pair_kernel(InsSegW w, BCN pts, int c_in, int n_pts, int tiles_per_item,
+                                                                     const float* __restrict__ gbias, float* __restrict__ logits,
+                                                                     uint8_t* __restrict__ mask, DecPlan plan) {
+    if (*w.dec_flag != 0) return;                      // (uniform: no wave of any workgroup reaches a barrier)
+    const int lane = threadIdx.x & 63;
+    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int h = lane >> 5, pt = lane & 31;
+    unsigned blk = blockIdx.x;
+    if (DAL3_DEC_XCD) {                                // a crop's workgroups share one XCD's L2 (see ins_seg_decode_kernel)
+        const unsigned per = gridDim.x >> 3, rem = gridDim.x & 7u, x = blockIdx.x & 7u;
+        blk = x * per + (x < rem ? x : rem) + (blockIdx.x >> 3);
+    }
+    const int64_t b = blk / tiles_per_item;
+    const int n0 = (blk % tiles_per_item) * 32;
+    const float* gb = gbias + b * 512;
+    int nch = plan.nch ? plan.nch[b] : 0;
+    const uint32_t* pk = plan.k + b * DEC_PLAN_LD;
+    const float* gbc = plan.gbc + b * 512;
+    if (nch <= 0) nch = 16, pk = w.dec_ident, gbc = gb;    // no plan: the identity, whatever the crop's dead share
+    extern __shared__ __attribute__((aligned(16))) float s_slab[];
+    float* slab = s_slab;
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    u32x2* kl = reinterpret_cast<u32x2*>(slab + DEC_P_LIST0 + DEC_P_PRIV * wv);
+    uint32_t* mw = reinterpret_cast<uint32_t*>(slab + DEC_P_MASK);
+    const uint32_t pend_off = DEC_P_LIST0 + DEC_P_PRIV * wv + DEC_P_PEND_OFF;
+    unsigned long long bar_wait = 0;
+    uint32_t bar_n = 0;
+    PSTAMP(0);
+
+    WRing<DAL3_PF> ring;
+    ring.init(w.dec_stream, lane);                     // conv2 only; dconv1's rows come from dw1c
+    f32x16 bias = tile_from_channels(w.b2, h);
+    const bool crop_bad = bits_nonfinite(gb[0]);
+    const __amdgpu_buffer_rsrc_t wc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(w.dw2c), 0, 512 * 1024, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wd1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(w.dw1c), 0, (DEC_NULL_K + 1) * 256, 0x00020000);
+    if (wv == 0) slab[DEC_Q_ZERO * 32 + pt] = 0.0f;
+    const int row_pos = 2 * ((lane & 3) + 4 * ((lane & 31) >> 3)) + ((lane >> 2) & 1);
+    // the wave's chunks are wv, wv + 2, ...: kf / kn the chain index of this lane's row in the chunk fetched next / after that
+    uint32_t kf = pk[32 * wv + row_pos], kn = pk[32 * (wv + 2) + row_pos];
+    f32x16 tA, tB;                                     // the wave's two chunks of a group; between groups: their terms gb
+    f32x16 x2[1][2];
+    {
+        float in[1][2];
+        load_points<2, 1>(pts, b, n0, n_pts, c_in, in, lane);
+        f32x16 x1[1][2];
+        first_layer<2, 2, 1>(w.w1, w.b1, in, x1, lane);
+        f32x16 c2a[1], c2b[1];                         // conv2 as in ins_seg_decode_tile's compacted body
+        c2a[0] = bias;
+        mma_block_ring<2, 1>(ring, x1, c2a, [&](int i) {
+            if (i == 0) bias = tile_from_channels(w.b2 + 32, h);
+        });
+        c2b[0] = bias;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const f32x4 a = ring.slot[i];
+            ring.slot[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wd1, kf * 256u + (uint32_t)h * 128u + 16u * i, 0, 0));
+#pragma unroll
+            for (int e = 0; e < 4; ++e) c2b[0] = mfma32(a[e], x1[0][i / 4][4 * (i % 4) + e], c2b[0]);
+            DAL3_SCHED_FENCE();
+            if (i == 0) tA = tile_from_channels(gbc + 32 * wv, h);
+            if (i == 1) tB = tile_from_channels(gbc + 32 * (wv + 2 < (uint32_t)nch ? wv + 2 : 0), h);
+            x2[0][0][2 * i] = relu1(c2a[0][2 * i]);
+            x2[0][0][2 * i + 1] = relu1(c2a[0][2 * i + 1]);
+            DAL3_SCHED_FENCE();
+        }
+        x2[0][1] = relu16(c2b[0]);
+        kf = kn;
+    }
+    f32x16 a2[4];
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) a2[mt] = tile_from_channels(w.db2 + 32 * (4 * wv + mt), h);
+    PSTAMP(1);
+
+    uint32_t halves = 0, kq0 = 0, kq1 = 0, pend = 0, n_steps = 0, n_live = 0;
+    u32x2 pend_e = {0u, DEC_Q_ZERO * 32u};
+    // ReLU of two registers, their rows (rows: the chunk's first row, this lane) and their live bits
+    auto relu_note = [&](f32x16& t, int i, float* rows, uint32_t& word) {
+        t[2 * i] = relu1(t[2 * i]);
+        t[2 * i + 1] = relu1(t[2 * i + 1]);
+        if (i == 0) halves = 0;
+#pragma unroll
+        for (int r = 2 * i; r < 2 * i + 2; ++r) {
+            const float v = t[r];
+            rows[2 * r * 32] = v;
+            note_halves(halves, live_ballot(v), r);
+        }
+        if (i == 7) word = live_word(halves);
+    };
+    // one dconv1 chunk: the slots hold its rows and are refilled with the wave's next chunk's (chain index kf); jn: the chunk
+    // after that, whose chain index is asked for (up to chunk 19 of the plan's 20: DEC_PLAN_LD)
+    auto dconv1_block = [&](f32x16& acc, int jn, auto side) {
+        const uint32_t voff = kf * 256u + (uint32_t)h * 128u;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const f32x4 a = ring.slot[i];
+            ring.slot[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wd1, voff + 16u * i, 0, 0));
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc = mfma32(a[e], x2[0][i / 4][4 * (i % 4) + e], acc);
+            DAL3_SCHED_FENCE();
+            if (i == 0) kn = pk[32 * jn + row_pos];
+            side(i);
+            DAL3_SCHED_FENCE();
+        }
+        kf = kn;
+    };
+    // the group of chunks c0 .. c0 + 3 (c0 .. c0 + 1 for the plan's last two): this wave's are c0 + wv and c0 + 2 + wv
+    auto produce = [&](int c0) {
+        const uint32_t buf = ((uint32_t)c0 >> 2) & 1u;
+        const bool two = c0 + 2 < nch;
+        kq0 = pk[32 * c0 + lane];                      // the plan's chain index of list position 64 j + lane of the group
+        kq1 = pk[32 * (c0 + 2) + lane];
+        float* rows = slab + (128 * buf + 32 * wv) * 32 + lane;
+        uint32_t mA = 0, mB = 0;
+        dconv1_block(tA, c0 + (int)wv + 4, [](int) {});
+        if (two) {
+            dconv1_block(tB, c0 + (int)wv + 6, [&](int i) { relu_note(tA, i, rows, mA); });
+#pragma unroll
+            for (int i = 0; i < 8; ++i) relu_note(tB, i, rows + 64 * 32, mB);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) relu_note(tA, i, rows, mA);
+        }
+        if (lane == 0) {
+            mw[4 * buf + wv] = mA;
+            mw[4 * buf + 2 + wv] = mB;                 // (0 for a chunk behind the plan's last)
+        }
+        const int ja = c0 + 4 + (int)wv, jb = c0 + 6 + (int)wv;    // the next group's terms, into the registers just freed
+        tA = tile_from_channels(gbc + 32 * (ja < nch ? ja : 0), h);
+        tB = tile_from_channels(gbc + 32 * (jb < nch ? jb : 0), h);
+    };
+    auto compact_mma = [&](const PStep& S) {
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) a2[mt] = mfma32(S.a[mt], S.b, a2[mt]);
+    };
+    auto compact_issue = [&](PStep& S, u32x2 e) {      // entry e: its row, and 16 bytes of the channel's weights (out-tiles 4 wv ..)
+        S.b = slab[e[1] + (uint32_t)pt];
+        S.a = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wc, e[0] + (uint32_t)pt * 32u + 16u * wv, 0, 0));
+    };
+    auto consume = [&](int c0) {
+        const uint32_t buf = ((uint32_t)c0 >> 2) & 1u;
+        uint32_t mg[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) mg[u] = __builtin_amdgcn_readfirstlane(mw[4 * buf + u]);
+        kl[0] = pend_e;
+        uint32_t total = pend;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const uint32_t w0 = mg[2 * j], w1 = mg[2 * j + 1];
+            const uint32_t below = __builtin_amdgcn_mbcnt_hi(w1, __builtin_amdgcn_mbcnt_lo(w0, 0u));
+            const uint32_t word = h ? w1 : w0;
+            if ((word >> pt) & 1u) {
+                u32x2 e;
+                e[0] = (j ? kq1 : kq0) * 1024u;
+                e[1] = (128u * buf + 64u * j + (uint32_t)lane) * 32u;
+                kl[total + below] = e;
+            }
+            total += __builtin_popcount(w0) + __builtin_popcount(w1);
+        }
+        if (lane < DEC_Q_OVER) {
+            u32x2 e;
+            e[0] = 0u, e[1] = DEC_Q_ZERO * 32u;
+            kl[total + (uint32_t)lane] = e;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const uint32_t steps = total >> 1;
+        const u32x2* kp = kl + h;
+        PStep S[DAL3_DEC_NB];
+        u32x2 K[DAL3_DEC_NB];
+#pragma unroll
+        for (int u = 0; u < DAL3_DEC_NB; ++u) K[u] = kp[2 * u];
+#pragma unroll
+        for (int u = 0; u < DAL3_DEC_NB; ++u) {
+            compact_issue(S[u], K[u]);
+            K[u] = kp[2 * (DAL3_DEC_NB + u)];
+        }
+        if (total & 1u) {                              // the leftover moves to the wave's own row, behind the reads above
+            pend_e = kl[total - 1u];
+            const float v = slab[pend_e[1] + (uint32_t)pt];
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            slab[pend_off + (uint32_t)pt] = v;
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            pend_e[1] = pend_off;
+        }
+        pend = total & 1u;
+        uint32_t s = 0;
+        for (; s + DAL3_DEC_NB <= steps; s += DAL3_DEC_NB) {
+            kp += 2 * DAL3_DEC_NB;
+#pragma unroll
+            for (int u = 0; u < DAL3_DEC_NB; ++u) {
+                compact_mma(S[u]);
+                compact_issue(S[u], K[u]);
+                K[u] = kp[2 * (DAL3_DEC_NB + u)];
+                DAL3_SCHED_FENCE();
+            }
+        }
+#pragma unroll
+        for (int u = 0; u + 1 < DAL3_DEC_NB; ++u) {
+            if (s + u < steps) compact_mma(S[u]);
+        }
+        n_steps += steps;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) n_live += __builtin_popcount(mg[u]);
+    };
+    produce(0);
+    for (int c0 = 0; c0 < nch; c0 += 4) {
+        PBARRIER();
+        consume(c0);
+        if (c0 + 4 < nch) produce(c0 + 4);
+    }
+    if (pend) {                                        // the very last live channel: its partner is the row of zeros
+        PStep S;
+        u32x2 e = pend_e;
+        if (h) e[1] = DEC_Q_ZERO * 32u;
+        compact_issue(S, e);
+        compact_mma(S);
+        ++n_steps;
+    }
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) a2[mt] = relu16(a2[mt]);
+    PSTAMP(2);
+#ifdef DAL3_STAMP
+    const unsigned long long stamp_steps2 = n_steps;
+#endif
+
+    f32x16 y3[2], y4[2];
+    uint32_t q_steps3 = 0, q_live3 = 0, q_steps4 = 0, q_live4 = 0;
+    uint32_t* ql = reinterpret_cast<uint32_t*>(kl);
+    dec_pair_queue_layer<8>(a2, y3, w.db3, w.dw3c, slab, ql, mw + 8, lane, wv, q_steps3, q_live3, bar_wait, bar_n);
+    PSTAMP(6);
+    dec_pair_queue_layer<4>(y3, y4, w.db4, w.dw4c, slab, ql, mw + 16, lane, wv, q_steps4, q_live4, bar_wait, bar_n);
+    PSTAMP(3);
+#ifdef DAL3_DEC_COUNT
+    if (lane == 0 && wv == 0) {
+        atomicAdd(&g_dec_count[0], 1ull);
+        atomicAdd(&g_dec_count[5], 1ull);
+        atomicAdd(&g_dec_count[2], (unsigned long long)nch);
+        atomicAdd(&g_dec_count[3], (unsigned long long)n_steps);
+        atomicAdd(&g_dec_count[4], (unsigned long long)n_live);
+        atomicAdd(&g_dec_count[6], (unsigned long long)q_steps3);
+        atomicAdd(&g_dec_count[7], (unsigned long long)q_live3);
+        atomicAdd(&g_dec_count[8], (unsigned long long)q_steps4);
+        atomicAdd(&g_dec_count[9], (unsigned long long)q_live4);
+    }
+#endif
+
+    // dconv5 on the VALU: the lane's chain runs over k-tiles 0 .. 3; wave 0 holds 0, 1 and starts it, wave 1 holds 2, 3
+    float* l5 = slab + DEC_P_L5;
+    float l0 = 0.0f, l1 = 0.0f;
+    if (wv == 1) {
+        PBARRIER();
+        l0 = l5[lane], l1 = l5[64 + lane];
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const f32x4 wa = *reinterpret_cast<const f32x4*>(w.dw5 + 32 * (2 * wv + i) + 8 * q + 4 * h);
+            const f32x4 wb = *reinterpret_cast<const f32x4*>(w.dw5 + 128 + 32 * (2 * wv + i) + 8 * q + 4 * h);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                l0 = fmaf(wa[e], y4[i][4 * q + e], l0);
+                l1 = fmaf(wb[e], y4[i][4 * q + e], l1);
+            }
+        }
+    }
+    if (wv == 0) {
+        l5[lane] = l0, l5[64 + lane] = l1;
+        PBARRIER();
+    } else {
+        float s0 = l0 + __shfl_xor(l0, 32) + w.db5[0];
+        float s1 = l1 + __shfl_xor(l1, 32) + w.db5[1];
+        if (crop_bad) s0 = s1 = __int_as_float(DAL3_QNAN_BITS);
+        const int n = n0 + pt;
+        if (h == 0 && n < n_pts) {
+            f32x2 o;
+            o[0] = s0;
+            o[1] = s1;
+            *reinterpret_cast<f32x2*>(logits + (b * n_pts + n) * 2) = o;
+            mask[b * n_pts + n] = (!crop_bad && s0 < s1) ? 1 : 0;      // strict '<': ties are background
+        }
+    }
+    PSTAMP(4);
+#ifdef DAL3_STAMP
+    if (lane == 0 && blockIdx.x < 4096) {
+        long long* st = g_stamps + (blockIdx.x * 2 + wv) * 16;
+        st[8] = (long long)bar_wait, st[9] = bar_n, st[10] = (long long)stamp_steps2, st[15] = 1;
+    }
+#endif
+}
+
+// The dense body for a blob whose guard flag is set, behind ins_seg_decode_pair_kernel; any other blob: nothing to do.
+__global__ __launch_bounds__(64 * DAL3_WG_WAVES) void ins_seg_decode_guarded_kernel(InsSegW w, BCN pts, int c_in, int n_pts,
+                                                                                    int tiles_per_item, const float* __restrict__ gbias,
+                                                                                    float* __restrict__ logits, uint8_t* __restrict__ mask) {
+    if (*w.dec_flag == 0) return;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int64_t b = blockIdx.x / tiles_per_item;
+    const int n0 = ((blockIdx.x % tiles_per_item) * DAL3_WG_WAVES + wave) * 32;
+    if (n0 >= n_pts) return;
+    ins_seg_decode_tile<1, false>(w, pts, c_in, n_pts, b, n0, gbias + b * 512, logits, mask, nullptr, lane, wave);
+}
+
+// ------------------------------------------------------------------------------------------------
 template <int KS, int C1, int C2, int C3, int T>
 __global__ __launch_bounds__(64 * DAL3_WG_WAVES) void point_head_kernel(PointHeadW w, BCN x, int c_in, int n_pts,
                                                          int tiles_per_item, float* __restrict__ feat,
@@ -1052,11 +1500,46 @@ hipError_t launch_ins_seg_encode(const InsSegW& w, BCN pts, int c_in, int B, int
     return hipGetLastError();
 }
 
+// The throughput decoder as pairs of waves (ins_seg_decode_pair_kernel): every job of the throughput family, unless the
+// caller's flags say otherwise (dal3.h: DAL3_BCN_NO_DEC_PAIR selects ins_seg_decode_kernel for any job). A pure function of
+// the job and the flags; both give the same bits. The blob's guard flag lives in device memory, so the decision about it is
+// taken on the device: see ins_seg_decode_guarded_kernel. DAL3_DEC_PAIR_MIN_TILES: the smallest job that takes the pairs
+// (profiles/LEDGER_r19.md).
+#ifndef DAL3_DEC_PAIR
+#define DAL3_DEC_PAIR 1                 // 0: never (A/B builds)
+#endif
+#ifndef DAL3_DEC_PAIR_MIN_TILES
+#define DAL3_DEC_PAIR_MIN_TILES 0
+#endif
+bool dec_pair_route(int flags, int B, int N) {
+    const int64_t tiles = (int64_t)B * ((N + 31) / 32);
+    if (!DAL3_DEC_PAIR || (flags & DAL3_BCN_NO_DEC_PAIR)) return false;
+    if (!DAL3_DEC_SPARSE || DAL3_DEC_T != 1) return false;
+    if (lat_use(tiles, flags, DAL3_LAT_MAX_TILES_DEC)) return false;
+    return tiles >= DAL3_DEC_PAIR_MIN_TILES;
+}
+// Which fp32 decoder launch_ins_seg_decode takes (dal3.h: dal3_ins_seg_decode_route); guarded: the blob's guard flag is set.
+int dec_route(int flags, int B, int N, bool guarded) {
+    if (lat_use((int64_t)B * ((N + 31) / 32), flags, DAL3_LAT_MAX_TILES_DEC)) return DAL3_DEC_ROUTE_LATENCY;
+    return dec_pair_route(flags, B, N) && !guarded ? DAL3_DEC_ROUTE_PAIR : DAL3_DEC_ROUTE_ONE_WAVE;
+}
+
 hipError_t launch_ins_seg_decode(const InsSegW& w, BCN pts, int c_in, int B, int N, const float* gbias,
                                  float* logits, uint8_t* mask, hipStream_t s, DecPlan plan) {
     if (lat_use((int64_t)B * ((N + 31) / 32), pts.flags, DAL3_LAT_MAX_TILES_DEC)) return launch_ins_seg_decode_lat(w, pts, c_in, B, N, gbias, logits, mask, s);
     constexpr int T = DAL3_DEC_T;
     const int tpi = tiles_per_item(N, T);
+    if (dec_pair_route(pts.flags, B, N)) {
+        constexpr size_t lds_pair = (size_t)DEC_P_FLOATS * sizeof(float);
+        const int tpi1 = (N + 31) / 32;
+        hipLaunchKernelGGL(ins_seg_decode_pair_kernel, dim3((unsigned)((int64_t)B * tpi1)), dim3(128), lds_pair, s, w, pts, c_in, N, tpi1,
+                           gbias, logits, mask, plan);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(ins_seg_decode_guarded_kernel, dim3((unsigned)((int64_t)B * tpi)), dim3(64 * DAL3_WG_WAVES), 0, s, w, pts, c_in,
+                           N, tpi, gbias, logits, mask);
+        return hipGetLastError();
+    }
     // the compacted body's row queues: one per wave, above the 64 KiB a kernel may take without asking
     constexpr size_t lds = DAL3_DEC_SPARSE != 0 && T == 1 ? (size_t)DAL3_WG_WAVES * DEC_Q_FLOATS * sizeof(float) : 0;
     if (lds) {

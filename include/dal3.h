@@ -146,9 +146,11 @@ typedef struct {
  *                                  jobs of many crops take (dal3_ins_seg_encoder_route)
  *   DAL3_BCN_NO_HEAD_RESIDENT      fp32 static box_est / point_emb heads: the screened conv4 as its two launches (dense
  *                                  seed tiles, then the other tiles) instead of one workgroup per item, which jobs of
- *                                  many items take (dal3_point_head_route) */
+ *                                  many items take (dal3_point_head_route)
+ *   DAL3_BCN_NO_DEC_PAIR           fp32 instance segmentation: the throughput decoder with one wave per 32-point tile
+ *                                  instead of a pair of waves per tile (dal3_ins_seg_decode_route) */
 enum { DAL3_BCN_NO_SMALL_JOB_KERNELS = 1, DAL3_BCN_NO_WORKLIST = 2, DAL3_BCN_NO_LDS_SAMPLER = 4, DAL3_BCN_NO_DEC_PLAN = 16,
-       DAL3_BCN_NO_ENC_RESIDENT = 32, DAL3_BCN_NO_HEAD_RESIDENT = 64 };
+       DAL3_BCN_NO_ENC_RESIDENT = 32, DAL3_BCN_NO_HEAD_RESIDENT = 64, DAL3_BCN_NO_DEC_PAIR = 128 };
 
 /* ---- PointNetInstanceSeg.forward (static_model.py:271-296, dynamic_model.py:187-212) plus
  * the mask of point_cloud_masking (static_model.py:59). logits (B,N,2) fp32, mask (B,N) u8.
@@ -169,6 +171,13 @@ int dal3_ins_seg_plan_layout(int B, size_t off[4], int* min_dead);
  * bad argument. For tests and measurements: results are bit-identical on every route. */
 enum { DAL3_ENC_ROUTE_LATENCY = 0, DAL3_ENC_ROUTE_DENSE = 1, DAL3_ENC_ROUTE_TWO_LAUNCH = 2, DAL3_ENC_ROUTE_RESIDENT = 3 };
 int dal3_ins_seg_encoder_route(int B, int N, int flags);
+/* Which decoder a DAL3_F32 instance-segmentation job of B crops x N points takes with `flags` on the blob `packed`: the
+ * small-job family, the throughput kernel with one wave per tile, or the one with a pair of waves per tile. A blob whose
+ * guard flag is set (a folded dconv2 - dconv4 weight is not finite, or a folded bias is -0) never takes the pairs. The
+ * flag is in device memory: this call reads it with a blocking copy (packed == NULL: taken as clear); the launch itself
+ * decides on the device. Negative (DAL3_EINVAL) for a bad argument. For tests and measurements: the same bits on every route. */
+enum { DAL3_DEC_ROUTE_LATENCY = 0, DAL3_DEC_ROUTE_ONE_WAVE = 1, DAL3_DEC_ROUTE_PAIR = 2 };
+int dal3_ins_seg_decode_route(const void* packed, int B, int N, int flags);
 int dal3_ins_seg_forward(const void* packed, int dtype, int c_in, dal3_bcn pts, int B, int N,
                          float* logits, uint8_t* mask, float* global_feat_out,
                          void* workspace, size_t workspace_bytes, dal3_stream stream);

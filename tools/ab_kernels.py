@@ -5,7 +5,8 @@ three shared-MLP kernels, median and min per build, outputs cross-checked agains
 them (`dec` alone is the stand-alone entry, which never has a plan); `seg0` the same call with DAL3_BCN_NO_DEC_PLAN.
 `enc2` / `seg2` are `enc` / `seg` with DAL3_BCN_NO_ENC_RESIDENT (the screened encoder's two launches) where the build knows
 that flag, the same call as `enc` / `seg` where it does not; `head2` likewise is `head` with DAL3_BCN_NO_HEAD_RESIDENT (the
-screened point head's two launches). A -DDAL3_SCREEN_COUNT build prints the screen's counters of one `seg` and one `seg2` call.
+screened point head's two launches). `dec1` / `seg1` are `dec` / `seg` with DAL3_BCN_NO_DEC_PAIR (the decoder with one wave
+per tile) where the build knows that flag; their logits and masks are cross-checked too. A -DDAL3_SCREEN_COUNT build prints the screen's counters of one `seg` and one `seg2` call.
 
   python tools/ab_kernels.py build_a.so build_b.so ... [--B 4096] [--N 1024] [--rounds 7]
 """
@@ -118,6 +119,17 @@ for name, lib in libs:
                                                             hip.ptr(d["logits"]), hip.ptr(d["mask"]), st)
     d["head"] = lambda lib=lib, d=d: lib.dal3_point_head_forward(hip.HEAD_STATIC_BOX_EST, hip.ptr(d["w_box"]), DT, xo, B, 512,
                                                                  hip.ptr(d["bp"]), 39, hip.ptr(d["ws"]), d["ws"].numel(), st)
+    d["has_pair"] = hasattr(lib, "dal3_ins_seg_decode_route")
+    one = hip.BCN_NO_DEC_PAIR if d["has_pair"] else 0
+    x1 = hip.bcn(pts)
+    x1.flags |= one
+    d["logits1"], d["mask1"] = torch.empty_like(logits), torch.empty_like(mask)
+    d["dec1"] = lambda lib=lib, d=d, x1=x1: lib.dal3_ins_seg_decode(hip.ptr(d["w_seg"]), DT, 3, x1, B, N, hip.ptr(d["gb"]),
+                                                                    hip.ptr(d["logits1"]), hip.ptr(d["mask1"]), st)
+    d["seg1"] = lambda seg=seg, one=one: seg(flags=one)
+    if d["has_pair"]:
+        print(f"{name}: decoder route {lib.dal3_ins_seg_decode_route(hip.ptr(w_seg), B, N, 0)} "
+              f"(with DAL3_BCN_NO_DEC_PAIR {lib.dal3_ins_seg_decode_route(hip.ptr(w_seg), B, N, one)})")
     d["has_head_res"] = hasattr(lib, "dal3_point_head_route")
     xo2 = hip.bcn(obj)
     xo2.flags |= hip.BCN_NO_HEAD_RESIDENT if d["has_head_res"] else 0
@@ -182,7 +194,8 @@ for name, lib in libs:
 torch.cuda.synchronize()
 ref = state[0]
 for (name, _), d in zip(libs, state):
-    same = (torch.equal(d["g"], ref["g"]), torch.equal(d["logits"], ref["logits"]), torch.equal(d["bp"], ref["bp"]))
+    same = (torch.equal(d["g"], ref["g"]), torch.equal(d["logits"].view(torch.int32), ref["logits"].view(torch.int32)),
+            torch.equal(d["mask"], ref["mask"]), torch.equal(d["bp"], ref["bp"]))
     assert d["enc2"]() == 0 and d["seg2"]() == 0 and d["head2"]() == 0, _.dal3_last_error()
     torch.cuda.synchronize()
     print(f"{name}: point head under DAL3_BCN_NO_HEAD_RESIDENT bitwise-equal to the first build (box_pred) = "
@@ -190,12 +203,18 @@ for (name, _), d in zip(libs, state):
     print(f"{name}: two-launch encoder bitwise-equal to the first build (g of enc2, g / logits / mask of seg2) = "
           f"{(torch.equal(d['g'], ref['g']), torch.equal(d['g_seg'].view(torch.int32), ref['g_seg'].view(torch.int32)), torch.equal(d['lg_seg'].view(torch.int32), ref['lg_seg0'].view(torch.int32)), torch.equal(d['mk_seg'], ref['mk_seg0']))}")
     bits = lambda t: t.view(torch.int32)
+    assert d["dec1"]() == 0 and d["seg1"]() == 0, _.dal3_last_error()
+    torch.cuda.synchronize()
+    print(f"{name}: one wave per tile (DAL3_BCN_NO_DEC_PAIR) bitwise-equal to the first build (logits / mask of dec1, logits / mask "
+          f"of seg1) = {(torch.equal(bits(d['logits1']), bits(ref['logits'])), torch.equal(d['mask1'], ref['mask']), torch.equal(bits(d['lg_seg']), bits(ref['lg_seg0'])), torch.equal(d['mk_seg'], ref['mk_seg0']))}")
+    assert d["seg"]() == 0, _.dal3_last_error()
+    torch.cuda.synchronize()
     seg_same = (torch.equal(bits(d["g_seg"]), bits(ref["g_seg"])), torch.equal(bits(d["lg_seg"]), bits(ref["lg_seg0"])),
                 torch.equal(d["mk_seg"], ref["mk_seg0"]), torch.equal(bits(d["lg_seg0"]), bits(ref["lg_seg0"])))
     print(f"{name}: ins_seg_forward bitwise-equal to the first build without a plan (g, logits, mask, logits of its own call "
           f"without a plan) = {seg_same}")
     dl = (d["logits"] - ref["logits"]).abs().max().item() / ref["logits"].abs().max().item()
-    print(f"{name}: bitwise-equal to first (g, logits, box_pred) = {same}, logits rel diff {dl:.2e}")
+    print(f"{name}: bitwise-equal to first (g, logits, mask, box_pred) = {same}, logits rel diff {dl:.2e}")
 
 
 def timed(fn, iters=5):
@@ -208,7 +227,7 @@ def timed(fn, iters=5):
     return a.elapsed_time(b) / iters
 
 
-KINDS = ("enc", "enc2", "dec", "head", "head2", "seg", "seg2", "seg0")
+KINDS = ("enc", "enc2", "dec", "dec1", "head", "head2", "seg", "seg1", "seg2", "seg0")
 res = {(n, k): [] for n, _ in libs for k in KINDS}
 for r in range(args.rounds):
     for k in KINDS:
