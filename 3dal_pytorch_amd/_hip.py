@@ -211,6 +211,15 @@ class CenterDecodeFlip4Args(C.Structure):
     _fields_ = [("decode", CenterDecodeArgs)]
 
 
+SWEEP_MAX = 16
+
+
+class SweepSegment(C.Structure):
+    """dal3_sweep_segment"""
+    _fields_ = [("xyz", vp), ("feature", vp), ("n", C.c_int64), ("out_row", C.c_int64), ("matrix", C.c_double * 12),
+                ("time", C.c_float), ("has_transform", C.c_int32)]
+
+
 PILLAR_OVERFLOW = 128
 PILLAR_PACK_FLOATS = 5120
 
@@ -507,6 +516,7 @@ SIGNATURES = {
     "dal3_center_decode_flip4_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "dal3_center_decode_flip4": (_i, [C.POINTER(CenterDecodeFlip4Args), vp]),
     "dal3_flip4_points": (_i, [vp, _i64, C.c_int32, vp, _i64, vp, vp, _i64, vp]),
+    "dal3_sweep_merge": (_i, [vp, _i64, C.c_int32, _i64, vp, vp, _i64, vp]),
     "dal3_voxelize_workspace_bytes": (_sz, [_i64, _i64]),
     "dal3_voxelize": (_i, [C.POINTER(VoxelizeArgs), vp]),
     "dal3_pillar_pack": (_i, [C.POINTER(Layer), _i, _i, C.c_double, vp, vp]),

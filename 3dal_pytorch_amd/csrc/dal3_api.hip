@@ -1178,6 +1178,21 @@ extern "C" int dal3_flip4_points(const float* points, int64_t N, int32_t C, cons
     return 0;
 }
 
+extern "C" int dal3_sweep_merge(const dal3_sweep_segment* segments, int64_t B, int32_t nsweeps, int64_t N, float* out,
+                                int64_t* point_offsets, int64_t max_workgroups, dal3_stream stream) {
+    if (nsweeps < 1 || nsweeps > DAL3_SWEEP_MAX) return fail(DAL3_EINVAL, "sweep_merge: bad nsweeps (1 .. DAL3_SWEEP_MAX)");
+    if (B < 0 || N < 0 || B * nsweeps > DAL3_MAX_ITEMS || N > DAL3_MAX_TILES)
+        return fail(DAL3_EINVAL, "sweep_merge: bad B / N (0 <= B * nsweeps <= DAL3_MAX_ITEMS, 0 <= N <= DAL3_MAX_TILES)");
+    if (max_workgroups < 0) return fail(DAL3_EINVAL, "sweep_merge: negative max_workgroups");
+    if (B == 0) return 0;
+    if (!segments || !point_offsets) return fail(DAL3_EINVAL, "sweep_merge: null segments / point_offsets");
+    if (reinterpret_cast<uintptr_t>(segments) % 8 || reinterpret_cast<uintptr_t>(point_offsets) % 8)
+        return fail(DAL3_EINVAL, "sweep_merge: segments and point_offsets must be 8-byte aligned");
+    if (N > 0 && (!out || reinterpret_cast<uintptr_t>(out) % 4)) return fail(DAL3_EINVAL, "sweep_merge: null or misaligned out");
+    HIP_TRY(launch_sweep_merge(segments, B, nsweeps, N, out, point_offsets, max_workgroups, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------- the PointPillars reader
 extern "C" size_t dal3_voxelize_workspace_bytes(int64_t B, int64_t N) {
     if (B < 0 || N < 0 || B > DAL3_MAX_ITEMS || N > DAL3_MAX_ITEMS) return 0;

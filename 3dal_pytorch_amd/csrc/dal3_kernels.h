@@ -363,6 +363,9 @@ hipError_t launch_center_decode(const dal3_center_decode_args* a, hipStream_t s)
 hipError_t launch_center_decode_flip4(const dal3_center_decode_flip4_args* a, hipStream_t s);
 hipError_t launch_flip4_points(const float* points, int64_t N, int C, const int64_t* offsets, int64_t B, float* out,
                                int64_t* out_offsets, int64_t max_workgroups, hipStream_t s);
+// the Waymo sweep merge of LoadPointCloudFromFile (dal3_sweeps.hip): raw planes -> the voxeliser's rows, one launch a batch
+hipError_t launch_sweep_merge(const dal3_sweep_segment* segments, int64_t B, int nsweeps, int64_t N, float* out,
+                              int64_t* point_offsets, int64_t max_workgroups, hipStream_t s);
 // the PointPillars reader (dal3_pillars.hip): voxelisation as a stable radix sort over chunks, the fused feature kernel
 size_t voxelize_workspace_bytes(int64_t B, int64_t N);
 hipError_t launch_voxelize(const dal3_voxelize_args* a, hipStream_t s);

@@ -363,3 +363,80 @@ def loss_case(seed, two_stage=False, batch=6, n_pts=64):
               (uniform(seed, t + "hcl", (batch,)) * 12).astype(np.int64), f32("hrl", (batch,), 0.1),
               (uniform(seed, t + "scl", (batch,)) * 3).astype(np.int64), f32("srl", (batch, 3), 0.3))
     return out, labels
+
+
+# --------------------------------------------------------------------------- a Waymo-style directory (the detection run)
+def waymo_frame_points(seed, tag, n_points, pc_range):
+    """one frame's raw rows: points_xyz (n, 3) in a few clumps and a thin background inside `pc_range` (a few fall
+    outside), points_feature (n, 2) = raw intensity (positive, some far above 1: the loader's tanh is not yet applied)
+    and elongation"""
+    lo, hi = np.asarray(pc_range[:3], np.float64), np.asarray(pc_range[3:], np.float64)
+    centre = uniform(seed, tag + "c", (4, 3), 0.25, 0.75) * (hi - lo) + lo
+    which = (uniform(seed, tag + "w", (n_points,)) * 5).astype(np.int64)
+    spread = (hi - lo) * np.array([0.08, 0.08, 0.1])
+    clump = centre[which % 4] + normal(seed, tag + "n", (n_points, 3)) * spread
+    back = uniform(seed, tag + "b", (n_points, 3), -0.02, 1.02) * (hi - lo) + lo
+    xyz = np.where((which == 4)[:, None], back, clump).astype(np.float32)
+    feature = np.stack([uniform(seed, tag + "i", (n_points,)) ** 4 * 30.0, uniform(seed, tag + "e", (n_points,), 0.0, 1.5)], 1)
+    return xyz, feature.astype(np.float32)
+
+
+def waymo_files(root, seed, n_sequences=2, n_frames=3, n_points=3000, nsweeps=2, pc_range=(-75.2, -75.2, -2.0, 75.2, 75.2, 4.0),
+                split="val", n_objects=3):
+    """A tiny data set in the on-disk formats of the reference's Waymo converter under `root`/`split`:
+    lidar/seq_{s}_frame_{f}.pkl ({scene_name, frame_name, frame_id, lidars: {points_xyz, points_feature}}),
+    annos/seq_{s}_frame_{f}.pkl (segment_files' format) and `root`/infos_{split}_{nsweeps:02d}sweeps_filter_zero_gt.pkl, a list
+    of {path, anno_path, token, timestamp, sweeps: [{path, token, transform_matrix, time_lag}]} in sequence order. Sweep i of a
+    frame is the frame i + 1 steps back, moved into the frame's vehicle frame (inverse(veh_to_global) . the earlier
+    veh_to_global); the first frames of a sequence repeat themselves with transform_matrix None and time_lag 0, as
+    waymo_common.py:331-370 does. Frame f of a sequence has n_points + 17 f points; frames lie 0.1 s apart.
+    -> (info_path, infos)"""
+    import os
+    import pickle
+    for sub in ("lidar", "annos"):
+        os.makedirs(os.path.join(root, split, sub), exist_ok=True)
+    infos = []
+    for s in range(n_sequences):
+        scene = f"synth{seed % 10000:04d}{s:02d}"
+        base = np.reshape(pose_veh_to_global(seed, f"wf{s}"), [4, 4])
+        poses, stamps = [], []
+        for f in range(n_frames):
+            m = base.copy()
+            m[:3, 3] += base[:3, :3] @ np.array([0.8 * f, 0.05 * f, 0.0])
+            poses.append(m)
+            stamps.append(1500000000000000 + 1000000 * s + 100000 * f)           # microseconds
+        for f in range(n_frames):
+            name = f"seq_{s}_frame_{f}.pkl"
+            tag = f"wf{s}_{f}"
+            xyz, feature = waymo_frame_points(seed, tag, n_points + 17 * f, pc_range)
+            lidar_path, anno_path = os.path.join(root, split, "lidar", name), os.path.join(root, split, "annos", name)
+            frame_name = f"{scene}_location_day_{stamps[f]}"
+            with open(lidar_path, "wb") as fh:
+                pickle.dump({"scene_name": scene, "frame_name": frame_name, "frame_id": f,
+                             "lidars": {"points_xyz": xyz, "points_feature": feature}}, fh)
+            centres = uniform(seed, tag + "oc", (n_objects, 3), -30.0, 30.0) * np.array([1.0, 1.0, 0.02])
+            sizes = np.array(arch.MEAN_SIZE)[np.arange(n_objects) % 3] + normal(seed, tag + "os", (n_objects, 3), 0.0, 0.1)
+            yaw = uniform(seed, tag + "oy", (n_objects,), -np.pi, np.pi)
+            objs = [{"id": k, "name": f"{scene}_obj{k}", "label": 1 + k % 2, "num_points": 10,
+                     "box": np.concatenate([centres[k], sizes[k], [0.0, 0.0], [yaw[k]]]).astype(np.float32)}
+                    for k in range(n_objects)]
+            with open(anno_path, "wb") as fh:
+                pickle.dump({"scene_name": scene, "frame_name": frame_name, "frame_id": f, "veh_to_global": poses[f].reshape(16),
+                             "objects": objs}, fh)
+            ref_time = 1e-6 * stamps[f]
+            sweeps, prev = [], f
+            while len(sweeps) < nsweeps - 1:
+                if prev <= 0:
+                    sweeps.append(sweeps[-1] if sweeps else {"path": lidar_path, "token": name, "transform_matrix": None,
+                                                             "time_lag": 0})
+                else:
+                    prev -= 1
+                    other = f"seq_{s}_frame_{prev}.pkl"
+                    sweeps.append({"path": os.path.join(root, split, "lidar", other), "token": other,
+                                   "transform_matrix": np.linalg.inv(poses[f]) @ poses[prev],
+                                   "time_lag": ref_time - 1e-6 * stamps[prev]})
+            infos.append({"path": lidar_path, "anno_path": anno_path, "token": name, "timestamp": ref_time, "sweeps": sweeps})
+    info_path = os.path.join(root, f"infos_{split}_{nsweeps:02d}sweeps_filter_zero_gt.pkl")
+    with open(info_path, "wb") as fh:
+        pickle.dump(infos, fh)
+    return info_path, infos

@@ -214,6 +214,16 @@ def match_ground_truth(result, boxes, gt_offsets, gt_boxes, thr=0.75):
     return mf, mo
 
 
+def det_anno(labels, scores, boxes_lidar, anno, info):
+    """one entry of det_annos.pkl (waymo_common.py:116-129), shared by this run and the detection run (dist_test.py): the
+    names of the labels, the scores, the boxes already in Waymo's convention, and the frame's identity from its annotation
+    file `anno` and its info"""
+    frame_id = anno["frame_id"]
+    return {"name": np.array([LABEL_TO_NAME[int(i)] for i in labels]), "score": scores, "boxes_lidar": boxes_lidar,
+            "frame_id": "segment-" + anno["scene_name"] + f"_with_camera_labels_{frame_id:03d}",
+            "metadata": {"context_name": anno["scene_name"], "timestamp_micros": int(str(info["timestamp"]).replace(".", ""))}}
+
+
 def regroup(track_data):
     """tools/trackData.py:24-45: {token: per-frame lists} -> {object id: per-track lists + 'token'}"""
     tracking = {}
@@ -315,10 +325,7 @@ def run(work_dir, checkpoint, info_path, max_age=3, vehicle=0.8, pedestrian=0.4,
         labels = np.asarray(fr["label"]).reshape(-1)[box_ids]
         scores = fr["score"][box_ids]
         box3d = ext[f]["boxes_lidar"]
-        det_annos.append({"name": np.array([LABEL_TO_NAME[int(i)] for i in labels]), "score": scores, "boxes_lidar": box3d,
-                          "frame_id": "segment-" + a["scene_name"] + f"_with_camera_labels_{a['frame_id']:03d}",
-                          "metadata": {"context_name": a["scene_name"],
-                                       "timestamp_micros": int(str(infos[tok]["timestamp"]).replace(".", ""))}})
+        det_annos.append(det_anno(labels, scores, box3d, a, infos[tok]))
         n = len(box_ids)
         match = []
         for r in range(n):

@@ -851,6 +851,36 @@ int dal3_center_decode_flip4(const dal3_center_decode_flip4_args* args, dal3_str
 int dal3_flip4_points(const float* points, int64_t N, int32_t C, const int64_t* offsets, int64_t B, float* out,
                       int64_t* out_offsets, int64_t max_workgroups, dal3_stream stream);
 
+/* dal3_sweep_merge: the WaymoDataset branch of LoadPointCloudFromFile (det3d/datasets/pipelines/loading.py:61-91,
+ * 140-168) for B samples in one enqueue. A sample is nsweeps (1 .. DAL3_SWEEP_MAX) segments, the current frame first and
+ * then info["sweeps"][0 .. nsweeps - 2] in that order; the table `segments` (DEVICE memory, B * nsweeps entries, sample b's
+ * at [b nsweeps, (b + 1) nsweeps)) names each one's raw rows where they lie, xyz (n, 3) and feature (n, 2) float32 in planes
+ * of their own (the frame file's lidars.points_xyz / points_feature, uploaded as they are). out (N, C) float32 contiguous,
+ * C = 5 for nsweeps == 1 and 6 otherwise: segment s fills rows [out_row, out_row + n) with
+ *     [x', y', z', tanh(feature0), feature1 (, time)]
+ * where (x', y', z') = (x, y, z) bit for bit without a transform, and with one the first three rows of
+ * matrix (3 x 4 row-major, float64) . [x, y, z, 1]: ((m0 x + m1 y) + m2 z) + m3 in float64, every product and sum rounded
+ * on its own, cast to float32 once. tanh is the float64 tanh of the float32 value cast once (1e5 gives exactly 1.0f); NaN
+ * and infinities go through as IEEE-754 has them. time is the segment's, 0 for a current frame. The segments' out_row
+ * must ascend and partition [0, N) in table order (out_row[s + 1] = out_row[s] + n[s]); a row that a table sends nowhere
+ * is not written, and no row outside out ever is. point_offsets (B + 1) int64, device, is written: point_offsets[b] =
+ * the out_row of sample b's current frame, point_offsets[B] = N. Every output element is written once by one lane: no
+ * atomic, the same bits for every max_workgroups (0: no cap). B == 0 succeeds with nothing launched.
+ * B * nsweeps <= DAL3_MAX_ITEMS, N <= DAL3_MAX_TILES. */
+#define DAL3_SWEEP_MAX 16
+typedef struct dal3_sweep_segment {
+    const float* xyz;                    /* (n, 3) device */
+    const float* feature;                /* (n, 2) device */
+    int64_t n;
+    int64_t out_row;
+    double matrix[12];                   /* the first three rows of transform_matrix; read only with has_transform */
+    float time;                          /* float32(time_lag); 0 for the current frame */
+    int32_t has_transform;               /* 0: transform_matrix is None, or the current frame */
+} dal3_sweep_segment;
+
+int dal3_sweep_merge(const dal3_sweep_segment* segments, int64_t B, int32_t nsweeps, int64_t N, float* out,
+                     int64_t* point_offsets, int64_t max_workgroups, dal3_stream stream);
+
 /* ---- the PointPillars reader: points_to_voxel (det3d/ops/point_cloud/point_cloud_ops.py:7-184, through
  * VoxelGenerator.generate and collate_kitti's batch column), PillarFeatureNet and PointPillarsScatter
  * (det3d/models/readers/pillar_encoder.py:15-209) and VoxelFeatureExtractorV3 (voxel_encoder.py:9-24), for B samples in
